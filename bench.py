@@ -10,7 +10,7 @@ One "step" = one SAC.training_step (sac/sac.py:306-327): fused rollout of S*N tr
 replay insert + sample of B*G rows + G sgd_steps (each: fwd/bwd of the three losses, [all-reduce,] clip+AdamW+Polyak).
 value = transitions written per second by the whole job = n_gpus * N * S * steps / time  (weak scaling: per-GPU work fixed).
 
-    python bench.py [--gpus N --steps K --warmup W]      # N > 1 without WORLD_SIZE in the environment: bench.py starts its N ranks itself
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]      # N > 1 without WORLD_SIZE in the environment: bench.py starts its N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 After the headline measurement rank 0 (single-GPU run only) also measures, and appends as extra keys of the same JSON line:
@@ -121,6 +121,47 @@ def time_rollout_alone(trainer, ts, env_state, buffer_state, reps=30):
     e1.record(st)
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e-3 / reps
+
+
+DUMP_REPLAY_SAMPLE = 2 ** 16     # rows of the replay buffer written by --dump-outputs (fixed, seeded choice)
+
+
+def dump_outputs(trainer, ts, env_state, buffer_state, out_dir: Path) -> None:
+    """--dump-outputs: what training_step hands its caller after the last timed step — the training state, the environment
+    state and the replay buffer — as <name>.npy (float32, or float64 where integers would not survive float32).  The buffer is
+    2^20 rows: the rows the last step inserted are written whole, plus a fixed seeded sample of the rest.  The device state
+    is authoritative (a hipGraph replay does not move the host mirrors), so the buffer's logical order comes from it."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    arrays = {
+        "policy_params": f32(ts.policy_params),
+        "q_params": f32(ts.q_params),
+        "target_q_params": f32(ts.target_q_params),
+        "alpha_params": f32(ts.alpha_params),
+        "policy_adam_m": f32(ts.policy_optimizer_state[0]), "policy_adam_v": f32(ts.policy_optimizer_state[1]),
+        "q_adam_m": f32(ts.q_optimizer_state[0]), "q_adam_v": f32(ts.q_optimizer_state[1]),
+        "alpha_adam_m": f32(ts.alpha_optimizer_state[0]), "alpha_adam_v": f32(ts.alpha_optimizer_state[1]),
+        "gradient_steps": ts.gradient_steps.detach().double().cpu().numpy(),
+        "normalizer_params": f32(ts.normalizer_params.vec),
+        "env_obs": f32(env_state.obs),
+        "env_done": f32(env_state.done),
+        "env_steps": f32(env_state.info["steps"]),
+        "env_first_obs": f32(env_state.info["first_obs"]),
+        "replay_state": buffer_state.state.detach().double().cpu().numpy(),
+    }
+    data, mx = buffer_state.data, buffer_state.data.shape[0]
+    insert_pos, head = (int(v) for v in buffer_state.state[[0, 2]].cpu())
+    logical = lambda i: data[(i.to(data.device) + head) % mx]
+    n_new = trainer._rollout_rows.shape[0]
+    arrays["replay_last_step_rows"] = f32(logical(torch.arange(insert_pos - n_new, insert_pos)))
+    pick = torch.randperm(mx, generator=torch.Generator().manual_seed(0))[:DUMP_REPLAY_SAMPLE].sort().values
+    arrays["replay_sample_index"] = pick.double().numpy()
+    arrays["replay_sample_rows"] = f32(logical(pick))
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    log(f"dumped {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2 ** 20:.1f} MB) to {out_dir}")
 
 
 def cpu_baseline(budget_s=12.0):
@@ -361,7 +402,11 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the ppo_c3 / bptt_c5 extra measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="after the timed steps, write the state the last step produced as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Libraries (RCCL's version banner) write to fd 1; the contract is ONE JSON line on stdout, so fd 1 points at stderr
     # until the result is printed.
@@ -498,6 +543,8 @@ def main():
             trainer, ts, env_state, buffer_state, graph, dt = measure()
 
     log(f"timed region done: {dt / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(trainer, ts, env_state, buffer_state, args.dump_outputs)     # before anything below moves the state on
     # the contract's timed region is K steps (tens of ms); the same graph over >= 500 replays, device time — EVERY rank replays
     # (the captured step holds the gradient exchange), the slowest rank's figure is reported
     steady_ms, n_steady = None, max(500, args.steps)

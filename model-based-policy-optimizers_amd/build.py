@@ -16,8 +16,9 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OUT_DIR = HERE / "mbpo" / "_lib"
 LIB = OUT_DIR / "libmbpo_hip.so"
-# objects and -save-temps output stay out of the tree (the tree is what gpurun ships); only the .so lives in-tree
-OBJ_DIR = Path(os.environ.get("MBPO_BUILD_DIR", "/tmp/mbpo_hip_build"))
+# objects and -save-temps output: per checkout and git-ignored, so that neither another checkout's objects nor another
+# user's directory is ever picked up
+OBJ_DIR = Path(os.environ.get("MBPO_BUILD_DIR", HERE / "build"))
 
 ARCH = "gfx950"
 CXXFLAGS = [

@@ -1,11 +1,11 @@
 """Per-kernel register / spill table from the -Rpass-analysis=kernel-resource-usage dump of `build.py --save-temps`
-(/tmp/mbpo_hip_build/resource_usage.txt): python scripts/resource_table.py [substring ...]"""
+(model-based-policy-optimizers_amd/build/resource_usage.txt): python scripts/resource_table.py [substring ...]"""
 import re
 import subprocess
 import sys
 from pathlib import Path
 
-txt = Path("/tmp/mbpo_hip_build/resource_usage.txt").read_text()
+txt = (Path(__file__).resolve().parent.parent / "model-based-policy-optimizers_amd" / "build" / "resource_usage.txt").read_text()
 blocks = re.findall(r"Function Name: (\S+).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)"
                     r".*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", txt, re.S)
 names = subprocess.run(["c++filt"], input="\n".join(b[0] for b in blocks), capture_output=True, text=True).stdout.splitlines()
