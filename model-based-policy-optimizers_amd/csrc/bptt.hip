@@ -47,6 +47,17 @@ extern "C" int mbpo_debug_set_bptt_stamps(void *buf) {
   return MBPO_OK;
 }
 
+// Test hook (not part of include/mbpo_hip.h): 0 = the backward sweep recomputes the members' pre-activations (no z store, the
+// workspace shrinks), -1 = MBPO_BPTT_ZSTORE_MAX_MB and its cap decide.  bptt_plan reads it, so mbpo_bptt_workspace_floats and
+// mbpo_bptt_actor_grads agree while it is unchanged; set it BEFORE sizing a workspace — a store switched back on would overrun one
+// sized under recompute.  tests/test_gpu_bptt.py compares the two paths.
+static int g_bptt_zstore = -1;
+extern "C" int mbpo_debug_set_bptt_zstore(int mode) {
+  MBPO_REQUIRE(mode == -1 || mode == 0, MBPO_ERR_ARG, "debug_set_bptt_zstore: mode must be -1 or 0");
+  g_bptt_zstore = mode;
+  return MBPO_OK;
+}
+
 // analytic pendulum step + vector-Jacobian product (dynamics/pendulum_dynamics.py:29-63)
 __device__ __forceinline__ void pend_fwd(const float *x, float u, const float *sp, float *xn) {
   const float ms = sp[0], mt = sp[1], dt = sp[2], g = sp[3], mm = sp[4], l = sp[5];
@@ -489,8 +500,9 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
         } else if (elem == E_DYE) {
           if (A.w_z) {
             // straight into LDS, one 256-byte tile row per wave instruction (global_load_lds_dword: wave-uniform LDS base + 4 * lane,
-            // so a padded row is exactly one instruction); no data registers, every row of the round in flight at once; the op's
-            // closing __syncthreads() waits for them (vmcnt(0))
+            // so a padded row is exactly one instruction); no data registers, every row of the round in flight at once.  A barrier does
+            // not wait for LDS-DMA: each wave drains its own loads with an EXPLICIT s_waitcnt vmcnt(0) (as p2p_push does) behind the
+            // s_dye fill below, and the op's closing __syncthreads() then makes every wave's rows visible to the R_ENS_DG chains of the next op
             const int nz = DL - 1, cnt = (E - rr * EC) < EC ? (E - rr * EC) : EC, rows = cnt * nz * 16;
             const float *const zg = A.w_z + ((((tile * HZ + t) * E + rr * EC) * nz) << 10);
             for (int rix = wave; rix < rows; rix += (nthreads >> 6)) {
@@ -506,6 +518,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             const float v = c < X ? s_gx[r * ld_x + c] / (float)E : 0.f;   // x' = base + mean_e mu_e: the same for every member
             for (int cc = 0; cc < EC; ++cc) s_dye[(cc * 16 + r) * ld_ye + c] = v;
           }
+          if (A.w_z) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's reloaded rows have landed in LDS
         } else if (elem == E_DXUACC) {
           for (int idx = tid; idx < 16 * (X + U); idx += nthreads) {
             const int r = idx / (X + U), c = idx - r * (X + U);
@@ -721,7 +734,7 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   // tile, step, member, hidden layer) — 1 GB at BASELINE config 5 (n = 4096, H = 32, E = 10); beyond MBPO_BPTT_ZSTORE_MAX_MB (default
   // 16384) the kernel recomputes instead
   pl->o_z = -1;
-  if (E > 0) {
+  if (E > 0 && g_bptt_zstore != 0) {
     static const long long max_mb = getenv("MBPO_BPTT_ZSTORE_MAX_MB") ? atoll(getenv("MBPO_BPTT_ZSTORE_MAX_MB")) : 16384;
     const long long zf = tiles * d->horizon * E * (pl->dyn.n_layers - 1) * 1024;
     if (zf * 4 <= max_mb * (1LL << 20)) pl->o_z = take(zf);

@@ -116,6 +116,10 @@ extern "C" int mbpo_icem_sample(const float *mean, const float *std, const float
 }
 
 // ---- objective + elite update ---------------------------------------------------------------------------------
+// max that propagates NaN, as jnp.max and jax.nn.relu do (fmaxf returns the other operand): a particle whose model diverged makes
+// the candidate's optimistic value NaN instead of being dropped.  For numbers it is fmaxf.
+__device__ __forceinline__ float icem_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+
 __global__ void __launch_bounds__(256) k_icem_values(const float *rows, int row_len, int reward_col, int NC, int P, int H, int use_max,
                                                       float *values, const float *particle_cost, float lambda_c, int cost_use_max) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -126,7 +130,7 @@ __global__ void __launch_bounds__(256) k_icem_values(const float *rows, int row_
     float acc = 0.f;
     for (int t = 0; t < H; ++t) acc += rows[((long long)t * N + (long long)c * P + p) * row_len + reward_col];
     const float m = acc / (float)H;                                   // jnp.mean(transitions.reward, axis=-1)
-    agg = (p == 0) ? m : (use_max ? fmaxf(agg, m) : agg + m);
+    agg = (p == 0) ? m : (use_max ? icem_max(agg, m) : agg + m);
   }
   float value = use_max ? agg : agg / (float)P;                        // summarize_raw_samples: mean (or max under optimism)
   if (particle_cost) {
@@ -135,10 +139,10 @@ __global__ void __launch_bounds__(256) k_icem_values(const float *rows, int row_
     float cagg = 0.f;
     for (int p = 0; p < P; ++p) {
       const float cp = particle_cost[(long long)c * P + p];
-      cagg = (p == 0) ? cp : (cost_use_max ? fmaxf(cagg, cp) : cagg + cp);
+      cagg = (p == 0) ? cp : (cost_use_max ? icem_max(cagg, cp) : cagg + cp);
     }
     const float cost = cost_use_max ? cagg : cagg / (float)P;
-    value = value - lambda_c * fmaxf(cost, 0.f);
+    value = value - lambda_c * icem_max(cost, 0.f);
   }
   values[c] = value;
 }
@@ -160,7 +164,7 @@ __global__ void __launch_bounds__(256) k_icem_values_wave(const float *rows, int
   float agg = 0.f;
   for (int p = 0; p < P; ++p) {
     const float mp = __shfl(m, p, 64);
-    agg = (p == 0) ? mp : (use_max ? fmaxf(agg, mp) : agg + mp);
+    agg = (p == 0) ? mp : (use_max ? icem_max(agg, mp) : agg + mp);
   }
   if (lane != 0) return;
   float value = use_max ? agg : agg / (float)P;                        // summarize_raw_samples: mean (or max under optimism)
@@ -168,12 +172,21 @@ __global__ void __launch_bounds__(256) k_icem_values_wave(const float *rows, int
     float cagg = 0.f;
     for (int p = 0; p < P; ++p) {
       const float cp = particle_cost[(long long)c * P + p];
-      cagg = (p == 0) ? cp : (cost_use_max ? fmaxf(cagg, cp) : cagg + cp);
+      cagg = (p == 0) ? cp : (cost_use_max ? icem_max(cagg, cp) : cagg + cp);
     }
     const float cost = cost_use_max ? cagg : cagg / (float)P;
-    value = value - lambda_c * fmaxf(cost, 0.f);
+    value = value - lambda_c * icem_max(cost, 0.f);
   }
   values[c] = value;
+}
+
+// Candidate (w, j) sorts before candidate (v, c): the total order of np.argsort(kind="stable") — NaN after every number (+inf
+// included), NaNs tied with each other, ties broken by candidate index.  A plain `w < v || (w == v && j < c)` gives every NaN rank 0:
+// the ranks stop being a permutation and the elite / best indices the update kernels read are never written.
+__device__ __forceinline__ bool icem_before(float w, int j, float v, int c) {
+  const bool wn = w != w, vn = v != v;
+  if (wn != vn) return vn;
+  return w < v || (!(v < w) && j < c);      // both numbers: w < v, or equal (-0 == +0); both NaN: neither is less
 }
 
 struct IcemUpdateArgs {
@@ -186,13 +199,14 @@ struct IcemUpdateArgs {
 
 __global__ void __launch_bounds__(1024) k_icem_update(IcemUpdateArgs A) {
   const int tid = threadIdx.x, NC = A.NC, HU = A.H * A.U;
+  __shared__ int s_best;
+  if (tid == 0) s_best = 0;      // in range whatever the ranking does (the barrier below orders it before the search)
   // stable ascending rank = position in np.argsort(values)
   for (int c = tid; c < NC; c += 1024) {
     const float v = A.values[c];
     int r = 0;
     for (int j = 0; j < NC; ++j) {
-      const float w = A.values[j];
-      r += (w < v || (w == v && j < c)) ? 1 : 0;
+      r += icem_before(A.values[j], j, v, c) ? 1 : 0;
     }
     A.rank[c] = r;
   }
@@ -200,7 +214,6 @@ __global__ void __launch_bounds__(1024) k_icem_update(IcemUpdateArgs A) {
   __syncthreads();
   const int first = NC - A.n_elites;      // elites = sorted positions [first, NC)
   // the best elite (rank NC-1) and the best-so-far sequence (:212-221)
-  __shared__ int s_best;
   for (int c = tid; c < NC; c += 1024)
     if (A.rank[c] == NC - 1) s_best = c;
   __syncthreads();
@@ -251,13 +264,15 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
   float *s_seq = reinterpret_cast<float *>(s_el + NE);      // [NE][HU]
   __shared__ int s_best;
   for (int c = tid; c < NC; c += 1024) s_val[c] = A.values[c];
+  // in range whatever the ranking does: every index read below comes from LDS that holds a candidate index before the ranking
+  if (tid == 0) s_best = 0;
+  for (int k = tid; k < NE; k += 1024) s_el[k] = k;
   __syncthreads();
   for (int c = tid; c < NC; c += 1024) {
     const float v = s_val[c];
     int r = 0;
     for (int j = 0; j < NC; ++j) {
-      const float w = s_val[j];
-      r += (w < v || (w == v && j < c)) ? 1 : 0;
+      r += icem_before(s_val[j], j, v, c) ? 1 : 0;
     }
     s_rank[c] = r;
     A.rank[c] = r;
@@ -269,7 +284,7 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
     if (s_rank[c] >= first) {
       int pos = 0;
       for (int j = 0; j < c; ++j) pos += (s_rank[j] >= first) ? 1 : 0;
-      s_el[pos] = c;              // the elites in ascending candidate order: the order k_icem_update adds them in
+      if (pos < NE) s_el[pos] = c;      // the elites in ascending candidate order: the order k_icem_update adds them in
     }
   }
   __syncthreads();
@@ -308,6 +323,15 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
   if (tid == 0 && take) A.best_value[0] = best_elite;
 }
 
+// Test hook (not part of include/mbpo_hip.h): 0 = always the global-memory k_icem_update, 1 = k_icem_update_lds wherever its LDS
+// need fits (today the same as the default), -1 = the default dispatch.  tests/test_gpu_icem.py runs every update case under 0 and 1.
+static int g_icem_update = -1;
+extern "C" int mbpo_debug_set_icem_update(int mode) {
+  MBPO_REQUIRE(mode >= -1 && mode <= 1, MBPO_ERR_ARG, "debug_set_icem_update: mode must be -1, 0 or 1");
+  g_icem_update = mode;
+  return MBPO_OK;
+}
+
 extern "C" int mbpo_icem_update_constrained(const float *rows, int32_t row_len, int32_t reward_col, int32_t n_candidates, int32_t n_particles,
                                             int32_t horizon, int32_t u_dim, const float *candidates, int32_t n_elites, int32_t n_prev,
                                             float alpha, int32_t use_max, const float *particle_cost, float lambda_constraint,
@@ -328,7 +352,7 @@ extern "C" int mbpo_icem_update_constrained(const float *rows, int32_t row_len, 
   IcemUpdateArgs A{values, candidates, n_candidates, horizon, u_dim, n_elites, n_prev, alpha, mean, std, best_value, best_sequence,
                    prev_elites, workspace};
   const size_t lds = (2ull * n_candidates + n_elites + (size_t)n_elites * horizon * u_dim) * sizeof(float);
-  if (lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds, dim3(1), dim3(1024), lds, st, A);
+  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds, dim3(1), dim3(1024), lds, st, A);
   else hipLaunchKernelGGL(k_icem_update, dim3(1), dim3(1024), 0, st, A);
   MBPO_CHECK_LAUNCH("icem_update");
   return MBPO_OK;

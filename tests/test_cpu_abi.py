@@ -1,6 +1,7 @@
 """The drop-in boundary without a GPU: libmbpo_hip.so loads, exports every entry point include/mbpo_hip.h declares, the ctypes
 mirror of the descriptor structs has the C layout, and size queries / argument validation (no launches) behave."""
 import ctypes as C
+import os
 import re
 import subprocess
 import sys
@@ -92,6 +93,41 @@ def test_size_queries_and_validation_without_a_device(lib):
     assert n_layered > (512 * 40 + 512) * 256 * 2 * 5              # stored z and h of five 256-wide layers for every row
     p.value_dims[6] = 2                                            # a value net ends in one output
     assert lib.mbpo_ppo_workspace_floats(C.byref(p)) < 0
+
+
+def test_test_hooks_without_a_device(lib):
+    """The kernel-selection hooks the GPU tests use are exported but not declared (not part of the API), reject unknown modes, and
+    mbpo_debug_set_bptt_zstore(0) removes exactly the z store from the BPTT workspace: 1024 floats per (trajectory tile, step,
+    member, hidden layer)."""
+    from mbpo import _hip
+    for name in ("mbpo_debug_set_icem_update", "mbpo_debug_set_bptt_zstore"):
+        assert hasattr(lib, name) and name not in _declared()
+        getattr(lib, name).argtypes = [C.c_int]
+        getattr(lib, name).restype = C.c_int
+    assert lib.mbpo_debug_set_icem_update(2) < 0 and b"mode" in lib.mbpo_last_error()
+    assert lib.mbpo_debug_set_bptt_zstore(1) < 0 and b"mode" in lib.mbpo_last_error()
+    X, U, H, n, E = 4, 1, 5, 48, 5
+    d = _hip.BpttDesc()
+    d.x_dim, d.u_dim, d.horizon, d.n = X, U, H, n
+    d.actor_layers = d.critic_layers = 4
+    for i, (a, c) in enumerate(zip([X, 64, 64, 64, 2 * U], [X, 64, 64, 64, 1])):
+        d.actor_dims[i], d.critic_dims[i] = a, c
+    d.actor_activation = d.critic_activation = _hip.ACT_IDS["swish"]
+    d.system_kind, d.reward_kind = _hip.SYS_ENSEMBLE, _hip.REWARD_QUADRATIC
+    m = d.dynamics
+    m.params, m.n_nets, m.n_layers, m.activation = 16, E, 4, _hip.ACT_IDS["swish"]      # (a size query never reads the parameters)
+    for i, v in enumerate([X + U, 64, 64, 64, 2 * X]):
+        m.dims[i] = v
+    m.net_stride = sum(m.dims[i] * m.dims[i + 1] + m.dims[i + 1] for i in range(4))
+    try:
+        with_store = lib.mbpo_bptt_workspace_floats(C.byref(d))
+        assert lib.mbpo_debug_set_bptt_zstore(0) == 0
+        recompute = lib.mbpo_bptt_workspace_floats(C.byref(d))
+    finally:
+        assert lib.mbpo_debug_set_bptt_zstore(-1) == 0
+    if os.environ.get("MBPO_BPTT_ZSTORE_MAX_MB") is None:      # (a cap in the environment may switch the store off already)
+        assert recompute > 0 and with_store - recompute == (n + 15) // 16 * H * E * 3 * 1024
+    assert lib.mbpo_bptt_workspace_floats(C.byref(d)) == with_store
 
 
 def test_product_path_refuses_cpu_tensors():

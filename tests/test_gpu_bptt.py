@@ -6,6 +6,7 @@ gradient atol 5e-6 + rtol 2e-3 against the fp32 oracle and rtol 1e-3 against fp6
 Jacobian products); losses 2e-5.
 """
 import math
+import os
 
 import numpy as np
 import pytest
@@ -74,12 +75,22 @@ def _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, n,
 ])
 def test_bptt_actor_grad_parity(dev, X, U, H, n, system, E):
     cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, tsys, extra = _setup(X, U, H, n, system, E, 0)
+    refs = _oracle(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, X, U, E)
+    op = _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, n)
+    _assert_matches_oracle(op, refs, X, U, H, n)
+
+
+def _oracle(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, X, U, E):
     g_ref, loss_ref, aux = obptt.actor_grads(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms[0], r_ms[1])
     d = lambda t: t.double()
     tsys64 = obptt.TorchPendulumSystem() if system == "pendulum" else obptt.TorchEnsembleSystem(
         d(extra["dp"]), extra["dd"], E, X, U, d(extra["tgt"]), d(extra["q"]), d(extra["r"]))
     g64, loss64, aux64 = obptt.actor_grads(cfg, tsys64, d(ap), d(cp), d(x0), d(noise), d(s_mean), d(s_std), d(r_ms[0]), d(r_ms[1]))
-    op = _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, n)
+    return g_ref, aux, g64, loss64, aux64
+
+
+def _assert_matches_oracle(op, refs, X, U, H, n):
+    g_ref, aux, g64, loss64, aux64 = refs
     rows = op.transitions.cpu().reshape(n, H, -1)
     torch.testing.assert_close(rows[..., :X], aux["observation"], atol=2e-4, rtol=2e-4)
     torch.testing.assert_close(rows[..., X:X + U], aux["action"], atol=2e-4, rtol=2e-4)
@@ -93,6 +104,46 @@ def test_bptt_actor_grad_parity(dev, X, U, H, n, system, E):
     g = op.grads.cpu()
     torch.testing.assert_close(g, g_ref, atol=5e-6, rtol=2e-3)
     torch.testing.assert_close(g.double(), g64, atol=5e-6, rtol=1e-3)
+
+
+def _set_zstore(mode: int) -> None:
+    import ctypes as C
+    from mbpo import _hip
+    lib = _hip.load()
+    lib.mbpo_debug_set_bptt_zstore.argtypes = [C.c_int]
+    lib.mbpo_debug_set_bptt_zstore.restype = C.c_int
+    assert lib.mbpo_debug_set_bptt_zstore(mode) == 0
+
+
+@pytest.mark.parametrize("X,U,H,n,E", [
+    (4, 1, 5, 48, 5),        # north-star shape: 2 member rounds of 4 + 1, three tiles
+    (4, 2, 6, 17, 3),        # one round of 3 members, ragged n
+    (17, 6, 32, 16, 10),     # BASELINE config 5 at H = 32: 10 members in several LDS rounds
+])
+def test_bptt_zstore_equals_recompute(dev, X, U, H, n, E):
+    """The backward sweep's two sources of the members' pre-activations: the z store (the forward sweep writes them to the workspace,
+    the E_DYE op reloads them into LDS by global_load_lds) and recompute (mbpo_debug_set_bptt_zstore(0): R_ENS_REFWD runs the members
+    again from the checkpointed x_t, a_t).  Each must match the oracle, and they must agree BIT FOR BIT: both fill the same LDS z
+    slots with the output of the same chain code on the same inputs, so the backward sweep sees the same bytes.  The mode is set
+    before the op sizes its workspace (the z store only ever enlarges it)."""
+    if os.environ.get("MBPO_BPTT_ZSTORE_MAX_MB") is not None:
+        pytest.skip("MBPO_BPTT_ZSTORE_MAX_MB caps the z store in this process: the store path may not run")
+    cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, tsys, extra = _setup(X, U, H, n, "ensemble", E, 0)
+    refs = _oracle(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms, "ensemble", extra, X, U, E)
+    res = {}
+    try:
+        for mode in (-1, 0):
+            _set_zstore(mode)
+            op = _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, "ensemble", extra, n)
+            _assert_matches_oracle(op, refs, X, U, H, n)
+            res[mode] = (op.workspace.numel(), op.grads.clone(), op.metrics.clone(), op.transitions.clone(), op.lambda_values.clone())
+    finally:
+        _set_zstore(-1)
+    # the store path really ran: its workspace holds 1024 floats per (tile, step, member, hidden layer) more than recompute's
+    tiles, hidden_layers = (n + 15) // 16, len(extra["dd"]) - 2
+    assert res[-1][0] - res[0][0] == tiles * H * E * hidden_layers * 1024
+    for a, b in zip(res[-1][1:], res[0][1:]):
+        assert torch.equal(a, b)
 
 
 def test_bptt_philox_noise_path(dev):

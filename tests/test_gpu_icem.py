@@ -50,43 +50,172 @@ def test_icem_sample_parity(dev, H, U, S, Kp, P, beta):
         assert abs(raw[inside].std() - 1.0) < 0.25
 
 
+def _set_icem_update(lib, mode: int) -> None:
+    import ctypes as C
+    lib.mbpo_debug_set_icem_update.argtypes = [C.c_int]
+    lib.mbpo_debug_set_icem_update.restype = C.c_int
+    assert lib.mbpo_debug_set_icem_update(mode) == 0
+
+
+def _rank_inverse(values):
+    """rank[c] = position of candidate c in np.argsort(values, kind='stable') (NaN last, ties by index)."""
+    inv = np.empty(len(values), np.int64)
+    inv[np.argsort(values, kind="stable")] = np.arange(len(values))
+    return inv
+
+
+# id, NC, H, U, n_elites, n_prev, P, rewards.  LDS need of k_icem_update_lds: 4 (2 NC + NE + NE H U) bytes.
+_UPDATE_CASES = [
+    ("ref", 157, 12, 2, 20, 6, 3, "coarse"),              # the original case: ~3 KB of LDS
+    ("nc1500", 1500, 10, 2, 50, 10, 2, "coarse"),         # more candidates than threads: the rank / elite loops run twice
+    ("hu1152", 64, 128, 9, 8, 3, 1, "coarse"),            # H U = 1152 > 1024 elements per thread loop, 37 KB: both kernels fit
+    ("lds69k", 300, 32, 4, 130, 20, 2, "coarse"),         # 69 KB > 60 KB: the default dispatch itself takes k_icem_update
+    ("all_elites", 40, 6, 3, 40, 0, 2, "coarse"),         # n_elites = NC, n_prev = 0 with prev_elites = NULL
+    ("prev_all", 100, 8, 2, 12, 12, 3, "coarse"),         # n_prev = n_elites
+    ("equal", 200, 5, 2, 16, 4, 2, "equal"),              # every value ties: elites = the highest indices
+    ("inf", 180, 6, 2, 25, 5, 2, "inf"),                  # +inf and -inf candidates
+    ("nan_few", 157, 12, 2, 20, 6, 3, "nan_few"),         # a few NaN candidates (inf - inf in one particle's rewards)
+    ("nan_fill", 1500, 10, 2, 50, 10, 2, "nan_fill"),     # more NaN candidates than elites: NaNs are the whole elite set
+]
+
+
 def test_icem_update_parity(dev):
+    """The original case (NC = 157, H U = 24, 20 elites), now under both update kernels: see _check_icem_update."""
+    _check_icem_update(dev, *_UPDATE_CASES[0])
+
+
+@pytest.mark.parametrize("name,NC,H,U,ne,nprev,P,kind", _UPDATE_CASES[1:], ids=[c[0] for c in _UPDATE_CASES[1:]])
+def test_icem_update_edge_cases(dev, name, NC, H, U, ne, nprev, P, kind):
+    _check_icem_update(dev, name, NC, H, U, ne, nprev, P, kind)
+
+
+def _check_icem_update(dev, name, NC, H, U, ne, nprev, P, kind):
+    """mbpo_icem_update (objective + rank + elite update) vs oracle/icem.update in fp64, under BOTH update kernels: the global-memory
+    k_icem_update (mode 0) and k_icem_update_lds (mode 1; where its LDS need is over 60 KB the default dispatch, which picks
+    k_icem_update too).  Ranks follow np.argsort(kind='stable'): NaN after +inf, ties by candidate index — every case asserts they
+    form a permutation.  NaN values come from rewards +inf and -inf within one particle, as from a diverged model; the candidates
+    themselves stay finite, so the elite mean / std stay finite even when NaN candidates are elites, and the best-so-far keeps its
+    previous value (`best_value <= NaN` is false).  The two kernels add the elites in the same order: their results are identical."""
     _hip, lib = _lib()
     rng = np.random.default_rng(0)
-    H, U, NC, P, X, ne, nprev, alpha = 12, 2, 157, 3, 4, 20, 6, 0.3
+    X, alpha = 4, 0.3
     D = 2 * X + U + 3
     rows = rng.standard_normal((H * NC * P, D)).astype(np.float32)
     rows[:, X + U] = np.round(rows[:, X + U], 1)           # coarse rewards: ties between candidates do occur
     cand = rng.standard_normal((NC, H, U)).astype(np.float32)
     mean, std = rng.standard_normal((H, U)).astype(np.float32), (rng.random((H, U)) + 0.2).astype(np.float32)
+    rew3 = rows[:, X + U].reshape(H, NC, P)                # (a view: edits below land in rows)
+    nan_rows = np.zeros(0, np.int64)
+    if kind == "equal":
+        rew3[...] = 0.25
+    elif kind == "inf":
+        pos, neg = rng.choice(NC, 20, replace=False).reshape(2, 10)
+        rew3[1, pos, P - 1] = np.inf                       # one particle suffices for the mean and the max
+        rew3[0, neg, :] = -np.inf                          # every particle: -inf under the max too
+    elif kind.startswith("nan"):
+        nan_rows = np.sort(rng.choice(NC, 5 if kind == "nan_few" else ne + 20, replace=False))
+        rew3[0, nan_rows, 0] = np.inf
+        rew3[H - 1, nan_rows, 0] = -np.inf                 # particle 0's mean reward: inf - inf = NaN
+    lds_fits = 4 * (2 * NC + ne + ne * H * U) <= 60 * 1024
+    assert lds_fits == (name != "lds69k")
+    modes = (0, 1) if lds_fits else (0, -1)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    drows, dcand = t(rows), t(cand)
+    try:
+        for use_max in (0, 1):
+            with np.errstate(invalid="ignore"):
+                per_p = rew3.mean(axis=0, dtype=np.float64)
+                values = per_p.max(axis=1) if use_max else per_p.mean(axis=1)
+            assert np.isnan(values).sum() == len(nan_rows)
+            for bv0 in (-np.inf, 10.0):
+                bs0 = rng.standard_normal((H, U)).astype(np.float32)
+                res = {}
+                for mode in modes:
+                    _set_icem_update(lib, mode)
+                    dmean, dstd, dbv, dbs = t(mean.copy()), t(std.copy()), torch.tensor([bv0], device=dev, dtype=torch.float32), t(bs0.copy())
+                    dprev = torch.zeros(nprev, H, U, device=dev)
+                    dvals, drank = torch.zeros(NC, device=dev), torch.zeros(NC, device=dev, dtype=torch.int32)
+                    _hip.check(lib.mbpo_icem_update(drows.data_ptr(), D, X + U, NC, P, H, U, dcand.data_ptr(), ne, nprev, alpha, use_max,
+                                                    dmean.data_ptr(), dstd.data_ptr(), dbv.data_ptr(), dbs.data_ptr(),
+                                                    dprev.data_ptr() if nprev else None, dvals.data_ptr(), drank.data_ptr(), None),
+                               "mbpo_icem_update")
+                    torch.cuda.synchronize()
+                    vals = dvals.cpu().numpy()
+                    np.testing.assert_allclose(vals, values, atol=1e-5, rtol=1e-5, equal_nan=True)
+                    # ranks from the device values: a permutation, the inverse of np.argsort(kind='stable')
+                    rank = drank.cpu().numpy()
+                    assert np.array_equal(np.sort(rank), np.arange(NC))
+                    assert np.array_equal(rank, _rank_inverse(vals))
+                    assert np.array_equal(np.argsort(rank), np.argsort(vals, kind="stable"))
+                    m2, s2, bv, bs, pe = oicem.update(vals.astype(np.float64), cand.astype(np.float64), mean.astype(np.float64),
+                                                      std.astype(np.float64), bv0, bs0.astype(np.float64), ne, nprev, alpha)
+                    np.testing.assert_allclose(dmean.cpu().numpy(), m2, atol=1e-5, rtol=1e-5, equal_nan=True)
+                    np.testing.assert_allclose(dstd.cpu().numpy(), s2, atol=1e-5, rtol=1e-5, equal_nan=True)
+                    if nprev:          # (the oracle's elites[-0:] is the whole elite set; the kernel writes no row)
+                        np.testing.assert_allclose(dprev.cpu().numpy(), pe, atol=0, rtol=0)
+                    np.testing.assert_allclose(dbs.cpu().numpy(), bs, atol=0, rtol=0)
+                    assert float(dbv) == np.float32(bv)
+                    if len(nan_rows):  # a NaN is the top elite: results in range, the best-so-far untouched
+                        assert np.isfinite(dmean.cpu().numpy()).all() and np.isfinite(dstd.cpu().numpy()).all()
+                        assert float(dbv) == np.float32(bv0)
+                        assert np.array_equal(dbs.cpu().numpy(), bs0)
+                        elites, nans = set(np.argsort(vals, kind="stable")[-ne:].tolist()), set(nan_rows.tolist())
+                        if len(nans) <= ne:
+                            assert nans <= elites
+                        else:
+                            assert elites <= nans
+                    res[mode] = (dvals, drank, dmean, dstd, dbv, dbs, dprev)
+                for a, b in zip(res[modes[0]], res[modes[1]]):
+                    torch.testing.assert_close(a, b, atol=0, rtol=0, equal_nan=True)
+    finally:
+        _set_icem_update(lib, -1)
+
+
+@pytest.mark.parametrize("P", [63, 64, 65, 130])
+def test_icem_values_particle_kernels(dev, P):
+    """The objective alone: P <= 64 runs k_icem_values_wave (one wave per candidate), P > 64 k_icem_values (one thread per
+    candidate).  values[c] = summarize_particles(mean_t reward) - lambda * relu(summarize_cost(cost)), against numpy in fp64, for
+    both summaries of the rewards and of the costs and without a cost.  Non-finite inputs propagate as in jnp.max / jax.nn.relu:
+    a NaN reward or cost in ONE particle makes the value NaN under the max too; +inf and -inf carry through."""
+    _hip, lib = _lib()
+    rng = np.random.default_rng(P)
+    X, U, H, NC, lam = 3, 1, 7, 37, 7.5
+    D = 2 * X + U + 3
+    N = NC * P
+    rows = rng.standard_normal((H * N, D)).astype(np.float32)
+    cost = rng.standard_normal(N).astype(np.float32)
+    rew3 = rows[:, X + U].reshape(H, NC, P)
+    rew3[2, 3, P - 1] = np.nan                 # the last particle (the last lane of the wave at P = 64)
+    rew3[4, 5, 0] = np.inf
+    rew3[0, 6, :] = -np.inf
+    cost.reshape(NC, P)[8, P // 2] = np.nan
+    cand = rng.standard_normal((NC, H, U)).astype(np.float32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    drows, dcand, dcost = t(rows), t(cand), t(cost)
+    per_p = rew3.mean(axis=0, dtype=np.float64)
+    c64 = cost.reshape(NC, P).astype(np.float64)
     for use_max in (0, 1):
-        rew = rows[:, X + U].reshape(H, NC, P)
-        per_p = rew.mean(axis=0, dtype=np.float64)
-        values = per_p.max(axis=1) if use_max else per_p.mean(axis=1)
-        for bv0 in (-np.inf, 10.0):
-            bs0 = rng.standard_normal((H, U)).astype(np.float32)
-            m2, s2, bv, bs, pe = oicem.update(values.astype(np.float32).astype(np.float64), cand.astype(np.float64), mean.astype(np.float64),
-                                              std.astype(np.float64), bv0, bs0.astype(np.float64), ne, nprev, alpha)
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            dmean, dstd, dbv, dbs, dprev = t(mean.copy()), t(std.copy()), torch.tensor([bv0], device=dev, dtype=torch.float32), t(bs0.copy()), \
-                torch.zeros(nprev, H, U, device=dev)
+        reward = per_p.max(axis=1) if use_max else per_p.mean(axis=1)
+        for cost_max in (None, 0, 1):
+            if cost_max is None:
+                want = reward
+            else:
+                c = c64.max(axis=1) if cost_max else c64.mean(axis=1)
+                with np.errstate(invalid="ignore"):
+                    want = reward - lam * np.maximum(c, 0.0)
             dvals, drank = torch.zeros(NC, device=dev), torch.zeros(NC, device=dev, dtype=torch.int32)
-            drows, dcand = t(rows), t(cand)
-            _hip.check(lib.mbpo_icem_update(drows.data_ptr(), D, X + U, NC, P, H, U, dcand.data_ptr(), ne, nprev, alpha, use_max, dmean.data_ptr(),
-                                            dstd.data_ptr(), dbv.data_ptr(), dbs.data_ptr(), dprev.data_ptr(), dvals.data_ptr(), drank.data_ptr(),
-                                            None), "mbpo_icem_update")
+            mean, std = torch.zeros(H, U, device=dev), torch.ones(H, U, device=dev)
+            bv, bs = torch.full((1,), -np.inf, device=dev), torch.zeros(H, U, device=dev)
+            _hip.check(lib.mbpo_icem_update_constrained(drows.data_ptr(), D, X + U, NC, P, H, U, dcand.data_ptr(), 4, 0, 0.1, use_max,
+                                                        dcost.data_ptr() if cost_max is not None else None, lam, cost_max or 0,
+                                                        mean.data_ptr(), std.data_ptr(), bv.data_ptr(), bs.data_ptr(), None,
+                                                        dvals.data_ptr(), drank.data_ptr(), None),
+                       "mbpo_icem_update_constrained")
             torch.cuda.synchronize()
-            np.testing.assert_allclose(dvals.cpu().numpy(), values, atol=1e-5, rtol=1e-5)
-            # ranks from the device values (ties broken by index, as np.argsort(kind='stable'))
-            order = np.argsort(dvals.cpu().numpy(), kind="stable")
-            assert np.array_equal(np.argsort(drank.cpu().numpy()), order)
-            m2, s2, bv, bs, pe = oicem.update(dvals.cpu().numpy().astype(np.float64), cand.astype(np.float64), mean.astype(np.float64),
-                                              std.astype(np.float64), bv0, bs0.astype(np.float64), ne, nprev, alpha)
-            np.testing.assert_allclose(dmean.cpu().numpy(), m2, atol=1e-5, rtol=1e-5)
-            np.testing.assert_allclose(dstd.cpu().numpy(), s2, atol=1e-5, rtol=1e-5)
-            np.testing.assert_allclose(dprev.cpu().numpy(), pe, atol=0, rtol=0)
-            np.testing.assert_allclose(dbs.cpu().numpy(), bs, atol=0, rtol=0)
-            assert float(dbv) == np.float32(bv)
+            got = dvals.cpu().numpy()
+            assert np.isnan(want[3]) and np.isposinf(want[5]) and np.isneginf(want[6]) and np.isnan(want[8]) == (cost_max is not None)
+            np.testing.assert_allclose(got, want, atol=1e-5, rtol=1e-5, equal_nan=True)
+            assert np.array_equal(np.sort(drank.cpu().numpy()), np.arange(NC))
 
 
 def test_icem_optimize_matches_oracle_loop_on_pendulum(dev):
