@@ -331,14 +331,23 @@ int mbpo_sac_finalize(const mbpo_sac_desc *d, void *stream);
  * of sgd_steps the step's randomness is used up and the device counter moves on). */
 int mbpo_sac_finalize_advance(const mbpo_sac_desc *d, uint64_t *rng_dev, uint64_t inc, void *stream);
 
-/* ---- P1-P3: PPO minibatch update (ppo/ppo.py:142-156, ppo/losses.py:56-126) -----------------------
- * replaces: PPO.minibatch_step = value_and_grad(PPOLoss.loss) + optax.adamw(lr, wd) over {policy, value} (ppo.py:128,139-140;
- *           no gradient clipping in this variant).  Inside the loss: policy logits and value baseline on [B,T] samples,
- *           bootstrap value, compute_gae (stop-gradient), advantage normalisation over the whole minibatch
- *           (losses.py:101-102), clipped surrogate, 0.5*MSE value loss, entropy bonus with a fresh NormalTanh sample.
+/* ---- P1-P3: PPO minibatch update (ppo/ppo.py:142-156, ppo/losses.py:56-126; ppo/ppo_brax_env.py + losses_new.py) ----------
+ * replaces: PPO.minibatch_step = value_and_grad(PPOLoss.loss) + the optimizer over {policy, value}, in either of the reference's
+ *           two variants:
+ *             ppo.py            optax.adamw(lr, wd), constant discount (ppo.py:128,139-140)          max_grad_norm <= 0, non_equidistant_time = 0
+ *             ppo_brax_env.py   optax.chain(clip_by_global_norm(max_grad_norm), adamw(lr, wd))      max_grad_norm > 0 (:137-141)
+ *                               and, with non_equidistant_time, a per-sample discount (losses_new.py:105-120,181-226)
+ *           A zero-filled tail (max_grad_norm = 0, non_equidistant_time = 0) is the ppo.py variant.
+ *           Inside the loss: policy logits and value baseline on [B,T] samples, bootstrap value, compute_gae (stop-gradient),
+ *           advantage normalisation over the whole minibatch (losses.py:101-102), clipped surrogate, 0.5*MSE value loss, entropy bonus
+ *           with a fresh NormalTanh sample.
  * Flat state: params [P+V] = [ policy | value ]; adam_m/adam_v [P+V]; step_count [1]; grads [P+V].
  *   mbpo_ppo_grads : grads, metrics[0..3] = total_loss, policy_loss, v_loss, entropy_loss (losses.py:121-126); bumps step_count
- *   mbpo_ppo_apply : grads *= grad_scale; AdamW.   All-reduce `grads` in between for N>1 ranks (ppo.py:149-154's pmean).
+ *   mbpo_ppo_apply : grads *= grad_scale; [clip_by_global_norm over the whole [P+V] gradient;] AdamW.  All-reduce `grads` in
+ *                    between for N>1 ranks (ppo.py:149-154's pmean): the clip norm is that of the reduced, scaled gradient.
+ * N1 discount: d = exp(-continuous_discounting * t), t = (tu - tl)/2 * a + (tu + tl)/2 floored to a multiple of env_dt, where
+ *       a = the last action component of the row and [tl, tu] = [min, max]_time_between_switches; d replaces `discounting` in the
+ *       deltas, the scan coefficient and the advantages.  non_equidistant_time with env_dt <= 0 -> MBPO_ERR_ARG.
  * data: one minibatch [batch_size, unroll_length, row_len] of PPO rows (row_len = 2x+2u+4), i.e. the rollout kernel's
  *       env_major output after the permutation gather.  entropy_noise [B,T,u] or NULL -> Philox(seed, offset [+ rng_dev], stream 9).
  * Network shapes (ppo.py:60-63 takes any tuple): as for SAC — one common hidden width in {64, 128} -> fused kernels, anything else
@@ -364,13 +373,17 @@ typedef struct mbpo_ppo_desc {
   float entropy_cost, discounting, reward_scaling, gae_lambda, clipping_epsilon;
   int32_t normalize_advantage;
   float lr, wd, grad_scale;
+  float max_grad_norm;            /* > 0: optax.clip_by_global_norm before AdamW (ppo_brax_env.py:137-141); <= 0: no clip (ppo.py) */
+  int32_t non_equidistant_time;   /* losses_new.py:105-112: per-sample discount from the last action component (see above) */
+  float continuous_discounting, min_time_between_switches, max_time_between_switches, env_dt;
 } mbpo_ppo_desc;
 
 int64_t mbpo_ppo_workspace_floats(const mbpo_ppo_desc *d);
 int mbpo_ppo_grads(const mbpo_ppo_desc *d, void *stream);
 int mbpo_ppo_apply(const mbpo_ppo_desc *d, void *stream);
 /* mbpo_ppo_grads + mbpo_ppo_apply with no seam for a collective between them (a single rank): the launch that sums the gradient
- * also applies AdamW to it — the same bits, one launch less per minibatch_step (ppo/ppo.py:142-156). */
+ * also applies AdamW to it — the same bits, one launch less per minibatch_step (ppo/ppo.py:142-156).  With max_grad_norm > 0 that
+ * launch leaves the norm's partial sums instead and one more launch clips and applies (the same bits as grads + apply). */
 int mbpo_ppo_step(const mbpo_ppo_desc *d, void *stream);
 
 /* ---- B1-B5: BPTT actor gradient (bptt_optimizer.py:327-378) -----------------------------------------

@@ -280,3 +280,19 @@ __device__ __forceinline__ void slab_group16_sum(float *slab, long long stride, 
     if (ok[k]) slab[(long long)t0 * stride + c0 + 256 * k] = acc[k];
 }
 
+// jnp.floor_divide for floats ([3P] jax.numpy: remainder-based, then rounded): x1 // x2
+__device__ __forceinline__ float floor_divide_f(float x1, float x2) {
+  const float mod = fmodf(x1, x2);
+  float div = (x1 - mod) / x2;
+  if (mod != 0.0f && ((x2 < 0.0f) != (mod < 0.0f))) div -= 1.0f;
+  return roundf(div);
+}
+
+// N1 per-sample discount of non_equidistant_time (sac/losses.py:90-96, ppo/losses_new.py:105-112): the switch time encoded in the
+// last action component `a`, mapped affinely from [-1, 1] to [tl, tu], floored to a multiple of env_dt; exp(-cd * t).  The
+// operation order of sac.hip's in-kernel form.
+__device__ __forceinline__ float n1_discount(float a, float cd, float tl, float tu, float dt) {
+  float t = (tu - tl) / 2.0f * a + (tu + tl) / 2.0f;
+  t = floor_divide_f(t, dt) * dt;
+  return expf(-cd * t);
+}

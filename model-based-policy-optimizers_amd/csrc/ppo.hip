@@ -8,7 +8,12 @@
 //                   a workgroup walks many 16-sample tiles and ACCUMULATES its weight gradients into its own slab
 //                   (8 waves: policy and value chains, 2 waves each; backward: dgrad + wgrad chains side by side).  [fp32 MFMA]
 //   k_ppo_reduce    grads = fixed-order sum of the slabs; loss metrics.                                    [HBM]
-//   k_ppo_apply     optax.adamw(lr, wd) (no clipping in this variant, ppo.py:128).                         [HBM]
+//   k_ppo_apply     optax.adamw(lr, wd) (ppo.py:128).                                                     [HBM]
+//   k_ppo_clip_apply  max_grad_norm > 0 (ppo_brax_env.py:137-141): every workgroup re-adds the per-64-element sum-of-squares
+//                   partials (k_ppo_reduce<true> / k_ppo_sumsq) in fixed order -> the global norm, clip_by_global_norm, AdamW.  [HBM]
+// non_equidistant_time (losses_new.py:105-120): every values/GAE launch takes a NEQ template flag; with it the per-sample discount
+// n1_discount(last action component) replaces `discounting` in compute_gae (an LDS array in the fused launches, a workspace array
+// for mbpo_gae_scan_discounts otherwise).  Without it the kernels are the constant-discount code, unchanged.
 // Algorithmic work per sample: 3*(2P + 2V) FLOP fwd+bwd (+2V for the value pre-pass), 4*(2x+2u+4) B of row data.
 #include "common.hpp"
 #include "chain_run.hpp"
@@ -38,10 +43,13 @@ struct PpoArgs {
   int vg_G;                  // k_ppo_values_gae: trajectories per workgroup; its workgroups leave {n, mean, M2} partials in mom_part
   float *step_count_rw;      // optax's count: bumped by block 0 of the FIRST launch of a minibatch_step (k_ppo_values), so that every
                              // later launch of the step — the reduce launch that also applies AdamW, or k_ppo_apply — reads the final value
+  // N1 (the NEQ instantiations only): per-sample discount n1_discount(row[X + U - 1], cd, tl, tu, dt); k_ppo_values writes it to disc [M]
+  float *disc;
+  float neq_cd, neq_tl, neq_tu, neq_dt;
 };
 
 // ------------------------------------------------------------------------------------------------ values pre-pass
-template <int H>
+template <int H, bool NEQ>
 __global__ void __launch_bounds__(256) k_ppo_values(PpoArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -77,6 +85,7 @@ __global__ void __launch_bounds__(256) k_ppo_values(PpoArgs A) {
         A.trunc[i] = tr;
         A.term[i] = (1.f - disc) * (1.f - tr);                 // termination = (1 - discount) * (1 - truncation)   (:89)
         A.rew[i] = row[X + U] * A.reward_scaling;              // rewards = data.reward * reward_scaling             (:87)
+        if (NEQ) A.disc[i] = n1_discount(row[X + U - 1], A.neq_cd, A.neq_tl, A.neq_tu, A.neq_dt);   // losses_new.py:105-112
       }
     }
     __syncthreads();
@@ -104,7 +113,8 @@ __device__ __forceinline__ float ppo_wave_sum(float v) {
 // compute_gae's recurrences backwards in the reference's own order (losses.py:150-184, as k_scan_time_major) and the first wave
 // leaves {n, mean, M2} of the workgroup's advantages (two passes over LDS: exact).  k_ppo_fwd_bwd combines the partials (Chan et
 // al.: M2 = sum M2_i + sum n_i (mean_i - mean)^2, fixed order).  Three launches and two kernel boundaries less per minibatch_step.
-template <int H, int NC>     // NC tiles at a time, each on its own chain of 4 waves (a trajectory of T = 40 is 3 tiles: one chain latency, not three)
+// NEQ: one more [G][T] LDS array, the per-sample discount (losses_new.py:105-120), read by the recurrence in place of `discounting`.
+template <int H, int NC, bool NEQ>     // NC tiles at a time, each on its own chain of 4 waves (a trajectory of T = 40 is 3 tiles: one chain latency, not three)
 __global__ void __launch_bounds__(256 * NC) k_ppo_values_gae(PpoArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -119,6 +129,7 @@ __global__ void __launch_bounds__(256 * NC) k_ppo_values_gae(PpoArgs A) {
   float *s_val = smem + NC * per_chain;      // [G][R] values (the last of each row: the bootstrap)
   float *s_tr = s_val + ((G * R + 3) & ~3);  // [G][T] truncation | termination | scaled reward | advantages
   float *s_te = s_tr + ((G * T + 3) & ~3), *s_rw = s_te + ((G * T + 3) & ~3), *s_adv = s_rw + ((G * T + 3) & ~3);
+  float *s_dc = s_adv + ((G * T + 3) & ~3);  // [G][T] per-sample discount (NEQ only)
   const long long b0 = (long long)blockIdx.x * G;
   const int g_here = (int)((A.B - b0 < G) ? A.B - b0 : G);
   const int rows = g_here * R;
@@ -153,6 +164,7 @@ __global__ void __launch_bounds__(256 * NC) k_ppo_values_gae(PpoArgs A) {
             s_tr[g * T + t] = tr;
             s_te[g * T + t] = (1.f - disc) * (1.f - tr);             // termination = (1 - discount) * (1 - truncation)   (:89)
             s_rw[g * T + t] = row[X + U] * A.reward_scaling;          // rewards = data.reward * reward_scaling             (:87)
+            if (NEQ) s_dc[g * T + t] = n1_discount(row[X + U - 1], A.neq_cd, A.neq_tl, A.neq_tu, A.neq_dt);   // losses_new.py:105-112
           }
         }
       }
@@ -174,7 +186,7 @@ __global__ void __launch_bounds__(256 * NC) k_ppo_values_gae(PpoArgs A) {
     for (int t = T - 1; t >= 0; --t) {
       const float tr = s_tr[g * T + t], te = s_te[g * T + t], r = s_rw[g * T + t], v = s_val[g * R + t];
       const float m = 1.f - tr;
-      const float g1 = A.discounting * (1.f - te);
+      const float g1 = (NEQ ? s_dc[g * T + t] : A.discounting) * (1.f - te);     // losses_new.py:182,193,221
       const float delta = (r + g1 * v_next - v) * m;        // :157-158
       acc = delta + g1 * m * A.gae_lambda * acc;            // :166
       const float vs = acc + v;                             // :176
@@ -516,32 +528,48 @@ struct PpoReduceArgs {
   // fused optimizer step (mbpo_ppo_step: no all-reduce sits between the gradient and AdamW): params != nullptr
   float *params, *adam_m, *adam_v;
   float lr, wd, grad_scale;
+  float *ss_part;            // SSQ: [gridDim.x] sum of (grad_scale * grads)^2 over this workgroup's 64 elements (clip_by_global_norm)
 };
+
+// optax.adamw on one element (constants as optax forms them: f32(0.1), f32(0.001) — see sac.hip); `count` is this step's count
+__device__ __forceinline__ void ppo_adamw(float *params, float *adam_m, float *adam_v, int i, float g, float count, float lr, float wd) {
+  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+  const float mu = b1 * adam_m[i] + 0.1f * g;
+  const float nu = b2 * adam_v[i] + 0.001f * (g * g);
+  adam_m[i] = mu;
+  adam_v[i] = nu;
+  const float mu_hat = mu / (1.f - powf(b1, count));
+  const float nu_hat = nu / (1.f - powf(b2, count));
+  const float p = params[i];
+  const float upd = mu_hat / (sqrtf(nu_hat) + eps) + wd * p;
+  params[i] = p + (-lr) * upd;
+}
+
+// one wave: the sum of squares of the scaled gradient over 64 consecutive elements, a fixed shuffle tree (k_ppo_reduce<true> on the
+// sums it has just formed, k_ppo_sumsq on `grads` after an all-reduce: the same values give the same bits)
+__device__ __forceinline__ float ppo_sumsq64(float g) {
+  const float q = g * g;
+  return ppo_wave_sum(q);
+}
 
 // stage 1 of the two-stage slab sum (many slabs): groups of 16 slabs, 4-KB contiguous runs (common.hpp slab_group16_sum)
 __global__ void __launch_bounds__(256) k_ppo_reduce_groups(float *slabs, int NPV, int n_slabs) { slab_group16_sum(slabs, NPV, n_slabs, NPV); }
 
+// SSQ (mbpo_ppo_step with max_grad_norm > 0): no AdamW here — the norm needs every workgroup's part first — but wave 0 leaves the
+// sum of squares of its 64 scaled sums in ss_part[blockIdx.x] for k_ppo_clip_apply.
+template <bool SSQ>
 __global__ void __launch_bounds__(256) k_ppo_reduce(PpoReduceArgs A) {
   // (A.slab_step = 16 after k_ppo_reduce_groups: the group sums sit in slabs 0, 16, 32, ...)
   const int i = blockIdx.x * 64 + (threadIdx.x & 63);
   const float gsum = slab_sum_wg64(A.slabs, (long long)A.NPV * A.slab_step, (A.n_slabs + A.slab_step - 1) / A.slab_step, i, i < A.NPV);
   if (threadIdx.x < 64 && i < A.NPV) {
     A.grads[i] = gsum;
-    if (A.params) {
-      // k_ppo_apply's arithmetic on the element this thread has just summed: one launch less per minibatch_step, the same bits
-      const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-      const float count = A.step_count[0];
-      const float g = gsum * A.grad_scale;
-      const float mu = b1 * A.adam_m[i] + 0.1f * g;
-      const float nu = b2 * A.adam_v[i] + 0.001f * (g * g);
-      A.adam_m[i] = mu;
-      A.adam_v[i] = nu;
-      const float mu_hat = mu / (1.f - powf(b1, count));
-      const float nu_hat = nu / (1.f - powf(b2, count));
-      const float p = A.params[i];
-      const float upd = mu_hat / (sqrtf(nu_hat) + eps) + A.wd * p;
-      A.params[i] = p + (-A.lr) * upd;
-    }
+    // k_ppo_apply's arithmetic on the element this thread has just summed: one launch less per minibatch_step, the same bits
+    if (!SSQ && A.params) ppo_adamw(A.params, A.adam_m, A.adam_v, i, gsum * A.grad_scale, A.step_count[0], A.lr, A.wd);
+  }
+  if (SSQ && threadIdx.x < 64) {
+    const float q = ppo_sumsq64(i < A.NPV ? gsum * A.grad_scale : 0.f);
+    if (threadIdx.x == 0) A.ss_part[blockIdx.x] = q;
   }
   if (blockIdx.x == 0) {
     // The loss partials (three per slab) are summed by the whole workgroup: thread t takes slabs t, t + 256, ..., then a fixed tree
@@ -596,19 +624,44 @@ struct PpoApplyArgs {
 __global__ void __launch_bounds__(256) k_ppo_apply(PpoApplyArgs A) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= A.NPV) return;
-  // [3P optax.adamw] (constants as optax forms them: f32(0.1), f32(0.001) — see sac.hip)
-  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+  // [3P optax.adamw]
+  ppo_adamw(A.params, A.adam_m, A.adam_v, i, A.grads[i] * A.grad_scale, A.step_count[0], A.lr, A.wd);
+}
+
+// mbpo_ppo_apply with max_grad_norm > 0, after an all-reduce changed `grads`: the partials k_ppo_reduce<true> would have formed
+__global__ void __launch_bounds__(64) k_ppo_sumsq(const float *grads, int NPV, float grad_scale, float *ss_part) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const float q = ppo_sumsq64(i < NPV ? grads[i] * grad_scale : 0.f);
+  if (threadIdx.x == 0) ss_part[blockIdx.x] = q;
+}
+
+struct PpoClipArgs {
+  float *params, *adam_m, *adam_v;
+  const float *grads, *step_count, *ss_part;
+  int NPV, n_parts;
+  float lr, wd, grad_scale, max_norm;
+};
+
+// [3P optax.chain(clip_by_global_norm(max_norm), adamw)] (ppo_brax_env.py:137-141).  Every workgroup forms the global norm from the
+// n_parts partials itself — thread t adds parts t, t + 256, ... in order, a fixed shuffle tree per wave, the four waves in order —
+// so it is the same float in every workgroup and on every run; then g <- g if norm < max_norm else (g / norm) * max_norm (optax's
+// form, as sac.hip) and AdamW on the workgroup's elements (grid-stride).
+__global__ void __launch_bounds__(256) k_ppo_clip_apply(PpoClipArgs A) {
+  __shared__ float s_w[4];
+  const int tid = threadIdx.x;
+  float a = 0.f;
+  for (int p = tid; p < A.n_parts; p += 256) a += A.ss_part[p];
+  a = ppo_wave_sum(a);
+  if ((tid & 63) == 0) s_w[tid >> 6] = a;
+  __syncthreads();
+  const float norm = sqrtf(((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]);
+  const bool clip = !(norm < A.max_norm);
   const float count = A.step_count[0];
-  const float g = A.grads[i] * A.grad_scale;
-  const float mu = b1 * A.adam_m[i] + 0.1f * g;
-  const float nu = b2 * A.adam_v[i] + 0.001f * (g * g);
-  A.adam_m[i] = mu;
-  A.adam_v[i] = nu;
-  const float mu_hat = mu / (1.f - powf(b1, count));
-  const float nu_hat = nu / (1.f - powf(b2, count));
-  const float p = A.params[i];
-  const float upd = mu_hat / (sqrtf(nu_hat) + eps) + A.wd * p;
-  A.params[i] = p + (-A.lr) * upd;
+  for (int i = blockIdx.x * 256 + tid; i < A.NPV; i += gridDim.x * 256) {
+    float g = A.grads[i] * A.grad_scale;
+    if (clip) g = (g / norm) * A.max_norm;
+    ppo_adamw(A.params, A.adam_m, A.adam_v, i, g, count, A.lr, A.wd);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -631,6 +684,11 @@ struct PpoPlan {
   bool layered;
   // the benchmark networks (64 x 3, swish, u = 1): k_ppo_lean (ppo_lean.hip) — one workgroup and ONE slab per CU
   bool lean;
+  // ppo_brax_env.py's options: neq -> per-sample discount (off_disc: [M], the separate-scan and layered paths); clip -> n_ss sum-of-
+  // squares partials at off_sspart (one per 64 gradient elements, k_ppo_reduce<true>'s grid).  Neither takes workspace when off.
+  bool neq, clip;
+  int n_ss;
+  long long off_disc, off_sspart;
 };
 
 // Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_ppo_fwd_bwd, 1 = k_ppo_lean where it applies,
@@ -674,6 +732,9 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d->policy_dims[0] == d->x_dim && d->policy_dims[d->policy_layers] == 2 * d->u_dim, MBPO_ERR_ARG,
                "ppo: policy must map [x_dim] -> [2*u_dim]");
   MBPO_REQUIRE(d->value_dims[0] == d->x_dim && d->value_dims[d->value_layers] == 1, MBPO_ERR_ARG, "ppo: value net must map [x_dim] -> [1]");
+  MBPO_REQUIRE(!d->non_equidistant_time || d->env_dt > 0.f, MBPO_ERR_ARG, "ppo: non_equidistant_time needs env_dt > 0");
+  pl->neq = d->non_equidistant_time != 0;
+  pl->clip = d->max_grad_norm > 0.f;
   const int Hp = ppo_same_hidden(d->policy_dims, d->policy_layers), Hv = ppo_same_hidden(d->value_dims, d->value_layers);
   static const int layered_env = getenv("MBPO_PPO_LAYERED") ? atoi(getenv("MBPO_PPO_LAYERED")) : 0;    // 1: force the layered path (tests)
   pl->layered = layered_env != 0 || !(Hp == Hv && (Hp == 64 || Hp == 128));
@@ -749,12 +810,18 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
     long long G = (d->batch_size + cap_wg - 1) / cap_wg;
     if (G < 1) G = 1;
     const long long R = (long long)d->unroll_length + 1;
-    pl->vg_G = (!pl->layered && vg_env != 0 && G * R <= 1024) ? (int)G : 0;
+    // the [G][R] / [G][T] LDS arrays: values, truncation, termination, reward, advantages (+ the per-sample discount with neq), each
+    // at most 1024 floats' worth of the constant-discount launch's five
+    const int n_arr = pl->neq ? 6 : 5;
+    pl->vg_G = (!pl->layered && vg_env != 0 && n_arr * G * R <= 5 * 1024) ? (int)G : 0;
     pl->n_vg = pl->vg_G ? (int)((d->batch_size + pl->vg_G - 1) / pl->vg_G) : 0;
     const long long GT = (long long)pl->vg_G * d->unroll_length;
-    pl->lds_vg = pl->lds_values + sizeof(float) * (size_t)(((pl->vg_G * R + 3) & ~3LL) + 4 * ((GT + 3) & ~3LL));
+    pl->lds_vg = pl->lds_values + sizeof(float) * (size_t)(((pl->vg_G * R + 3) & ~3LL) + (n_arr - 1) * ((GT + 3) & ~3LL));
     pl->off_mompart = take(4LL * (pl->n_vg > 0 ? pl->n_vg : 1));
   }
+  pl->off_disc = take(pl->neq ? pl->M : 0);
+  pl->n_ss = (pl->NPV + 63) / 64;
+  pl->off_sspart = take(pl->clip ? pl->n_ss : 0);
   pl->off_layered = o;
   if (pl->layered) o += ppo_layered_floats(d, pl->pi, pl->v);
   pl->total = o;
@@ -769,6 +836,16 @@ extern "C" int64_t mbpo_ppo_workspace_floats(const mbpo_ppo_desc *d) {
   int rc = ppo_plan(d, &pl, false);
   if (rc != MBPO_OK) return rc;
   return pl.total;
+}
+
+static void ppo_clip_apply_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, hipStream_t st) {
+  PpoClipArgs C;
+  C.params = d->params; C.adam_m = d->adam_m; C.adam_v = d->adam_v; C.grads = d->grads; C.step_count = d->step_count;
+  C.ss_part = d->workspace + pl.off_sspart; C.NPV = pl.NPV; C.n_parts = pl.n_ss;
+  C.lr = d->lr; C.wd = d->wd; C.grad_scale = d->grad_scale; C.max_norm = d->max_grad_norm;
+  // a few elements per thread: every workgroup re-adds all n_ss partials, so the grid is kept to at most 4 per CU
+  const int want = (pl.NPV + 255) / 256, cap = 4 * ppo_num_cus();
+  hipLaunchKernelGGL(k_ppo_clip_apply, dim3(want < cap ? want : cap), dim3(256), 0, st, C);
 }
 
 static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply) {
@@ -794,13 +871,16 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
   A.rew = ws + pl.off_rew; A.vs = ws + pl.off_vs; A.adv = ws + pl.off_adv; A.mom = ws + pl.off_mom;
   A.slabs = ws + pl.off_slabs; A.extras = ws + pl.off_extras; A.n_slabs = pl.n_slabs;
   A.ld_x = pl.ld_x; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
+  A.disc = pl.neq ? ws + pl.off_disc : nullptr;
+  A.neq_cd = d->continuous_discounting; A.neq_tl = d->min_time_between_switches; A.neq_tu = d->max_time_between_switches;
+  A.neq_dt = d->env_dt;
   hipStream_t st = (hipStream_t)stream;
   // 1. values pre-pass
   long long vt = (pl.M + d->batch_size + 15) / 16;
   int vgrid = (int)(vt < 4LL * ppo_num_cus() ? vt : 4LL * ppo_num_cus());
   if (pl.layered) {
     float *values = nullptr;
-    rc = ppo_layered_values(d, pl.pi, pl.v, ws + pl.off_layered, A.trunc, A.term, A.rew, &values, st);
+    rc = ppo_layered_values(d, pl.pi, pl.v, ws + pl.off_layered, A.trunc, A.term, A.rew, A.disc, &values, st);
     if (rc != MBPO_OK) return rc;
     A.baseline = values;
     A.boot = values + pl.M;
@@ -811,8 +891,9 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
     V.B = d->batch_size; V.T = d->unroll_length; V.D = A.D; V.G = pl.vg_G; V.n_hid = d->value_layers - 2;
     V.reward_scaling = d->reward_scaling; V.discounting = d->discounting; V.gae_lambda = d->gae_lambda;
     V.vs = A.vs; V.adv = A.adv; V.mom_part = A.mom_part; V.step_count_rw = A.step_count_rw;
+    V.neq = pl.neq ? 1 : 0; V.neq_cd = A.neq_cd; V.neq_tl = A.neq_tl; V.neq_tu = A.neq_tu; V.neq_dt = A.neq_dt;
     const long long GR = (long long)pl.vg_G * (d->unroll_length + 1), GT = (long long)pl.vg_G * d->unroll_length;
-    rc = ppo_vg_lean_launch(V, d->x_dim, pl.n_vg, (size_t)(((GR + 3) & ~3LL) + 4 * ((GT + 3) & ~3LL)), stream);
+    rc = ppo_vg_lean_launch(V, d->x_dim, pl.n_vg, (size_t)(((GR + 3) & ~3LL) + (pl.neq ? 5 : 4) * ((GT + 3) & ~3LL)), stream);
     if (rc != MBPO_OK) return rc;
     if (d->normalize_advantage)
       hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.n_vg, (float)pl.M, A.mom);
@@ -821,11 +902,15 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
     const int tiles_wg = (int)(((long long)pl.vg_G * (d->unroll_length + 1) + 15) / 16);
     const int NCv = tiles_wg >= 4 ? 4 : tiles_wg;
     const size_t lds = pl.lds_vg + (size_t)(NCv - 1) * pl.lds_values;
+#define LVG_(H_, N_, Q_)                                                                             \
+  {                                                                                                  \
+    rc = mbpo_ensure_lds<k_ppo_values_gae<H_, N_, Q_>>(lds, "ppo_grads");                            \
+    if (rc != MBPO_OK) return rc;                                                                    \
+    hipLaunchKernelGGL((k_ppo_values_gae<H_, N_, Q_>), dim3(pl.n_vg), dim3(256 * N_), lds, st, A);    \
+  }
 #define LVG(H_, N_)                                                                                  \
   {                                                                                                  \
-    rc = mbpo_ensure_lds<k_ppo_values_gae<H_, N_>>(lds, "ppo_grads");                                \
-    if (rc != MBPO_OK) return rc;                                                                    \
-    hipLaunchKernelGGL((k_ppo_values_gae<H_, N_>), dim3(pl.n_vg), dim3(256 * N_), lds, st, A);        \
+    if (pl.neq) LVG_(H_, N_, true) else LVG_(H_, N_, false)                                          \
   }
     if (pl.H == 64) {
       if (NCv == 1) LVG(64, 1) else if (NCv == 2) LVG(64, 2) else if (NCv == 3) LVG(64, 3) else LVG(64, 4)
@@ -833,21 +918,31 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
       if (NCv == 1) LVG(128, 1) else if (NCv == 2) LVG(128, 2) else if (NCv == 3) LVG(128, 3) else LVG(128, 4)
     }
 #undef LVG
+#undef LVG_
     if (d->normalize_advantage)
       hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.n_vg, (float)pl.M, A.mom);
-  } else if (pl.H == 64) {
-    rc = mbpo_ensure_lds<k_ppo_values<64>>(pl.lds_values, "ppo_grads");
-    if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL(k_ppo_values<64>, dim3(vgrid), dim3(256), pl.lds_values, st, A);
   } else {
-    rc = mbpo_ensure_lds<k_ppo_values<128>>(pl.lds_values, "ppo_grads");
-    if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL(k_ppo_values<128>, dim3(vgrid), dim3(256), pl.lds_values, st, A);
+#define LV(H_, Q_)                                                                                   \
+  {                                                                                                  \
+    rc = mbpo_ensure_lds<k_ppo_values<H_, Q_>>(pl.lds_values, "ppo_grads");                          \
+    if (rc != MBPO_OK) return rc;                                                                    \
+    hipLaunchKernelGGL((k_ppo_values<H_, Q_>), dim3(vgrid), dim3(256), pl.lds_values, st, A);        \
   }
-  // 2. GAE on [B,T] (batch-major: the data's native layout, no transpose)   losses.py:94-99,128-184
+    if (pl.H == 64) {
+      if (pl.neq) LV(64, true) else LV(64, false)
+    } else {
+      if (pl.neq) LV(128, true) else LV(128, false)
+    }
+#undef LV
+  }
+  // 2. GAE on [B,T] (batch-major: the data's native layout, no transpose)   losses.py:94-99,128-184 (losses_new.py:181-226 with neq)
   if (!pl.vg_G) {
-    rc = mbpo_gae_scan(A.trunc, A.term, A.rew, A.baseline, A.boot, A.vs, A.adv, d->batch_size, d->unroll_length, d->discounting,
-                       d->gae_lambda, 0, stream);
+    if (pl.neq)
+      rc = mbpo_gae_scan_discounts(A.trunc, A.term, A.rew, A.baseline, A.boot, A.disc, A.vs, A.adv, d->batch_size, d->unroll_length,
+                                   d->gae_lambda, 0, stream);
+    else
+      rc = mbpo_gae_scan(A.trunc, A.term, A.rew, A.baseline, A.boot, A.vs, A.adv, d->batch_size, d->unroll_length, d->discounting,
+                         d->gae_lambda, 0, stream);
     if (rc != MBPO_OK) return rc;
   }
   // 3. advantage moments over the whole minibatch
@@ -902,6 +997,7 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
   R.grads = d->grads; R.metrics = d->metrics; R.metrics_accum = d->metrics_accum; R.step_count = d->step_count;
   R.params = fuse_apply ? d->params : nullptr; R.adam_m = d->adam_m; R.adam_v = d->adam_v;
   R.lr = d->lr; R.wd = d->wd; R.grad_scale = d->grad_scale;
+  R.ss_part = ws + pl.off_sspart;
   // The one-stage sum reads 256-byte pieces 68 KB apart: 22.7 us for the 35 MB of 512 slabs (C3, T = 40), unchanged by 4x the loads
   // in flight or by 1-KB pieces.  With many slabs: first groups of 16 over 4-KB contiguous runs, in place, then the 32 group sums.
   R.slab_step = 1;
@@ -910,7 +1006,14 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
                        pl.n_slabs);
     R.slab_step = 16;
   }
-  hipLaunchKernelGGL(k_ppo_reduce, dim3((pl.NPV + 63) / 64), dim3(256), 0, st, R);
+  if (fuse_apply && pl.clip) {
+    // clip_by_global_norm needs every workgroup's part of the norm before any element may move: the reduce launch leaves the
+    // partials, one more launch clips and applies (the same partials and arithmetic as mbpo_ppo_apply: the same bits)
+    hipLaunchKernelGGL(k_ppo_reduce<true>, dim3(pl.n_ss), dim3(256), 0, st, R);
+    ppo_clip_apply_launch(d, pl, st);
+  } else {
+    hipLaunchKernelGGL(k_ppo_reduce<false>, dim3((pl.NPV + 63) / 64), dim3(256), 0, st, R);
+  }
   MBPO_CHECK_LAUNCH("ppo_grads");
   return MBPO_OK;
 }
@@ -925,6 +1028,14 @@ extern "C" int mbpo_ppo_apply(const mbpo_ppo_desc *d, void *stream) {
   PpoPlan pl;
   int rc = ppo_plan(d, &pl, true);
   if (rc != MBPO_OK) return rc;
+  if (pl.clip) {
+    // the norm of the (all-reduced) scaled gradient as it stands in `grads` now, then the clipped step
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(pl.n_ss), dim3(64), 0, (hipStream_t)stream, (const float *)d->grads, pl.NPV, d->grad_scale,
+                       d->workspace + pl.off_sspart);
+    ppo_clip_apply_launch(d, pl, (hipStream_t)stream);
+    MBPO_CHECK_LAUNCH("ppo_apply");
+    return MBPO_OK;
+  }
   PpoApplyArgs A;
   A.params = d->params; A.adam_m = d->adam_m; A.adam_v = d->adam_v; A.grads = d->grads; A.step_count = d->step_count;
   A.NPV = pl.NPV; A.lr = d->lr; A.wd = d->wd; A.grad_scale = d->grad_scale;

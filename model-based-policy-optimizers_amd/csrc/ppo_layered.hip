@@ -21,7 +21,10 @@ struct PrepArgs {
   int B, T, D, X, U;
   float reward_scaling;
   float *x_all, *trunc, *term, *rew, *step_count;
+  float *disc;                                   // NEQ: per-sample discount [M]
+  float neq_cd, neq_tl, neq_tu, neq_dt;
 };
+template <bool NEQ>
 __global__ void __launch_bounds__(256) k_ppol_prep(PrepArgs A) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long M = (long long)A.B * A.T, rows = M + A.B;
@@ -40,6 +43,7 @@ __global__ void __launch_bounds__(256) k_ppol_prep(PrepArgs A) {
     A.trunc[i] = tr;
     A.term[i] = (1.f - disc) * (1.f - tr);       // :89
     A.rew[i] = row[X + U] * A.reward_scaling;    // :87
+    if (NEQ) A.disc[i] = n1_discount(row[X + U - 1], A.neq_cd, A.neq_tl, A.neq_tu, A.neq_dt);   // losses_new.py:105-112
   }
 }
 
@@ -157,14 +161,16 @@ long long ppo_layered_floats(const mbpo_ppo_desc *d, const MlpDev &pi, const Mlp
 }
 
 int ppo_layered_values(const mbpo_ppo_desc *d, const MlpDev &pi, const MlpDev &v, float *ws, float *trunc, float *term, float *rew,
-                       float **values_out, hipStream_t st) {
+                       float *disc, float **values_out, hipStream_t st) {
   const LayeredNet npi = layered_net(pi, d->params, 0, 1), nv = layered_net(v, d->params + pi.n_params, 0, 1);
   Bufs b;
   carve_all(ws, d, npi, nv, &b);
   const long long M = (long long)d->batch_size * d->unroll_length, R = M + d->batch_size;
   PrepArgs A = {d->data, d->norm_mean, d->norm_std, d->batch_size, d->unroll_length, d->row_len, d->x_dim, d->u_dim, d->reward_scaling,
-                b.x_all, trunc, term, rew, d->step_count};
-  hipLaunchKernelGGL(k_ppol_prep, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, A);
+                b.x_all, trunc, term, rew, d->step_count, disc, d->continuous_discounting, d->min_time_between_switches,
+                d->max_time_between_switches, d->env_dt};
+  if (d->non_equidistant_time) hipLaunchKernelGGL(k_ppol_prep<true>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, A);
+  else hipLaunchKernelGGL(k_ppol_prep<false>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, A);
   // the value net on all R rows and — it depends on nothing the GAE / moments launches produce — the policy on the M loss rows, level by
   // level in one launch each (ppo_layered_fwd_bwd of the same step finds outp / Zp / Hp in the workspace)
   const LayeredFwd f[2] = {{nv, b.x_all, 0, (int)R, b.Zv, b.Hv, b.values}, {npi, b.x_all, 0, (int)M, b.Zp, b.Hp, b.outp}};

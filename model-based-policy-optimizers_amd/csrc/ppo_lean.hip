@@ -397,10 +397,11 @@ __global__ void __launch_bounds__(512) k_ppo_lean(const PpoLeanArgs A) {
 namespace {
 constexpr int VG_X = 0;                 // [2 chains][16][8] input tiles
 constexpr int VG_TILES = 256;           // [2 chains][2] hidden tiles
-constexpr int VG_ARR = VG_TILES + 4 * LT;     // s_val [G R] | s_tr | s_te | s_rw | s_adv [G T] each (rounded up to 4)
+constexpr int VG_ARR = VG_TILES + 4 * LT;     // s_val [G R] | s_tr | s_te | s_rw | s_adv [G T] each (rounded up to 4) [| s_dc [G T]]
 }  // namespace
 
-template <int X>
+// NEQ: non_equidistant_time — one more [G][T] array, the per-sample discount, read by the recurrence in place of `discounting`
+template <int X, bool NEQ>
 __global__ void __launch_bounds__(512) k_ppo_vg_lean(const PpoVgLeanArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int U = 1;
@@ -413,6 +414,7 @@ __global__ void __launch_bounds__(512) k_ppo_vg_lean(const PpoVgLeanArgs A) {
   float *s_tr = s_val + ((G * R + 3) & ~3);
   const int GT4 = (G * T + 3) & ~3;
   float *s_te = s_tr + GT4, *s_rw = s_te + GT4, *s_adv = s_rw + GT4;
+  float *s_dc = s_adv + GT4;                 // (NEQ only)
   const long long b0 = (long long)blockIdx.x * G;
   const int g_here = (int)((A.B - b0 < G) ? A.B - b0 : G);
   const int rows = g_here * R;
@@ -478,6 +480,7 @@ __global__ void __launch_bounds__(512) k_ppo_vg_lean(const PpoVgLeanArgs A) {
             s_tr[g * T + t] = tr;
             s_te[g * T + t] = (1.f - disc) * (1.f - tr);             // termination = (1 - discount) * (1 - truncation)   (:89)
             s_rw[g * T + t] = row[X + U] * A.reward_scaling;          // rewards = data.reward * reward_scaling             (:87)
+            if (NEQ) s_dc[g * T + t] = n1_discount(row[X + U - 1], A.neq_cd, A.neq_tl, A.neq_tu, A.neq_dt);   // losses_new.py:105-112
           }
         }
       }
@@ -524,7 +527,7 @@ __global__ void __launch_bounds__(512) k_ppo_vg_lean(const PpoVgLeanArgs A) {
     for (int t = T - 1; t >= 0; --t) {
       const float tr = s_tr[g * T + t], te = s_te[g * T + t], r = s_rw[g * T + t], v = s_val[g * R + t];
       const float m = 1.f - tr;
-      const float g1 = A.discounting * (1.f - te);
+      const float g1 = (NEQ ? s_dc[g * T + t] : A.discounting) * (1.f - te);     // losses_new.py:182,193,221
       const float delta = (r + g1 * v_next - v) * m;        // :157-158
       acc = delta + g1 * m * A.gae_lambda * acc;            // :166
       const float vs = acc + v;                             // :176
@@ -564,15 +567,17 @@ int ppo_vg_lean_launch(const PpoVgLeanArgs &A, int x_dim, int n_wgs, size_t arr_
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)(VG_ARR + arr_floats) * sizeof(float);
   int rc;
-#define VG_X_(X_)                                                                       \
-  if (x_dim == X_) {                                                                    \
-    rc = mbpo_ensure_lds<k_ppo_vg_lean<X_>>(lds, "ppo_vg_lean");                        \
+#define VG_XQ_(X_, Q_)                                                                  \
+  if (x_dim == X_ && (A.neq != 0) == Q_) {                                              \
+    rc = mbpo_ensure_lds<k_ppo_vg_lean<X_, Q_>>(lds, "ppo_vg_lean");                    \
     if (rc != MBPO_OK) return rc;                                                       \
-    hipLaunchKernelGGL(k_ppo_vg_lean<X_>, dim3(n_wgs), dim3(512), lds, st, A);          \
+    hipLaunchKernelGGL((k_ppo_vg_lean<X_, Q_>), dim3(n_wgs), dim3(512), lds, st, A);    \
     return MBPO_OK;                                                                     \
   }
+#define VG_X_(X_) VG_XQ_(X_, false) VG_XQ_(X_, true)
   VG_X_(2) VG_X_(3) VG_X_(4) VG_X_(5) VG_X_(6)
 #undef VG_X_
+#undef VG_XQ_
   {
     mbpo_set_error("ppo_vg_lean: x_dim %d has no instantiation", x_dim);
     return MBPO_ERR_UNSUPPORTED;

@@ -34,7 +34,10 @@ struct PpoVgLeanArgs {
   float *vs, *adv;                      // [B][T]
   float *mom_part;                      // [workgroups][4]: {n, mean, M2, -}
   float *step_count_rw;
+  int neq;                              // non_equidistant_time (losses_new.py:105-120): per-sample discount n1_discount(action[-1], ...)
+  float neq_cd, neq_tl, neq_tu, neq_dt; // continuous_discounting, min/max_time_between_switches, env_dt
 };
+// lds_extra_floats: the [G][R] values array + four [G][T] arrays (five with neq), each rounded up to a multiple of 4
 int ppo_vg_lean_launch(const PpoVgLeanArgs &A, int x_dim, int n_wgs, size_t lds_extra_floats, void *stream);
 // the value network alone: x -> 64 -> 64 [-> 64] -> 1, swish, x = 2 .. 6
 bool ppo_vg_lean_supports(int x_dim, const int *value_dims, int value_layers, int value_act);

@@ -92,14 +92,6 @@ __device__ __forceinline__ void sac_clip_fixup(const SacOptArgs &O, const float 
   }
 }
 
-// jnp.floor_divide for floats ([3P] jax.numpy: remainder-based, then rounded): x1 // x2
-__device__ __forceinline__ float floor_divide_f(float x1, float x2) {
-  const float mod = fmodf(x1, x2);
-  float div = (x1 - mod) / x2;
-  if (mod != 0.0f && ((x2 < 0.0f) != (mod < 0.0f))) div -= 1.0f;
-  return roundf(div);
-}
-
 // per action-dim pieces of NormalTanh (sac/parametric_distribution.py:66-73,117-120)
 struct ActSample {
   float z, a, sigma, lp;

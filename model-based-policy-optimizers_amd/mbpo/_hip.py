@@ -135,6 +135,9 @@ class PpoDesc(C.Structure):
         ("entropy_cost", C.c_float), ("discounting", C.c_float), ("reward_scaling", C.c_float), ("gae_lambda", C.c_float),
         ("clipping_epsilon", C.c_float), ("normalize_advantage", C.c_int32),
         ("lr", C.c_float), ("wd", C.c_float), ("grad_scale", C.c_float),
+        ("max_grad_norm", C.c_float), ("non_equidistant_time", C.c_int32),
+        ("continuous_discounting", C.c_float), ("min_time_between_switches", C.c_float), ("max_time_between_switches", C.c_float),
+        ("env_dt", C.c_float),
     ]
 
 

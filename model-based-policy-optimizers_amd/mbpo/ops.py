@@ -783,13 +783,22 @@ class SacUpdater:
 # ------------------------------------------------------------------------------------------------ PPO minibatch update (P1-P3)
 class PpoUpdater:
     """Owns the flat PPO train state ([policy | value] params, Adam moments, step count) on one GPU and drives
-    mbpo_ppo_grads / mbpo_ppo_apply.  `all_reduce(t)` (SUM over ranks, in place) sits at ppo.py:149-154's pmean position."""
+    mbpo_ppo_grads / mbpo_ppo_apply.  `all_reduce(t)` (SUM over ranks, in place) sits at ppo.py:149-154's pmean position.
+
+    ppo_brax_env.py's options: max_grad_norm (None: no clip, ppo.py; > 0: clip_by_global_norm of the reduced, scaled gradient
+    before AdamW, :137-141) and non_equidistant_time with its four parameters (the per-sample discount of losses_new.py:105-120)."""
 
     def __init__(self, *, x_dim: int, u_dim: int, policy_dims: Sequence[int], value_dims: Sequence[int], batch_size: int,
                  unroll_length: int, device, policy_activation: str = "swish", value_activation: str = "swish",
                  entropy_cost: float = 1e-4, discounting: float = 0.9, reward_scaling: float = 1.0, gae_lambda: float = 0.95,
                  clipping_epsilon: float = 0.3, normalize_advantage: bool = True, lr: float = 1e-4, wd: float = 1e-5,
-                 seed: int = 0, all_reduce=None, world_size: int = 1):
+                 seed: int = 0, all_reduce=None, world_size: int = 1, max_grad_norm: Optional[float] = None,
+                 non_equidistant_time: bool = False, continuous_discounting: float = 0.0, min_time_between_switches: float = 0.0,
+                 max_time_between_switches: float = 0.0, env_dt: float = 0.0):
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be > 0 (or None: no clipping), got {max_grad_norm}")
+        if non_equidistant_time and not env_dt > 0:
+            raise ValueError("non_equidistant_time needs env_dt > 0 (losses_new.py:110 floors the switch time to multiples of it)")
         self.lib = load()
         self.x_dim, self.u_dim, self.batch_size, self.unroll_length = x_dim, u_dim, batch_size, unroll_length
         self.policy_spec = MlpSpec(list(policy_dims), policy_activation, 1)
@@ -814,6 +823,10 @@ class PpoUpdater:
         d.entropy_cost, d.discounting, d.reward_scaling = entropy_cost, discounting, reward_scaling
         d.gae_lambda, d.clipping_epsilon, d.normalize_advantage = gae_lambda, clipping_epsilon, int(normalize_advantage)
         d.lr, d.wd, d.grad_scale = lr, wd, 1.0 / world_size
+        d.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        d.non_equidistant_time = int(bool(non_equidistant_time))
+        d.continuous_discounting, d.env_dt = continuous_discounting, env_dt
+        d.min_time_between_switches, d.max_time_between_switches = min_time_between_switches, max_time_between_switches
         d.seed, d.offset = seed, 0
         nws = self.lib.mbpo_ppo_workspace_floats(C.byref(d))
         if nws < 0:

@@ -86,12 +86,31 @@ class PPO:
                  critic_hidden_layer_sizes: Sequence[int] = (64, 64, 64),
                  critic_activation: str = "swish",
                  wandb_logging: bool = False,
+                 # --- ppo_brax_env.py's options.  Keyword arguments placed after ppo.py's own, NOT at ppo_brax_env.py's positional
+                 #     slot for max_grad_norm (after wd), so positional calls written against ppo.py keep their meaning ---
+                 max_grad_norm: Optional[float] = None,
+                 return_best_model: bool = False,
+                 non_equidistant_time: bool = False,
+                 continuous_discounting: float = 0,
+                 min_time_between_switches: float = 0,
+                 max_time_between_switches: float = 0,
+                 env_dt: float = 0,
                  # --- MI355X-side knobs (not in the reference) ---
                  use_graph: bool = True,
                  process_group=None,
                  ):
+        """max_grad_norm: None (ppo.py) -> plain adamw; > 0 -> optax.chain(clip_by_global_norm(max_grad_norm), adamw), the
+        ppo_brax_env.py form (:137-141).  return_best_model: run_training returns the snapshot of the evaluation with the highest
+        eval/episode_reward (:315-367).  non_equidistant_time: compute_gae discounts each sample by exp(-continuous_discounting * t),
+        t = the switch time the last action component encodes, mapped to [min, max]_time_between_switches and floored to a multiple
+        of env_dt (losses_new.py:105-120)."""
         if wandb_logging:
             raise NotImplementedError("wandb is not available in this environment")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be > 0 (or None: no clipping), got {max_grad_norm}")
+        if non_equidistant_time and not env_dt > 0:
+            raise ValueError("non_equidistant_time needs env_dt > 0 (losses_new.py:110 floors the switch time to multiples of it)")
+        self.return_best_model = return_best_model
         self.episode_length = episode_length
         self.action_repeat = action_repeat
         self.num_timesteps = num_timesteps
@@ -147,7 +166,9 @@ class PPO:
             unroll_length=unroll_length, device=self.device, policy_activation=policy_activation,
             value_activation=critic_activation, entropy_cost=entropy_cost, discounting=discounting,
             reward_scaling=reward_scaling, gae_lambda=gae_lambda, clipping_epsilon=clipping_epsilon,
-            normalize_advantage=normalize_advantage, lr=lr, wd=wd, all_reduce=self._all_reduce, world_size=self.dp.world_size)
+            normalize_advantage=normalize_advantage, lr=lr, wd=wd, all_reduce=self._all_reduce, world_size=self.dp.world_size,
+            max_grad_norm=max_grad_norm, non_equidistant_time=non_equidistant_time, continuous_discounting=continuous_discounting,
+            min_time_between_switches=min_time_between_switches, max_time_between_switches=max_time_between_switches, env_dt=env_dt)
         self.row_len = ops.transition_row_len(self.x_dim, self.u_dim, True)
         n_traj = batch_size * num_minibatches
         self._data = torch.empty(n_traj, unroll_length, self.row_len, device=self.device)       # [B*M, T, D]
@@ -334,7 +355,7 @@ class PPO:
         return training_state, env_state, metrics
 
     def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
-        """ppo.py:279-339."""
+        """ppo.py:279-339 (ppo_brax_env.py:315-367 with return_best_model)."""
         key, subkey = K.split(key)
         training_state = self.init_training_state(subkey)
         key, rb_key, env_key, eval_key = K.split(key, 4)
@@ -343,6 +364,9 @@ class PPO:
         evaluator = Evaluator(self, self.env, num_eval_envs=self.num_eval_envs, episode_length=self.episode_length,
                               action_repeat=self.action_repeat, key=eval_key)
         all_metrics: List[Metrics] = []
+        # ppo_brax_env.py:321-322: the initial evaluation is not a candidate; before any later one the initial state is "best"
+        highest_eval_episode_reward = -float('inf')
+        best_params = self._snapshot(training_state)
         if self.num_evals > 1:
             metrics = evaluator.run_evaluation(self._snapshot(training_state), training_metrics={})
             all_metrics.append(metrics)
@@ -353,10 +377,15 @@ class PPO:
             key, epoch_key = K.split(key)
             training_state, env_state, training_metrics = self.training_epoch_with_timing(training_state, env_state, rk(epoch_key))
             current_step = training_state.env_steps
-            metrics = evaluator.run_evaluation(self._snapshot(training_state), training_metrics)
+            snapshot = self._snapshot(training_state)
+            metrics = evaluator.run_evaluation(snapshot, training_metrics)
+            if metrics['eval/episode_reward'] > highest_eval_episode_reward:                     # ppo_brax_env.py:350-352
+                highest_eval_episode_reward = metrics['eval/episode_reward']
+                best_params = snapshot
             all_metrics.append(metrics)
             progress_fn(current_step, metrics)
-        return self._snapshot(training_state), all_metrics
+        last_params = self._snapshot(training_state)
+        return (best_params if self.return_best_model else last_params), all_metrics
 
     def close(self) -> None:
         self._graph = self._graph_key = self._graph_refs = None

@@ -263,9 +263,9 @@ def main():
     if want("sac_case"): attempt(sac_case, 4, 1, (256, 256, 256), 4096, 20)
 
     # ---------------------------------------------------------------- P3-P6: PPO minibatch_step (C3)
-    def ppo_case(X, U, hidden, B, T, reps):
+    def ppo_case(X, U, hidden, B, T, reps, opts=None):
         pd, vd = [X, *hidden, 2 * U], [X, *hidden, 1]
-        up = ops.PpoUpdater(x_dim=X, u_dim=U, policy_dims=pd, value_dims=vd, batch_size=B, unroll_length=T, device=dev)
+        up = ops.PpoUpdater(x_dim=X, u_dim=U, policy_dims=pd, value_dims=vd, batch_size=B, unroll_length=T, device=dev, **(opts or {}))
         up.load_state(torch.cat([lecun_flat(pd, g), lecun_flat(vd, g)]).to(dev))
         Dp = ops.transition_row_len(X, U, True)
         data = torch.randn(B, T, Dp, generator=g) * 0.5
@@ -275,14 +275,19 @@ def main():
         t, te = both(lambda: up.minibatch_step(data), reps)
         flop = B * T * 2 * 3 * (mlp_macs(pd) + mlp_macs(vd)) + B * 2 * mlp_macs(vd)
         out.append(mfma_entry("k_ppo_values + k_ppo_fwd_bwd + reduce/apply", "mbpo_ppo_grads + mbpo_ppo_apply",
-                              {"x": X, "u": U, "hidden": list(hidden), "B": B, "T": T}, t, flop,
+                              {"x": X, "u": U, "hidden": list(hidden), "B": B, "T": T, **({"options": opts} if opts else {})}, t, flop,
                               "3*2*(P+V) FLOP per (sample, step) + bootstrap value; includes the in-kernel GAE",
                               {"gae_elements_per_s": B * T / t}))
-        log(f"ppo minibatch_step B={B} T={T}: {t * 1e6:.1f} us")
+        log(f"ppo minibatch_step B={B} T={T}{' ' + str(opts) if opts else ''}: {t * 1e6:.1f} us")
 
     if want("ppo_case"): ppo_case(4, 1, (64, 64, 64), 512, 5, 100)
     if want("ppo_case"): attempt(ppo_case, 4, 1, (64, 64, 64), 512, 40, 50)
     if want("ppo_case"): attempt(ppo_case, 3, 1, (64, 64), 128, 40, 100)        # the reference's own PPO test shape (tests/test_ppo.py:30-56)
+    # ppo_brax_env.py's options at C3: clip_by_global_norm (one more launch per minibatch_step; max_grad_norm small enough to clip),
+    # and the per-sample discount of non_equidistant_time
+    if want("ppo_case"): attempt(ppo_case, 4, 1, (64, 64, 64), 512, 40, 50, {"max_grad_norm": 1e-3})
+    if want("ppo_case"): attempt(ppo_case, 4, 1, (64, 64, 64), 512, 40, 50, {"non_equidistant_time": True, "continuous_discounting": 0.5,
+                                                                            "max_time_between_switches": 0.5, "env_dt": 0.05})
 
     # ---------------------------------------------------------------- B1-B5: BPTT actor gradient (C5)
     def bptt_case(X, U, E, H, n, reps):
