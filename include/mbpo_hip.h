@@ -68,6 +68,10 @@ int mbpo_rng_advance(uint64_t *rng_dev, uint64_t inc, void *stream);
  * loops around a user-defined System (BPTT: the noise of jr.normal in act(), bptt_optimizer.py:305-325). */
 int mbpo_philox_normal_fill(uint64_t seed, uint64_t offset, const uint64_t *rng_dev, uint32_t stream, uint64_t elem_base, int64_t n,
                             float *out, void *stream_);
+/* out[i] = uniform integer in [lo, hi) of element (elem_base + i) of `stream`, keyed as above — exactly philox_randint on the device
+ * (e.g. the MEMBER stream's draws of trajectory sampling, for the host-side BPTT horizon loop). */
+int mbpo_philox_randint_fill(uint64_t seed, uint64_t offset, const uint64_t *rng_dev, uint32_t stream, uint64_t elem_base, int64_t n,
+                             int32_t lo, int32_t hi, int32_t *out, void *stream_);
 
 /* ---- R2: ensemble MLP forward -------------------------------------------------------------
  * replaces: the (new) learned Dynamics.next_state evaluated under vmap —
@@ -397,6 +401,16 @@ int mbpo_ppo_step(const mbpo_ppo_desc *d, void *stream);
  * [n*horizon, 2x+u+2] = [obs, action, reward(raw), discount=1, next_obs] (what :478-479 inserts into the sampling buffer);
  * lambda_values [n*horizon] (the critic targets of :385-419); metrics = {actor_loss, entropy_loss}.
  * Log-prob for u_dim > 1 uses sum_A logN - sum_A log(1-a^2) per step (identical to the reference at u_dim = 1).
+ * Ensemble model: every mode of mbpo_model_rollout.  The reference's actor loss threads SystemParams.key through rollout_policy
+ * (utils/optimizer_utils.py:81-97) and the optimizer splits a fresh system key each train step (bptt_optimizer.py:357-363, :435-436),
+ * so a stochastic System is differentiated by reparameterisation.  For trajectory i and step t:
+ *   MBPO_ENS_MEAN : x' = base + mean_e mu_e                         (ens_sample_noise has no effect, as in the rollout)
+ *   MBPO_ENS_TS1  : m = member_idx[i, t], or Philox(seed, offset [+ rng_dev], stream MEMBER, i*H + t) in [0, E)
+ *   MBPO_ENS_TSINF: m = i % E
+ *   TS modes      : x' = base + mu_m (+ (softplus(raw_m) + ens_min_std) * eps with ens_sample_noise; eps = model_noise[i, t, c],
+ *                   or Philox(..., stream MODEL_NOISE, (i*H + t)*x + c)),  base = x if ens_predict_delta else 0.
+ * The gradient is the pathwise one: only member m receives dL/dmu_m = dL/dx' (and dL/draw_m = dL/dx' * eps * sigmoid(raw_m));
+ * the member draw itself is not differentiated.  member_idx values in [0, E) are the caller's contract.
  */
 typedef struct mbpo_bptt_desc {
   int32_t x_dim, u_dim, horizon;
@@ -409,7 +423,7 @@ typedef struct mbpo_bptt_desc {
   const float *actor_params;                 /* [P] */
   const float *target_critic_params;         /* [2*C] = [critic_1 | critic_2] */
   int32_t system_kind;                       /* MBPO_SYS_* */
-  mbpo_mlp_desc dynamics;                    /* ensemble (MBPO_ENS_MEAN semantics), ignored for MBPO_SYS_PENDULUM */
+  mbpo_mlp_desc dynamics;                    /* ensemble ([x+u] -> [x] or [2x] = [mu, raw std]), ignored for MBPO_SYS_PENDULUM */
   int32_t ens_predict_delta;
   int32_t reward_kind;                       /* MBPO_REWARD_* */
   const float *reward_params, *sys_params;
@@ -423,6 +437,11 @@ typedef struct mbpo_bptt_desc {
   float discount, lambda_, ent_coef;
   float *transitions, *lambda_values, *grads, *metrics;
   float *workspace;                          /* >= mbpo_bptt_workspace_floats() floats */
+  int32_t ens_mode;                          /* MBPO_ENS_*; TS1 / TSINF need MBPO_SYS_ENSEMBLE */
+  int32_t ens_sample_noise;                  /* 1 (TS modes): x' += sigma_m * eps; needs dynamics outputs >= 2*x_dim */
+  float ens_min_std;                         /* sigma = softplus(raw) + ens_min_std */
+  const int32_t *member_idx;                 /* [n, horizon] in [0, E) or NULL -> Philox (MBPO_ENS_TS1) */
+  const float *model_noise;                  /* [n, horizon, x_dim] standard normal or NULL -> Philox */
 } mbpo_bptt_desc;
 
 int64_t mbpo_bptt_workspace_floats(const mbpo_bptt_desc *d);

@@ -78,3 +78,24 @@ extern "C" int mbpo_philox_normal_fill(uint64_t seed, uint64_t offset, const uin
   MBPO_CHECK_LAUNCH("philox_normal_fill");
   return MBPO_OK;
 }
+
+__global__ void __launch_bounds__(256) k_philox_randint_fill(unsigned long long seed, unsigned long long offset, const unsigned long long *rng_dev,
+                                                             unsigned int stream, unsigned long long elem_base, long long n, int lo, int hi,
+                                                             int *out) {
+  const RngKey k = rng_resolve(seed, offset, rng_dev);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    out[i] = philox_randint(k.seed, k.offset, stream, elem_base + (unsigned long long)i, lo, hi);
+}
+
+extern "C" int mbpo_philox_randint_fill(uint64_t seed, uint64_t offset, const uint64_t *rng_dev, uint32_t stream, uint64_t elem_base,
+                                        int64_t n, int32_t lo, int32_t hi, int32_t *out, void *stream_) {
+  MBPO_REQUIRE(out && n > 0, MBPO_ERR_ARG, "philox_randint_fill: null out / n <= 0");
+  MBPO_REQUIRE(stream >= 1 && stream <= 10, MBPO_ERR_ARG, "philox_randint_fill: unknown stream id %u", stream);
+  MBPO_REQUIRE(hi > lo, MBPO_ERR_ARG, "philox_randint_fill: empty range [%d, %d)", lo, hi);
+  const long long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_philox_randint_fill, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream_,
+                     (unsigned long long)seed, (unsigned long long)offset, (const unsigned long long *)rng_dev, stream,
+                     (unsigned long long)elem_base, (long long)n, (int)lo, (int)hi, (int *)out);
+  MBPO_CHECK_LAUNCH("philox_randint_fill");
+  return MBPO_OK;
+}

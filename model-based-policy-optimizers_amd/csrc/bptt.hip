@@ -19,6 +19,16 @@
 #include <string.h>
 
 #define LOG_SQRT_2PI_B 0.91893853320467274178f
+// BpttArgs::ts bits
+#define TS_TSINF 1        // member = trajectory % E (else TS1: drawn per trajectory and step)
+#define TS_NOISE 2        // x' += sigma_m * eps
+#define TS_MEM_GIVEN 4    // member_idx was copied into the member checkpoints: read, do not draw
+#define TS_EPS_GIVEN 8    // model_noise was copied into the eps checkpoints: read, do not draw
+#define TS_ON 16
+
+// float offsets of the TS checkpoints inside BpttArgs::w_ts (and inside the workspace block bptt_plan reserves for them)
+__host__ __device__ __forceinline__ long long ts_eps_off(long long n, int H) { return (n * H + 3) & ~3LL; }
+__host__ __device__ __forceinline__ long long ts_raw_off(long long n, int H, int X) { return ts_eps_off(n, H) + ((n * H * X + 3) & ~3LL); }
 
 struct BpttArgs {
   MlpDev pi, cr, dyn;
@@ -37,6 +47,11 @@ struct BpttArgs {
   int ld_x, ld_xu, ld_h, ld_y, ld_ye, LH, EC;
   NetShape sh_pi, sh_cr, sh_dyn;
   unsigned long long *stamps;   // measurement hook (mbpo_debug_set_bptt_stamps): [16] cycles per op kind + [16] op counts, block 0; or NULL
+  // trajectory sampling (read by the TS instantiation only): the TS_* bits.  Three words of arguments: explicit draws are copied into
+  // their checkpoint slots before the launch and read back from there.
+  int ts;
+  float ens_min_std;             // sigma = softplus(raw_m) + ens_min_std
+  float *w_ts;                   // checkpoints: member [n*H] (int), then with noise eps and raw_m [n*H*X] each (ts_eps_off, ts_raw_off)
 };
 
 static unsigned long long *g_bptt_stamps = nullptr;
@@ -143,7 +158,10 @@ __device__ __forceinline__ float bp_ftanh(float x) {
   return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
 }
 
-template <int H, bool WIDE>
+// TS: the trajectory-sampling instantiation ('ts1' / 'tsinf').  A uniform branch on A.ts alone kept the mean path's results but not its
+// register allocation (+3 VGPRs, +30 SGPR spills, +1 % per BASELINE config-5 train step); with TS = false every TS branch is compiled
+// out and the mean kernel is the one it was.
+template <int H, bool WIDE, bool TS>
 __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -177,6 +195,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   float *s_a = s_dye + EC * 16 * ld_ye;       // [16][U]
   float *s_eps = s_a + U4;
   float *s_scal = s_eps + U4;                 // [8][16] per-row scalars
+  int *const s_mem = reinterpret_cast<int *>(s_scal + 32);   // [16] TS modes: the member of each row at this step
   float *s_gR = s_scal + 128;                 // [HZ+1]  dL/dR_t (row independent)
   float *s_pi = s_gR + ((HZ + 4) & ~3);       // 2*LH tiles: policy z, h
   float *s_B = s_pi + 2 * LH * T;             // shared region: critics (2*LH z + 4 pp) | ensemble round EC*(LH+2) | policy deltas
@@ -186,6 +205,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   const float r_mean = A.r_ms[0], r_std = A.r_ms[1];
   const float invNH = 1.0f / ((float)A.n * (float)HZ);
   const float w_lp = -A.ent_coef * invNH;      // dL/d log_prob_t   (entropy_loss = -mean_t lp, weight ent_coef)
+  const int ts = TS ? A.ts : 0;
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
   const int PL = A.pi.n_layers, CL = A.cr.n_layers, DL = A.dyn.n_layers;
@@ -365,12 +385,52 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             s_xu[r * ld_xu + c] = xv;
             if (ens) s_xn[r * ld_x + c] = A.predict_delta ? xv : 0.f;   // the member means are added round by round
           }
+          if (ts && tid < 16) {   // the row's member for this step, drawn once (rollout.hip's rule)
+            const long long i = row0 + tid;
+            int m = 0;
+            if (i < A.n) {
+              const long long k = i * HZ + t;
+              int *const w_mem = reinterpret_cast<int *>(A.w_ts);
+              if (ts & TS_MEM_GIVEN) m = w_mem[k];
+              else {
+                m = (ts & TS_TSINF) ? (int)(i % E) : philox_randint(rng_seed, rng_off, MBPO_STREAM_MEMBER, (unsigned long long)k, 0, E);
+                w_mem[k] = m;
+              }
+            }
+            s_mem[tid] = m;
+          }
         } else if (elem == E_ACCUM) {
-          for (int idx = tid; idx < 16 * X; idx += nthreads) {
-            const int r = idx / X, c = idx - r * X;
-            float acc = 0.f;
-            for (int cc = 0; cc < EC && rr * EC + cc < E; ++cc) acc += s_ye[(cc * 16 + r) * ld_ye + c];
-            s_xn[r * ld_x + c] += acc / (float)E;
+          if (!ts) {
+            for (int idx = tid; idx < 16 * X; idx += nthreads) {
+              const int r = idx / X, c = idx - r * X;
+              float acc = 0.f;
+              for (int cc = 0; cc < EC && rr * EC + cc < E; ++cc) acc += s_ye[(cc * 16 + r) * ld_ye + c];
+              s_xn[r * ld_x + c] += acc / (float)E;
+            }
+          } else {
+            // trajectory sampling: a row takes its own member, in the round that holds it (x' = base + mu_m [+ sigma_m * eps])
+            for (int idx = tid; idx < 16 * X; idx += nthreads) {
+              const int r = idx / X, c = idx - r * X;
+              const int cc = s_mem[r] - rr * EC;
+              if (cc < 0 || cc >= EC) continue;
+              const float *ye = s_ye + (cc * 16 + r) * ld_ye;
+              const long long i = row0 + r;
+              float v = s_xn[r * ld_x + c] + ye[c];
+              if ((ts & TS_NOISE) && i < A.n) {
+                const long long k = (i * HZ + t) * X + c;
+                float *const w_eps = A.w_ts + ts_eps_off(A.n, HZ);
+                const float raw = ye[X + c];
+                float eps;
+                if (ts & TS_EPS_GIVEN) eps = w_eps[k];
+                else {
+                  eps = philox_normal(rng_seed, rng_off, MBPO_STREAM_MODEL_NOISE, (unsigned long long)k);
+                  w_eps[k] = eps;
+                }
+                v += (softplus_f(raw) + A.ens_min_std) * eps;
+                A.w_ts[ts_raw_off(A.n, HZ, X) + k] = raw;
+              }
+              s_xn[r * ld_x + c] = v;
+            }
           }
           if (A.w_z) {
             // the round's pre-activation tiles -> global memory: the backward sweep reloads them instead of running the members'
@@ -475,6 +535,10 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             s_eps[idx] = i < A.n ? A.w_eps[(i * HZ + t) * U + d] : 0.f;
             s_xu[r * ld_xu + X + d] = a;
           }
+          if (ts && tid < 16) {
+            const long long i = row0 + tid;
+            s_mem[tid] = i < A.n ? reinterpret_cast<const int *>(A.w_ts)[i * HZ + t] : 0;
+          }
         } else if (elem == E_DV) {
           if (tid < 16) {   // dL/dV_t on the arg-min target critic
             const long long i = row0 + tid;
@@ -513,10 +577,27 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             }
           }
           const int dout = A.dyn.dims[DL];
-          for (int idx = tid; idx < 16 * dout; idx += nthreads) {
-            const int r = idx / dout, c = idx - r * dout;
-            const float v = c < X ? s_gx[r * ld_x + c] / (float)E : 0.f;   // x' = base + mean_e mu_e: the same for every member
-            for (int cc = 0; cc < EC; ++cc) s_dye[(cc * 16 + r) * ld_ye + c] = v;
+          if (!ts) {
+            for (int idx = tid; idx < 16 * dout; idx += nthreads) {
+              const int r = idx / dout, c = idx - r * dout;
+              const float v = c < X ? s_gx[r * ld_x + c] / (float)E : 0.f;   // x' = base + mean_e mu_e: the same for every member
+              for (int cc = 0; cc < EC; ++cc) s_dye[(cc * 16 + r) * ld_ye + c] = v;
+            }
+          } else {
+            // pathwise gradient: only the row's member gets dL/dmu_m = dL/dx', and with noise dL/draw_m = dL/dx' * eps * sigmoid(raw_m)
+            for (int idx = tid; idx < 16 * dout; idx += nthreads) {
+              const int r = idx / dout, c = idx - r * dout;
+              const long long i = row0 + r;
+              const int sel = s_mem[r] - rr * EC;
+              float v = 0.f;
+              if (c < X) {
+                v = s_gx[r * ld_x + c];
+              } else if ((ts & TS_NOISE) && c < 2 * X && i < A.n) {
+                const long long k = (i * HZ + t) * X + (c - X);
+                v = s_gx[r * ld_x + (c - X)] * A.w_ts[ts_eps_off(A.n, HZ) + k] * sigmoid_f(A.w_ts[ts_raw_off(A.n, HZ, X) + k]);
+              }
+              for (int cc = 0; cc < EC; ++cc) s_dye[(cc * 16 + r) * ld_ye + c] = cc == sel ? v : 0.f;
+            }
           }
           if (A.w_z) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's reloaded rows have landed in LDS
         } else if (elem == E_DXUACC) {
@@ -626,7 +707,7 @@ struct BpttPlan {
   int P, C, H, LH, EC, n_slabs;
   int ld_x, ld_xu, ld_h, ld_y, ld_ye;
   size_t lds;
-  long long o_xs, o_as, o_eps, o_rs, o_vs, o_km, o_z, o_slabs, o_extras, total;
+  long long o_xs, o_as, o_eps, o_rs, o_vs, o_km, o_ts, o_z, o_slabs, o_extras, total;
 };
 
 static int bptt_hidden(const int *dims, int n_layers) {
@@ -654,6 +735,10 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
                MBPO_ERR_ARG, "bptt: networks need at least one hidden layer");
   MBPO_REQUIRE(d->actor_dims[0] == d->x_dim && d->actor_dims[d->actor_layers] == 2 * d->u_dim, MBPO_ERR_ARG, "bptt: actor must map [x] -> [2u]");
   MBPO_REQUIRE(d->critic_dims[0] == d->x_dim && d->critic_dims[d->critic_layers] == 1, MBPO_ERR_ARG, "bptt: critic must map [x] -> [1]");
+  MBPO_REQUIRE(d->ens_mode == MBPO_ENS_MEAN || d->ens_mode == MBPO_ENS_TS1 || d->ens_mode == MBPO_ENS_TSINF, MBPO_ERR_ARG,
+               "bptt: unknown ens_mode %d", d->ens_mode);
+  const bool ts = d->ens_mode != MBPO_ENS_MEAN, ts_noise = ts && d->ens_sample_noise;
+  MBPO_REQUIRE(!ts || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG, "bptt: ens_mode ts1 / tsinf needs system_kind ENSEMBLE");
   const int Ha = bptt_hidden(d->actor_dims, d->actor_layers), Hc = bptt_hidden(d->critic_dims, d->critic_layers);
   MBPO_REQUIRE(Ha == Hc && Ha == 64, MBPO_ERR_UNSUPPORTED, "bptt: actor/critic hidden layers must all be 64 wide (got %d, %d)", Ha, Hc);
   mbpo_mlp_desc md;
@@ -686,6 +771,7 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
     MBPO_REQUIRE(pl->dyn.dims[0] == d->x_dim + d->u_dim && dyn_out >= d->x_dim, MBPO_ERR_ARG, "bptt: dynamics must map [x+u] -> [>= x]");
     MBPO_REQUIRE(pl->dyn.n_layers >= 2 && bptt_hidden(pl->dyn.dims, pl->dyn.n_layers) == 64, MBPO_ERR_UNSUPPORTED,
                  "bptt: dynamics hidden layers must all be 64 wide");
+    MBPO_REQUIRE(!ts_noise || dyn_out >= 2 * d->x_dim, MBPO_ERR_ARG, "bptt: sampled model noise needs dynamics outputs [mu, raw std] (>= 2x)");
     if (pl->dyn.n_layers - 1 > lh) lh = pl->dyn.n_layers - 1;
   } else if (d->system_kind == MBPO_SYS_PENDULUM) {
     MBPO_REQUIRE(d->x_dim == 3 && d->u_dim == 1 && d->sys_params, MBPO_ERR_ARG, "bptt: pendulum system needs x=3,u=1,sys_params");
@@ -730,6 +816,9 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   pl->o_rs = take(d->n * d->horizon);
   pl->o_vs = take(d->n * d->horizon);
   pl->o_km = take(d->n * d->horizon);
+  // trajectory sampling: the member of every (trajectory, step), and with noise eps and the selected member's raw std output, so the
+  // backward sweep never redraws (and works the same on the z store and on recompute)
+  pl->o_ts = ts ? take(ts_noise ? ts_raw_off(d->n, d->horizon, d->x_dim) + d->n * d->horizon * d->x_dim : d->n * d->horizon) : -1;
   // member pre-activations kept from the forward sweep (the backward sweep then skips the members' recompute): 4 KB per (trajectory
   // tile, step, member, hidden layer) — 1 GB at BASELINE config 5 (n = 4096, H = 32, E = 10); beyond MBPO_BPTT_ZSTORE_MAX_MB (default
   // 16384) the kernel recomputes instead
@@ -775,17 +864,43 @@ extern "C" int mbpo_bptt_actor_grads(const mbpo_bptt_desc *d, void *stream) {
   A.w_xs = ws + pl.o_xs; A.w_as = ws + pl.o_as; A.w_eps = ws + pl.o_eps; A.w_rs = ws + pl.o_rs; A.w_vs = ws + pl.o_vs;
   A.w_km = ws + pl.o_km; A.w_z = pl.o_z >= 0 ? ws + pl.o_z : nullptr; A.slabs = ws + pl.o_slabs; A.extras = ws + pl.o_extras;
   A.ld_x = pl.ld_x; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.ld_ye = pl.ld_ye; A.LH = pl.LH; A.EC = pl.EC;
+  hipStream_t st = (hipStream_t)stream;
+  A.ts = 0;
+  A.ens_min_std = d->ens_min_std;
+  A.w_ts = pl.o_ts >= 0 ? ws + pl.o_ts : nullptr;
+  if (A.w_ts) {
+    A.ts = TS_ON | (d->ens_mode == MBPO_ENS_TSINF ? TS_TSINF : 0) | (d->ens_sample_noise ? TS_NOISE : 0);
+    if (d->ens_mode == MBPO_ENS_TS1 && d->member_idx) {
+      A.ts |= TS_MEM_GIVEN;
+      MBPO_REQUIRE(hipMemcpyAsync(A.w_ts, d->member_idx, sizeof(int32_t) * d->n * d->horizon, hipMemcpyDeviceToDevice, st) == hipSuccess,
+                   MBPO_ERR_LAUNCH, "bptt_actor_grads: member_idx copy failed");
+    }
+    if ((A.ts & TS_NOISE) && d->model_noise) {
+      A.ts |= TS_EPS_GIVEN;
+      MBPO_REQUIRE(hipMemcpyAsync(A.w_ts + ts_eps_off(d->n, d->horizon), d->model_noise, sizeof(float) * d->n * d->horizon * d->x_dim,
+                                  hipMemcpyDeviceToDevice, st) == hipSuccess,
+                   MBPO_ERR_LAUNCH, "bptt_actor_grads: model_noise copy failed");
+    }
+  }
   A.stamps = g_bptt_stamps;
   A.sh_pi = NetShape{A.pi.dims[0], A.pi.n_layers, A.pi.dims[A.pi.n_layers], A.pi.act};
   A.sh_cr = NetShape{A.cr.dims[0], A.cr.n_layers, A.cr.dims[A.cr.n_layers], A.cr.act};
   if (A.system_kind == MBPO_SYS_ENSEMBLE) A.sh_dyn = NetShape{A.dyn.dims[0], A.dyn.n_layers, A.dyn.dims[A.dyn.n_layers], A.dyn.act};
   else A.sh_dyn = NetShape{A.X + A.U, 0, A.X, 0};
   const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_cr) || net_is_wide(A.sh_dyn);
-  rc = wide ? mbpo_ensure_lds<k_bptt_actor<64, true>>(pl.lds, "bptt_actor_grads") : mbpo_ensure_lds<k_bptt_actor<64, false>>(pl.lds, "bptt_actor_grads");
-  if (rc != MBPO_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (wide) hipLaunchKernelGGL((k_bptt_actor<64, true>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
-  else hipLaunchKernelGGL((k_bptt_actor<64, false>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+  if (A.ts) {
+    rc = wide ? mbpo_ensure_lds<k_bptt_actor<64, true, true>>(pl.lds, "bptt_actor_grads")
+              : mbpo_ensure_lds<k_bptt_actor<64, false, true>>(pl.lds, "bptt_actor_grads");
+    if (rc != MBPO_OK) return rc;
+    if (wide) hipLaunchKernelGGL((k_bptt_actor<64, true, true>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+    else hipLaunchKernelGGL((k_bptt_actor<64, false, true>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+  } else {
+    rc = wide ? mbpo_ensure_lds<k_bptt_actor<64, true, false>>(pl.lds, "bptt_actor_grads")
+              : mbpo_ensure_lds<k_bptt_actor<64, false, false>>(pl.lds, "bptt_actor_grads");
+    if (rc != MBPO_OK) return rc;
+    if (wide) hipLaunchKernelGGL((k_bptt_actor<64, true, false>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+    else hipLaunchKernelGGL((k_bptt_actor<64, false, false>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+  }
   BpttReduceArgs R;
   R.slabs = A.slabs; R.extras = A.extras; R.n_slabs = pl.n_slabs; R.P = pl.P; R.H = d->horizon; R.n = d->n; R.ent_coef = d->ent_coef;
   R.grads = d->grads; R.metrics = d->metrics;

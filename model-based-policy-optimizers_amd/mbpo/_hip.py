@@ -18,6 +18,7 @@ ACT_IDS = {"swish": 0, "silu": 0, "relu": 1, "tanh": 2}
 SYS_PENDULUM, SYS_ENSEMBLE = 0, 1
 SYS_GENERIC = 100      # host-side only: a user-defined System, stepped outside the fused kernel (ops.generic_rollout)
 ENS_MEAN, ENS_TS1, ENS_TSINF = 0, 1, 2
+STREAM_POLICY_NOISE, STREAM_MODEL_NOISE, STREAM_MEMBER = 1, 2, 3     # Philox stream ids (csrc/common.hpp)
 REWARD_PENDULUM, REWARD_QUADRATIC = 0, 1
 
 _LIB_PATH = Path(__file__).resolve().parent / "_lib" / "libmbpo_hip.so"
@@ -157,6 +158,8 @@ class BpttDesc(C.Structure):
         ("discount", C.c_float), ("lambda_", C.c_float), ("ent_coef", C.c_float),
         ("transitions", C.c_void_p), ("lambda_values", C.c_void_p), ("grads", C.c_void_p), ("metrics", C.c_void_p),
         ("workspace", C.c_void_p),
+        ("ens_mode", C.c_int32), ("ens_sample_noise", C.c_int32), ("ens_min_std", C.c_float),
+        ("member_idx", C.c_void_p), ("model_noise", C.c_void_p),
     ]
 
 
@@ -241,6 +244,8 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_policy_act.argtypes = [C.POINTER(MlpDesc), vp, i64, vp, vp, i32, f32, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp]
     lib.mbpo_philox_normal_fill.restype = C.c_int
     lib.mbpo_philox_normal_fill.argtypes = [C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, i64, vp, vp]
+    lib.mbpo_philox_randint_fill.restype = C.c_int
+    lib.mbpo_philox_randint_fill.argtypes = [C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, i64, i32, i32, vp, vp]
     lib.mbpo_mlp_vjp_workspace_floats.restype = C.c_int64
     lib.mbpo_mlp_vjp_workspace_floats.argtypes = [C.POINTER(MlpDesc), i64]
     lib.mbpo_mlp_vjp.restype = C.c_int

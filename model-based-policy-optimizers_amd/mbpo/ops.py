@@ -911,7 +911,10 @@ class BpttActorGrad:
 
     def __call__(self, *, actor_params, target_critic_params, init_states, state_mean, state_std, reward_mean_std,
                  system_kind: int, reward_kind: int, reward_params, sys_params=None, dyn_params=None, dyn_spec: Optional[MlpSpec] = None,
-                 ens_predict_delta: bool = True, act_noise=None, offset: int = 0, rng_dev=None):
+                 ens_predict_delta: bool = True, ens_mode: int = _hip.ENS_MEAN, ens_sample_noise: bool = False,
+                 ens_min_std: float = 1e-3, member_idx=None, model_noise=None, act_noise=None, offset: int = 0, rng_dev=None):
+        """ens_mode / ens_sample_noise / ens_min_std: the ensemble's trajectory sampling (include/mbpo_hip.h, mbpo_bptt_desc).
+        member_idx [n, H] int32 (ENS_TS1) and model_noise [n, H, x] replace the Philox draws when given."""
         d = self.desc
         for t, nm in ((actor_params, "actor_params"), (target_critic_params, "target_critic_params"), (init_states, "init_states"),
                       (state_mean, "state_mean"), (state_std, "state_std"), (reward_mean_std, "reward_mean_std"),
@@ -936,6 +939,18 @@ class BpttActorGrad:
             if act_noise.numel() != self.n * self.horizon * self.u_dim:
                 raise ValueError("act_noise must be [n,H,u]")
         d.act_noise = ptr(act_noise)
+        if ens_mode not in (_hip.ENS_MEAN, _hip.ENS_TS1, _hip.ENS_TSINF):
+            raise ValueError(f"unknown ens_mode {ens_mode}")
+        if member_idx is not None:
+            _req(member_idx, "member_idx", torch.int32)
+            if member_idx.numel() != self.n * self.horizon:
+                raise ValueError("member_idx must be int32 [n,H]")
+        if model_noise is not None:
+            _req(model_noise, "model_noise")
+            if model_noise.numel() != self.n * self.horizon * self.x_dim:
+                raise ValueError("model_noise must be [n,H,x]")
+        d.ens_mode, d.ens_sample_noise, d.ens_min_std = int(ens_mode), int(bool(ens_sample_noise)), float(ens_min_std)
+        d.member_idx, d.model_noise = ptr(member_idx), ptr(model_noise)
         d.offset = offset
         d.rng_dev = rng_ptr(rng_dev)
         d.transitions, d.lambda_values = self.transitions.data_ptr(), self.lambda_values.data_ptr()
@@ -957,6 +972,17 @@ def philox_normal(n: int, seed: int, offset: int = 0, stream: int = 1, rng_dev: 
     out = torch.empty(int(n), device=dev, dtype=torch.float32)
     check(load().mbpo_philox_normal_fill(int(seed) & ((1 << 64) - 1), int(offset) & ((1 << 64) - 1), rng_ptr(rng_dev), int(stream),
                                          int(elem_base), int(n), out.data_ptr(), current_stream_ptr()), "mbpo_philox_normal_fill")
+    return out
+
+
+def philox_randint(n: int, lo: int, hi: int, seed: int, offset: int = 0, stream: int = _hip.STREAM_MEMBER,
+                   rng_dev: Optional[torch.Tensor] = None, elem_base: int = 0, device=None) -> torch.Tensor:
+    """mbpo_philox_randint_fill: n int32 uniform in [lo, hi) of `stream` (3 = ensemble member) — the integers the fused kernels draw."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty(int(n), device=dev, dtype=torch.int32)
+    check(load().mbpo_philox_randint_fill(int(seed) & ((1 << 64) - 1), int(offset) & ((1 << 64) - 1), rng_ptr(rng_dev), int(stream),
+                                          int(elem_base), int(n), int(lo), int(hi), out.data_ptr(), current_stream_ptr()),
+          "mbpo_philox_randint_fill")
     return out
 
 
@@ -987,6 +1013,9 @@ class BpttActorGradGeneric:
     System.step -> next step;  then HipMlp (twin target critics on the next states, HIP), LambdaReturnFn (HIP scans), the loss of
     :346-353, and one backward through the graph: torch autograd differentiates the user's step, mbpo_mlp_vjp the networks.
     Same Philox noise (stream POLICY_NOISE, element (traj*H + t)*u + d) and the same A > 1 log-prob form as the fused kernel.
+    A system with `ens_mode` other than ENS_MEAN (torch_steps.DifferentiableBuiltin of a trajectory-sampling EnsembleSystem) gets the
+    fused kernel's draws too: members [n, H] (stream MEMBER, element traj*H + t) and with `sample_noise` model noise [n, H, x] (stream
+    MODEL_NOISE, element (traj*H + t)*x + c), drawn once per call; step t receives member=[:, t], noise=[:, t].
     Not hipGraph-captured (user code runs between the kernels)."""
 
     def __init__(self, *, x_dim: int, u_dim: int, horizon: int, actor_dims: Sequence[int], critic_dims: Sequence[int], n: int,
@@ -1007,14 +1036,27 @@ class BpttActorGradGeneric:
         self.desc = types.SimpleNamespace(seed=seed)       # the field the optimizer sets on BpttActorGrad.desc
 
     def __call__(self, *, actor_params, target_critic_params, init_states, state_mean, state_std, reward_mean_std, system,
-                 system_params, act_noise=None, offset: int = 0, rng_dev=None):
+                 system_params, act_noise=None, member_idx=None, model_noise=None, offset: int = 0, rng_dev=None):
         import math
         n, H, X, U = self.n, self.horizon, self.x_dim, self.u_dim
         if tuple(init_states.shape) != (n, X):
             raise ValueError(f"init_states must be [{n},{X}]")
         if act_noise is None:
-            act_noise = philox_normal(n * H * U, self.desc.seed, offset, 1, rng_dev, device=self.device)
+            act_noise = philox_normal(n * H * U, self.desc.seed, offset, _hip.STREAM_POLICY_NOISE, rng_dev, device=self.device)
         noise = act_noise.reshape(n, H, U)
+        ens_mode = getattr(system, "ens_mode", _hip.ENS_MEAN)
+        members = eps_m = None
+        if ens_mode != _hip.ENS_MEAN:
+            E = system.n_members
+            if ens_mode == _hip.ENS_TSINF:
+                members = (torch.arange(n, device=self.device, dtype=torch.int32) % E)[:, None].expand(n, H)
+            elif member_idx is not None:
+                members = member_idx.reshape(n, H)
+            else:
+                members = philox_randint(n * H, 0, E, self.desc.seed, offset, _hip.STREAM_MEMBER, rng_dev, device=self.device).reshape(n, H)
+            if system.sample_noise:
+                eps_m = (model_noise if model_noise is not None else
+                         philox_normal(n * H * X, self.desc.seed, offset, _hip.STREAM_MODEL_NOISE, rng_dev, device=self.device)).reshape(n, H, X)
         p = actor_params.detach().clone().requires_grad_(True)
         tcp = target_critic_params.detach()
         s_mean, s_std = state_mean.detach().contiguous(), state_std.detach().contiguous()
@@ -1030,7 +1072,10 @@ class BpttActorGradGeneric:
         for t in range(H):        # rollout_policy (optimizer_utils.py:79-101): policy(stop_gradient(obs)), then System.step
             mu, sig = actor(obs.detach())
             a = torch.clamp(torch.tanh(mu + noise[:, t] * sig), -0.999, 0.999)          # act (:313-317)
-            st = system.step(obs, a, sp)
+            if members is None:
+                st = system.step(obs, a, sp)
+            else:
+                st = system.step(obs, a, sp, member=members[:, t], noise=None if eps_m is None else eps_m[:, t])
             nxt = st.x_next.reshape(n, X).to(torch.float32)
             r = torch.as_tensor(st.reward, device=self.device, dtype=torch.float32).reshape(-1).expand(n)
             o_l.append(obs); a_l.append(a); r_l.append(r); n_l.append(nxt)

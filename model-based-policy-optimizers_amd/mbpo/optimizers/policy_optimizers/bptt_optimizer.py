@@ -354,13 +354,12 @@ class BPTTOptimizer(BaseOptimizer):
             # (utils/optimizer_utils.py:62-116) is walked on the host — ops.BpttActorGradGeneric: the networks' forward and VJP in HIP
             # (mbpo_ensemble_mlp_forward / mbpo_mlp_vjp), lambda-return in HIP, the user's step differentiated by torch autograd
             return spec, dict(system=self.system, system_params=system_params)
-        if spec["system_kind"] == _hip.SYS_ENSEMBLE and spec.get("ens_mode", _hip.ENS_MEAN) != _hip.ENS_MEAN:
-            raise _hip.MbpoHipError("BPTT needs a differentiable model: EnsembleSystem mode must be 'mean'")
-        if spec.get("ens_sample_noise", False):
-            raise _hip.MbpoHipError("BPTT through sampled model noise is not supported (ens_sample_noise must be False)")
+        # an EnsembleSystem in any mode: 'ts1' / 'tsinf' draw members (and model noise) from Philox under the actor's
+        # (seed, offset + rng_dev) — a fresh draw every train step, as the reference's fresh system key (:357-363, :435-436)
         kw = dict(system_kind=spec["system_kind"], reward_kind=spec["reward_kind"], reward_params=spec["reward_params"],
                   sys_params=spec.get("sys_params"), dyn_params=spec.get("dyn_params"), dyn_spec=spec.get("dyn_spec"),
-                  ens_predict_delta=spec.get("ens_predict_delta", True))
+                  ens_predict_delta=spec.get("ens_predict_delta", True), ens_mode=spec.get("ens_mode", _hip.ENS_MEAN),
+                  ens_sample_noise=spec.get("ens_sample_noise", False), ens_min_std=spec.get("ens_min_std", 1e-3))
         return spec, kw
 
     def _train_step(self, w: "_Work", buff: ReplayBufferState, seeds: Tuple[int, int, int]) -> ReplayBufferState:

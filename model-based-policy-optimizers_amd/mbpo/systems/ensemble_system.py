@@ -8,6 +8,9 @@ model plugs into.  Semantics (build-defined, parity-unpinned; restated in oracle
     'mean' : x' = base + mean_e(mu_e)               — what System.step's `.mean()` consumes
     'ts1'  : member drawn per (env, step);  x' = base + mu_m (+ sigma_m * eps when sample_noise)   — MBPO-style
     'tsinf': member = env % E
+BPTT differentiates every mode (include/mbpo_hip.h, mbpo_bptt_desc): in 'ts1' / 'tsinf' by reparameterisation through the selected
+member — mu_m, and with sample_noise sigma_m * eps — with the member and eps drawn from Philox per train step (the reference threads
+SystemParams.key through rollout_policy, utils/optimizer_utils.py:81-97).  sample_noise has no effect in 'mean' mode.
 """
 from __future__ import annotations
 

@@ -4,8 +4,10 @@ takes (bptt_optimizer.py:183-186 accepts any `actor_features` / `critic_features
 
     PendulumSystem   dynamics/pendulum_dynamics.py:29-63, rewards/pendulum_reward.py:27-42 (restated; the fused kernels hold the
                      same arithmetic in csrc/rollout.hip)
-    EnsembleSystem   'mean' mode without sampled noise (what BPTT requires): x' = [x +] mean_e mu_e([x, u]) with the member MLPs as
-                     HIP autograd nodes (ops.HipMlp), quadratic or Pendulum reward in torch
+    EnsembleSystem   every mode, with the member MLPs as HIP autograd nodes (ops.HipMlp), quadratic or Pendulum reward in torch:
+                     'mean': x' = [x +] mean_e mu_e([x, u]);  'ts1' / 'tsinf': x' = [x +] mu_m (+ (softplus(raw_m) + min_std) * eps),
+                     the member m and eps of the step handed in by ops.BpttActorGradGeneric (the fused kernel's Philox draws), the
+                     gradient pathwise through the selected member (the draw itself is not differentiated)
 """
 from __future__ import annotations
 
@@ -40,27 +42,40 @@ def quadratic_reward(x: torch.Tensor, u: torch.Tensor, rvec: torch.Tensor, X: in
 
 class DifferentiableBuiltin:
     """`system.step(x [n, x], u [n, u], params)` -> SystemState with torch-differentiable x_next / reward, for a built-in System
-    described by its rollout spec (System.rollout_spec)."""
+    described by its rollout spec (System.rollout_spec).  Trajectory sampling ('ts1' / 'tsinf') takes the step's draws:
+    member [n] and, with sample_noise, noise [n, x]."""
     fused = False
 
     def __init__(self, system, spec: dict):
         self.system, self.spec = system, spec
         self.x_dim, self.u_dim = system.x_dim, system.u_dim
+        self.ens_mode, self.sample_noise, self.n_members = _hip.ENS_MEAN, False, 0
         kind = spec["system_kind"]
         if kind == _hip.SYS_ENSEMBLE:
-            if spec.get("ens_mode", _hip.ENS_MEAN) != _hip.ENS_MEAN or spec.get("ens_sample_noise", False):
-                raise _hip.MbpoHipError("BPTT needs a differentiable model: EnsembleSystem in 'mean' mode without sampled noise")
+            self.ens_mode = spec.get("ens_mode", _hip.ENS_MEAN)
+            self.sample_noise = self.ens_mode != _hip.ENS_MEAN and bool(spec.get("ens_sample_noise", False))   # (no effect in 'mean')
+            self.n_members = spec["dyn_spec"].n_nets
         elif kind != _hip.SYS_PENDULUM:
             raise _hip.MbpoHipError(f"no differentiable torch form for system kind {kind}")
 
-    def step(self, x, u, system_params):
+    def step(self, x, u, system_params, member=None, noise=None):
         from mbpo import ops
         spec, X, U = self.spec, self.x_dim, self.u_dim
         if spec["system_kind"] == _hip.SYS_PENDULUM:
             nxt = pendulum_next_state(x, u, system_params.dynamics_params)
         else:
-            mu = ops.HipMlp.apply(spec["dyn_params"], torch.cat([x, u], dim=1), spec["dyn_spec"], None, None)[..., :X].mean(0)
-            nxt = x + mu if spec.get("ens_predict_delta", True) else mu
+            y = ops.HipMlp.apply(spec["dyn_params"], torch.cat([x, u], dim=1), spec["dyn_spec"], None, None)    # [E, n, out]
+            base = x if spec.get("ens_predict_delta", True) else 0.0
+            if self.ens_mode == _hip.ENS_MEAN:
+                nxt = base + y[..., :X].mean(0)
+            else:
+                if member is None or (self.sample_noise and noise is None):
+                    raise _hip.MbpoHipError("trajectory sampling: step needs the step's member (and noise) draws")
+                n = x.shape[0]
+                ym = y.gather(0, member.long().reshape(1, n, 1).expand(1, n, y.shape[-1]))[0]     # row i: member[i]'s outputs
+                nxt = base + ym[:, :X]
+                if self.sample_noise:
+                    nxt = nxt + (torch.nn.functional.softplus(ym[:, X:2 * X]) + spec["ens_min_std"]) * noise
         if spec["reward_kind"] == _hip.REWARD_PENDULUM:
             rew = pendulum_reward(x, u, system_params.reward_params)
         else:
