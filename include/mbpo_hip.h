@@ -73,6 +73,14 @@ int mbpo_philox_normal_fill(uint64_t seed, uint64_t offset, const uint64_t *rng_
 int mbpo_philox_randint_fill(uint64_t seed, uint64_t offset, const uint64_t *rng_dev, uint32_t stream, uint64_t elem_base, int64_t n,
                              int32_t lo, int32_t hi, int32_t *out, void *stream_);
 
+/* out[(s * n_problems + b) * group + j] = element (s * group + j) of `stream` under (seeds[b], offset), s < n_steps, j < group:
+ * standard normals (as_int = 0, out float) or uniform integers in [lo, hi) (as_int = 1, out int32).  Problem b's numbers are the
+ * ones a fused kernel draws for a rollout of its own `group`-element steps with seed = seeds[b]; the layout is that of one rollout
+ * over all problems' envs.  seeds: device uint64[n_problems].  For the batched iCEM path (icem_optimizer.py:168-175 per problem):
+ * member_idx [H][B NC P] (group = NC P, MEMBER stream) and model_noise [H][B NC P][x] (group = NC P x, MODEL_NOISE stream). */
+int mbpo_philox_fill_grouped(const uint64_t *seeds, uint64_t offset, uint32_t stream, int32_t n_steps, int32_t n_problems, int64_t group,
+                             int32_t as_int, int32_t lo, int32_t hi, void *out, void *stream_);
+
 /* ---- R2: ensemble MLP forward -------------------------------------------------------------
  * replaces: the (new) learned Dynamics.next_state evaluated under vmap —
  *           mbpo/systems/dynamics/base_dynamics.py:15-20 called from
@@ -549,6 +557,23 @@ int mbpo_icem_update_constrained(const float *rows, int32_t row_len, int32_t rew
                                  int32_t use_max, const float *particle_cost, float lambda_constraint, int32_t cost_use_max, float *mean,
                                  float *std, float *best_value, float *best_sequence, float *prev_elites, float *values,
                                  int32_t *workspace, void *stream);
+
+/* Batched MPC: n_problems independent iCEM problems in one launch chain (icem_optimizer.py:135-252 vmapped over states).
+ * Problem b's state sits at mean/std/best_sequence + b*horizon*u_dim, best_value + b, prev_elites + b*n_prev*horizon*u_dim,
+ * candidates + b*(n_samples+n_prev)*horizon*u_dim; values/workspace + b*n_candidates.  Its envs are (b*NC + c)*n_particles + p of
+ * actions [horizon][n_problems*NC*n_particles][u_dim] and of the rollout rows (NC = n_samples + n_prev = n_candidates).
+ * mbpo_icem_sample_batched: problem b draws with seed = seeds[b] (device uint64[n_problems]) at the shared `offset` — bit for bit
+ *   mbpo_icem_sample(seed = seeds[b], offset, rng_dev = NULL) on problem b's slices.  n_problems <= 65535.
+ * mbpo_icem_update_batched: one workgroup per problem, bit for bit mbpo_icem_update_constrained on problem b's slices
+ *   (particle_cost [n_problems*NC*n_particles] or NULL).  workspace: n_problems*n_candidates int32. */
+int mbpo_icem_sample_batched(const float *mean, const float *std, const float *prev_elites, const float *u_min, const float *u_max,
+                             int32_t n_samples, int32_t n_prev, int32_t horizon, int32_t u_dim, int32_t n_particles, float exponent,
+                             int32_t n_problems, const uint64_t *seeds, uint64_t offset, float *actions, float *candidates, void *stream);
+int mbpo_icem_update_batched(const float *rows, int32_t row_len, int32_t reward_col, int32_t n_problems, int32_t n_candidates,
+                             int32_t n_particles, int32_t horizon, int32_t u_dim, const float *candidates, int32_t n_elites, int32_t n_prev,
+                             float alpha, int32_t use_max, const float *particle_cost, float lambda_constraint, int32_t cost_use_max,
+                             float *mean, float *std, float *best_value, float *best_sequence, float *prev_elites, float *values,
+                             int32_t *workspace, void *stream);
 
 /* ---- one-shot all-reduce over xGMI peer memory (multi-GPU SAC gradient exchange) ------------------------
  * replaces: the live form of the reference's jax.lax.pmean(grad) (sac/utils.py:29-33) for vectors small enough that a

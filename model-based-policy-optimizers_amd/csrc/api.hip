@@ -99,3 +99,40 @@ extern "C" int mbpo_philox_randint_fill(uint64_t seed, uint64_t offset, const ui
   MBPO_CHECK_LAUNCH("philox_randint_fill");
   return MBPO_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- grouped fill (batched problems)
+// out[(s B + b) G + j] = draw(seeds[b], offset, stream, s G + j): the numbers n_problems independent launches over G elements per
+// step would draw, each under its own seed, laid out step-major over the problems — the [S][B G] layout of a batched rollout whose
+// problem b owns envs [b G', (b+1) G').
+template <bool INT>
+__global__ void __launch_bounds__(256) k_philox_fill_grouped(const unsigned long long *seeds, unsigned long long offset, unsigned int stream,
+                                                             long long n_problems, long long group, long long n, int lo, int hi,
+                                                             void *out) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long sb = i / group, j = i - sb * group, s = sb / n_problems, b = sb - s * n_problems;
+    const unsigned long long idx = (unsigned long long)(s * group + j);
+    if constexpr (INT) ((int *)out)[i] = philox_randint(seeds[b], offset, stream, idx, lo, hi);
+    else ((float *)out)[i] = philox_normal(seeds[b], offset, stream, idx);
+  }
+}
+
+extern "C" int mbpo_philox_fill_grouped(const uint64_t *seeds, uint64_t offset, uint32_t stream, int32_t n_steps, int32_t n_problems,
+                                        int64_t group, int32_t as_int, int32_t lo, int32_t hi, void *out, void *stream_) {
+  MBPO_REQUIRE(seeds, MBPO_ERR_ARG, "philox_fill_grouped: seeds is NULL");
+  MBPO_REQUIRE(out, MBPO_ERR_ARG, "philox_fill_grouped: out is NULL");
+  MBPO_REQUIRE(n_problems > 0, MBPO_ERR_ARG, "philox_fill_grouped: n_problems=%d <= 0", n_problems);
+  MBPO_REQUIRE(n_steps > 0 && group > 0, MBPO_ERR_ARG, "philox_fill_grouped: n_steps=%d, group=%lld must be > 0", n_steps, (long long)group);
+  MBPO_REQUIRE(stream >= 1 && stream <= 10, MBPO_ERR_ARG, "philox_fill_grouped: unknown stream id %u", stream);
+  MBPO_REQUIRE(!as_int || hi > lo, MBPO_ERR_ARG, "philox_fill_grouped: empty range [%d, %d)", lo, hi);
+  const long long n = (long long)n_steps * n_problems * group;
+  const long long blocks = (n + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+  if (as_int)
+    hipLaunchKernelGGL(k_philox_fill_grouped<true>, grid, dim3(256), 0, (hipStream_t)stream_, (const unsigned long long *)seeds,
+                       (unsigned long long)offset, stream, (long long)n_problems, (long long)group, n, (int)lo, (int)hi, out);
+  else
+    hipLaunchKernelGGL(k_philox_fill_grouped<false>, grid, dim3(256), 0, (hipStream_t)stream_, (const unsigned long long *)seeds,
+                       (unsigned long long)offset, stream, (long long)n_problems, (long long)group, n, 0, 0, out);
+  MBPO_CHECK_LAUNCH("philox_fill_grouped");
+  return MBPO_OK;
+}

@@ -6,6 +6,9 @@
 //   k_icem_values  objective: summarize_particles( mean_t reward )                                      (:146-163)
 //   k_icem_update  one workgroup: stable rank of the candidates (np.argsort), elite mean / population variance, soft update,
 //                  best-so-far, the elite fraction carried to the next iteration                          (:196-232)
+//   *_batched      the same for B independent problems in one launch each (batched MPC): k_icem_sample_batched (grid.y = problem,
+//                  seed = seeds[b]) and k_icem_update[_lds]<true> (one workgroup per problem); the objective kernels run unchanged
+//                  over all problems' candidates.  Problem b's bits are the single-problem launches' with its seed and slices.
 // HBM-bound bookkeeping around the rollout; everything stays on the device, the host only sequences the launches.
 #include "common.hpp"
 
@@ -25,7 +28,11 @@ struct IcemSampleArgs {
 // per thread), then every (series, t) thread forms its inverse-DFT sum over k in order and writes its element and the particles'
 // copies.  (Round 3's one-thread-per-series form — same values bit for bit — spent 43 us on 550 series at the reference's test sizes;
 // this one 5 us.)
-__global__ void __launch_bounds__(256) k_icem_sample_par(IcemSampleArgs A) {
+// BATCHED: blockIdx.y = problem b of n_problems independent ones; its mean / std / prev_elites / candidates sit at strides H U,
+// n_prev H U and NC H U, its seed is seeds[b] (offset shared), the draw index is the problem-local series index, and its envs are
+// (b NC + c) P + p of actions [H][n_problems NC P][U] — problem b's numbers are the single call's with seed = seeds[b].
+template <bool BATCHED>
+__device__ __forceinline__ void icem_sample_body(const IcemSampleArgs &A, const unsigned long long *seeds, int n_problems) {
   extern __shared__ float s_tab[];             // cos / sin tables [H][K], scale [K], coefficients [SB][K] x 2
   const int H = A.H, U = A.U, K = H / 2 + 1;
   const int SB = 256 / H;                       // series per block
@@ -48,8 +55,15 @@ __global__ void __launch_bounds__(256) k_icem_sample_par(IcemSampleArgs A) {
     wsum += w * w;
   }
   const float sigma = 2.0f * sqrtf(wsum) / (float)H;
-  const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
-  const unsigned long long off = rk_.offset, rng_seed = rk_.seed;
+  unsigned long long off, rng_seed;
+  if constexpr (BATCHED) {
+    off = A.offset;
+    rng_seed = seeds[blockIdx.y];
+  } else {
+    const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
+    off = rk_.offset;
+    rng_seed = rk_.seed;
+  }
   const int NC = A.S + A.Kp, N = NC * A.P;
   const int sd0 = blockIdx.x * SB;
   // coefficients of this block's sampled series
@@ -75,9 +89,18 @@ __global__ void __launch_bounds__(256) k_icem_sample_par(IcemSampleArgs A) {
   const int j = threadIdx.x / H, t = threadIdx.x - j * H, sd = sd0 + j;
   if (j >= SB || sd >= NC * U) return;
   const int c = sd / U, d = sd - c * U;
+  const float *mean = A.mean, *std = A.std, *prev_elites = A.prev_elites;
+  float *candidates = A.candidates;
+  if constexpr (BATCHED) {
+    const long long b = blockIdx.y, HU = (long long)H * U;
+    mean += b * HU;
+    std += b * HU;
+    prev_elites += b * A.Kp * HU;
+    candidates += b * NC * HU;
+  }
   float a;
   if (c >= A.S) {        // previous elites ride along unchanged (:190)
-    a = A.prev_elites[((long long)(c - A.S) * H + t) * U + d];
+    a = prev_elites[((long long)(c - A.S) * H + t) * U + d];
   } else {
     const float *sr = s_r + j * K, *si = s_i + j * K;
     // irfft: y_t = (1/H) [ s_0 + 2 sum_{0<k<H/2} (sr_k cos - si_k sin) + (H even) s_{H/2} cos(pi t) ]
@@ -86,11 +109,22 @@ __global__ void __launch_bounds__(256) k_icem_sample_par(IcemSampleArgs A) {
     for (int k = 1; k < kmax; ++k) y += 2.0f * (sr[k] * s_cos[t * K + k] - si[k] * s_sin[t * K + k]);
     if (!(H % 2)) y += sr[K - 1] * s_cos[t * K + K - 1];
     y = y / (float)H / sigma;
-    a = A.mean[t * U + d] + y * A.std[t * U + d];                      // :186
+    a = mean[t * U + d] + y * std[t * U + d];                          // :186
     a = fminf(fmaxf(a, A.u_min[d]), A.u_max[d]);                       // :187
   }
-  A.candidates[((long long)c * H + t) * U + d] = a;
-  for (int p = 0; p < A.P; ++p) A.actions[((long long)t * N + c * A.P + p) * U + d] = a;
+  candidates[((long long)c * H + t) * U + d] = a;
+  if constexpr (BATCHED) {
+    const long long n_all = (long long)n_problems * N, e0 = (long long)blockIdx.y * N + (long long)c * A.P;
+    for (int p = 0; p < A.P; ++p) A.actions[((long long)t * n_all + e0 + p) * U + d] = a;
+  } else {
+    for (int p = 0; p < A.P; ++p) A.actions[((long long)t * N + c * A.P + p) * U + d] = a;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_icem_sample_par(IcemSampleArgs A) { icem_sample_body<false>(A, nullptr, 1); }
+
+__global__ void __launch_bounds__(256) k_icem_sample_batched(IcemSampleArgs A, const unsigned long long *seeds, int n_problems) {
+  icem_sample_body<true>(A, seeds, n_problems);
 }
 
 extern "C" int mbpo_icem_sample(const float *mean, const float *std, const float *prev_elites, const float *u_min, const float *u_max,
@@ -112,6 +146,32 @@ extern "C" int mbpo_icem_sample(const float *mean, const float *std, const float
   }
   hipLaunchKernelGGL(k_icem_sample_par, dim3((work + SB - 1) / SB), dim3(256), lds, (hipStream_t)stream, A);
   MBPO_CHECK_LAUNCH("icem_sample");
+  return MBPO_OK;
+}
+
+extern "C" int mbpo_icem_sample_batched(const float *mean, const float *std, const float *prev_elites, const float *u_min, const float *u_max,
+                                        int32_t n_samples, int32_t n_prev, int32_t horizon, int32_t u_dim, int32_t n_particles, float exponent,
+                                        int32_t n_problems, const uint64_t *seeds, uint64_t offset, float *actions, float *candidates,
+                                        void *stream) {
+  MBPO_REQUIRE(mean && std && u_min && u_max && actions && candidates, MBPO_ERR_ARG, "icem_sample_batched: null pointer");
+  MBPO_REQUIRE(seeds, MBPO_ERR_ARG, "icem_sample_batched: seeds is NULL");
+  MBPO_REQUIRE(n_problems > 0 && n_problems <= 65535, MBPO_ERR_ARG, "icem_sample_batched: n_problems=%d out of [1, 65535]", n_problems);
+  MBPO_REQUIRE(n_samples > 0 && n_prev >= 0 && u_dim > 0 && n_particles > 0, MBPO_ERR_ARG, "icem_sample_batched: bad sizes");
+  MBPO_REQUIRE(horizon >= 2 && horizon <= 128, MBPO_ERR_UNSUPPORTED, "icem_sample_batched: horizon must be in [2, 128]");
+  MBPO_REQUIRE(n_prev == 0 || prev_elites, MBPO_ERR_ARG, "icem_sample_batched: prev_elites is NULL");
+  IcemSampleArgs A{mean, std, prev_elites, u_min, u_max, n_samples, n_prev, horizon, u_dim, n_particles, exponent, 0ull, offset, nullptr,
+                   actions, candidates};
+  const int K = horizon / 2 + 1;
+  const int work = (n_samples + n_prev) * u_dim;
+  const int SB = 256 / horizon;
+  const size_t lds = sizeof(float) * (2ull * horizon * K + K + 2ull * SB * K);
+  {
+    const int rc = mbpo_ensure_lds<k_icem_sample_batched>(lds, "icem_sample_batched");
+    if (rc != MBPO_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_icem_sample_batched, dim3((work + SB - 1) / SB, n_problems), dim3(256), lds, (hipStream_t)stream, A,
+                     (const unsigned long long *)seeds, (int)n_problems);
+  MBPO_CHECK_LAUNCH("icem_sample_batched");
   return MBPO_OK;
 }
 
@@ -197,7 +257,25 @@ struct IcemUpdateArgs {
   int *rank;   // workspace [NC]
 };
 
+// One workgroup per problem: problem b's values / ranks at b NC, candidates at b NC H U, mean / std / best_sequence at b H U,
+// best_value at b, prev_elites at b n_prev H U — the single-problem arithmetic in the same order.
+__device__ __forceinline__ IcemUpdateArgs icem_update_problem(IcemUpdateArgs A) {
+  const long long b = blockIdx.x, NC = A.NC, HU = (long long)A.H * A.U;
+  A.values += b * NC;
+  A.rank += b * NC;
+  A.candidates += b * NC * HU;
+  A.mean += b * HU;
+  A.std += b * HU;
+  A.best_sequence += b * HU;
+  A.best_value += b;
+  A.prev_elites += b * A.n_prev * HU;
+  return A;
+}
+
+// BATCHED = true: one workgroup per problem over a grid of n_problems (mbpo_icem_update_batched).
+template <bool BATCHED>
 __global__ void __launch_bounds__(1024) k_icem_update(IcemUpdateArgs A) {
+  if constexpr (BATCHED) A = icem_update_problem(A);
   const int tid = threadIdx.x, NC = A.NC, HU = A.H * A.U;
   __shared__ int s_best;
   if (tid == 0) s_best = 0;      // in range whatever the ranking does (the barrier below orders it before the search)
@@ -255,7 +333,9 @@ __global__ void __launch_bounds__(1024) k_icem_update(IcemUpdateArgs A) {
 // per-element sums then walk LDS in the SAME order as k_icem_update (ascending candidate index) — identical results; the one-workgroup
 // form above spent its time in 2 x NC dependent global round trips per element on H x U threads (144 us at the reference's test sizes).
 // LDS floats: 2 NC + n_elites + n_elites * H * U.
+template <bool BATCHED>
 __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
+  if constexpr (BATCHED) A = icem_update_problem(A);
   extern __shared__ float sm[];
   const int tid = threadIdx.x, NC = A.NC, HU = A.H * A.U, NE = A.n_elites;
   float *s_val = sm;
@@ -324,7 +404,8 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
 }
 
 // Test hook (not part of include/mbpo_hip.h): 0 = always the global-memory k_icem_update, 1 = k_icem_update_lds wherever its LDS
-// need fits (today the same as the default), -1 = the default dispatch.  tests/test_gpu_icem.py runs every update case under 0 and 1.
+// need fits (today the same as the default), -1 = the default dispatch.  tests/test_gpu_icem.py runs every update case under 0 and 1;
+// mbpo_icem_update_batched follows the same switch.
 static int g_icem_update = -1;
 extern "C" int mbpo_debug_set_icem_update(int mode) {
   MBPO_REQUIRE(mode >= -1 && mode <= 1, MBPO_ERR_ARG, "debug_set_icem_update: mode must be -1, 0 or 1");
@@ -352,8 +433,8 @@ extern "C" int mbpo_icem_update_constrained(const float *rows, int32_t row_len, 
   IcemUpdateArgs A{values, candidates, n_candidates, horizon, u_dim, n_elites, n_prev, alpha, mean, std, best_value, best_sequence,
                    prev_elites, workspace};
   const size_t lds = (2ull * n_candidates + n_elites + (size_t)n_elites * horizon * u_dim) * sizeof(float);
-  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds, dim3(1), dim3(1024), lds, st, A);
-  else hipLaunchKernelGGL(k_icem_update, dim3(1), dim3(1024), 0, st, A);
+  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<false>, dim3(1), dim3(1024), lds, st, A);
+  else hipLaunchKernelGGL(k_icem_update<false>, dim3(1), dim3(1024), 0, st, A);
   MBPO_CHECK_LAUNCH("icem_update");
   return MBPO_OK;
 }
@@ -364,4 +445,35 @@ extern "C" int mbpo_icem_update(const float *rows, int32_t row_len, int32_t rewa
                                 float *values, int32_t *workspace, void *stream) {
   return mbpo_icem_update_constrained(rows, row_len, reward_col, n_candidates, n_particles, horizon, u_dim, candidates, n_elites, n_prev, alpha,
                                       use_max, nullptr, 0.f, 0, mean, std, best_value, best_sequence, prev_elites, values, workspace, stream);
+}
+
+extern "C" int mbpo_icem_update_batched(const float *rows, int32_t row_len, int32_t reward_col, int32_t n_problems, int32_t n_candidates,
+                                        int32_t n_particles, int32_t horizon, int32_t u_dim, const float *candidates, int32_t n_elites,
+                                        int32_t n_prev, float alpha, int32_t use_max, const float *particle_cost, float lambda_constraint,
+                                        int32_t cost_use_max, float *mean, float *std, float *best_value, float *best_sequence,
+                                        float *prev_elites, float *values, int32_t *workspace, void *stream) {
+  MBPO_REQUIRE(rows && candidates && mean && std && best_value && best_sequence && values && workspace, MBPO_ERR_ARG,
+               "icem_update_batched: null pointer");
+  MBPO_REQUIRE(n_problems > 0, MBPO_ERR_ARG, "icem_update_batched: n_problems=%d <= 0", n_problems);
+  MBPO_REQUIRE(n_candidates > 0 && n_particles > 0 && horizon > 0 && u_dim > 0, MBPO_ERR_ARG, "icem_update_batched: bad sizes");
+  MBPO_REQUIRE((long long)n_problems * n_candidates <= 0x7fffffffLL, MBPO_ERR_ARG, "icem_update_batched: n_problems * n_candidates overflows int32");
+  MBPO_REQUIRE(n_elites > 0 && n_elites <= n_candidates && n_prev >= 0 && n_prev <= n_elites, MBPO_ERR_ARG,
+               "icem_update_batched: bad elite counts");
+  MBPO_REQUIRE(n_prev == 0 || prev_elites, MBPO_ERR_ARG, "icem_update_batched: prev_elites is NULL");
+  MBPO_REQUIRE(reward_col >= 0 && reward_col < row_len, MBPO_ERR_ARG, "icem_update_batched: bad reward column");
+  hipStream_t st = (hipStream_t)stream;
+  const int nc_all = n_problems * n_candidates;      // the objective kernels index per global candidate: rows / costs line up
+  if (n_particles <= 64)
+    hipLaunchKernelGGL(k_icem_values_wave, dim3((nc_all + 3) / 4), dim3(256), 0, st, rows, row_len, reward_col, nc_all, n_particles,
+                       horizon, use_max, values, particle_cost, lambda_constraint, cost_use_max);
+  else
+    hipLaunchKernelGGL(k_icem_values, dim3((nc_all + 255) / 256), dim3(256), 0, st, rows, row_len, reward_col, nc_all, n_particles,
+                       horizon, use_max, values, particle_cost, lambda_constraint, cost_use_max);
+  IcemUpdateArgs A{values, candidates, n_candidates, horizon, u_dim, n_elites, n_prev, alpha, mean, std, best_value, best_sequence,
+                   prev_elites, workspace};
+  const size_t lds = (2ull * n_candidates + n_elites + (size_t)n_elites * horizon * u_dim) * sizeof(float);      // per problem
+  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<true>, dim3(n_problems), dim3(1024), lds, st, A);
+  else hipLaunchKernelGGL(k_icem_update<true>, dim3(n_problems), dim3(1024), 0, st, A);
+  MBPO_CHECK_LAUNCH("icem_update_batched");
+  return MBPO_OK;
 }

@@ -246,6 +246,8 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_philox_normal_fill.argtypes = [C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, i64, vp, vp]
     lib.mbpo_philox_randint_fill.restype = C.c_int
     lib.mbpo_philox_randint_fill.argtypes = [C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint64, i64, i32, i32, vp, vp]
+    lib.mbpo_philox_fill_grouped.restype = C.c_int
+    lib.mbpo_philox_fill_grouped.argtypes = [vp, C.c_uint64, C.c_uint32, i32, i32, i64, i32, i32, i32, vp, vp]
     lib.mbpo_mlp_vjp_workspace_floats.restype = C.c_int64
     lib.mbpo_mlp_vjp_workspace_floats.argtypes = [C.POINTER(MlpDesc), i64]
     lib.mbpo_mlp_vjp.restype = C.c_int
@@ -270,6 +272,11 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_icem_update_constrained.restype = C.c_int
     lib.mbpo_icem_update_constrained.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp,
                                                  vp, vp]
+    lib.mbpo_icem_sample_batched.restype = C.c_int
+    lib.mbpo_icem_sample_batched.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, u64, vp, vp, vp]
+    lib.mbpo_icem_update_batched.restype = C.c_int
+    lib.mbpo_icem_update_batched.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, f32, i32, vp, vp, vp, vp, vp,
+                                             vp, vp, vp]
     # one-shot peer-memory all-reduce (csrc/p2p.hip)
     lib.mbpo_p2p_region_bytes.restype = C.c_int64
     lib.mbpo_p2p_region_bytes.argtypes = [i32, i64]

@@ -10,6 +10,14 @@ trajectory, `cost_fn(observation [H, x], action [H, u]) -> scalar`) cannot run i
 rollout launch and the update launch, vmapped over all (candidate, particle) trajectories with torch.func.vmap on the device rows
 (the reference vmaps it too), and enters the objective inside mbpo_icem_update_constrained: reward - lambda_constraint * relu(cost),
 cost summarised over particles by mean (use_pessimism: max).  use_optimism -> max over particles of the reward.
+
+Batched MPC: `init(key, batch_size=B)` makes a state for B independent problems (best_sequence [B, H, U], best_reward [B], key = B
+host integers) and `optimize` / `act` on such a state plan for obs [B, x] in one launch chain per iteration —
+mbpo_icem_sample_batched -> one rollout over all B*NC*P envs -> mbpo_icem_update_batched (one workgroup per problem).  Problem b
+is bit for bit the single-problem `optimize` with key[b], best_sequence[b] and obs[b]: its noise is drawn under its own split
+keys, and a stochastic EnsembleSystem's members and model noise are drawn per problem up front (mbpo_philox_fill_grouped) instead
+of from the global env index in the rollout kernel.  A user-defined (non-fused) System has its `step` called once per horizon step
+over all B*NC*P rows; bit-equality with the single calls then needs that step to be row-independent and deterministic.
 """
 from __future__ import annotations
 
@@ -18,6 +26,7 @@ import dataclasses
 from dataclasses import dataclass
 from typing import Any, Generic, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from mbpo import _hip, ops
@@ -48,12 +57,16 @@ class iCemParams(NamedTuple):
 
 @dataclass
 class iCemOptimizerState(OptimizerState, Generic[DynamicsParams, RewardParams]):
-    best_sequence: torch.Tensor = None     # [horizon, action_dim]
-    best_reward: torch.Tensor = None       # scalar
+    best_sequence: torch.Tensor = None     # [horizon, action_dim]; batched: [B, horizon, action_dim]
+    best_reward: torch.Tensor = None       # scalar; batched: [B]
+
+    @property
+    def batched(self) -> bool:
+        return self.best_sequence is not None and self.best_sequence.dim() == 3
 
     @property
     def action(self):
-        return self.best_sequence[0]
+        return self.best_sequence[..., 0, :]      # [action_dim]; batched: [B, action_dim]
 
 
 @dataclass
@@ -77,14 +90,25 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         if not (0 < p.num_elites <= p.num_samples + self.num_prev):
             raise ValueError("num_elites must be in (0, num_samples + carried elites]")
         self._bufs = None
+        self._bbufs = None
 
     # -- reference API ------------------------------------------------------------------------------------------------
-    def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None) -> iCemOptimizerState:
+    def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None, batch_size: Optional[int] = None) -> iCemOptimizerState:
+        """batch_size=B: a state for B independent problems (see the module docstring); key = K.split(k, B) of the key k the
+        single-problem state would hold."""
         assert self.system is not None, "iCem optimizer requires system to be defined."
         init_key, dummy_buffer_key, key = K.split(key, 3)
         dev = torch.device("cuda", torch.cuda.current_device())
+        if batch_size is None:
+            return iCemOptimizerState(true_buffer_state=self.dummy_true_buffer_state(dummy_buffer_key),
+                                      system_params=self.system.init_params(init_key), best_sequence=torch.zeros(self.opt_dim, device=dev),
+                                      best_reward=torch.zeros((), device=dev), key=key)
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("batch_size must be >= 1")
         return iCemOptimizerState(true_buffer_state=self.dummy_true_buffer_state(dummy_buffer_key), system_params=self.system.init_params(init_key),
-                                  best_sequence=torch.zeros(self.opt_dim, device=dev), best_reward=torch.zeros((), device=dev), key=key)
+                                  best_sequence=torch.zeros((B,) + self.opt_dim, device=dev), best_reward=torch.zeros(B, device=dev),
+                                  key=K.split(key, B))
 
     def _buffers(self, dev):
         if self._bufs is None or self._bufs["dev"] != dev:
@@ -93,17 +117,35 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             N = NC * p.num_particles
             f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
 
-            def vec(v):      # scalar or per-dimension bound -> [U] device vector
-                t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
-                return (t.expand(U) if t.numel() == 1 else t.reshape(U)).contiguous().to(dev)
+            vec = lambda v: _bound_vec(v, U, dev)
             self._bufs = dict(dev=dev, NC=NC, N=N, mean=f(H, U), std=f(H, U), best_value=f(1), best_seq=f(H, U), prev=f(self.num_prev, H, U),
                               actions=f(H, N, U), cand=f(NC, H, U), values=f(NC), rank=torch.zeros(NC, device=dev, dtype=torch.int32),
                               u_min=vec(p.u_min), u_max=vec(p.u_max), obs=f(N, self.system.x_dim), first=f(N, self.system.x_dim),
                               steps=f(N), done=f(N), rows=f(H * N, 2 * self.system.x_dim + U + 3))
         return self._bufs
 
+    def _batched_buffers(self, dev, B: int):
+        """The buffers of `_buffers` for B problems.  rows alone is H*B*NC*P*(2x+u+3) floats: about 1 GB at B = 256 with the
+        default iCemParams on the Pendulum (H = 20, NC*P = 5150, x = 3)."""
+        bb = self._bbufs
+        if bb is None or bb["dev"] != dev or bb["B"] != B:
+            self._bbufs = None      # (release the old set before allocating the new one)
+            p, H, U, X = self.opt_params, self.horizon, self.action_dim, self.system.x_dim
+            NC = p.num_samples + self.num_prev
+            N = NC * p.num_particles
+            NT = B * N
+            f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+            self._bbufs = dict(dev=dev, B=B, NC=NC, N=N, NT=NT, mean=f(B, H, U), std=f(B, H, U), best_value=f(B), best_seq=f(B, H, U),
+                               prev=f(B, self.num_prev, H, U), actions=f(H, NT, U), cand=f(B, NC, H, U), values=f(B * NC),
+                               rank=torch.zeros(B * NC, device=dev, dtype=torch.int32), u_min=_bound_vec(p.u_min, U, dev),
+                               u_max=_bound_vec(p.u_max, U, dev), obs=f(NT, X), first=f(NT, X), steps=f(NT), done=f(NT),
+                               rows=f(H * NT, 2 * X + U + 3))
+        return self._bbufs
+
     def optimize(self, initial_state: torch.Tensor, opt_state: iCemOptimizerState) -> iCemOptimizerState:
         assert self.system is not None, "iCem optimizer requires system to be defined."
+        if opt_state.batched:
+            return self._optimize_batched(initial_state, opt_state)
         p, H, U = self.opt_params, self.horizon, self.action_dim
         dev = initial_state.device if initial_state.is_cuda else torch.device("cuda", torch.cuda.current_device())
         b = self._buffers(dev)
@@ -151,25 +193,130 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                 b["values"].data_ptr(), b["rank"].data_ptr(), st), "mbpo_icem_update_constrained")
         return opt_state.replace(key=key, best_sequence=b["best_seq"].clone(), best_reward=b["best_value"][0].clone())
 
+    def _optimize_batched(self, initial_state: torch.Tensor, opt_state: iCemOptimizerState) -> iCemOptimizerState:
+        """`optimize` for B problems in one launch chain per iteration: problem b equals the single call on (initial_state[b],
+        best_sequence[b], key[b]) bit for bit."""
+        p, H, U = self.opt_params, self.horizon, self.action_dim
+        B = opt_state.best_sequence.shape[0]
+        keys = list(opt_state.key)
+        if len(keys) != B:
+            raise ValueError(f"a batched state needs {B} keys, got {len(keys)}")
+        dev = initial_state.device if initial_state.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        b = self._batched_buffers(dev, B)
+        X, N, NT = self.system.x_dim, b["N"], b["NT"]
+        x0 = initial_state.reshape(B, X).to(dev, torch.float32)
+        b["mean"].zero_()
+        if p.warm_start:
+            b["mean"][:, :-1].copy_(opt_state.best_sequence[:, 1:])
+            b["mean"][:, -1].copy_(opt_state.best_sequence[:, -1])
+        b["std"].fill_(p.init_std)
+        b["best_value"].fill_(float("-inf"))
+        b["best_seq"].copy_(b["mean"])
+        b["prev"].zero_()
+        # the single path's key chain, for all problems at once: seeds[it] = (sampling keys, particle keys), uploaded once
+        ks = K.split_many(keys, 2)
+        carry, next_keys = ks[:, 0], ks[:, 1]
+        seeds = np.empty((p.num_steps, 2, B), dtype=np.uint64)
+        for it in range(p.num_steps):
+            sk = K.split_many(carry, 2)
+            seeds[it, 0], seeds[it, 1] = sk[:, 0], sk[:, 1]
+            carry = K.split_many(sk[:, 0], 2)[:, 0]
+        seeds_dev = torch.from_numpy(seeds.view(np.int64)).to(dev)
+        spec = self.system.rollout_spec(opt_state.system_params, dev)
+        draw = self._batched_ensemble_draws(spec, b)
+        st = _hip.current_stream_ptr()
+        lib = self.lib
+        for it in range(p.num_steps):
+            _hip.check(lib.mbpo_icem_sample_batched(b["mean"].data_ptr(), b["std"].data_ptr(), b["prev"].data_ptr(), b["u_min"].data_ptr(),
+                                                    b["u_max"].data_ptr(), p.num_samples, self.num_prev, H, U, p.num_particles,
+                                                    float(p.exponent), B, seeds_dev[it, 0].data_ptr(), it, b["actions"].data_ptr(),
+                                                    b["cand"].data_ptr(), st), "mbpo_icem_sample_batched")
+            b["obs"].view(B, N, X).copy_(x0[:, None, :].expand(B, N, X))
+            b["first"].copy_(b["obs"])
+            b["steps"].zero_(); b["done"].zero_()
+            pseeds = seeds_dev[it, 1].data_ptr()
+            if draw.get("draw_member"):
+                _hip.check(lib.mbpo_philox_fill_grouped(pseeds, it, _hip.STREAM_MEMBER, H, B, N, 1, 0, draw["E"], draw["member_idx"].data_ptr(), st),
+                           "mbpo_philox_fill_grouped")
+            if draw.get("model_noise") is not None:
+                _hip.check(lib.mbpo_philox_fill_grouped(pseeds, it, _hip.STREAM_MODEL_NOISE, H, B, N * X, 0, 0, 0, draw["model_noise"].data_ptr(),
+                                                        st), "mbpo_philox_fill_grouped")
+            ops.model_rollout(x_dim=X, u_dim=U, actions=b["actions"], obs=b["obs"], first_obs=b["first"], steps=b["steps"], done=b["done"],
+                              n_steps=H, episode_length=2 ** 30, seed=0, offset=it, out=b["rows"], member_idx=draw.get("member_idx"),
+                              model_noise=draw.get("model_noise"), **spec)
+            cost_ptr = None
+            if self.cost_fn is not None:
+                rows3 = b["rows"].reshape(H, NT, -1)
+                obs_t = rows3[:, :, :X].transpose(0, 1)
+                act_t = rows3[:, :, X:X + U].transpose(0, 1)
+                cost = torch.func.vmap(self.cost_fn)(obs_t, act_t)
+                cost = torch.as_tensor(cost, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+                assert cost.numel() == NT, "cost_fn must return one scalar per trajectory"
+                b["cost"] = cost
+                cost_ptr = cost.data_ptr()
+            _hip.check(lib.mbpo_icem_update_batched(
+                b["rows"].data_ptr(), b["rows"].shape[1], X + U, B, b["NC"], p.num_particles, H, U, b["cand"].data_ptr(), p.num_elites,
+                self.num_prev, float(p.alpha), int(self.use_optimism), cost_ptr, float(p.lambda_constraint), int(self.use_pessimism),
+                b["mean"].data_ptr(), b["std"].data_ptr(), b["best_value"].data_ptr(), b["best_seq"].data_ptr(), b["prev"].data_ptr(),
+                b["values"].data_ptr(), b["rank"].data_ptr(), st), "mbpo_icem_update_batched")
+        return opt_state.replace(key=[int(k) for k in next_keys], best_sequence=b["best_seq"].clone(), best_reward=b["best_value"].clone())
+
+    def _batched_ensemble_draws(self, spec: dict, b: dict) -> dict:
+        """A stochastic EnsembleSystem draws its members / model noise in the rollout kernel from the GLOBAL env index, so a rollout
+        over all problems would not reproduce problem b's single-call draws.  Here they are drawn per problem (each under its
+        particle key) into member_idx [H, B*NC*P] / model_noise [H, B*NC*P, x] buffers the rollout consumes instead.  'tsinf'
+        (member = env % E in the kernel) runs as 'ts1' with member_idx = problem-local env % E: the two modes differ only in the
+        member selection in every rollout kernel the open-loop dispatch can pick.  Edits `spec` in place."""
+        if spec.get("system_kind") != _hip.SYS_ENSEMBLE or spec.get("ens_mode", _hip.ENS_MEAN) == _hip.ENS_MEAN:
+            return {}
+        H, X, B, N, dev = self.horizon, self.system.x_dim, b["B"], b["N"], b["dev"]
+        E = int(spec["dyn_spec"].n_nets)
+        out = dict(E=E)
+        if spec["ens_mode"] == _hip.ENS_TSINF:
+            if b.get("tsinf_E") != E:
+                b["tsinf_member"] = (torch.arange(N, device=dev, dtype=torch.int32) % E).repeat(H * B).contiguous()
+                b["tsinf_E"] = E
+            out["member_idx"] = b["tsinf_member"]
+            spec["ens_mode"] = _hip.ENS_TS1
+        else:
+            if "member" not in b:
+                b["member"] = torch.zeros(H * b["NT"], device=dev, dtype=torch.int32)
+            out["member_idx"], out["draw_member"] = b["member"], True
+        if spec.get("ens_sample_noise"):
+            if "model_noise" not in b:
+                b["model_noise"] = torch.zeros(H * b["NT"] * X, device=dev, dtype=torch.float32)
+            out["model_noise"] = b["model_noise"]
+        return out
+
     def act(self, obs: torch.Tensor, opt_state: iCemOptimizerState, evaluate: bool = True) -> Tuple[torch.Tensor, iCemOptimizerState]:
         new_opt_state = self.optimize(initial_state=obs, opt_state=opt_state)
         return new_opt_state.action, new_opt_state
 
 
+def _bound_vec(v, U: int, dev) -> torch.Tensor:
+    """scalar or per-dimension bound -> [U] device vector"""
+    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+    return (t.expand(U) if t.numel() == 1 else t.reshape(U)).contiguous().to(dev)
+
+
 class iCEMOptimizer(BaseOptimizer):
-    """iCEM wrapper with the SAC/PPO optimizers' interface (icem_optimizer.py:259-320)."""
+    """iCEM wrapper with the SAC/PPO optimizers' interface (icem_optimizer.py:259-320).  batch_size=B: plans for B environments at
+    once (init makes a batched state, act(obs [B, x]) returns actions [B, u]); None keeps the single-state interface."""
 
     def __init__(self, horizon: int, opt_params: iCemParams = iCemParams(), system: Optional[System] = None, key: int = K.PRNGKey(0),
-                 **agent_kwargs):
+                 batch_size: Optional[int] = None, **agent_kwargs):
         super().__init__(system, key)
         self.horizon, self.key, self.opt_params = horizon, key, opt_params
+        self.batch_size = None if batch_size is None else int(batch_size)
+        if self.batch_size is not None and self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
         self.agent_class, self.agent_kwargs = iCemTO, agent_kwargs
         if system is not None:
             self.set_system(system)
 
     @property
     def can_act_in_batches(self):
-        return False
+        return self.batch_size is not None
 
     def init(self, key: int, true_buffer_state=None) -> iCemOptimizerState:
         assert self.system is not None, "iCEM optimizer requires system to be defined."
@@ -179,11 +326,14 @@ class iCEMOptimizer(BaseOptimizer):
         if true_buffer_state is None:
             dummy_buffer_key, key = K.split(key, 2)
             true_buffer_state = self.dummy_true_buffer_state(dummy_buffer_key)
-        agent_state = self.agent.init(key)
+        agent_state = self.agent.init(key, batch_size=self.batch_size)
         return agent_state.replace(true_buffer_state=true_buffer_state)
 
     def act(self, obs: torch.Tensor, opt_state: iCemOptimizerState, evaluate: bool = True) -> Tuple[torch.Tensor, iCemOptimizerState]:
         assert self.system is not None, "iCEM optimizer requires system to be defined."
+        if self.batch_size is not None:
+            action, opt_state = self.agent.act(obs.reshape(self.batch_size, -1), opt_state, evaluate)
+            return action.reshape(self.batch_size, -1), opt_state
         action, opt_state = self.agent.act(obs.reshape(-1), opt_state, evaluate)
         return action.reshape(1, -1), opt_state
 

@@ -385,6 +385,41 @@ def main():
 
     if want("icem_case"): attempt(icem_case, 20, 100)
 
+    # ---------------------------------------------------------------- batched MPC: one optimize for B problems vs B single calls
+    def icem_batched_case(H):
+        from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
+        from mbpo.systems import PendulumSystem
+        p = iCemParams()
+        system = PendulumSystem()
+        X, U = system.x_dim, system.u_dim
+        opt = iCemTO(horizon=H, action_dim=U, opt_params=p, system=system)
+        cfg = {"num_samples": p.num_samples, "num_particles": p.num_particles, "num_elites": p.num_elites, "num_steps": p.num_steps,
+               "horizon": H, "x": X, "u": U, "system": "Pendulum"}
+        single = {}
+        st1 = opt.init(0)
+        x1 = torch.tensor([-1.0, 0.0, 0.0], device=dev)
+        for B in (8, 64):      # B sequential single-problem calls (the Python loop this replaces), same session
+            t = timed(lambda: [opt.optimize(x1, st1) for _ in range(B)], 3, warm=1)
+            single[B] = t
+            log(f"icem {B} sequential optimize: {t * 1e3:.2f} ms")
+        opt._bufs = None
+        for B in (1, 8, 64, 256):
+            st = opt.init(0, batch_size=B)
+            x0 = x1.expand(B, X).contiguous()
+            t = timed(lambda: opt.optimize(x0, st), 10 if B <= 64 else 3, warm=2)
+            row = {"kernel": "iCemTO.optimize batched (B problems, one launch chain)",
+                   "entry": "mbpo_icem_sample_batched + mbpo_model_rollout + mbpo_icem_update_batched x num_steps",
+                   "config": dict(cfg, B=B), "eager_us": t * 1e6, "bound": "launch" if B <= 8 else "rollout",
+                   "note": "HIP-event time of one eager optimize call (host key chain, one seed upload, 3 launches per iteration)"}
+            if B in single:
+                row["sequential_single_us"] = single[B] * 1e6
+                row["speedup_vs_sequential"] = single[B] / t
+            out.append(row)
+            log(f"icem batched optimize B={B}: {t * 1e3:.3f} ms" + (f"  ({single[B] / t:.1f}x {B} single calls)" if B in single else ""))
+            opt._bbufs = None
+
+    if want("icem_batched_case"): attempt(icem_batched_case, 20)
+
     res = {"device": torch.cuda.get_device_name(0), "roofs": {"hbm_GBs": HBM_PEAK_GBS, "mfma_f32_TFLOPs": MFMA_F32_PEAK_TF},
            "note": "device_us = HIP-event average per call with the calls captured into a hipGraph and replayed (device time, inputs resident in HBM; multi-launch ops timed whole); eager_us = the same call issued from Python",
            "kernels": out}
