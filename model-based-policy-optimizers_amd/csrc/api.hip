@@ -136,3 +136,40 @@ extern "C" int mbpo_philox_fill_grouped(const uint64_t *seeds, uint64_t offset, 
   MBPO_CHECK_LAUNCH("philox_fill_grouped");
   return MBPO_OK;
 }
+
+// Test hook (not part of include/mbpo_hip.h): y[i] = helper fn (x[i]) for the fast_math.hpp helpers the elementwise sections use —
+// 0 fm_exp, 1 fm_log, 2 fm_softplus, 3 fm_tanh, 4 fm_atanh, 5 fast_sigmoid, 6 swish (act_apply), 7 swish' (act_grad),
+// 8 fm_softplus_fast, 9 fm_tanh_fast.
+// tests/test_gpu_fastmath.py sweeps each against fp64.
+enum { FM_EXP, FM_LOG, FM_SOFTPLUS, FM_TANH, FM_ATANH, FM_SIGMOID, FM_SWISH, FM_SWISH_GRAD, FM_SOFTPLUS_FAST, FM_TANH_FAST, FM_N };
+__global__ void __launch_bounds__(256) k_debug_eval_fastmath(int fn, const float *x, float *y, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float v = x[i];
+    float r;
+    switch (fn) {
+      case FM_EXP: r = fm_exp(v); break;
+      case FM_LOG: r = fm_log(v); break;
+      case FM_SOFTPLUS: r = fm_softplus(v); break;
+      case FM_TANH: r = fm_tanh(v); break;
+      case FM_ATANH: r = fm_atanh(v); break;
+      case FM_SIGMOID: r = fast_sigmoid(v); break;
+      case FM_SWISH: r = act_apply(v, MBPO_ACT_SWISH); break;
+      case FM_SWISH_GRAD: r = act_grad(v, MBPO_ACT_SWISH); break;
+      case FM_SOFTPLUS_FAST: r = fm_softplus_fast(v); break;
+      default: r = fm_tanh_fast(v); break;
+    }
+    y[i] = r;
+  }
+}
+
+extern "C" int mbpo_debug_eval_fastmath(int fn, const float *x, float *y, int64_t n, void *stream) {
+  MBPO_REQUIRE(fn >= 0 && fn < FM_N, MBPO_ERR_ARG, "debug_eval_fastmath: unknown helper fn=%d (0..%d)", fn, FM_N - 1);
+  MBPO_REQUIRE(n >= 0, MBPO_ERR_ARG, "debug_eval_fastmath: n=%lld < 0", (long long)n);
+  if (n == 0) return MBPO_OK;
+  MBPO_REQUIRE(x && y, MBPO_ERR_ARG, "debug_eval_fastmath: null pointer");
+  const long long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_debug_eval_fastmath, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, fn, x, y,
+                     (long long)n);
+  MBPO_CHECK_LAUNCH("debug_eval_fastmath");
+  return MBPO_OK;
+}

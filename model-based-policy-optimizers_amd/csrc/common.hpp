@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/mbpo_hip.h"
+#include "fast_math.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -68,13 +69,7 @@ struct MlpDev {
 int mbpo_make_mlp_dev(const mbpo_mlp_desc *d, MlpDev *out, const char *name);
 
 // ---------------------------------------------------------------- math
-// sigmoid on the hardware transcendental path: v_exp_f32 (2^x) + v_rcp_f32, both ~1 ulp.  One wave evaluates 16
-// activations per layer, so the libm expf + IEEE-division expansion (~50 VALU instructions per element) cost as much
-// as the layer's MFMAs; this form is ~5 instructions.  |relative error| <~ 1e-6 for |v| <= 20 (tests state tolerances).
-__device__ __forceinline__ float fast_sigmoid(float v) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * v));
-}
-
+// fast_sigmoid and the other hardware-transcendental helpers: fast_math.hpp
 __device__ __forceinline__ float act_apply(float v, int act) {
   // swish(x) = x * sigmoid(x)  (flax.linen.swish); relu; tanh
   if (act == MBPO_ACT_SWISH) return v * fast_sigmoid(v);

@@ -285,16 +285,9 @@ __global__ void __launch_bounds__(1024) k_moments_fused(const float *x, long lon
 }
 
 // ------------------------------------------------------------------------------------------------ loss fwd/bwd
-// hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp; as sac.hip and rollout.hip): the loss section runs on a few
-// lanes while the other waves of the workgroup wait at its barrier, so its instruction count is tile latency.  libm's
-// expf / log1pf / logf / tanhf are 30-60 instructions each.
-__device__ __forceinline__ float pp_fexp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float pp_flog(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float pp_fsoftplus(float x) { return fmaxf(x, 0.0f) + pp_flog(1.0f + pp_fexp(-fabsf(x))); }
-__device__ __forceinline__ float pp_ftanh(float x) {
-  const float e = pp_fexp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
+// The loss section runs on a few lanes while the other waves of the workgroup wait at its barrier, so its instruction count is tile
+// latency: it takes its transcendentals from fast_math.hpp (libm's expf / log1pf / logf / tanhf are 30-60 instructions each).
+
 // The advantage moments from the per-workgroup partials {n_i, mean_i, M2_i} of k_ppo_values_gae (Chan et al.: mean = sum n_i mean_i / M,
 // M2 = sum M2_i + sum n_i (mean_i - mean)^2), one workgroup, fixed order.  A launch of its own: k_ppo_fwd_bwd<64,2> sits at 128 VGPRs
 // with ~50 spilled, and ANY code added to it — this combine inlined, behind a barrier-free LDS hand-off, or behind a noinline call —
@@ -428,13 +421,13 @@ __global__ void __launch_bounds__(256 * SP, (H == 64 && SP == 2) ? 4 : 1) k_ppo_
       const int r = idx / U, d = idx - r * U;
       const float *row = s_row + r * D;
       const float loc = y_pi[r * ld_y + d], raw = y_pi[r * ld_y + U + d];
-      const float sg = pp_fsoftplus(raw) + 0.001f;
+      const float sg = fm_softplus(raw) + 0.001f;
       const float z = row[2 * X + U + 3 + d];                      // raw_action
       const float q = (z - loc) / sg;
-      const float lsg = pp_flog(sg);
-      s_lpt[idx] = -0.5f * q * q - lsg - LOG_SQRT_2PI - 2.0f * (LOG_2 - z - pp_fsoftplus(-2.0f * z));   // log_prob (:91-92)
+      const float lsg = fm_log(sg);
+      s_lpt[idx] = -0.5f * q * q - lsg - LOG_SQRT_2PI - 2.0f * (LOG_2 - z - fm_softplus(-2.0f * z));   // log_prob (:91-92)
       const float zf = loc + sg * s_eps[idx];
-      s_ent[idx] = 0.5f + LOG_SQRT_2PI + lsg + 2.0f * (LOG_2 - zf - pp_fsoftplus(-2.0f * zf));          // entropy (:117)
+      s_ent[idx] = 0.5f + LOG_SQRT_2PI + lsg + 2.0f * (LOG_2 - zf - fm_softplus(-2.0f * zf));          // entropy (:117)
     }
     __syncthreads();
     if (tid < 16) {
@@ -450,7 +443,7 @@ __global__ void __launch_bounds__(256 * SP, (H == 64 && SP == 2) ? 4 : 1) k_ppo_
         lp_t += s_lpt[r * U + d];
         ent += s_ent[r * U + d];
       }
-      const float rho = pp_fexp(lp_t - lp_b);                                                             // :103
+      const float rho = fm_exp(lp_t - lp_b);                                                             // :103
       const float lo = 1.f - A.clip_eps, hi = 1.f + A.clip_eps;
       const float s1 = rho * adv, s2 = fminf(fmaxf(rho, lo), hi) * adv;
       // d min(s1,s2)/d rho: inside the clip range s1 == s2 (tie, both branches carry adv); outside only s1 can carry it
@@ -473,11 +466,11 @@ __global__ void __launch_bounds__(256 * SP, (H == 64 && SP == 2) ? 4 : 1) k_ppo_
       const float g_lp = s_scal[48 + r];
       const float g_ent = ok ? -A.entropy_cost * invM : 0.f;        // d entropy_loss / d entropy_i
       const float loc = y_pi[r * ld_y + d], raw = y_pi[r * ld_y + U + d];
-      const float sg = pp_fsoftplus(raw) + 0.001f;
+      const float sg = fm_softplus(raw) + 0.001f;
       const float z = row[2 * X + U + 3 + d];
       const float q = (z - loc) / sg;
       const float eps = s_eps[idx];
-      const float th = pp_ftanh(loc + sg * eps);
+      const float th = fm_tanh(loc + sg * eps);
       // lp_t: d/dloc = q/sg, d/dsigma = (q*q - 1)/sg ; entropy: d/dloc = -2 tanh(zf), d/dsigma = 1/sg - 2 tanh(zf) eps
       const float g_loc = g_lp * (q / sg) + g_ent * (-2.f * th);
       const float g_sig = g_lp * ((q * q - 1.f) / sg) + g_ent * (1.f / sg - 2.f * th * eps);

@@ -8,13 +8,6 @@
 namespace {
 constexpr float P_LOG_2 = 0.69314718055994530942f;
 constexpr float P_LOG_SQRT_2PI = 0.91893853320467274178f;
-__device__ __forceinline__ float p_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float p_log(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float p_softplus(float x) { return fmaxf(x, 0.0f) + p_log(1.0f + p_exp(-fabsf(x))); }
-__device__ __forceinline__ float p_tanh(float x) {
-  const float e = p_exp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
 
 struct PrepArgs {
   const float *data, *mean, *std;
@@ -77,18 +70,18 @@ __global__ void __launch_bounds__(256) k_ppol_heads(HeadArgs A) {
     float lp_t = 0.f, ent = 0.f;
     for (int d = 0; d < U; ++d) {
       const float loc = A.outp[i * 2 * U + d], raw = A.outp[i * 2 * U + U + d];
-      const float sg = p_softplus(raw) + 0.001f;
+      const float sg = fm_softplus(raw) + 0.001f;
       const float z = row[2 * X + U + 3 + d];
-      const float q = (z - loc) / sg, lsg = p_log(sg);
-      lp_t += -0.5f * q * q - lsg - P_LOG_SQRT_2PI - 2.0f * (P_LOG_2 - z - p_softplus(-2.0f * z));      // :91-92
+      const float q = (z - loc) / sg, lsg = fm_log(sg);
+      lp_t += -0.5f * q * q - lsg - P_LOG_SQRT_2PI - 2.0f * (P_LOG_2 - z - fm_softplus(-2.0f * z));      // :91-92
       const long long nidx = i * U + d;
       const float eps = A.ent_noise ? A.ent_noise[nidx] : philox_normal(rk.seed, rk.offset, MBPO_STREAM_ENTROPY, (unsigned long long)nidx);
       const float zf = loc + sg * eps;
-      ent += 0.5f + P_LOG_SQRT_2PI + lsg + 2.0f * (P_LOG_2 - zf - p_softplus(-2.0f * zf));              // :117
+      ent += 0.5f + P_LOG_SQRT_2PI + lsg + 2.0f * (P_LOG_2 - zf - fm_softplus(-2.0f * zf));              // :117
     }
     const float lp_b = row[2 * X + U + 2];
     const float adv = (A.adv[i] - adv_mean) * adv_istd, vs = A.vs[i], v = A.values[i];
-    const float rho = p_exp(lp_t - lp_b);                                                                // :103
+    const float rho = fm_exp(lp_t - lp_b);                                                                // :103
     const float lo = 1.f - A.clip_eps, hi = 1.f + A.clip_eps;
     const float s1 = rho * adv, s2 = fminf(fmaxf(rho, lo), hi) * adv;
     const bool inside = (rho >= lo) && (rho <= hi);
@@ -100,12 +93,12 @@ __global__ void __launch_bounds__(256) k_ppol_heads(HeadArgs A) {
     A.dy_v[i] = -(vs - v) * invM;                                                                        // :112-114
     for (int d = 0; d < U; ++d) {
       const float loc = A.outp[i * 2 * U + d], raw = A.outp[i * 2 * U + U + d];
-      const float sg = p_softplus(raw) + 0.001f;
+      const float sg = fm_softplus(raw) + 0.001f;
       const float z = row[2 * X + U + 3 + d];
       const float q = (z - loc) / sg;
       const long long nidx = i * U + d;
       const float eps = A.ent_noise ? A.ent_noise[nidx] : philox_normal(rk.seed, rk.offset, MBPO_STREAM_ENTROPY, (unsigned long long)nidx);
-      const float th = p_tanh(loc + sg * eps);
+      const float th = fm_tanh(loc + sg * eps);
       A.dy_pi[i * 2 * U + d] = g_lp * (q / sg) + g_ent * (-2.f * th);
       A.dy_pi[i * 2 * U + U + d] = (g_lp * ((q * q - 1.f) / sg) + g_ent * (1.f / sg - 2.f * th * eps)) * fast_sigmoid(raw);
     }

@@ -33,14 +33,6 @@ namespace {
 #define LOG_SQRT_2PI 0.91893853320467274178f
 #define LOG_2 0.69314718055994530942f
 
-__device__ __forceinline__ float pl_fexp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float pl_flog(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float pl_fsoftplus(float x) { return fmaxf(x, 0.0f) + pl_flog(1.0f + pl_fexp(-fabsf(x))); }
-__device__ __forceinline__ float pl_ftanh(float x) {
-  const float e = pl_fexp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
-
 template <int X, int NH>      // NH: 64 x 64 layers per network — 2 (64 x 3 networks) or 1 (64 x 2: tests/test_ppo.py, the reference's experiments)
 struct PNet {
   static constexpr int D = 2 * X + 6;                                     // obs, action, reward, discount, next_obs, log_prob, raw_action, truncation
@@ -226,23 +218,23 @@ __global__ void __launch_bounds__(512) k_ppo_lean(const PpoLeanArgs A) {
         const float z = s_aux[r * 4 + 0], lp_b = s_aux[r * 4 + 1];
         const float eps = smem[P_EPS + 16 * par + r];
         const float adv = ok ? (s_aux[r * 4 + 2] - adv_mean) * adv_istd : 0.f;
-        const float sg = pl_fsoftplus(raw) + 0.001f;
+        const float sg = fm_softplus(raw) + 0.001f;
         const float q = (z - loc) / sg;
-        const float lsg = pl_flog(sg);
-        const float lpt = -0.5f * q * q - lsg - LOG_SQRT_2PI - 2.0f * (LOG_2 - z - pl_fsoftplus(-2.0f * z));      // log_prob (:91-92)
+        const float lsg = fm_log(sg);
+        const float lpt = -0.5f * q * q - lsg - LOG_SQRT_2PI - 2.0f * (LOG_2 - z - fm_softplus(-2.0f * z));      // log_prob (:91-92)
         const float zf = loc + sg * eps;
-        const float ent_d = 0.5f + LOG_SQRT_2PI + lsg + 2.0f * (LOG_2 - zf - pl_fsoftplus(-2.0f * zf));          // entropy (:117)
+        const float ent_d = 0.5f + LOG_SQRT_2PI + lsg + 2.0f * (LOG_2 - zf - fm_softplus(-2.0f * zf));          // entropy (:117)
         float lp_t = 0.f, ent = 0.f;
         lp_t += lpt;
         ent += ent_d;
-        const float rho = pl_fexp(lp_t - lp_b);                                                                   // :103
+        const float rho = fm_exp(lp_t - lp_b);                                                                   // :103
         const float lo = 1.f - A.clip_eps, hi = 1.f + A.clip_eps;
         const float s1 = rho * adv, s2 = fminf(fmaxf(rho, lo), hi) * adv;
         const bool inside = (rho >= lo) && (rho <= hi);
         const float w = inside ? 1.f : (s1 < s2 ? 1.f : 0.f);
         const float g_lp = ok ? -invM * rho * adv * w : 0.f;
         const float g_ent = ok ? -A.entropy_cost * invM : 0.f;
-        const float th = pl_ftanh(loc + sg * eps);
+        const float th = fm_tanh(loc + sg * eps);
         const float g_loc = g_lp * (q / sg) + g_ent * (-2.f * th);
         const float g_sig = g_lp * ((q * q - 1.f) / sg) + g_ent * (1.f / sg - 2.f * th * eps);
         if (lane < 16) {

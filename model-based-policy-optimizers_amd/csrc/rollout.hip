@@ -575,7 +575,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
           const int r = idx & 15, d = idx >> 4;
           const long long env = env0 + r;
           const float loc = s_y[r * ld_y + d], raw = s_y[r * ld_y + U + d];
-          const float sigma = ro_fsoftplus(raw) + 0.001f;
+          const float sigma = fm_softplus_fast(raw) + 0.001f;
           float eps = 0.f;
           if (!A.deterministic && env < N) {
             const long long nidx = ((long long)s * N + env) * U + d;
@@ -583,14 +583,14 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
                                  : philox_normal(rng_seed, rng_off, MBPO_STREAM_POLICY_NOISE, (unsigned long long)nidx);
           }
           const float z = loc + sigma * eps;
-          float a = ro_ftanh(z);
+          float a = fm_tanh_fast(z);
           if (A.action_clip > 0.f) a = fminf(fmaxf(a, -A.action_clip), A.action_clip);
           s_xu[r * ld_xu + X + d] = a;
           s_row[r * D + X + d] = a;
           if (A.ppo_extras) {
             // log N(z; loc, sigma) - log|d tanh/dz|, per action dim; summed in section D
-            const float lp = -0.5f * eps * eps - ro_flog(sigma) - 0.91893853320467274178f;
-            const float ldj = 2.0f * (0.69314718055994530942f - z - ro_fsoftplus(-2.0f * z));
+            const float lp = -0.5f * eps * eps - fm_log(sigma) - 0.91893853320467274178f;
+            const float ldj = 2.0f * (0.69314718055994530942f - z - fm_softplus_fast(-2.0f * z));
             s_row[r * D + 2 * X + U + 2 + 1 + d] = z;               // raw_action
             s_scr[16 * X + r * U + d] = lp - ldj;                   // per-dim log-prob (behind the next-state scratch)
           }

@@ -66,16 +66,16 @@ __device__ __forceinline__ void rl_sample(const RolloutArgs &A, const f32x4 acc,
                                           float *s_lp, int D, int r) {
   constexpr int U = 1;
   const float loc = acc[0] + bo[0], raw = acc[1] + bo[1];
-  const float sigma = ro_fsoftplus(raw) + 0.001f;
+  const float sigma = fm_softplus_fast(raw) + 0.001f;
   const float z = loc + sigma * eps;
-  float a = ro_ftanh(z);
+  float a = fm_tanh_fast(z);
   if (A.action_clip > 0.f) a = fminf(fmaxf(a, -A.action_clip), A.action_clip);
   s_xu[r * LDX + X] = a;
   s_row[r * D + X] = a;
   if (A.ppo_extras) {
     // log N(z; loc, sigma) - log|d tanh/dz|
-    const float lp = -0.5f * eps * eps - ro_flog(sigma) - 0.91893853320467274178f;
-    const float ldj = 2.0f * (0.69314718055994530942f - z - ro_fsoftplus(-2.0f * z));
+    const float lp = -0.5f * eps * eps - fm_log(sigma) - 0.91893853320467274178f;
+    const float ldj = 2.0f * (0.69314718055994530942f - z - fm_softplus_fast(-2.0f * z));
     s_row[r * D + 2 * X + U + 2 + 1] = z;               // raw_action
     s_lp[r] = 0.f + (lp - ldj);                          // (the generic kernel sums the action dims from 0)
   }

@@ -58,11 +58,4 @@ __device__ __forceinline__ float pendulum_reward(const float *x, float u, const 
   return -(angle_cost * (d * d) + 0.1f * (omega * omega)) - control_cost * (u * u);
 }
 
-__device__ __forceinline__ float ro_fexp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float ro_flog(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float ro_fsoftplus(float x) { return fmaxf(x, 0.0f) + ro_flog(1.0f + ro_fexp(-fabsf(x))); }
-__device__ __forceinline__ float ro_ftanh(float x) {
-  const float e = ro_fexp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
 

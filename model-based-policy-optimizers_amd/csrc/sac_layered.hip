@@ -9,24 +9,17 @@ namespace {
 constexpr float L_LOG_2 = 0.69314718055994530942f;
 constexpr float L_LOG_SQRT_2PI = 0.91893853320467274178f;
 
-__device__ __forceinline__ float l_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float l_log(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float l_softplus(float x) { return fmaxf(x, 0.0f) + l_log(1.0f + l_exp(-fabsf(x))); }
-__device__ __forceinline__ float l_tanh(float x) {
-  const float e = l_exp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
 // NormalTanh pieces per action dimension (sac/parametric_distribution.py:66-73,117-120) — the forms of k_sac_fwd_bwd
 struct LSample {
   float a, sigma, lp;
 };
 __device__ __forceinline__ LSample l_sample(float loc, float raw, float eps) {
   LSample o;
-  o.sigma = l_softplus(raw) + 0.001f;
+  o.sigma = fm_softplus(raw) + 0.001f;
   const float z = loc + o.sigma * eps;
-  o.a = l_tanh(z);
-  const float ldj = 2.0f * (L_LOG_2 - z - l_softplus(-2.0f * z));
-  o.lp = -0.5f * eps * eps - l_log(o.sigma) - L_LOG_SQRT_2PI - ldj;
+  o.a = fm_tanh(z);
+  const float ldj = 2.0f * (L_LOG_2 - z - fm_softplus(-2.0f * z));
+  o.lp = -0.5f * eps * eps - fm_log(o.sigma) - L_LOG_SQRT_2PI - ldj;
   return o;
 }
 __device__ __forceinline__ float l_floor_divide(float x1, float x2) {

@@ -97,22 +97,14 @@ struct ActSample {
   float z, a, sigma, lp;
 };
 // The elementwise sections run on ONE wave while 15 wait at the barrier, and a lone wave issues one instruction per 4 cycles:
-// libm's expf/log1pf/tanhf/logf (~30-60 instructions each) made one sample cost ~1400 cycles.  These forms use the hardware
-// v_exp_f32 / v_log_f32 / v_rcp_f32 (~1 ulp each); absolute errors stay ~1e-7, far inside the parity tolerances.
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896340736f * x); }
-__device__ __forceinline__ float flog(float x) { return 0.69314718055994530942f * __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float fsoftplus(float x) { return fmaxf(x, 0.0f) + flog(1.0f + fexp(-fabsf(x))); }
-__device__ __forceinline__ float ftanh(float x) {
-  const float e = fexp(2.0f * fminf(fmaxf(x, -15.0f), 15.0f));
-  return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
-}
+// libm's expf/log1pf/tanhf/logf (~30-60 instructions each) made one sample cost ~1400 cycles.  Hence fast_math.hpp's helpers.
 __device__ __forceinline__ ActSample normal_tanh_sample(float loc, float raw, float eps) {
   ActSample o;
-  o.sigma = fsoftplus(raw) + 0.001f;
+  o.sigma = fm_softplus_fast(raw) + 0.001f;
   o.z = loc + o.sigma * eps;
-  o.a = ftanh(o.z);
+  o.a = fm_tanh_fast(o.z);
   // log N(z; loc, sigma) with (z-loc)/sigma == eps, minus Tanh.forward_log_det_jacobian(z)
-  const float ldj = 2.0f * (LOG_2 - o.z - fsoftplus(-2.0f * o.z));
-  o.lp = -0.5f * eps * eps - flog(o.sigma) - LOG_SQRT_2PI - ldj;
+  const float ldj = 2.0f * (LOG_2 - o.z - fm_softplus_fast(-2.0f * o.z));
+  o.lp = -0.5f * eps * eps - fm_log(o.sigma) - LOG_SQRT_2PI - ldj;
   return o;
 }

@@ -96,9 +96,9 @@ def test_size_queries_and_validation_without_a_device(lib):
 
 
 def test_test_hooks_without_a_device(lib):
-    """The kernel-selection hooks the GPU tests use are exported but not declared (not part of the API), reject unknown modes, and
-    mbpo_debug_set_bptt_zstore(0) removes exactly the z store from the BPTT workspace: 1024 floats per (trajectory tile, step,
-    member, hidden layer)."""
+    """The kernel-selection hooks and the fast-math helper hook the GPU tests use are exported but not declared (not part of the API),
+    reject unknown modes or helpers, and mbpo_debug_set_bptt_zstore(0) removes exactly the z store from the BPTT workspace: 1024
+    floats per (trajectory tile, step, member, hidden layer)."""
     from mbpo import _hip
     for name in ("mbpo_debug_set_icem_update", "mbpo_debug_set_bptt_zstore"):
         assert hasattr(lib, name) and name not in _declared()
@@ -106,6 +106,14 @@ def test_test_hooks_without_a_device(lib):
         getattr(lib, name).restype = C.c_int
     assert lib.mbpo_debug_set_icem_update(2) < 0 and b"mode" in lib.mbpo_last_error()
     assert lib.mbpo_debug_set_bptt_zstore(1) < 0 and b"mode" in lib.mbpo_last_error()
+    # the fast-math helper hook (tests/test_gpu_fastmath.py): an unknown helper is refused before anything is launched
+    assert hasattr(lib, "mbpo_debug_eval_fastmath") and "mbpo_debug_eval_fastmath" not in _declared()
+    lib.mbpo_debug_eval_fastmath.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.mbpo_debug_eval_fastmath.restype = C.c_int
+    for fn in (-1, 10, 1 << 20):
+        assert lib.mbpo_debug_eval_fastmath(fn, None, None, 4, None) < 0 and b"unknown helper" in lib.mbpo_last_error()
+    assert lib.mbpo_debug_eval_fastmath(2, None, None, -1, None) < 0 and b"n=-1" in lib.mbpo_last_error()
+    assert lib.mbpo_debug_eval_fastmath(2, None, None, 4, None) < 0 and b"null" in lib.mbpo_last_error()
     X, U, H, n, E = 4, 1, 5, 48, 5
     d = _hip.BpttDesc()
     d.x_dim, d.u_dim, d.horizon, d.n = X, U, H, n
