@@ -5,7 +5,10 @@
                       ->  SACOptimizer on EnsembleSystem (short model rollouts branched from true states + SAC updates)
                       ->  the policy acts on the TRUE PendulumSystem.
 
-    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000]
+    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward]
+
+--learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
+so the model rollouts never see the Pendulum's reward formula.
 """
 from __future__ import annotations
 
@@ -40,10 +43,10 @@ def true_return(system, optimizer, opt_state, steps=200):
     return total
 
 
-def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True):
+def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
-    from mbpo.systems import EnsembleDynamics, EnsembleSystem, PendulumReward, PendulumSystem
+    from mbpo.systems import EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
     from mbpo.types import Transition
     dev = torch.device("cuda", torch.cuda.current_device())
     gen = torch.Generator().manual_seed(seed)
@@ -53,8 +56,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                        discount=torch.tensor(0.99, device=dev), next_observation=s0.x_next)
     true_buffer = UniformSamplingQueue(max_replay_size=iters * n_true, dummy_data_sample=dummy, sample_batch_size=1, device=dev)
     tbs = true_buffer.init(seed)
-    dyn = EnsembleDynamics(3, 1, n_members=5)
-    model = EnsembleSystem(dyn, PendulumReward(), mode="mean", predict_delta=True)
+    dyn = EnsembleDynamics(3, 1, n_members=5, learn_reward=learn_reward)
+    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), mode="mean", predict_delta=True)
     dyn_params = dyn.init_params(seed + 1)
     history = []
     for it in range(iters):
@@ -70,7 +73,10 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                  max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16, deterministic_eval=True, tau=0.005,
                                  num_env_steps_between_updates=5)
         state = optimizer.init(key=seed + 3, true_buffer_state=tbs)
-        state = state.replace(system_params=state.system_params.replace(dynamics_params=dyn_params))
+        sp = state.system_params.replace(dynamics_params=dyn_params)
+        if learn_reward:
+            sp = sp.replace(reward_params=dyn_params)      # the learned reward's parameters are the model's
+        state = state.replace(system_params=sp)
         out = optimizer.train(opt_state=state)
         ret = true_return(true_system, optimizer, out.optimizer_state)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
@@ -86,5 +92,6 @@ if __name__ == "__main__":
     ap.add_argument("--model-steps", type=int, default=1500)
     ap.add_argument("--sac-steps", type=int, default=40_000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--learn-reward", action="store_true")
     a = ap.parse_args()
-    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed)
+    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward)

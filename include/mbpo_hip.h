@@ -108,10 +108,19 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
 
 #define MBPO_REWARD_PENDULUM 0  /* rewards/pendulum_reward.py:27-42; params [angle_cost, control_cost, target_angle] */
 #define MBPO_REWARD_QUADRATIC 1 /* -(sum q_d (x_d - t_d)^2) - sum r_d u_d^2; params [t[x], q[x], r[u]] */
+/* Learned reward: the ensemble predicts it.  Needs MBPO_SYS_ENSEMBLE with member output [mu_x (x) | raw_x (x) | mu_r | raw_r]
+ * (dout = 2x + 2; every state column keeps its offset).  The reward is the head at the pre-step (x, u), like the analytic rewards:
+ *   MBPO_ENS_MEAN : r = mean_e mu_r,e
+ *   TS1 / TSINF   : r = mu_r,m with m the member the state takes at that (env, step) (same member_idx entry / Philox MEMBER draw)
+ * summed over action_repeat.  ens_sample_noise perturbs the state only: the reward carries no noise (raw_r is trained by
+ * mbpo_ens_nll_grads and reported as the reward's std by the host API, never read by a rollout).  reward_params may be NULL.
+ * The analytic rewards accept a 2x + 2 ensemble too and ignore its reward head. */
+#define MBPO_REWARD_LEARNED 2
 
 typedef struct mbpo_rollout_desc {
   mbpo_mlp_desc policy;   /* [x_dim] -> [2*u_dim] */
-  mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std); ignored for MBPO_SYS_PENDULUM */
+  mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std) or [2*x_dim+2] (+ reward mean, raw std: MBPO_REWARD_LEARNED);
+                             ignored for MBPO_SYS_PENDULUM */
   int32_t x_dim, u_dim;
   int64_t n_envs;          /* N */
   int32_t n_steps;         /* S = num_env_steps_between_updates (SAC) or unroll_length (PPO) */
@@ -419,6 +428,8 @@ int mbpo_ppo_step(const mbpo_ppo_desc *d, void *stream);
  *                   or Philox(..., stream MODEL_NOISE, (i*H + t)*x + c)),  base = x if ens_predict_delta else 0.
  * The gradient is the pathwise one: only member m receives dL/dmu_m = dL/dx' (and dL/draw_m = dL/dx' * eps * sigmoid(raw_m));
  * the member draw itself is not differentiated.  member_idx values in [0, E) are the caller's contract.
+ * MBPO_REWARD_LEARNED: r_t is read from the reward head (column 2x) as mbpo_model_rollout reads it, and dL/dr_t enters the member
+ * output gradient at that column (divided by E in MBPO_ENS_MEAN; the selected member alone in the TS modes).
  */
 typedef struct mbpo_bptt_desc {
   int32_t x_dim, u_dim, horizon;
@@ -431,7 +442,8 @@ typedef struct mbpo_bptt_desc {
   const float *actor_params;                 /* [P] */
   const float *target_critic_params;         /* [2*C] = [critic_1 | critic_2] */
   int32_t system_kind;                       /* MBPO_SYS_* */
-  mbpo_mlp_desc dynamics;                    /* ensemble ([x+u] -> [x] or [2x] = [mu, raw std]), ignored for MBPO_SYS_PENDULUM */
+  mbpo_mlp_desc dynamics;                    /* ensemble ([x+u] -> [x] or [2x] = [mu, raw std], or [2x+2] with the reward head of
+                                                MBPO_REWARD_LEARNED), ignored for MBPO_SYS_PENDULUM */
   int32_t ens_predict_delta;
   int32_t reward_kind;                       /* MBPO_REWARD_* */
   const float *reward_params, *sys_params;
@@ -514,6 +526,9 @@ int mbpo_soft_update(const float *target, const float *online, float *out, int64
  *   loss_e = mean_b sum_d [ 0.5 ((x'_d - mean_d)/sigma_d)^2 + log sigma_d ].
  * rows: [R, row_len] transitions (x at column 0, u at x_dim, next_obs at next_obs_off); idx: [E, batch] row indices (one
  * bootstrapped minibatch per member); grads [E * n_params] in the dynamics' flat layout; metrics [E] = loss_e.
+ * reward_off >= 0 (a [x+u] -> [2x+2] ensemble, MBPO_REWARD_LEARNED): the reward head is fitted too; the target r = row[reward_off]
+ * (never delta-encoded), sigma_r = softplus(raw_r) + min_std, and loss_e gains mean_b [ 0.5 ((r - mu_r)/sigma_r)^2 + log sigma_r ].
+ * reward_off = -1: no reward term (a 2x + 2 ensemble then gets zero gradient on its reward head).
  * Apply with mbpo_adamw_step on the whole flat vector (members are independent, AdamW is elementwise).  Hidden width 64. */
 typedef struct mbpo_ens_train_desc {
   int32_t x_dim, u_dim;
@@ -525,6 +540,9 @@ typedef struct mbpo_ens_train_desc {
   int32_t predict_delta;
   float min_std;
   float *grads, *metrics, *workspace;
+  /* Callers MUST set reward_off: a zero-initialised descriptor asks for the reward from column 0 (an error on a 2x net, a wrong
+   * target on a 2x+2 net).  Set -1 for no reward head. */
+  int32_t reward_off;     /* column of the reward target in rows, or -1: no reward head fitted */
 } mbpo_ens_train_desc;
 
 int64_t mbpo_ens_nll_workspace_floats(const mbpo_ens_train_desc *d);

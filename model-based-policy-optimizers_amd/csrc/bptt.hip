@@ -154,7 +154,10 @@ __device__ __forceinline__ float reward_grad_comp(const BpttArgs &A, const float
 // TS: the trajectory-sampling instantiation ('ts1' / 'tsinf').  A uniform branch on A.ts alone kept the mean path's results but not its
 // register allocation (+3 VGPRs, +30 SGPR spills, +1 % per BASELINE config-5 train step); with TS = false every TS branch is compiled
 // out and the mean kernel is the one it was.
-template <int H, bool WIDE, bool TS>
+// LR: MBPO_REWARD_LEARNED — the reward is read from the members' reward head (column 2X) in the forward sweep and its gradient enters the
+// member output gradient (E_DYE); reward_grad_comp is skipped.  A template flag for the same reason as TS: the other instantiations keep
+// their register allocation.
+template <int H, bool WIDE, bool TS, bool LR>
 __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -189,6 +192,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   float *s_eps = s_a + U4;
   float *s_scal = s_eps + U4;                 // [8][16] per-row scalars
   int *const s_mem = reinterpret_cast<int *>(s_scal + 32);   // [16] TS modes: the member of each row at this step
+  float *const s_rl = s_scal + 64;            // [16] MBPO_REWARD_LEARNED: the row's reward, accumulated over the ensemble rounds
   float *s_gR = s_scal + 128;                 // [HZ+1]  dL/dR_t (row independent)
   float *s_pi = s_gR + ((HZ + 4) & ~3);       // 2*LH tiles: policy z, h
   float *s_B = s_pi + 2 * LH * T;             // shared region: critics (2*LH z + 4 pp) | ensemble round EC*(LH+2) | policy deltas
@@ -221,6 +225,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   bool first_tile = true;
   const long long n_tiles = (A.n + 15) >> 4;
   const bool ens = A.system_kind == MBPO_SYS_ENSEMBLE;
+  constexpr bool lrw = LR;                    // (ensemble only: the reward is the members' head, column 2X)
   const int NR = ens ? (E + EC - 1) / EC : 0;   // ensemble rounds of EC member chains
   const int Rm = ens ? NR : 1;                  // model ops of a forward step (pendulum: one elementwise op)
   const int nF = Rm + 3, nB = 5 + (ens ? 2 * NR : 1);
@@ -378,6 +383,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             s_xu[r * ld_xu + c] = xv;
             if (ens) s_xn[r * ld_x + c] = A.predict_delta ? xv : 0.f;   // the member means are added round by round
           }
+          if (lrw && tid < 16) s_rl[tid] = 0.f;
           if (ts && tid < 16) {   // the row's member for this step, drawn once (rollout.hip's rule)
             const long long i = row0 + tid;
             int m = 0;
@@ -400,7 +406,16 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
               for (int cc = 0; cc < EC && rr * EC + cc < E; ++cc) acc += s_ye[(cc * 16 + r) * ld_ye + c];
               s_xn[r * ld_x + c] += acc / (float)E;
             }
+            if (lrw && tid < 16) {     // r = mean_e mu_r,e, round by round like the state
+              float acc = 0.f;
+              for (int cc = 0; cc < EC && rr * EC + cc < E; ++cc) acc += s_ye[(cc * 16 + tid) * ld_ye + 2 * X];
+              s_rl[tid] += acc / (float)E;
+            }
           } else {
+            if (lrw && tid < 16) {     // r = mu_r,m of the row's member, in the round that holds it
+              const int cc = s_mem[tid] - rr * EC;
+              if (cc >= 0 && cc < EC) s_rl[tid] = s_ye[(cc * 16 + tid) * ld_ye + 2 * X];
+            }
             // trajectory sampling: a row takes its own member, in the round that holds it (x' = base + mu_m [+ sigma_m * eps])
             for (int idx = tid; idx < 16 * X; idx += nthreads) {
               const int r = idx / X, c = idx - r * X;
@@ -447,7 +462,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
         } else if (elem == E_NN) {
           if (tid < 16) {
             const long long i = row0 + tid;
-            const float rew = reward_fwd(A, s_xu + tid * ld_xu);
+            const float rew = lrw ? s_rl[tid] : reward_fwd(A, s_xu + tid * ld_xu);
             if (i < A.n) A.w_rs[i * HZ + t] = rew;
             s_scal[tid] = rew;
           }
@@ -573,7 +588,8 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
           if (!ts) {
             for (int idx = tid; idx < 16 * dout; idx += nthreads) {
               const int r = idx / dout, c = idx - r * dout;
-              const float v = c < X ? s_gx[r * ld_x + c] / (float)E : 0.f;   // x' = base + mean_e mu_e: the same for every member
+              float v = c < X ? s_gx[r * ld_x + c] / (float)E : 0.f;   // x' = base + mean_e mu_e: the same for every member
+              if (lrw && c == 2 * X) v = (row0 + r < A.n ? s_gR[t] / r_std : 0.f) / (float)E;      // r = mean_e mu_r,e
               for (int cc = 0; cc < EC; ++cc) s_dye[(cc * 16 + r) * ld_ye + c] = v;
             }
           } else {
@@ -585,6 +601,8 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
               float v = 0.f;
               if (c < X) {
                 v = s_gx[r * ld_x + c];
+              } else if (lrw && c == 2 * X) {
+                v = i < A.n ? s_gR[t] / r_std : 0.f;                                               // r = mu_r,m
               } else if ((ts & TS_NOISE) && c < 2 * X && i < A.n) {
                 const long long k = (i * HZ + t) * X + (c - X);
                 v = s_gx[r * ld_x + (c - X)] * A.w_ts[ts_eps_off(A.n, HZ) + k] * sigmoid_f(A.w_ts[ts_raw_off(A.n, HZ, X) + k]);
@@ -612,7 +630,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             const int r = idx / X, c = idx - r * X;
             const bool ok = row0 + r < A.n;
-            s_dxu[r * ld_xu + c] += reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, c);   // dL/dr_t = dL/dR_t / r_std
+            if (!LR) s_dxu[r * ld_xu + c] += reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, c);   // dL/dr_t = dL/dR_t / r_std
           }
           for (int idx = tid; idx < 16 * U; idx += nthreads) {
             const int r = idx / U, d = idx - r * U;
@@ -630,7 +648,8 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             const float q = (u - mu) / sg;
             const float lp = -0.5f * q * q - fm_log(sg) - LOG_SQRT_2PI_B - fm_log(om);
             const float dlp_da = (-q / sg) / om + 2.f * a / om;
-            const float Ga = s_dxu[r * ld_xu + X + d] + reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, X + d) + w_lp * dlp_da;
+            const float Ga = s_dxu[r * ld_xu + X + d] + (LR ? 0.f : reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, X + d)) +
+                             w_lp * dlp_da;
             const float l_mu = w_lp * (q / sg), l_sr = w_lp * ((q * q - 1.f) / sg) * dsig;
             const float a_mu = Ga * dadw, a_sr = Ga * dadw * eps * dsig;
             s_dyl[r * ld_y + d] = ok ? l_mu : 0.f;
@@ -773,8 +792,9 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   } else {
     MBPO_REQUIRE(false, MBPO_ERR_ARG, "bptt: unknown system_kind");
   }
-  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_QUADRATIC || (d->reward_kind == MBPO_REWARD_PENDULUM && d->x_dim == 3 && d->u_dim == 1),
-               MBPO_ERR_ARG, "bptt: bad reward_kind");
+  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_QUADRATIC || (d->reward_kind == MBPO_REWARD_PENDULUM && d->x_dim == 3 && d->u_dim == 1) ||
+                   (d->reward_kind == MBPO_REWARD_LEARNED && E > 0 && dyn_out == 2 * d->x_dim + 2),
+               MBPO_ERR_ARG, "bptt: bad reward_kind (the learned reward needs an ensemble with outputs 2x + 2)");
   pl->H = 64;
   pl->LH = lh;
   auto up4 = [](int v) { return (v + 3) & ~3; };
@@ -825,7 +845,7 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   pl->o_extras = take((long long)pl->n_slabs * 2);
   pl->total = o;
   if (need_ptrs)
-    MBPO_REQUIRE(d->actor_params && d->target_critic_params && d->reward_params && d->state_mean && d->state_std && d->reward_mean_std &&
+    MBPO_REQUIRE(d->actor_params && d->target_critic_params && (d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED) && d->state_mean && d->state_std && d->reward_mean_std &&
                      d->init_states && d->transitions && d->lambda_values && d->grads && d->metrics && d->workspace,
                  MBPO_ERR_ARG, "bptt: null pointer");
   return MBPO_OK;
@@ -881,19 +901,25 @@ extern "C" int mbpo_bptt_actor_grads(const mbpo_bptt_desc *d, void *stream) {
   if (A.system_kind == MBPO_SYS_ENSEMBLE) A.sh_dyn = NetShape{A.dyn.dims[0], A.dyn.n_layers, A.dyn.dims[A.dyn.n_layers], A.dyn.act};
   else A.sh_dyn = NetShape{A.X + A.U, 0, A.X, 0};
   const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_cr) || net_is_wide(A.sh_dyn);
-  if (A.ts) {
-    rc = wide ? mbpo_ensure_lds<k_bptt_actor<64, true, true>>(pl.lds, "bptt_actor_grads")
-              : mbpo_ensure_lds<k_bptt_actor<64, false, true>>(pl.lds, "bptt_actor_grads");
-    if (rc != MBPO_OK) return rc;
-    if (wide) hipLaunchKernelGGL((k_bptt_actor<64, true, true>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
-    else hipLaunchKernelGGL((k_bptt_actor<64, false, true>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
-  } else {
-    rc = wide ? mbpo_ensure_lds<k_bptt_actor<64, true, false>>(pl.lds, "bptt_actor_grads")
-              : mbpo_ensure_lds<k_bptt_actor<64, false, false>>(pl.lds, "bptt_actor_grads");
-    if (rc != MBPO_OK) return rc;
-    if (wide) hipLaunchKernelGGL((k_bptt_actor<64, true, false>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
-    else hipLaunchKernelGGL((k_bptt_actor<64, false, false>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);
+  const bool lr = A.reward_kind == MBPO_REWARD_LEARNED;
+#define LAUNCH_BPTT(W_, TS_, LR_)                                                                          \
+  {                                                                                                        \
+    rc = mbpo_ensure_lds<k_bptt_actor<64, W_, TS_, LR_>>(pl.lds, "bptt_actor_grads");                      \
+    if (rc != MBPO_OK) return rc;                                                                          \
+    hipLaunchKernelGGL((k_bptt_actor<64, W_, TS_, LR_>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);      \
   }
+  if (lr) {
+    if (A.ts) {
+      if (wide) LAUNCH_BPTT(true, true, true) else LAUNCH_BPTT(false, true, true)
+    } else {
+      if (wide) LAUNCH_BPTT(true, false, true) else LAUNCH_BPTT(false, false, true)
+    }
+  } else if (A.ts) {
+    if (wide) LAUNCH_BPTT(true, true, false) else LAUNCH_BPTT(false, true, false)
+  } else {
+    if (wide) LAUNCH_BPTT(true, false, false) else LAUNCH_BPTT(false, false, false)
+  }
+#undef LAUNCH_BPTT
   BpttReduceArgs R;
   R.slabs = A.slabs; R.extras = A.extras; R.n_slabs = pl.n_slabs; R.P = pl.P; R.H = d->horizon; R.n = d->n; R.ent_coef = d->ent_coef;
   R.grads = d->grads; R.metrics = d->metrics;

@@ -4,6 +4,8 @@
 // chosen to be the exact inverse of what the rollout kernel consumes (EnsembleDynamics.next_state):
 //     (mu, raw) = MLP_e([x, u]);  mean = mu (+ x if predict_delta);  sigma = softplus(raw) + min_std
 //     loss_e = mean_b sum_d [ 0.5 ((x'_d - mean_d) / sigma_d)^2 + log sigma_d ]          (+ const)
+// With a reward head (reward_off >= 0, outputs [mu | raw | mu_r | raw_r]) the loss gains the same term for r = row[reward_off] at
+// output columns 2X, 2X + 1 (staged as target column X); its loss element is summed after the state's.
 // One workgroup = (member, 16-row tile): forward chain with stored activations, elementwise output gradient, then a dgrad
 // and a wgrad chain side by side (chain_run.hpp); a workgroup walks tiles and accumulates into its slab; fixed-order reduce.
 // fp32 MFMA; algorithmic work per (member, sample): 3 * 2M FLOP, HBM 4*(2x+u) B gathered.
@@ -14,7 +16,7 @@ struct EnsTrainArgs {
   NetShape sh;
   const float *params;
   long long net_stride;
-  int n_params, E, X, U, D, noff;
+  int n_params, E, X, U, D, noff, roff;   // roff: reward target column, or -1
   const float *rows;
   const int *idx;
   long long batch;
@@ -35,7 +37,7 @@ __global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
   const int X = A.X, U = A.U, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y, LH = A.LH;
   const int T = 16 * ld_h;
   float *s_xu = smem;                       // [16][ld_xu]  [x, u]
-  float *s_t = s_xu + 16 * ld_xu;           // [16][ld_y]   regression target (first X columns)
+  float *s_t = s_xu + 16 * ld_xu;           // [16][ld_y]   regression target (X state columns, then the reward), loss elements from X + 1
   float *s_y = s_t + 16 * ld_y;             // [16][ld_y]   (mu, raw)
   float *s_dy = s_y + 16 * ld_y;            // [16][ld_y]
   float *s_st = s_dy + 16 * ld_y;           // 2*LH tiles: z, h
@@ -70,6 +72,10 @@ __global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
       }
       s_t[r * ld_y + c] = t;
     }
+    if (A.roff >= 0 && tid < 16) {
+      const long long j = j0 + tid;
+      s_t[tid * ld_y + X] = (j < A.batch) ? A.rows[(long long)idx[j] * A.D + A.roff] : 0.f;
+    }
     __syncthreads();
     if (chain == 0) chain_fwd_run<HT, SP, WIDE>(A.sh, params, s_xu, ld_xu, nullptr, nullptr, s_st, s_st + LH * T, s_y, ld_y, ld_h, L, sub, lane, R);
     else chain_idle_run(L);
@@ -83,12 +89,23 @@ __global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
       const float q = (s_t[r * ld_y + c] - mu) / sg;
       s_dy[r * ld_y + c] = ok ? -(q / sg) * invB : 0.f;
       s_dy[r * ld_y + X + c] = ok ? ((1.f - q * q) / sg) * sigmoid_f(raw) * invB : 0.f;
-      s_t[r * ld_y + X + c] = ok ? 0.5f * q * q + logf(sg) : 0.f;      // per-element loss, summed below
+      s_t[r * ld_y + X + 1 + c] = ok ? 0.5f * q * q + logf(sg) : 0.f;      // per-element loss, summed below
+    }
+    if (A.sh.N_out > 2 * X && tid < 16) {       // the reward head: its term, or zero gradient when it is not fitted
+      const int r = tid;
+      const bool ok = j0 + r < A.batch && A.roff >= 0;
+      const float mu = s_y[r * ld_y + 2 * X], raw = s_y[r * ld_y + 2 * X + 1];
+      const float sg = softplus_f(raw) + A.min_std;
+      const float q = (s_t[r * ld_y + X] - mu) / sg;
+      s_dy[r * ld_y + 2 * X] = ok ? -(q / sg) * invB : 0.f;
+      s_dy[r * ld_y + 2 * X + 1] = ok ? ((1.f - q * q) / sg) * sigmoid_f(raw) * invB : 0.f;
+      s_t[r * ld_y + 2 * X + 1] = ok ? 0.5f * q * q + logf(sg) : 0.f;
     }
     __syncthreads();
     if (tid < 16) {
       float a = 0.f;
-      for (int c = 0; c < X; ++c) a += s_t[tid * ld_y + X + c];
+      for (int c = 0; c < X; ++c) a += s_t[tid * ld_y + X + 1 + c];
+      if (A.roff >= 0) a += s_t[tid * ld_y + 2 * X + 1];
       s_ls[tid] = a;
     }
     if (chain == 0) chain_dgrad_run<HT, SP, WIDE>(A.sh, params, s_dy, ld_y, s_st, s_pp, s_pp + T, nullptr, ld_xu, ld_h, L, sub, lane, R);
@@ -138,7 +155,10 @@ static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   int rc = mbpo_make_mlp_dev(&md, &pl->dyn, "ens_nll.dynamics");
   if (rc != MBPO_OK) return rc;
   const int X = d->x_dim, U = d->u_dim, L = pl->dyn.n_layers;
-  MBPO_REQUIRE(pl->dyn.dims[0] == X + U && pl->dyn.dims[L] == 2 * X, MBPO_ERR_ARG, "ens_nll: dynamics must map [x+u] -> [2x] (mean, raw std)");
+  MBPO_REQUIRE(pl->dyn.dims[0] == X + U && (pl->dyn.dims[L] == 2 * X || pl->dyn.dims[L] == 2 * X + 2), MBPO_ERR_ARG,
+               "ens_nll: dynamics must map [x+u] -> [2x] (mean, raw std) or [2x+2] (+ reward mean, raw std)");
+  MBPO_REQUIRE(d->reward_off >= -1 && d->reward_off < d->row_len, MBPO_ERR_ARG, "ens_nll: reward_off %d outside the row", d->reward_off);
+  MBPO_REQUIRE(d->reward_off < 0 || pl->dyn.dims[L] == 2 * X + 2, MBPO_ERR_ARG, "ens_nll: reward_off needs a [x+u] -> [2x+2] ensemble");
   MBPO_REQUIRE(L >= 2, MBPO_ERR_ARG, "ens_nll: the member networks need at least one hidden layer");
   for (int l = 1; l < L; ++l)
     MBPO_REQUIRE(pl->dyn.dims[l] == 64, MBPO_ERR_UNSUPPORTED, "ens_nll: hidden layers must all be 64 wide (got %d)", pl->dyn.dims[l]);
@@ -147,7 +167,7 @@ static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   pl->LH = L - 1;
   pl->ld_xu = up4(X + U) + 4;
   pl->ld_h = 68;
-  pl->ld_y = up4(2 * X) + 4;
+  pl->ld_y = up4(pl->dyn.dims[L]) + 4;
   pl->lds = sizeof(float) * (16ull * pl->ld_xu + 3ull * 16 * pl->ld_y + (size_t)(2 * pl->LH + 2) * 16 * pl->ld_h + 16);
   MBPO_REQUIRE(pl->lds <= 160 * 1024, MBPO_ERR_UNSUPPORTED, "ens_nll: shapes do not fit 160 KiB of LDS");
   const long long tiles = (d->batch + 15) / 16;
@@ -176,7 +196,7 @@ extern "C" int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream) {
   const int L = pl.dyn.n_layers, E = pl.dyn.n_nets;
   A.sh = NetShape{pl.dyn.dims[0], L, pl.dyn.dims[L], pl.dyn.act};
   A.params = d->dynamics.params; A.net_stride = pl.dyn.net_stride; A.n_params = pl.dyn.n_params; A.E = E;
-  A.X = d->x_dim; A.U = d->u_dim; A.D = d->row_len; A.noff = d->next_obs_off;
+  A.X = d->x_dim; A.U = d->u_dim; A.D = d->row_len; A.noff = d->next_obs_off; A.roff = d->reward_off;
   A.rows = d->rows; A.idx = d->idx; A.batch = d->batch; A.predict_delta = d->predict_delta; A.min_std = d->min_std;
   A.slabs = d->workspace; A.extras = d->workspace + (long long)E * pl.n_slots * pl.dyn.n_params;
   A.n_slots = pl.n_slots; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;

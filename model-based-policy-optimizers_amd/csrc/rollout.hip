@@ -169,7 +169,8 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 // ------------------------------------------------------------------------------------------------
 // R1-R8 fused rollout.
 // ------------------------------------------------------------------------------------------------
-template <int H>
+// LR: MBPO_REWARD_LEARNED (a flag of its own, as in k_model_rollout64)
+template <int H, bool LR>
 __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -306,7 +307,9 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
           const int r = tid;
           const float *xr = s_xu + r * A.ld_xu;
           float rew;
-          if (A.reward_kind == MBPO_REWARD_PENDULUM) {
+          if (LR) {
+            rew = learned_reward(A, s_y, A.ld_y, E, r, env0 + r, ((long long)s * AR + ar) * N + env0 + r, rng_seed, rng_off);
+          } else if (A.reward_kind == MBPO_REWARD_PENDULUM) {
             rew = pendulum_reward(xr, xr[X], A.reward_params);
           } else {
             const float *tp = A.reward_params, *qp = tp + X, *rp = qp + X;
@@ -467,7 +470,9 @@ __device__ __forceinline__ int ro_tid_now(int wave) {
   return (wave << 6) | l;
 }
 
-template <bool WIDE>
+// LR: MBPO_REWARD_LEARNED (section C reads the reward from the members' outputs; a flag of its own so the other instantiations stay
+// as they were)
+template <bool WIDE, bool LR>
 __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64 AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -500,7 +505,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
   // reward parameters staged once: section C read them from global memory inside a runtime-trip loop (one exposed scalar
   // load per term: ~1.5 k of that section's 3.6 k cycles)
   float *s_rp = s_scr + ((16 * (X + U) + 16 + 3) & ~3);   // [2X+U] quadratic (target, q, r) or [3] pendulum
-  {
+  if (!LR) {
     const int n_rp = (A.reward_kind == MBPO_REWARD_PENDULUM) ? 3 : 2 * X + U;
     for (int idx = tid_; idx < n_rp; idx += nthreads) s_rp[idx] = A.reward_params[idx];
   }
@@ -628,7 +633,9 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
           const int r = tid;
           const float *xr = s_xu + r * ld_xu;
           float rew;
-          if (A.reward_kind == MBPO_REWARD_PENDULUM) {
+          if (LR) {
+            rew = learned_reward(A, s_y, ld_y, E, r, env0 + r, ((long long)s * AR + ar) * N + env0 + r, rng_seed, rng_off);
+          } else if (A.reward_kind == MBPO_REWARD_PENDULUM) {
             rew = pendulum_reward(xr, xr[X], s_rp);
           } else {
             const float *tp = s_rp, *qp = tp + X, *rp = qp + X;
@@ -820,12 +827,14 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
                "model_rollout: null state/output pointer");
   MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG,
                "model_rollout: norm_mean and norm_std must both be set or both NULL");
-  MBPO_REQUIRE(d->reward_params, MBPO_ERR_ARG, "model_rollout: reward_params is NULL");
+  MBPO_REQUIRE(d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED, MBPO_ERR_ARG, "model_rollout: reward_params is NULL");
   const int X = d->x_dim, U = d->u_dim;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
   MBPO_REQUIRE(d->row_len == want_row, MBPO_ERR_ARG, "model_rollout: row_len %d != expected %d", d->row_len, want_row);
-  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_PENDULUM || d->reward_kind == MBPO_REWARD_QUADRATIC, MBPO_ERR_ARG,
-               "model_rollout: unknown reward_kind %d", d->reward_kind);
+  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_PENDULUM || d->reward_kind == MBPO_REWARD_QUADRATIC || d->reward_kind == MBPO_REWARD_LEARNED,
+               MBPO_ERR_ARG, "model_rollout: unknown reward_kind %d", d->reward_kind);
+  MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_LEARNED || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG,
+               "model_rollout: the learned reward needs system_kind ENSEMBLE");
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && U == 1), MBPO_ERR_ARG,
                "model_rollout: pendulum reward needs x_dim=3,u_dim=1");
   RolloutArgs A;
@@ -849,8 +858,11 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     E = A.dyn.n_nets;
     dyn_out = A.dyn.dims[A.dyn.n_layers];
     MBPO_REQUIRE(A.dyn.dims[0] == X + U, MBPO_ERR_ARG, "model_rollout: dynamics input must be x_dim+u_dim");
-    MBPO_REQUIRE(dyn_out == 2 * X || (dyn_out == X && !(d->ens_sample_noise && d->ens_mode != MBPO_ENS_MEAN)),
-                 MBPO_ERR_ARG, "model_rollout: dynamics output must be 2*x_dim (mean, raw std) or x_dim (mean only, no sampling)");
+    MBPO_REQUIRE(dyn_out == 2 * X || dyn_out == 2 * X + 2 || (dyn_out == X && !(d->ens_sample_noise && d->ens_mode != MBPO_ENS_MEAN)),
+                 MBPO_ERR_ARG, "model_rollout: dynamics output must be 2*x_dim (mean, raw std), 2*x_dim+2 (+ reward mean, raw std) or "
+                 "x_dim (mean only, no sampling)");
+    MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_LEARNED || dyn_out == 2 * X + 2, MBPO_ERR_ARG,
+                 "model_rollout: the learned reward needs dynamics output 2*x_dim+2 (got %d)", dyn_out);
     MBPO_REQUIRE(d->ens_mode >= 0 && d->ens_mode <= 2, MBPO_ERR_ARG, "model_rollout: unknown ens_mode");
     int Hd = hidden_width(A.dyn);
     if (!has_policy || A.policy.n_layers == 1) H = Hd;
@@ -903,11 +915,15 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     MBPO_CHECK_LAUNCH("model_rollout");
     return MBPO_OK;
   }
+#define LAUNCH_RO_LR(HH, LR_)                                                                  \
+  {                                                                                            \
+    rc = mbpo_ensure_lds<k_model_rollout<HH, LR_>>(lds, "model_rollout");                      \
+    if (rc != MBPO_OK) return rc;                                                              \
+    hipLaunchKernelGGL((k_model_rollout<HH, LR_>), dim3(grid), dim3(n_waves * 64), lds, st, A); \
+  }
 #define LAUNCH_RO(HH)                                                        \
   {                                                                          \
-    rc = mbpo_ensure_lds<k_model_rollout<HH>>(lds, "model_rollout");                 \
-    if (rc != MBPO_OK) return rc;                                            \
-    hipLaunchKernelGGL(k_model_rollout<HH>, dim3(grid), dim3(n_waves * 64), lds, st, A); \
+    if (d->reward_kind == MBPO_REWARD_LEARNED) LAUNCH_RO_LR(HH, true) else LAUNCH_RO_LR(HH, false) \
   }
   if (H == 64) {
     // the kernel specialised for the benchmark networks (rollout_lean.hip): MBPO_ROLLOUT_LEAN=0 / mbpo_debug_set_rollout_lean(0) keep the
@@ -942,12 +958,22 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     if (AA.a.n_chains < 1) AA.a.n_chains = 1;
     lds = (fixed_f + 2ull * (AA.a.n_chains > 1 ? AA.a.n_chains : 1) * 16 * A.ld_h) * sizeof(float);
     const bool wide = net_is_wide(AA.sh_pi) || net_is_wide(AA.sh_dyn);
-    rc = wide ? mbpo_ensure_lds<k_model_rollout64<true>>(lds, "model_rollout") : mbpo_ensure_lds<k_model_rollout64<false>>(lds, "model_rollout");
-    if (rc != MBPO_OK) return rc;
-    if (wide) hipLaunchKernelGGL(k_model_rollout64<true>, dim3(grid), dim3(64 * RO64_WAVES), lds, st, AA);
-    else hipLaunchKernelGGL(k_model_rollout64<false>, dim3(grid), dim3(64 * RO64_WAVES), lds, st, AA);
+    const bool lr = d->reward_kind == MBPO_REWARD_LEARNED;
+#define LAUNCH_RO64(W_, LR_)                                                                      \
+  {                                                                                               \
+    rc = mbpo_ensure_lds<k_model_rollout64<W_, LR_>>(lds, "model_rollout");                       \
+    if (rc != MBPO_OK) return rc;                                                                 \
+    hipLaunchKernelGGL((k_model_rollout64<W_, LR_>), dim3(grid), dim3(64 * RO64_WAVES), lds, st, AA); \
+  }
+    if (lr) {
+      if (wide) LAUNCH_RO64(true, true) else LAUNCH_RO64(false, true)
+    } else {
+      if (wide) LAUNCH_RO64(true, false) else LAUNCH_RO64(false, false)
+    }
+#undef LAUNCH_RO64
   } else if (H == 128) LAUNCH_RO(128) else LAUNCH_RO(256)
 #undef LAUNCH_RO
+#undef LAUNCH_RO_LR
   MBPO_CHECK_LAUNCH("model_rollout");
   return MBPO_OK;
 }

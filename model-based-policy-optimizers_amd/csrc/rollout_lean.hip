@@ -1,7 +1,7 @@
 // rollout_lean.hip — k_rollout_lean<X>: the fused model rollout (R1-R8 of SURVEY §8a: get_experience / generate_unroll, sac/acting.py:
 // 25-79 over the BraxWrapper step, brax_utils/training.py:85-137) specialised for the benchmark networks: policy X -> 64 -> 64 -> 64 -> 2
 // (or the reference experiments' 64 x 2: one hidden-to-hidden layer less, a run-time count per network),
-// members (X + 1) -> 64 -> 64 -> 64 -> (X | 2X), swish, u = 1, X = 2 .. 4, at most five members (or the analytic Pendulum system), action_repeat 1.
+// members (X + 1) -> 64 -> 64 -> 64 -> (X | 2X | 2X + 2: with the learned reward's head), swish, u = 1, X = 2 .. 4, at most five members (or the analytic Pendulum system), action_repeat 1.
 //
 // The generic k_model_rollout64 (rollout.hip) walks the same 16-env tile per workgroup on the shared runners: every layer of every chain
 // re-requests its weights each env step, activations go to LDS as 4 x b32 per lane, four bookkeeping sections of all 768 threads sit
@@ -27,7 +27,7 @@
 
 namespace {
 constexpr int RL_WAVES = 12, RL_THREADS = 64 * RL_WAVES;
-constexpr int RL_LDY = 20;                          // row stride of a member's output tile (<= 16 outputs)
+constexpr int RL_LDY = 20;                          // row stride of a member's output tile (<= 16 outputs; 2X + 2 <= 10 used)
 constexpr int RL_MAX_E = 5;
 // LDS carve (floats)
 constexpr int R_PIN = 0;                            // [16][8]  normalised obs (policy input)
@@ -85,7 +85,9 @@ __device__ __forceinline__ void rl_sample(const RolloutArgs &A, const f32x4 acc,
 // lane of a row its steps / done): AutoReset pre-step (training.py:119-124), reward on the pre-step (x, u), next state, EpisodeWrapper /
 // AutoReset post-step (training.py:98-107, 126-137), Transition (acting.py:46-55), and the next step's inputs (n_row: the row buffer of
 // step s + 1, or NULL after the last step).
-template <int X, bool PEND>
+// LR (MBPO_REWARD_LEARNED): the reward is the members' reward head (output column 2X) at the pre-step (x, u) — the mean over members,
+// or in the TS modes the member the row's state takes (the lanes of column 0 hold the row's member already); no reward parameters.
+template <int X, bool PEND, bool LR>
 __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, long long env0, int lane, float *smem, float *s_pin, float *s_xu,
                                          const float *s_lp, float *s_row, float *n_row, float &o, float fo, float &steps, float &done,
                                          unsigned long long rng_seed, unsigned long long rng_off) {
@@ -97,8 +99,10 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
   done = 0.f;
   const float *xr = s_xu + sr * LDX;
   const float *s_rp = smem + R_RP;
-  float rew;
-  if (PEND && A.reward_kind == MBPO_REWARD_PENDULUM) {
+  float rew = 0.f;
+  if (LR) {
+    // (set in the member section below)
+  } else if (PEND && A.reward_kind == MBPO_REWARD_PENDULUM) {
     rew = pendulum_reward(xr, xr[X], s_rp);
   } else {
     const float *tp = s_rp, *qp = tp + X, *rp = qp + X;
@@ -124,6 +128,11 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
       float acc = 0.f;
       for (int e = 0; e < E; ++e) acc += s_y[(e * 16 + r) * RL_LDY + c];
       v = base + acc / (float)E;
+      if (LR) {
+        float racc = 0.f;
+        for (int e = 0; e < E; ++e) racc += s_y[(e * 16 + r) * RL_LDY + 2 * X];
+        rew = 0.f + racc / (float)E;                // (s_rew starts the step at zero in the generic kernel)
+      }
     } else {
       int mem = 0;
       const long long eidx = (long long)s * N + env;
@@ -133,6 +142,7 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
       }
       const float mu = s_y[(mem * 16 + r) * RL_LDY + c];
       v = base + mu;
+      if (LR) rew = 0.f + s_y[(mem * 16 + r) * RL_LDY + 2 * X];
       if (A.ens_sample_noise && env < N) {
         const float sg = softplus_f(s_y[(mem * 16 + r) * RL_LDY + X + c]) + A.ens_min_std;
         const long long nidx = eidx * X + c;
@@ -173,7 +183,8 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
 // PEND: the analytic Pendulum step / reward are compiled in (their atan2f / sinf / cosf / fmodf expansions need ~40 more registers than
 // the resident weights leave; the ensemble + quadratic-reward instantiation — the benchmark's — carries neither)
 // PIPE: two tiles in flight per workgroup — the policy phase of one beside the member phase of the other (see the pipelined loop below)
-template <int X, bool PEND, bool PIPE>
+// LR: MBPO_REWARD_LEARNED (the reward read from the members' outputs; a flag of its own so the other instantiations stay as they were)
+template <int X, bool PEND, bool PIPE, bool LR>
 __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -237,7 +248,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
     bias[3 * LH + (lane - 32)] = bv0;
   }
   float *const tiles = smem + R_TILES + chain * 2 * LT;
-  {
+  if (!LR) {
     const int n_rp = (A.reward_kind == MBPO_REWARD_PENDULUM) ? 3 : 2 * X + U;
     if (tid < n_rp) smem[R_RP + tid] = A.reward_params[tid];
   }
@@ -321,7 +332,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
         __syncthreads();
         if (is_sw && my_slot == ms && mv) {
           float *const row = my_base + S_ROW;
-          rl_fused<X, PEND>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo, steps, done,
+          rl_fused<X, PEND, LR>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo, steps, done,
                             rng_seed, rng_off);
           // the finished rows of step sm leave from here (this wave's own LDS writes and reads stay in order); then the next step's inputs
           if (A.env_major) {
@@ -433,7 +444,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
       // ---- one section on the state wave: AutoReset pre-step (training.py:119-124), reward on the pre-step (x, u), next state,
       //      EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137), Transition (acting.py:46-55), next step's inputs ----
       if (wave == SW)
-        rl_fused<X, PEND>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
+        rl_fused<X, PEND, LR>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
                           s + 1 < A.n_steps ? smem + R_ROWS + ((s + 1) & 1) * 16 * D4 : nullptr, o, fo, steps, done, rng_seed, rng_off);
       __syncthreads();
       RL_STAMP(9);
@@ -481,7 +492,8 @@ bool rollout_lean_supports(const RolloutArgs &A, bool has_policy, int E) {
   if (!net_ok(A.policy, X) || A.policy.dims[A.policy.n_layers] != 2) return false;
   if (A.system_kind == MBPO_SYS_ENSEMBLE) {
     if (E < 1 || E > RL_MAX_E || !net_ok(A.dyn, X + 1)) return false;
-    if (A.dyn.dims[A.dyn.n_layers] != X && A.dyn.dims[A.dyn.n_layers] != 2 * X) return false;
+    const int dout = A.dyn.dims[A.dyn.n_layers];
+    if (dout != X && dout != 2 * X && dout != 2 * X + 2) return false;      // (the output image holds <= 16 columns, RL_LDY 20)
   } else if (A.system_kind != MBPO_SYS_PENDULUM || X != 3) {
     return false;
   }
@@ -492,13 +504,23 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   hipStream_t st = (hipStream_t)stream;
   int rc;
   const bool pend = A.a.system_kind == MBPO_SYS_PENDULUM || A.a.reward_kind == MBPO_REWARD_PENDULUM;
-#define RL_LAUNCH(X_, P_, PP_)                                                                              \
-  {                                                                                                         \
-    rc = mbpo_ensure_lds<k_rollout_lean<X_, P_, PP_>>(RL_LDS_BYTES, "rollout_lean");                        \
-    if (rc != MBPO_OK) return rc;                                                                           \
-    hipLaunchKernelGGL((k_rollout_lean<X_, P_, PP_>), dim3(grid), dim3(RL_THREADS), RL_LDS_BYTES, st, A);   \
+  const bool lr = A.a.reward_kind == MBPO_REWARD_LEARNED;      // (an ensemble: never with pend)
+#define RL_LAUNCH_LR(X_, P_, PP_, LR_)                                                                              \
+  {                                                                                                                 \
+    rc = mbpo_ensure_lds<k_rollout_lean<X_, P_, PP_, LR_>>(RL_LDS_BYTES, "rollout_lean");                           \
+    if (rc != MBPO_OK) return rc;                                                                                   \
+    hipLaunchKernelGGL((k_rollout_lean<X_, P_, PP_, LR_>), dim3(grid), dim3(RL_THREADS), RL_LDS_BYTES, st, A);      \
   }
-  if (pipe) {
+#define RL_LAUNCH(X_, P_, PP_) RL_LAUNCH_LR(X_, P_, PP_, false)
+  if (lr) {
+    if (A.a.x_dim == 3) {
+      if (pipe) RL_LAUNCH_LR(3, false, true, true) else RL_LAUNCH_LR(3, false, false, true)
+    } else if (A.a.x_dim == 2) {
+      if (pipe) RL_LAUNCH_LR(2, false, true, true) else RL_LAUNCH_LR(2, false, false, true)
+    } else {
+      if (pipe) RL_LAUNCH_LR(4, false, true, true) else RL_LAUNCH_LR(4, false, false, true)
+    }
+  } else if (pipe) {
     if (A.a.x_dim == 3) {
       if (pend) RL_LAUNCH(3, true, true) else RL_LAUNCH(3, false, true)
     } else if (A.a.x_dim == 2) {
@@ -516,5 +538,6 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
     }
   }
 #undef RL_LAUNCH
+#undef RL_LAUNCH_LR
   return MBPO_OK;
 }

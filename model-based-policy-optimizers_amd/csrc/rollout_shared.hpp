@@ -58,4 +58,21 @@ __device__ __forceinline__ float pendulum_reward(const float *x, float u, const 
   return -(angle_cost * (d * d) + 0.1f * (omega * omega)) - control_cost * (u * u);
 }
 
-
+// MBPO_REWARD_LEARNED: the reward of row r (env `env`, member-draw index eidx = (s * action_repeat + ar) * N + env) from the members'
+// outputs s_y = [E][16][ld_y], reward head at column 2X: the mean over members, or in the TS modes the member the row's state takes
+// (the same member_idx entry or Philox MEMBER draw as the state's section).
+__device__ __forceinline__ float learned_reward(const RolloutArgs &A, const float *s_y, int ld_y, int E, int r, long long env, long long eidx,
+                                                unsigned long long rng_seed, unsigned long long rng_off) {
+  const int c = 2 * A.x_dim;
+  if (A.ens_mode == MBPO_ENS_MEAN) {
+    float acc = 0.f;
+    for (int e = 0; e < E; ++e) acc += s_y[(e * 16 + r) * ld_y + c];
+    return acc / (float)E;
+  }
+  int mem = 0;
+  if (env < A.n_envs) {
+    if (A.ens_mode == MBPO_ENS_TSINF) mem = (int)(env % E);
+    else mem = A.member_idx ? A.member_idx[eidx] : philox_randint(rng_seed, rng_off, MBPO_STREAM_MEMBER, (unsigned long long)eidx, 0, E);
+  }
+  return s_y[(mem * 16 + r) * ld_y + c];
+}

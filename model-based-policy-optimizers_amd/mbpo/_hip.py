@@ -19,7 +19,7 @@ SYS_PENDULUM, SYS_ENSEMBLE = 0, 1
 SYS_GENERIC = 100      # host-side only: a user-defined System, stepped outside the fused kernel (ops.generic_rollout)
 ENS_MEAN, ENS_TS1, ENS_TSINF = 0, 1, 2
 STREAM_POLICY_NOISE, STREAM_MODEL_NOISE, STREAM_MEMBER = 1, 2, 3     # Philox stream ids (csrc/common.hpp)
-REWARD_PENDULUM, REWARD_QUADRATIC = 0, 1
+REWARD_PENDULUM, REWARD_QUADRATIC, REWARD_LEARNED = 0, 1, 2
 
 _LIB_PATH = Path(__file__).resolve().parent / "_lib" / "libmbpo_hip.so"
 
@@ -97,7 +97,8 @@ class EnsTrainDesc(C.Structure):
     """mbpo_ens_train_desc"""
     _fields_ = [("x_dim", C.c_int32), ("u_dim", C.c_int32), ("dynamics", MlpDesc), ("rows", C.c_void_p), ("row_len", C.c_int32),
                 ("next_obs_off", C.c_int32), ("idx", C.c_void_p), ("batch", C.c_int64), ("predict_delta", C.c_int32),
-                ("min_std", C.c_float), ("grads", C.c_void_p), ("metrics", C.c_void_p), ("workspace", C.c_void_p)]
+                ("min_std", C.c_float), ("grads", C.c_void_p), ("metrics", C.c_void_p), ("workspace", C.c_void_p),
+                ("reward_off", C.c_int32)]
 
 
 class SacDesc(C.Structure):

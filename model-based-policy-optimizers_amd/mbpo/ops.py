@@ -283,8 +283,10 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
     lib = load()
     n_envs = obs.shape[0]
     D = transition_row_len(x_dim, u_dim, ppo_extras)
-    for t, nm in ((obs, "obs"), (first_obs, "first_obs"), (steps, "steps"), (done, "done"), (reward_params, "reward_params")):
+    for t, nm in ((obs, "obs"), (first_obs, "first_obs"), (steps, "steps"), (done, "done")):
         _req(t, nm)
+    if reward_params is not None or reward_kind != _hip.REWARD_LEARNED:      # (the learned reward has no parameter vector)
+        _req(reward_params, "reward_params")
     if obs.shape != (n_envs, x_dim) or first_obs.shape != (n_envs, x_dim):
         raise ValueError("obs/first_obs must be [N, x_dim]")
     if steps.shape != (n_envs,) or done.shape != (n_envs,):
@@ -314,7 +316,7 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
     d.system_kind, d.ens_mode = system_kind, ens_mode
     d.ens_predict_delta, d.ens_sample_noise, d.ens_min_std = int(ens_predict_delta), int(ens_sample_noise), ens_min_std
     d.reward_kind = reward_kind
-    d.reward_params = reward_params.data_ptr()
+    d.reward_params = reward_params.data_ptr() if reward_params is not None else None
     d.sys_params = ptr(_req(sys_params, "sys_params")) if sys_params is not None else None
     d.norm_mean = ptr(_req(norm_mean, "norm_mean")) if norm_mean is not None else None
     d.norm_std = ptr(_req(norm_std, "norm_std")) if norm_std is not None else None
@@ -917,9 +919,10 @@ class BpttActorGrad:
         member_idx [n, H] int32 (ENS_TS1) and model_noise [n, H, x] replace the Philox draws when given."""
         d = self.desc
         for t, nm in ((actor_params, "actor_params"), (target_critic_params, "target_critic_params"), (init_states, "init_states"),
-                      (state_mean, "state_mean"), (state_std, "state_std"), (reward_mean_std, "reward_mean_std"),
-                      (reward_params, "reward_params")):
+                      (state_mean, "state_mean"), (state_std, "state_std"), (reward_mean_std, "reward_mean_std")):
             _req(t, nm)
+        if reward_params is not None or reward_kind != _hip.REWARD_LEARNED:      # (the learned reward has no parameter vector)
+            _req(reward_params, "reward_params")
         if tuple(init_states.shape) != (self.n, self.x_dim):
             raise ValueError(f"init_states must be [{self.n},{self.x_dim}]")
         if actor_params.numel() != self.P or target_critic_params.numel() != 2 * self.C:
@@ -930,7 +933,7 @@ class BpttActorGrad:
             if dyn_params is None or dyn_spec is None:
                 raise ValueError("ensemble system needs dyn_params and dyn_spec")
             d.dynamics = dyn_spec.desc(dyn_params)
-        d.reward_params = reward_params.data_ptr()
+        d.reward_params = reward_params.data_ptr() if reward_params is not None else None
         d.sys_params = ptr(_req(sys_params, "sys_params")) if sys_params is not None else None
         d.state_mean, d.state_std, d.reward_mean_std = state_mean.data_ptr(), state_std.data_ptr(), reward_mean_std.data_ptr()
         d.init_states = init_states.data_ptr()
@@ -1207,7 +1210,8 @@ class AdamW:
 
 
 class EnsembleNllGrad:
-    """Drives mbpo_ens_nll_grads: per-member Gaussian NLL loss and gradient on per-member minibatches (N3)."""
+    """Drives mbpo_ens_nll_grads: per-member Gaussian NLL loss and gradient on per-member minibatches (N3).  reward_off (call
+    argument): the rows' reward column, fitted by the reward head of a [x+u] -> [2x+2] ensemble; None: no reward term."""
 
     def __init__(self, *, x_dim: int, u_dim: int, spec: MlpSpec, batch: int, device, predict_delta: bool = True, min_std: float = 1e-3):
         self.lib = load()
@@ -1217,12 +1221,14 @@ class EnsembleNllGrad:
         d = _hip.EnsTrainDesc()
         d.x_dim, d.u_dim, d.batch = x_dim, u_dim, self.batch
         d.predict_delta, d.min_std = int(predict_delta), min_std
+        d.reward_off = -1
         self.desc = d
         self.grads = torch.zeros(self.E * self.n_params, device=self.device, dtype=torch.float32)
         self.metrics = torch.zeros(self.E, device=self.device, dtype=torch.float32)
         self.workspace = None
 
-    def __call__(self, params: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor, next_obs_off: Optional[int] = None) -> torch.Tensor:
+    def __call__(self, params: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor, next_obs_off: Optional[int] = None,
+                 reward_off: Optional[int] = None) -> torch.Tensor:
         _req(params, "params"); _req(rows, "rows"); _req(idx, "idx", torch.int32)
         if params.numel() != self.E * self.n_params:
             raise ValueError("params must hold E * n_params floats")
@@ -1232,6 +1238,7 @@ class EnsembleNllGrad:
         d.dynamics = self.spec.desc(params)
         d.rows, d.row_len = rows.data_ptr(), rows.shape[1]
         d.next_obs_off = self.x_dim + self.u_dim + 2 if next_obs_off is None else next_obs_off
+        d.reward_off = -1 if reward_off is None else int(reward_off)
         d.idx = idx.data_ptr()
         d.grads, d.metrics = self.grads.data_ptr(), self.metrics.data_ptr()
         if self.workspace is None:

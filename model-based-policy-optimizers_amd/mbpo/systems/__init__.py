@@ -4,5 +4,5 @@ from mbpo.systems.pendulum_system import PendulumSystem, PendulumDynamics, Pendu
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams, Dynamics, Normal
 from mbpo.systems.rewards.base_rewards import RewardParams, Reward
 # not in the reference (its learned model would come from the external `bsm` package, setup.py:22)
-from mbpo.systems.ensemble_system import EnsembleDynamics, EnsembleDynamicsParams, EnsembleSystem
+from mbpo.systems.ensemble_system import EnsembleDynamics, EnsembleDynamicsParams, EnsembleSystem, LearnedReward
 from mbpo.systems.rewards.pendulum_reward import QuadraticReward

@@ -11,6 +11,11 @@ model plugs into.  Semantics (build-defined, parity-unpinned; restated in oracle
 BPTT differentiates every mode (include/mbpo_hip.h, mbpo_bptt_desc): in 'ts1' / 'tsinf' by reparameterisation through the selected
 member — mu_m, and with sample_noise sigma_m * eps — with the member and eps drawn from Philox per train step (the reference threads
 SystemParams.key through rollout_policy, utils/optimizer_utils.py:81-97).  sample_noise has no effect in 'mean' mode.
+
+Learned reward (EnsembleDynamics(learn_reward=True) + LearnedReward): the members also predict the reward,
+    out_e = [mu_e (x_dim), raw_std_e (x_dim), mu_r,e, raw_r,e]
+and the reward of a step is the head at the pre-step (x, u): 'mean' r = mean_e mu_r,e; 'ts1' / 'tsinf' r = mu_r,m with the member m
+the state takes.  sample_noise perturbs the state only.  `fit` adds the reward's Gaussian NLL (target: the rows' reward column).
 """
 from __future__ import annotations
 
@@ -49,11 +54,14 @@ def lecun_uniform_flat(dims: Sequence[int], gen: torch.Generator) -> torch.Tenso
 
 
 class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
+    """learn_reward: the members also predict the reward (two more outputs, [mu_r, raw_r]); see LearnedReward."""
+
     def __init__(self, x_dim: int, u_dim: int, n_members: int = 5, hidden_layer_sizes: Sequence[int] = (64, 64, 64),
-                 activation: str = "swish", device=None):
+                 activation: str = "swish", device=None, learn_reward: bool = False):
         super().__init__(x_dim, u_dim)
         self.n_members = n_members
-        self.dims = [x_dim + u_dim, *hidden_layer_sizes, 2 * x_dim]
+        self.learn_reward = bool(learn_reward)
+        self.dims = [x_dim + u_dim, *hidden_layer_sizes, 2 * x_dim + (2 if self.learn_reward else 0)]
         self.spec = ops.MlpSpec(self.dims, activation, n_members)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
@@ -64,12 +72,18 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
 
     def fit(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, num_steps: int, batch_size: int = 256,
             learning_rate: float = 1e-3, weight_decay: float = 0.0, key: int = 0, predict_delta: bool = True,
-            min_std: float = 1e-3, n_rows: Optional[int] = None, next_obs_off: Optional[int] = None):
+            min_std: float = 1e-3, n_rows: Optional[int] = None, next_obs_off: Optional[int] = None,
+            reward_off: Optional[int] = None):
         """Model learning (N3 — not in the reference, whose model would come from `bsm`): `num_steps` AdamW steps on the
         members' Gaussian negative log-likelihood, each member on its own bootstrapped minibatch (sampling with replacement
         from rows[:n_rows]; Philox randint on the device).  `rows` are true-buffer transition rows (obs, action, reward,
-        discount, next_obs, ...).  Updates dynamics_params.params in place; returns (dynamics_params, losses [num_steps, E])."""
+        discount, next_obs, ...).  With learn_reward the reward head is fitted to column `reward_off` (default x_dim + u_dim, the
+        Transition's reward).  Updates dynamics_params.params in place; returns (dynamics_params, losses [num_steps, E])."""
         dev = self.device
+        if reward_off is not None and not self.learn_reward:
+            raise ValueError("reward_off needs EnsembleDynamics(learn_reward=True)")
+        if self.learn_reward and reward_off is None:
+            reward_off = self.x_dim + self.u_dim
         rows = rows.to(dev, torch.float32).contiguous()
         R = int(rows.shape[0] if n_rows is None else n_rows)
         if R <= 0:
@@ -90,13 +104,14 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         col0 = rows[:, :1].contiguous()          # the sampler gathers something; one column keeps that cheap
         for it in range(num_steps):
             ops.replay_sample(col0, self._fit_state, E * batch_size, seed=seed, offset=it, out=self._fit_scratch, idx_out=self._fit_idx)
-            g = self._nll(dynamics_params.params, rows, self._fit_idx.view(E, batch_size), next_obs_off=next_obs_off)
+            g = self._nll(dynamics_params.params, rows, self._fit_idx.view(E, batch_size), next_obs_off=next_obs_off,
+                          reward_off=reward_off)
             self._opt.step(dynamics_params.params, g)
             losses[it].copy_(self._nll.metrics)
         return dynamics_params, losses
 
     def member_outputs(self, x: torch.Tensor, u: torch.Tensor, dynamics_params: EnsembleDynamicsParams) -> torch.Tensor:
-        """[E, N, 2*x_dim] raw member outputs — mbpo_ensemble_mlp_forward."""
+        """[E, N, 2*x_dim] raw member outputs (+ [mu_r, raw_r] with learn_reward) — mbpo_ensemble_mlp_forward."""
         xu = torch.cat([x.reshape(-1, self.x_dim), u.reshape(-1, self.u_dim)], dim=1).to(self.device, torch.float32).contiguous()
         return ops.ensemble_mlp_forward(dynamics_params.params, self.spec, xu)
 
@@ -105,12 +120,48 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         y = self.member_outputs(x, u, dynamics_params)
         X = self.x_dim
         mu = y[..., :X] + (x.reshape(-1, X) if predict_delta else 0.0)
-        sig = torch.nn.functional.softplus(y[..., X:]) + min_std
+        sig = torch.nn.functional.softplus(y[..., X:2 * X]) + min_std
         mean = mu.mean(dim=0)
         std = torch.sqrt((sig ** 2).mean(dim=0) + mu.var(dim=0, unbiased=False))
         if x.dim() == 1:
             mean, std = mean[0], std[0]
         return Normal(mean, std), dynamics_params
+
+    def reward(self, x, u, dynamics_params, min_std: float = 1e-3) -> Normal:
+        """The reward head's mixture moments over members at (x, u): mean = E_e[mu_r,e], std = sqrt(E_e[sigma_r,e^2] + Var_e[mu_r,e])."""
+        if not self.learn_reward:
+            raise ValueError("this ensemble has no reward head (EnsembleDynamics(learn_reward=True))")
+        y = self.member_outputs(x, u, dynamics_params)
+        X = self.x_dim
+        mu = y[..., 2 * X]
+        sig = torch.nn.functional.softplus(y[..., 2 * X + 1]) + min_std
+        mean = mu.mean(dim=0)
+        std = torch.sqrt((sig ** 2).mean(dim=0) + mu.var(dim=0, unbiased=False))
+        if x.dim() == 1:
+            mean, std = mean[0], std[0]
+        return Normal(mean, std)
+
+
+class LearnedReward(Reward[EnsembleDynamicsParams]):
+    """The reward an EnsembleDynamics(learn_reward=True) predicts (MBPO_REWARD_LEARNED): its parameters ARE the dynamics'
+    (EnsembleSystem.init_params binds the same EnsembleDynamicsParams object to both, so fit's in-place updates reach both).
+    min_std (the floor of the reported std): None takes the EnsembleSystem's own min_std when the reward is bound to one, 1e-3 alone."""
+
+    def __init__(self, dynamics: EnsembleDynamics, min_std: Optional[float] = None):
+        if not isinstance(dynamics, EnsembleDynamics) or not dynamics.learn_reward:
+            raise ValueError("LearnedReward needs an EnsembleDynamics(learn_reward=True)")
+        super().__init__(dynamics.x_dim, dynamics.u_dim)
+        self.dynamics, self.min_std = dynamics, min_std
+
+    def init_params(self, key: int) -> EnsembleDynamicsParams:
+        return self.dynamics.init_params(key)
+
+    def kernel_spec(self, reward_params, device):
+        return _hip.REWARD_LEARNED, None        # the kernels read the reward head of the dynamics' own parameters
+
+    def __call__(self, x, u, reward_params, x_next=None):
+        """Host evaluation: Normal(mean_e mu_r,e, mixture std) — the mean is what System.step returns in 'mean' mode."""
+        return self.dynamics.reward(x, u, reward_params, 1e-3 if self.min_std is None else self.min_std), reward_params
 
 
 class EnsembleSystem(System):
@@ -119,11 +170,26 @@ class EnsembleSystem(System):
         super().__init__(dynamics=dynamics, reward=reward)
         if mode not in _MODES:
             raise ValueError(f"mode must be one of {sorted(_MODES)}")
+        if isinstance(reward, LearnedReward):
+            if reward.dynamics is not dynamics or not dynamics.learn_reward:
+                raise ValueError("a LearnedReward must wrap this system's own EnsembleDynamics(learn_reward=True)")
+            if reward.min_std is None:
+                reward.min_std = min_std                   # one std floor for the state and the reward heads
+            elif reward.min_std != min_std:
+                raise ValueError(f"LearnedReward.min_std {reward.min_std} differs from the system's min_std {min_std}")
         self.mode, self.predict_delta, self.sample_noise, self.min_std = mode, predict_delta, sample_noise, min_std
+
+    def init_params(self, key: int) -> SystemParams:
+        if not isinstance(self.reward, LearnedReward):
+            return super().init_params(key)
+        keys = K.split(key, 3)                                     # System.init_params's split: the same dynamics parameters
+        dp = self.dynamics.init_params(keys[0])
+        return SystemParams(dynamics_params=dp, reward_params=dp, key=keys[2])      # one parameter object: fit updates both
 
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         rp = system_params.reward_params
-        ck = (repr(rp), str(device))
+        # (the learned reward has no parameter vector: its params hold a device tensor, whose repr would copy it to the host)
+        ck = ("learned" if isinstance(self.reward, LearnedReward) else repr(rp), str(device))
         if getattr(self, "_rspec_key", None) != ck:    # cached: no H2D copy inside a captured graph
             self._rspec = self.reward.kernel_spec(rp, device)
             self._rspec_key = ck

@@ -7,7 +7,8 @@ takes (bptt_optimizer.py:183-186 accepts any `actor_features` / `critic_features
     EnsembleSystem   every mode, with the member MLPs as HIP autograd nodes (ops.HipMlp), quadratic or Pendulum reward in torch:
                      'mean': x' = [x +] mean_e mu_e([x, u]);  'ts1' / 'tsinf': x' = [x +] mu_m (+ (softplus(raw_m) + min_std) * eps),
                      the member m and eps of the step handed in by ops.BpttActorGradGeneric (the fused kernel's Philox draws), the
-                     gradient pathwise through the selected member (the draw itself is not differentiated)
+                     gradient pathwise through the selected member (the draw itself is not differentiated); a learned reward
+                     (MBPO_REWARD_LEARNED) is the reward head y[..., 2x] of the same members: mean over members, or member m
 """
 from __future__ import annotations
 
@@ -61,6 +62,7 @@ class DifferentiableBuiltin:
     def step(self, x, u, system_params, member=None, noise=None):
         from mbpo import ops
         spec, X, U = self.spec, self.x_dim, self.u_dim
+        rew = None
         if spec["system_kind"] == _hip.SYS_PENDULUM:
             nxt = pendulum_next_state(x, u, system_params.dynamics_params)
         else:
@@ -68,16 +70,20 @@ class DifferentiableBuiltin:
             base = x if spec.get("ens_predict_delta", True) else 0.0
             if self.ens_mode == _hip.ENS_MEAN:
                 nxt = base + y[..., :X].mean(0)
+                if spec["reward_kind"] == _hip.REWARD_LEARNED:
+                    rew = y[..., 2 * X].mean(0)
             else:
                 if member is None or (self.sample_noise and noise is None):
                     raise _hip.MbpoHipError("trajectory sampling: step needs the step's member (and noise) draws")
                 n = x.shape[0]
                 ym = y.gather(0, member.long().reshape(1, n, 1).expand(1, n, y.shape[-1]))[0]     # row i: member[i]'s outputs
                 nxt = base + ym[:, :X]
+                if spec["reward_kind"] == _hip.REWARD_LEARNED:
+                    rew = ym[:, 2 * X]
                 if self.sample_noise:
                     nxt = nxt + (torch.nn.functional.softplus(ym[:, X:2 * X]) + spec["ens_min_std"]) * noise
-        if spec["reward_kind"] == _hip.REWARD_PENDULUM:
+        if rew is None and spec["reward_kind"] == _hip.REWARD_PENDULUM:
             rew = pendulum_reward(x, u, system_params.reward_params)
-        else:
+        elif rew is None:
             rew = quadratic_reward(x, u, spec["reward_params"], X, U)
         return SystemState(x_next=nxt, reward=rew, system_params=system_params)

@@ -176,8 +176,9 @@ def main():
         del p, gr, tgt, opt
 
     # ---------------------------------------------------------------- R1-R7: fused model rollout
-    def rollout_case(N, X, U, E, S, hid_pi, hid_dyn, reps):
-        pd, dd = [X, *hid_pi, 2 * U], [X + U, *hid_dyn, 2 * X]
+    def rollout_case(N, X, U, E, S, hid_pi, hid_dyn, reps, learned_reward=False):
+        # learned_reward: the members carry the reward head (2X + 2 outputs) and the rollout reads it (MBPO_REWARD_LEARNED)
+        pd, dd = [X, *hid_pi, 2 * U], [X + U, *hid_dyn, 2 * X + (2 if learned_reward else 0)]
         pp = lecun_flat(pd, g).to(dev)
         dp = lecun_flat(dd, g, E).to(dev)
         pd_k, dd_k = pd, dd
@@ -190,21 +191,24 @@ def main():
         obs = torch.randn(N, X, generator=g).to(dev)
         first = obs.clone()
         steps, done = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
-        rp = torch.cat([torch.zeros(X), torch.ones(X), torch.ones(U) * 0.1]).to(dev)
+        rp = None if learned_reward else torch.cat([torch.zeros(X), torch.ones(X), torch.ones(U) * 0.1]).to(dev)
+        rk = _hip.REWARD_LEARNED if learned_reward else _hip.REWARD_QUADRATIC
         rows = torch.empty(S * N, 2 * X + U + 3, device=dev)
 
         def run():
             ops.model_rollout(policy_params=pp, policy_spec=ops.MlpSpec(pd_k), x_dim=X, u_dim=U, obs=obs, first_obs=first, steps=steps,
                               done=done, n_steps=S, episode_length=S, system_kind=_hip.SYS_ENSEMBLE, dyn_params=dp,
-                              dyn_spec=ops.MlpSpec(dd_k, "swish", E), reward_kind=_hip.REWARD_QUADRATIC, reward_params=rp, seed=1,
+                              dyn_spec=ops.MlpSpec(dd_k, "swish", E), reward_kind=rk, reward_params=rp, seed=1,
                               offset=0, out=rows)
         t, te = both(run, reps)
         flop = N * S * (2 * E * mlp_macs(dd) + 2 * mlp_macs(pd))
         e = mfma_entry("k_model_rollout", "mbpo_model_rollout",
-                       {"N": N, "x": X, "u": U, "E": E, "S": S, "policy": list(hid_pi), "member": list(hid_dyn)}, t, flop,
+                       {"N": N, "x": X, "u": U, "E": E, "S": S, "policy": list(hid_pi), "member": list(hid_dyn),
+                        "reward": "learned" if learned_reward else "quadratic"}, t, flop,
                        "2*E*M + 2*P FLOP per transition", {"transitions_per_s": N * S / t})
         out.append(e)
-        log(f"rollout N={N} x={X} E={E} {hid_dyn}: {t * 1e6:.1f} us  {N * S / t / 1e6:.1f} M transitions/s")
+        log(f"rollout N={N} x={X} E={E} {hid_dyn}{' learned reward' if learned_reward else ''}: {t * 1e6:.1f} us  "
+            f"{N * S / t / 1e6:.1f} M transitions/s")
 
     def attempt(fn, *a):
         try:
@@ -214,6 +218,7 @@ def main():
             log(f"{fn.__name__}{a}: {e}")
 
     if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50)       # C2
+    if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50, learned_reward=True)   # C2, learned reward
     if want("rollout_case"): rollout_case(32768, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 20)      # C4's global env count on one GPU
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (64, 64, 64), (256, 256), 20)   # "also report 256x2" members
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (256, 256), (256, 256), 20)
