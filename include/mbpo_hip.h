@@ -529,7 +529,11 @@ int mbpo_soft_update(const float *target, const float *online, float *out, int64
  * reward_off >= 0 (a [x+u] -> [2x+2] ensemble, MBPO_REWARD_LEARNED): the reward head is fitted too; the target r = row[reward_off]
  * (never delta-encoded), sigma_r = softplus(raw_r) + min_std, and loss_e gains mean_b [ 0.5 ((r - mu_r)/sigma_r)^2 + log sigma_r ].
  * reward_off = -1: no reward term (a 2x + 2 ensemble then gets zero gradient on its reward head).
- * Apply with mbpo_adamw_step on the whole flat vector (members are independent, AdamW is elementwise).  Hidden width 64. */
+ * Apply with mbpo_adamw_step on the whole flat vector (members are independent, AdamW is elementwise).
+ * Any hidden sizes.  Hidden layers all 64 wide whose 16-row tile fits 160 KiB of LDS: the fused kernel (two launches).  Any other
+ * shape (other widths, unequal widths, deeper or wider-output 64 stacks): a layer-by-layer path (gather, one GEMM launch per Dense
+ * layer, NLL head, backward GEMM levels writing grads directly), the same loss and gradient, deterministic.  The workspace size
+ * depends on the path; mbpo_ens_nll_workspace_floats needs no device. */
 typedef struct mbpo_ens_train_desc {
   int32_t x_dim, u_dim;
   mbpo_mlp_desc dynamics;

@@ -430,7 +430,14 @@ class BPTTOptimizer(BaseOptimizer):
         n = eval_obs.shape[0]
         obs = eval_obs.clone()
         zeros = torch.zeros(n, device=self.device)
-        rows = ops.model_rollout(policy_params=w.actor_params, policy_spec=self.actor_spec, x_dim=X, u_dim=U, obs=obs,
+        params, spec = w.actor_params, self.actor_spec
+        dyn_spec = w.rollout_spec.get("dyn_spec")
+        dyn_width = dyn_spec.dims[1] if dyn_spec is not None and len(dyn_spec.dims) > 2 else None
+        if dyn_width is not None and dyn_width != self.actor_width and dyn_width in ops.ROLLOUT_WIDTHS:
+            # the rollout kernel runs the policy at the model's hidden width: the actor zero-padded (the same network)
+            params = ops.embed_mlp_params(params, self.actor_dims, dyn_width)
+            spec = ops.MlpSpec(ops.padded_dims(self.actor_dims, dyn_width), self.policy_activation, 1)
+        rows = ops.model_rollout(policy_params=params, policy_spec=spec, x_dim=X, u_dim=U, obs=obs,
                                  first_obs=obs.clone(), steps=zeros, done=zeros.clone(), n_steps=self.evaluation_horizon,
                                  episode_length=2 ** 30, norm_mean=w.state_norm.mean.contiguous(), norm_std=w.state_norm.std.contiguous(),
                                  deterministic=True, action_clip=0.999, seed=0, **w.rollout_spec)
@@ -539,8 +546,12 @@ class _Work:
         self.state_norm = st.state_normalizer_state.clone()
         self.reward_norm = st.reward_normalizer_state.clone()
         self.rollout_spec, self.sys_kw = opt._system_kwargs(st.system_params)
-        self.generic = self.rollout_spec["system_kind"] == _hip.SYS_GENERIC or opt.wide
-        if opt.wide and self.rollout_spec["system_kind"] != _hip.SYS_GENERIC:
+        # the fused BPTT kernel also needs a 64-wide learned model: any other ensemble (e.g. MBPO's 4 x 200, stored at 256) takes the
+        # wide path even under 64-wide actor and critic networks
+        dyn_spec = self.rollout_spec.get("dyn_spec")
+        wide_model = dyn_spec is not None and any(int(h) != 64 for h in dyn_spec.dims[1:-1])
+        self.generic = self.rollout_spec["system_kind"] == _hip.SYS_GENERIC or opt.wide or wide_model
+        if self.generic and self.rollout_spec["system_kind"] != _hip.SYS_GENERIC:
             # wider networks than the fused BPTT kernel takes: the built-in System as a node of the torch autograd graph
             from mbpo.systems.torch_steps import DifferentiableBuiltin
             self.sys_kw = dict(system=DifferentiableBuiltin(opt.system, self.rollout_spec), system_params=st.system_params)

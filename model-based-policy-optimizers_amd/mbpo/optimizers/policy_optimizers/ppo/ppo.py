@@ -133,6 +133,8 @@ class PPO:
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.policy_dims_logical = [self.x_dim, *policy_hidden_layer_sizes, 2 * self.u_dim]
         self.value_dims_logical = [self.x_dim, *critic_hidden_layer_sizes, 1]
+        # the ensemble's KERNEL hidden sizes (EnsembleDynamics.dims: a 4 x 200 model is stored zero-padded to 256), which the fused
+        # rollout runs beside the policy
         dyn_hidden = list(getattr(getattr(self.env.system, "dynamics", None), "dims", [])[1:-1]) if self.env.system.fused else []
         widest = max([int(h) for h in (*policy_hidden_layer_sizes, *critic_hidden_layer_sizes, *dyn_hidden)], default=0)
         if widest <= ops.KERNEL_WIDTHS[-1]:

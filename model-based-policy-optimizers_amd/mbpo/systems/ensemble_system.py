@@ -53,22 +53,53 @@ def lecun_uniform_flat(dims: Sequence[int], gen: torch.Generator) -> torch.Tenso
     return torch.cat(parts)
 
 
+def kernel_width_for(hidden_layer_sizes: Sequence[int]) -> Optional[int]:
+    """The hidden width an ensemble of these hidden sizes is stored at: the smallest of ops.ROLLOUT_WIDTHS that holds every layer
+    (200 -> 256, (200, 100) -> 256), so that the rollout kernels take it; None above 256 (the logical sizes, layer by layer only)."""
+    hid = [int(h) for h in hidden_layer_sizes]
+    if not hid or max(hid) > ops.ROLLOUT_WIDTHS[-1]:
+        return None
+    return ops.common_width(hid, supported=ops.ROLLOUT_WIDTHS, what="EnsembleDynamics")
+
+
 class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
-    """learn_reward: the members also predict the reward (two more outputs, [mu_r, raw_r]); see LearnedReward."""
+    """learn_reward: the members also predict the reward (two more outputs, [mu_r, raw_r]); see LearnedReward.
+
+    Any hidden sizes.  dims_logical are the sizes asked for; dims / spec are the KERNEL shapes the parameters are stored at: every
+    hidden layer zero-padded to kernel_width (kernel_width_for; ops.py "hidden-width padding"), so that the rollout kernels run the
+    members.  64, 128 and 256 wide stacks are their own kernel shapes.  The padding is a fixed point of `fit` (padded entries get
+    exactly zero gradient and AdamW keeps them at zero), so the stored network stays the logical one; logical_params /
+    from_logical_params convert.  Above 256 kernel_width is None and the parameters are logical: fit, member_outputs and
+    next_state run layer by layer; the rollout consumers refuse the shape."""
 
     def __init__(self, x_dim: int, u_dim: int, n_members: int = 5, hidden_layer_sizes: Sequence[int] = (64, 64, 64),
                  activation: str = "swish", device=None, learn_reward: bool = False):
         super().__init__(x_dim, u_dim)
         self.n_members = n_members
         self.learn_reward = bool(learn_reward)
-        self.dims = [x_dim + u_dim, *hidden_layer_sizes, 2 * x_dim + (2 if self.learn_reward else 0)]
+        self.dims_logical = [x_dim + u_dim, *[int(h) for h in hidden_layer_sizes], 2 * x_dim + (2 if self.learn_reward else 0)]
+        self.kernel_width = kernel_width_for(hidden_layer_sizes)
+        self.dims = ops.padded_dims(self.dims_logical, self.kernel_width)
         self.spec = ops.MlpSpec(self.dims, activation, n_members)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
     def init_params(self, key: int) -> EnsembleDynamicsParams:
         gen = torch.Generator().manual_seed(K.PRNGKey(key) % (2 ** 63))
-        flat = torch.cat([lecun_uniform_flat(self.dims, gen) for _ in range(self.n_members)])
-        return EnsembleDynamicsParams(params=flat.to(self.device))
+        flat = torch.cat([lecun_uniform_flat(self.dims_logical, gen) for _ in range(self.n_members)])
+        return self.from_logical_params(flat)
+
+    def logical_params(self, dynamics_params: EnsembleDynamicsParams) -> torch.Tensor:
+        """The members' flat parameters at dims_logical ([E * P_logical], on the parameters' device)."""
+        if self.kernel_width is None:
+            return dynamics_params.params
+        return ops.extract_mlp_params(dynamics_params.params, self.dims_logical, self.kernel_width, self.n_members)
+
+    def from_logical_params(self, flat: torch.Tensor) -> EnsembleDynamicsParams:
+        """Flat parameters at dims_logical ([E * P_logical]) -> EnsembleDynamicsParams stored at the kernel shapes."""
+        flat = flat.reshape(-1).to(torch.float32)
+        if self.kernel_width is not None:
+            flat = ops.embed_mlp_params(flat, self.dims_logical, self.kernel_width, self.n_members)
+        return EnsembleDynamicsParams(params=flat.to(self.device).contiguous())
 
     def fit(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, num_steps: int, batch_size: int = 256,
             learning_rate: float = 1e-3, weight_decay: float = 0.0, key: int = 0, predict_delta: bool = True,

@@ -182,10 +182,10 @@ def main():
         pp = lecun_flat(pd, g).to(dev)
         dp = lecun_flat(dd, g, E).to(dev)
         pd_k, dd_k = pd, dd
-        if max(hid_pi) != max(hid_dyn):
-            # the fused kernel walks policy and members at ONE hidden width: the host zero-pads the narrower net (as the trainers
-            # do, INTEGRATION.md "Network shapes"); FLOP are counted on the logical shapes
-            w = max(max(hid_pi), max(hid_dyn))
+        w = ops.common_width(hid_pi, hid_dyn, supported=ops.ROLLOUT_WIDTHS)
+        if any(h != w for h in (*hid_pi, *hid_dyn)):
+            # the fused kernel walks policy and members at ONE hidden width in {64, 128, 256}: the host zero-pads the narrower nets
+            # (as the trainers and EnsembleDynamics do, INTEGRATION.md "Network shapes"); FLOP are counted on the logical shapes
             pp, dp = ops.embed_mlp_params(pp, pd, w), ops.embed_mlp_params(dp, dd, w, E)
             pd_k, dd_k = ops.padded_dims(pd, w), ops.padded_dims(dd, w)
         obs = torch.randn(N, X, generator=g).to(dev)
@@ -223,6 +223,7 @@ def main():
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (64, 64, 64), (256, 256), 20)   # "also report 256x2" members
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (256, 256), (256, 256), 20)
     if want("rollout_case"): attempt(rollout_case, 4096, 17, 6, 10, 5, (64, 64, 64), (64, 64, 64), 20)     # C5 shape through the rollout kernel
+    if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 7, 5, (64, 64, 64), (200, 200, 200, 200), 20)   # MBPO's model, stored at 256
 
     # ---------------------------------------------------------------- R2: vmapped ensemble forward (System.step outside the fused rollout)
     def ens_fwd_case(N, X, U, E, hid, reps):
@@ -330,6 +331,27 @@ def main():
     out.append(mfma_entry("k_ens_nll_fwd_bwd + k_ens_reduce", "mbpo_ens_nll_grads", {"x": X, "u": U, "E": E, "B": Bn}, t,
                           E * Bn * 3 * 2 * mlp_macs(dd), "3*(2M) FLOP per (member, sample)"))
     log(f"ensemble nll: {t * 1e6:.1f} us")
+
+    # one EnsembleDynamics.fit step on MBPO's model (7 x 4 x 200, stored zero-padded at 256): Philox minibatch draw, the layered NLL path
+    # (gather, one GEMM launch per Dense layer forward, NLL head, the backward's GEMM levels) and AdamW, as fit issues them
+    def fit_case(X, U, E, hid, B, reps):
+        from mbpo.systems import EnsembleDynamics
+        dyn = EnsembleDynamics(X, U, n_members=E, hidden_layer_sizes=hid, device=dev)
+        p = dyn.init_params(0)
+        rows = torch.randn(8192, 2 * X + U + 2, generator=g).to(dev)
+        dyn.fit(p, rows, num_steps=1, batch_size=B)          # builds the fit state (descriptor, workspace, optimizer)
+        col0 = rows[:, :1].contiguous()
+
+        def step():
+            ops.replay_sample(col0, dyn._fit_state, E * B, seed=1, offset=0, out=dyn._fit_scratch, idx_out=dyn._fit_idx)
+            dyn._opt.step(p.params, dyn._nll(p.params, rows, dyn._fit_idx.view(E, B)))
+        t, te = both(step, reps)
+        out.append(mfma_entry("k_replay_sample + layered NLL path + AdamW", "mbpo_ens_nll_grads", {"x": X, "u": U, "E": E, "B": B,
+                              "member": list(hid), "stored": dyn.dims[1:-1]}, t, E * B * 3 * 2 * mlp_macs(dyn.dims_logical),
+                              "3*(2M) FLOP per (member, sample), logical shapes"))
+        log(f"ensemble fit step E={E} {hid} B={B}: {t * 1e6:.1f} us (eager {te * 1e6:.1f} us)")
+
+    if want("fit_case"): attempt(fit_case, 4, 1, 7, (200, 200, 200, 200), 256, 50)
 
     # ---------------------------------------------------------------- N4: iCEM planner at the reference's defaults (icem_optimizer.py:25-50)
     def icem_case(H, reps):
