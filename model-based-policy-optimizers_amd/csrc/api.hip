@@ -1,5 +1,7 @@
 // api.hip — library-level entry points and host-side argument validation shared by all kernels.
 #include "common.hpp"
+#include <atomic>
+#include <stdlib.h>
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -41,6 +43,73 @@ int mbpo_make_mlp_dev(const mbpo_mlp_desc *d, MlpDev *out, const char *name) {
   out->n_layers = d->n_layers;
   out->act = d->activation;
   out->n_params = off;
+  return MBPO_OK;
+}
+
+int mbpo_make_mlp_dev_from(const int *dims, int n_layers, int activation, const float *params, int n_nets, const char *name,
+                           MlpDev *out) {
+  mbpo_mlp_desc md;
+  md.params = params ? params : (const float *)16;      // placeholder for size queries
+  md.net_stride = 0;
+  md.n_nets = n_nets;
+  md.n_layers = n_layers;
+  for (int l = 0; l <= n_layers && l <= MBPO_MAX_LAYERS; ++l) md.dims[l] = dims[l];
+  md.activation = activation;
+  return mbpo_make_mlp_dev(&md, out, name);
+}
+
+int mbpo_num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
+    if (n <= 0) n = 256;
+  }
+  return n;
+}
+
+// ---------------------------------------------------------------------------------------------- knobs (knobs.hpp)
+namespace {
+struct KnobDef {
+  const char *env;
+  long long dflt;
+  bool reread;
+};
+const KnobDef g_knob_def[KNOB_COUNT] = {
+#define MBPO_KNOB_DEF_(id, env, dflt, reread, meaning) {env, dflt, reread},
+    MBPO_KNOB_TABLE(MBPO_KNOB_DEF_)
+#undef MBPO_KNOB_DEF_
+};
+struct KnobState {
+  std::atomic<bool> cached{false};
+  std::atomic<long long> value{0};
+  std::atomic<int> override_{-1};
+};
+KnobState g_knob[KNOB_COUNT];
+}  // namespace
+
+long long mbpo_knob(KnobId id) {
+  const KnobDef &k = g_knob_def[id];
+  KnobState &s = g_knob[id];
+  // the environment is read on the first query even under an override (what a function-level static did before the table)
+  long long v;
+  if (!k.reread && s.cached.load(std::memory_order_acquire)) {
+    v = s.value.load(std::memory_order_relaxed);
+  } else {
+    const char *e = k.env ? getenv(k.env) : nullptr;
+    v = e ? atoll(e) : k.dflt;
+    s.value.store(v, std::memory_order_relaxed);
+    s.cached.store(true, std::memory_order_release);
+  }
+  const int o = s.override_.load(std::memory_order_relaxed);
+  return o >= 0 ? o : v;
+}
+
+int mbpo_knob_override(KnobId id) { return g_knob[id].override_.load(std::memory_order_relaxed); }
+
+int mbpo_knob_set_override(KnobId id, int mode) {
+  g_knob[id].override_.store(mode, std::memory_order_relaxed);
   return MBPO_OK;
 }
 

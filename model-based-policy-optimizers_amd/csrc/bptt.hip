@@ -66,11 +66,9 @@ extern "C" int mbpo_debug_set_bptt_stamps(void *buf) {
 // workspace shrinks), -1 = MBPO_BPTT_ZSTORE_MAX_MB and its cap decide.  bptt_plan reads it, so mbpo_bptt_workspace_floats and
 // mbpo_bptt_actor_grads agree while it is unchanged; set it BEFORE sizing a workspace — a store switched back on would overrun one
 // sized under recompute.  tests/test_gpu_bptt.py compares the two paths.
-static int g_bptt_zstore = -1;
 extern "C" int mbpo_debug_set_bptt_zstore(int mode) {
   MBPO_REQUIRE(mode == -1 || mode == 0, MBPO_ERR_ARG, "debug_set_bptt_zstore: mode must be -1 or 0");
-  g_bptt_zstore = mode;
-  return MBPO_OK;
+  return mbpo_knob_set_override(KNOB_BPTT_ZSTORE, mode);
 }
 
 // analytic pendulum step + vector-Jacobian product (dynamics/pendulum_dynamics.py:29-63)
@@ -722,24 +720,6 @@ struct BpttPlan {
   long long o_xs, o_as, o_eps, o_rs, o_vs, o_km, o_ts, o_z, o_slabs, o_extras, total;
 };
 
-static int bptt_hidden(const int *dims, int n_layers) {
-  if (n_layers < 2) return -1;
-  for (int l = 2; l < n_layers; ++l)
-    if (dims[l] != dims[1]) return -1;
-  return dims[1];
-}
-
-static int bptt_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "bptt: null descriptor");
   MBPO_REQUIRE(d->x_dim > 0 && d->u_dim > 0 && d->horizon > 0 && d->horizon <= 1024 && d->n > 0, MBPO_ERR_ARG, "bptt: bad sizes");
@@ -751,22 +731,12 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
                "bptt: unknown ens_mode %d", d->ens_mode);
   const bool ts = d->ens_mode != MBPO_ENS_MEAN, ts_noise = ts && d->ens_sample_noise;
   MBPO_REQUIRE(!ts || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG, "bptt: ens_mode ts1 / tsinf needs system_kind ENSEMBLE");
-  const int Ha = bptt_hidden(d->actor_dims, d->actor_layers), Hc = bptt_hidden(d->critic_dims, d->critic_layers);
+  const int Ha = same_hidden(d->actor_dims, d->actor_layers), Hc = same_hidden(d->critic_dims, d->critic_layers);
   MBPO_REQUIRE(Ha == Hc && Ha == 64, MBPO_ERR_UNSUPPORTED, "bptt: actor/critic hidden layers must all be 64 wide (got %d, %d)", Ha, Hc);
-  mbpo_mlp_desc md;
-  md.net_stride = 0; md.n_nets = 1;
-  md.params = d->actor_params ? d->actor_params : (const float *)16;
-  md.n_layers = d->actor_layers;
-  for (int l = 0; l <= d->actor_layers; ++l) md.dims[l] = d->actor_dims[l];
-  md.activation = d->actor_activation;
-  int rc = mbpo_make_mlp_dev(&md, &pl->pi, "bptt.actor");
+  int rc = mbpo_make_mlp_dev_from(d->actor_dims, d->actor_layers, d->actor_activation, d->actor_params, 1, "bptt.actor", &pl->pi);
   if (rc != MBPO_OK) return rc;
   pl->P = pl->pi.n_params;
-  md.params = d->target_critic_params ? d->target_critic_params : (const float *)16;
-  md.n_layers = d->critic_layers;
-  for (int l = 0; l <= d->critic_layers; ++l) md.dims[l] = d->critic_dims[l];
-  md.activation = d->critic_activation;
-  rc = mbpo_make_mlp_dev(&md, &pl->cr, "bptt.critic");
+  rc = mbpo_make_mlp_dev_from(d->critic_dims, d->critic_layers, d->critic_activation, d->target_critic_params, 1, "bptt.critic", &pl->cr);
   if (rc != MBPO_OK) return rc;
   pl->C = pl->cr.n_params;
   pl->cr.n_nets = 2;
@@ -781,7 +751,7 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
     E = pl->dyn.n_nets;
     dyn_out = pl->dyn.dims[pl->dyn.n_layers];
     MBPO_REQUIRE(pl->dyn.dims[0] == d->x_dim + d->u_dim && dyn_out >= d->x_dim, MBPO_ERR_ARG, "bptt: dynamics must map [x+u] -> [>= x]");
-    MBPO_REQUIRE(pl->dyn.n_layers >= 2 && bptt_hidden(pl->dyn.dims, pl->dyn.n_layers) == 64, MBPO_ERR_UNSUPPORTED,
+    MBPO_REQUIRE(pl->dyn.n_layers >= 2 && same_hidden(pl->dyn.dims, pl->dyn.n_layers) == 64, MBPO_ERR_UNSUPPORTED,
                  "bptt: dynamics hidden layers must all be 64 wide");
     MBPO_REQUIRE(!ts_noise || dyn_out >= 2 * d->x_dim, MBPO_ERR_ARG, "bptt: sampled model noise needs dynamics outputs [mu, raw std] (>= 2x)");
     if (pl->dyn.n_layers - 1 > lh) lh = pl->dyn.n_layers - 1;
@@ -797,7 +767,6 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
                MBPO_ERR_ARG, "bptt: bad reward_kind (the learned reward needs an ensemble with outputs 2x + 2)");
   pl->H = 64;
   pl->LH = lh;
-  auto up4 = [](int v) { return (v + 3) & ~3; };
   pl->ld_x = up4(d->x_dim) + 4;
   pl->ld_xu = up4(d->x_dim + d->u_dim) + 4;
   pl->ld_h = 64 + 4;
@@ -819,7 +788,7 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   }
   MBPO_REQUIRE(pl->EC >= 1, MBPO_ERR_UNSUPPORTED, "bptt: shapes do not fit 160 KiB of LDS");
   long long tiles = (d->n + 15) / 16;
-  long long cap = bptt_num_cus();
+  long long cap = mbpo_num_cus();
   pl->n_slabs = (int)(tiles < cap ? tiles : cap);
   long long o = 0;
   auto take = [&](long long n) { long long at = o; o += (n + 3) & ~3LL; return at; };
@@ -836,8 +805,8 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   // tile, step, member, hidden layer) — 1 GB at BASELINE config 5 (n = 4096, H = 32, E = 10); beyond MBPO_BPTT_ZSTORE_MAX_MB (default
   // 16384) the kernel recomputes instead
   pl->o_z = -1;
-  if (E > 0 && g_bptt_zstore != 0) {
-    static const long long max_mb = getenv("MBPO_BPTT_ZSTORE_MAX_MB") ? atoll(getenv("MBPO_BPTT_ZSTORE_MAX_MB")) : 16384;
+  if (E > 0 && mbpo_knob(KNOB_BPTT_ZSTORE) != 0) {
+    const long long max_mb = mbpo_knob(KNOB_BPTT_ZSTORE_MAX_MB);
     const long long zf = tiles * d->horizon * E * (pl->dyn.n_layers - 1) * 1024;
     if (zf * 4 <= max_mb * (1LL << 20)) pl->o_z = take(zf);
   }
@@ -896,30 +865,20 @@ extern "C" int mbpo_bptt_actor_grads(const mbpo_bptt_desc *d, void *stream) {
     }
   }
   A.stamps = g_bptt_stamps;
-  A.sh_pi = NetShape{A.pi.dims[0], A.pi.n_layers, A.pi.dims[A.pi.n_layers], A.pi.act};
-  A.sh_cr = NetShape{A.cr.dims[0], A.cr.n_layers, A.cr.dims[A.cr.n_layers], A.cr.act};
-  if (A.system_kind == MBPO_SYS_ENSEMBLE) A.sh_dyn = NetShape{A.dyn.dims[0], A.dyn.n_layers, A.dyn.dims[A.dyn.n_layers], A.dyn.act};
+  A.sh_pi = net_shape(A.pi);
+  A.sh_cr = net_shape(A.cr);
+  if (A.system_kind == MBPO_SYS_ENSEMBLE) A.sh_dyn = net_shape(A.dyn);
   else A.sh_dyn = NetShape{A.X + A.U, 0, A.X, 0};
   const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_cr) || net_is_wide(A.sh_dyn);
   const bool lr = A.reward_kind == MBPO_REWARD_LEARNED;
-#define LAUNCH_BPTT(W_, TS_, LR_)                                                                          \
-  {                                                                                                        \
-    rc = mbpo_ensure_lds<k_bptt_actor<64, W_, TS_, LR_>>(pl.lds, "bptt_actor_grads");                      \
-    if (rc != MBPO_OK) return rc;                                                                          \
-    hipLaunchKernelGGL((k_bptt_actor<64, W_, TS_, LR_>), dim3(pl.n_slabs), dim3(512), pl.lds, st, A);      \
-  }
-  if (lr) {
-    if (A.ts) {
-      if (wide) LAUNCH_BPTT(true, true, true) else LAUNCH_BPTT(false, true, true)
-    } else {
-      if (wide) LAUNCH_BPTT(true, false, true) else LAUNCH_BPTT(false, false, true)
-    }
-  } else if (A.ts) {
-    if (wide) LAUNCH_BPTT(true, true, false) else LAUNCH_BPTT(false, true, false)
-  } else {
-    if (wide) LAUNCH_BPTT(true, false, false) else LAUNCH_BPTT(false, false, false)
-  }
-#undef LAUNCH_BPTT
+  rc = mbpo_with_bool(lr, [&](auto LR) {
+    return mbpo_with_bool(A.ts != 0, [&](auto TS) {
+      return mbpo_with_bool(wide, [&](auto W) {
+        return mbpo_launch<k_bptt_actor<64, W.value, TS.value, LR.value>>(pl.n_slabs, 512, pl.lds, st, "bptt_actor_grads", A);
+      });
+    });
+  });
+  if (rc != MBPO_OK) return rc;
   BpttReduceArgs R;
   R.slabs = A.slabs; R.extras = A.extras; R.n_slabs = pl.n_slabs; R.P = pl.P; R.H = d->horizon; R.n = d->n; R.ent_coef = d->ent_coef;
   R.grads = d->grads; R.metrics = d->metrics;
@@ -1022,17 +981,14 @@ static int critic_plan(int x_dim, int critic_layers, const int *critic_dims, lon
   MBPO_REQUIRE(x_dim > 0 && batch > 0 && critic_dims, MBPO_ERR_ARG, "critic: bad sizes");
   MBPO_REQUIRE(critic_layers >= 2 && critic_layers <= MBPO_MAX_LAYERS, MBPO_ERR_ARG, "critic: need at least one hidden layer");
   MBPO_REQUIRE(critic_dims[0] == x_dim && critic_dims[critic_layers] == 1, MBPO_ERR_ARG, "critic must map [x] -> [1]");
-  MBPO_REQUIRE(bptt_hidden(critic_dims, critic_layers) == 64, MBPO_ERR_UNSUPPORTED, "critic: hidden layers must all be 64 wide");
-  mbpo_mlp_desc md;
-  md.net_stride = 0; md.n_nets = 1; md.params = (const float *)16; md.n_layers = critic_layers; md.activation = 0;
-  for (int l = 0; l <= critic_layers; ++l) md.dims[l] = critic_dims[l];
-  int rc = mbpo_make_mlp_dev(&md, cr, "critic");
+  MBPO_REQUIRE(same_hidden(critic_dims, critic_layers) == 64, MBPO_ERR_UNSUPPORTED, "critic: hidden layers must all be 64 wide");
+  int rc = mbpo_make_mlp_dev_from(critic_dims, critic_layers, 0, nullptr, 1, "critic", cr);
   if (rc != MBPO_OK) return rc;
   *LH = critic_layers - 1;
-  *ld_x = ((x_dim + 3) & ~3) + 4;
+  *ld_x = up4(x_dim) + 4;
   *ld_h = 68;
   *lds = sizeof(float) * (16ull * *ld_x + 128 + 128 + 16 + 32 + (size_t)(4 * *LH + 4) * 16 * *ld_h);
-  long long tiles = (batch + 15) / 16, cap = 1LL * bptt_num_cus();   // one 1024-thread workgroup fills a CU: one slab per CU (see ppo.hip)
+  long long tiles = (batch + 15) / 16, cap = 1LL * mbpo_num_cus();   // one 1024-thread workgroup fills a CU: one slab per CU (see ppo.hip)
   *n_slabs = (int)(tiles < cap ? tiles : cap);
   *total = (long long)*n_slabs * 2 * cr->n_params + ((*n_slabs + 3) & ~3);
   return MBPO_OK;
@@ -1059,13 +1015,10 @@ extern "C" int mbpo_critic_grads(const float *critic_params, int32_t x_dim, int3
   A.cr.params = critic_params; A.cr.act = activation; A.cr.n_nets = 2; A.cr.net_stride = A.cr.n_params;
   A.X = x_dim; A.D = row_len; A.transitions = transitions; A.lambda_values = lambda_values; A.s_mean = state_mean; A.s_std = state_std;
   A.idx = idx; A.batch = batch; A.slabs = workspace; A.extras = workspace + (long long)ns * 2 * A.cr.n_params;
-  A.sh = NetShape{x_dim, critic_layers, 1, activation};
-  const bool wide = net_is_wide(A.sh);
-  rc = wide ? mbpo_ensure_lds<k_critic_fwd_bwd<64, 4, true>>(lds, "critic_grads") : mbpo_ensure_lds<k_critic_fwd_bwd<64, 4, false>>(lds, "critic_grads");
-  if (rc != MBPO_OK) return rc;
+  A.sh = net_shape(A.cr);
   hipStream_t st = (hipStream_t)stream;
-  if (wide) hipLaunchKernelGGL((k_critic_fwd_bwd<64, 4, true>), dim3(ns), dim3(1024), lds, st, A);
-  else hipLaunchKernelGGL((k_critic_fwd_bwd<64, 4, false>), dim3(ns), dim3(1024), lds, st, A);
+  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_critic_fwd_bwd<64, 4, W.value>>(ns, 1024, lds, st, "critic_grads", A); });
+  if (rc != MBPO_OK) return rc;
   const int C2 = 2 * A.cr.n_params;
   hipLaunchKernelGGL(k_critic_reduce, dim3((C2 + 63) / 64), dim3(256), 0, st, (const float *)A.slabs, (const float *)A.extras, ns, C2,
                      (long long)batch, grads, metrics);

@@ -22,6 +22,8 @@ struct NetShape {
   int act;
 };
 
+static inline NetShape net_shape(const MlpDev &m) { return NetShape{m.dims[0], m.n_layers, m.dims[m.n_layers], m.act}; }
+
 // Re-materialise the lane id inside a loop body: hipcc otherwise hoists every per-lane address of every phase out of the
 // phase loop (LICM), keeps them all live (256 VGPRs, ~90 spills) and the hot loop pays for the spill traffic.
 __device__ __forceinline__ int opaque(int v) {

@@ -4,8 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/mbpo_hip.h"
 #include "fast_math.hpp"
+#include "knobs.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -52,6 +54,36 @@ int mbpo_ensure_lds(size_t bytes, const char *what) {
   return MBPO_OK;
 }
 
+// mbpo_ensure_lds<Kern> followed by the launch of Kern; returns the ensure status (launch errors surface in MBPO_CHECK_LAUNCH).
+// Launches without dynamic LDS keep plain hipLaunchKernelGGL.
+template <auto Kern, class... Args>
+int mbpo_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const char *what, const Args &...args) {
+  const int rc = mbpo_ensure_lds<Kern>(lds, what);
+  if (rc != MBPO_OK) return rc;
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  return MBPO_OK;
+}
+
+// A runtime bool selects a template bool: f is called with std::true_type{} or std::false_type{} and returns a status.
+template <class F>
+int mbpo_with_bool(bool b, F &&f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// ---------------------------------------------------------------- plan helpers (host)
+// compute units of the current device (cached; 256 when no device is visible, e.g. size queries on a build machine)
+int mbpo_num_cus();
+
+static inline int up4(int v) { return (v + 3) & ~3; }
+
+// the one width all hidden layers share, or -1 (none, or mixed widths)
+static inline int same_hidden(const int *dims, int n_layers) {
+  if (n_layers < 2) return -1;
+  for (int l = 2; l < n_layers; ++l)
+    if (dims[l] != dims[1]) return -1;
+  return dims[1];
+}
+
 // ---------------------------------------------------------------- device-side MLP description
 struct MlpDev {
   const float *params;
@@ -67,6 +99,9 @@ struct MlpDev {
 
 // host: validate + fill offsets. Returns MBPO_OK or error.
 int mbpo_make_mlp_dev(const mbpo_mlp_desc *d, MlpDev *out, const char *name);
+// the same from a descriptor's (dims, layers, activation) triple; params == NULL (a size query) validates against a placeholder
+int mbpo_make_mlp_dev_from(const int *dims, int n_layers, int activation, const float *params, int n_nets, const char *name,
+                           MlpDev *out);
 
 // ---------------------------------------------------------------- math
 // fast_sigmoid and the other hardware-transcendental helpers: fast_math.hpp

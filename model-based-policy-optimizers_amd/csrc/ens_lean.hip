@@ -115,21 +115,12 @@ bool ens_lean_supports(const int *dims, int n_layers, int act) {
 int ens_lean_launch(const EnsLeanArgs &A, int K, int n_cus, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   const int grid = A.E * A.wgs_per_member;
-  int rc;
-#define EL_K_(K_)                                                                                     \
-  if (K == K_) {                                                                                      \
-    rc = mbpo_ensure_lds<k_ens_fwd_lean<K_>>(ENS_LEAN_LDS_BYTES, "ens_lean");                         \
-    if (rc != MBPO_OK) return rc;                                                                     \
-    hipLaunchKernelGGL(k_ens_fwd_lean<K_>, dim3(grid), dim3(512), ENS_LEAN_LDS_BYTES, st, A);         \
-    (void)n_cus;                                                                                      \
-    return MBPO_OK;                                                                                   \
-  }
-  EL_K_(3) EL_K_(4) EL_K_(5) EL_K_(6) EL_K_(7)
-#undef EL_K_
-  {
-    mbpo_set_error("ens_lean: %d inputs have no instantiation", K);
-    return MBPO_ERR_UNSUPPORTED;
-  }
   (void)n_cus;
-  return MBPO_OK;
+  if (K == 3) return mbpo_launch<k_ens_fwd_lean<3>>(grid, 512, ENS_LEAN_LDS_BYTES, st, "ens_lean", A);
+  if (K == 4) return mbpo_launch<k_ens_fwd_lean<4>>(grid, 512, ENS_LEAN_LDS_BYTES, st, "ens_lean", A);
+  if (K == 5) return mbpo_launch<k_ens_fwd_lean<5>>(grid, 512, ENS_LEAN_LDS_BYTES, st, "ens_lean", A);
+  if (K == 6) return mbpo_launch<k_ens_fwd_lean<6>>(grid, 512, ENS_LEAN_LDS_BYTES, st, "ens_lean", A);
+  if (K == 7) return mbpo_launch<k_ens_fwd_lean<7>>(grid, 512, ENS_LEAN_LDS_BYTES, st, "ens_lean", A);
+  mbpo_set_error("ens_lean: %d inputs have no instantiation", K);
+  return MBPO_ERR_UNSUPPORTED;
 }

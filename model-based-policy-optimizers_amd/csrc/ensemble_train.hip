@@ -192,17 +192,6 @@ __global__ void __launch_bounds__(256) k_ens_nll_head(const float *y, const floa
   if (tid == 0) metrics[e] = s_red[0] / (float)B;
 }
 
-static int ens_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 struct EnsPlan {
   MlpDev dyn;
   bool layered;
@@ -229,7 +218,6 @@ static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d->row_len >= d->next_obs_off + X && d->next_obs_off >= X + U, MBPO_ERR_ARG, "ens_nll: bad row_len / next_obs_off");
   bool all64 = true;
   for (int l = 1; l < L; ++l) all64 = all64 && pl->dyn.dims[l] == 64;
-  auto up4 = [](int v) { return (v + 3) & ~3; };
   pl->LH = L - 1;
   pl->ld_xu = up4(X + U) + 4;
   pl->ld_h = 68;
@@ -239,7 +227,7 @@ static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   pl->layered = !all64 || pl->lds > 160 * 1024;
   if (!pl->layered) {
     const long long tiles = (d->batch + 15) / 16;
-    long long cap = (2LL * ens_num_cus() + E - 1) / E;
+    long long cap = (2LL * mbpo_num_cus() + E - 1) / E;
     if (cap < 1) cap = 1;
     pl->n_slots = (int)(tiles < cap ? tiles : cap);
     pl->total = (long long)E * pl->n_slots * pl->dyn.n_params + (((long long)E * pl->n_slots + 3) & ~3LL);
@@ -307,19 +295,16 @@ extern "C" int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream) {
   if (rc != MBPO_OK) return rc;
   if (pl.layered) return ens_nll_layered(d, pl, (hipStream_t)stream);
   EnsTrainArgs A;
-  const int L = pl.dyn.n_layers, E = pl.dyn.n_nets;
-  A.sh = NetShape{pl.dyn.dims[0], L, pl.dyn.dims[L], pl.dyn.act};
+  const int E = pl.dyn.n_nets;
+  A.sh = net_shape(pl.dyn);
   A.params = d->dynamics.params; A.net_stride = pl.dyn.net_stride; A.n_params = pl.dyn.n_params; A.E = E;
   A.X = d->x_dim; A.U = d->u_dim; A.D = d->row_len; A.noff = d->next_obs_off; A.roff = d->reward_off;
   A.rows = d->rows; A.idx = d->idx; A.batch = d->batch; A.predict_delta = d->predict_delta; A.min_std = d->min_std;
   A.slabs = d->workspace; A.extras = d->workspace + (long long)E * pl.n_slots * pl.dyn.n_params;
   A.n_slots = pl.n_slots; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
-  const bool wide = net_is_wide(A.sh);
-  rc = wide ? mbpo_ensure_lds<k_ens_nll_fwd_bwd<4, true>>(pl.lds, "ens_nll_grads") : mbpo_ensure_lds<k_ens_nll_fwd_bwd<4, false>>(pl.lds, "ens_nll_grads");
-  if (rc != MBPO_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (wide) hipLaunchKernelGGL((k_ens_nll_fwd_bwd<4, true>), dim3(E * pl.n_slots), dim3(512), pl.lds, st, A);
-  else hipLaunchKernelGGL((k_ens_nll_fwd_bwd<4, false>), dim3(E * pl.n_slots), dim3(512), pl.lds, st, A);
+  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_ens_nll_fwd_bwd<4, W.value>>(E * pl.n_slots, 512, pl.lds, st, "ens_nll_grads", A); });
+  if (rc != MBPO_OK) return rc;
   hipLaunchKernelGGL(k_ens_reduce, dim3((pl.dyn.n_params + 63) / 64, E), dim3(256), 0, st, (const float *)A.slabs, (const float *)A.extras,
                      pl.n_slots, pl.dyn.n_params, (long long)d->batch, d->grads, d->metrics);
   MBPO_CHECK_LAUNCH("ens_nll_grads");

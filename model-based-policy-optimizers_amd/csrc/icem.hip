@@ -140,11 +140,9 @@ extern "C" int mbpo_icem_sample(const float *mean, const float *std, const float
   const int work = (n_samples + n_prev) * u_dim;
   const int SB = 256 / horizon;      // series per block of the one-thread-per-(series, step) form (horizon <= 128: SB >= 2)
   const size_t lds = sizeof(float) * (2ull * horizon * K + K + 2ull * SB * K);
-  {      // (horizons above ~120 need more than the default 64 KB of dynamic LDS for the cos / sin tables)
-    const int rc = mbpo_ensure_lds<k_icem_sample_par>(lds, "icem_sample");
-    if (rc != MBPO_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_icem_sample_par, dim3((work + SB - 1) / SB), dim3(256), lds, (hipStream_t)stream, A);
+  // (horizons above ~120 need more than the default 64 KB of dynamic LDS for the cos / sin tables)
+  const int rc = mbpo_launch<k_icem_sample_par>((work + SB - 1) / SB, 256, lds, (hipStream_t)stream, "icem_sample", A);
+  if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("icem_sample");
   return MBPO_OK;
 }
@@ -165,12 +163,9 @@ extern "C" int mbpo_icem_sample_batched(const float *mean, const float *std, con
   const int work = (n_samples + n_prev) * u_dim;
   const int SB = 256 / horizon;
   const size_t lds = sizeof(float) * (2ull * horizon * K + K + 2ull * SB * K);
-  {
-    const int rc = mbpo_ensure_lds<k_icem_sample_batched>(lds, "icem_sample_batched");
-    if (rc != MBPO_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_icem_sample_batched, dim3((work + SB - 1) / SB, n_problems), dim3(256), lds, (hipStream_t)stream, A,
-                     (const unsigned long long *)seeds, (int)n_problems);
+  const int rc = mbpo_launch<k_icem_sample_batched>(dim3((work + SB - 1) / SB, n_problems), 256, lds, (hipStream_t)stream, "icem_sample_batched",
+                                                    A, (const unsigned long long *)seeds, (int)n_problems);
+  if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("icem_sample_batched");
   return MBPO_OK;
 }
@@ -406,11 +401,9 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
 // Test hook (not part of include/mbpo_hip.h): 0 = always the global-memory k_icem_update, 1 = k_icem_update_lds wherever its LDS
 // need fits (today the same as the default), -1 = the default dispatch.  tests/test_gpu_icem.py runs every update case under 0 and 1;
 // mbpo_icem_update_batched follows the same switch.
-static int g_icem_update = -1;
 extern "C" int mbpo_debug_set_icem_update(int mode) {
   MBPO_REQUIRE(mode >= -1 && mode <= 1, MBPO_ERR_ARG, "debug_set_icem_update: mode must be -1, 0 or 1");
-  g_icem_update = mode;
-  return MBPO_OK;
+  return mbpo_knob_set_override(KNOB_ICEM_UPDATE, mode);
 }
 
 extern "C" int mbpo_icem_update_constrained(const float *rows, int32_t row_len, int32_t reward_col, int32_t n_candidates, int32_t n_particles,
@@ -433,7 +426,7 @@ extern "C" int mbpo_icem_update_constrained(const float *rows, int32_t row_len, 
   IcemUpdateArgs A{values, candidates, n_candidates, horizon, u_dim, n_elites, n_prev, alpha, mean, std, best_value, best_sequence,
                    prev_elites, workspace};
   const size_t lds = (2ull * n_candidates + n_elites + (size_t)n_elites * horizon * u_dim) * sizeof(float);
-  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<false>, dim3(1), dim3(1024), lds, st, A);
+  if (mbpo_knob(KNOB_ICEM_UPDATE) != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<false>, dim3(1), dim3(1024), lds, st, A);
   else hipLaunchKernelGGL(k_icem_update<false>, dim3(1), dim3(1024), 0, st, A);
   MBPO_CHECK_LAUNCH("icem_update");
   return MBPO_OK;
@@ -472,7 +465,7 @@ extern "C" int mbpo_icem_update_batched(const float *rows, int32_t row_len, int3
   IcemUpdateArgs A{values, candidates, n_candidates, horizon, u_dim, n_elites, n_prev, alpha, mean, std, best_value, best_sequence,
                    prev_elites, workspace};
   const size_t lds = (2ull * n_candidates + n_elites + (size_t)n_elites * horizon * u_dim) * sizeof(float);      // per problem
-  if (g_icem_update != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<true>, dim3(n_problems), dim3(1024), lds, st, A);
+  if (mbpo_knob(KNOB_ICEM_UPDATE) != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<true>, dim3(n_problems), dim3(1024), lds, st, A);
   else hipLaunchKernelGGL(k_icem_update<true>, dim3(n_problems), dim3(1024), 0, st, A);
   MBPO_CHECK_LAUNCH("icem_update_batched");
   return MBPO_OK;

@@ -191,8 +191,7 @@ static int gemm_prepare(int mode, const GemmArgs &G, GemmArgs *H, long long *wg6
 // net (M = 20 992 rows: 328 x 4 tiles of 64) 1404 us per minibatch step with 64-tiles, 1298 with 32-tiles; SAC 256x3 at B = 4096
 // 883 -> 829 us (scripts/layered_ppo_timing.py, layered_timing.py; MBPO_LAYERED_T2_MIN overrides)
 static int tile_factor(long long wg64) {
-  static const long long t2_min = getenv("MBPO_LAYERED_T2_MIN") ? atoll(getenv("MBPO_LAYERED_T2_MIN")) : 4096;
-  return wg64 >= t2_min ? 2 : 1;
+  return wg64 >= mbpo_knob(KNOB_LAYERED_T2_MIN) ? 2 : 1;
 }
 
 int layered_gemm(int mode, const GemmArgs &G, hipStream_t st) {
@@ -231,7 +230,7 @@ struct GemmBatch {
     return MBPO_OK;
   }
   int flush(hipStream_t st) {
-    static const bool grouped = !(getenv("MBPO_LAYERED_GROUP") && atoi(getenv("MBPO_LAYERED_GROUP")) == 0);
+    const bool grouped = mbpo_knob(KNOB_LAYERED_GROUP) != 0;
     const int n = a.n;
     a.n = 0;
     const long long w = wg64;

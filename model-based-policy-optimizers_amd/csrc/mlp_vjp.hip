@@ -110,17 +110,6 @@ __global__ void __launch_bounds__(256) k_vjp_reduce(const float *slabs, int n_sl
   if (threadIdx.x < 64 && i < NW) dw[i] = g;
 }
 
-static int vjp_num_cus() {
-  static int n = 0;
-  if (!n) {
-    hipDeviceProp_t p;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 struct VjpPlan {
   MlpDev net;
   int n_slabs, ld_x, ld_h, ld_y, LH;
@@ -143,11 +132,11 @@ static int vjp_plan(const mbpo_mlp_desc *mlp, long long n, VjpPlan *pl, bool nee
   MBPO_REQUIRE(md.dims[0] <= 32 && md.dims[md.n_layers] <= 32, MBPO_ERR_UNSUPPORTED,
                "mlp_vjp: input width %d / output width %d beyond the register-image shapes (<= 32)", md.dims[0], md.dims[md.n_layers]);
   pl->LH = md.n_layers - 1;
-  pl->ld_x = ((md.dims[0] + 3) & ~3) + 4;
+  pl->ld_x = up4(md.dims[0]) + 4;
   pl->ld_h = 68;
-  pl->ld_y = ((md.dims[md.n_layers] + 3) & ~3) + 4;
+  pl->ld_y = up4(md.dims[md.n_layers]) + 4;
   pl->lds = sizeof(float) * (3ull * 16 * pl->ld_x + 4ull * 16 * pl->ld_y + (size_t)(4 * pl->LH + 4) * 16 * pl->ld_h);
-  const long long tiles = (n + 15) / 16, cap = 1LL * vjp_num_cus();   // one 1024-thread workgroup fills a CU: one slab per CU
+  const long long tiles = (n + 15) / 16, cap = 1LL * mbpo_num_cus();   // one 1024-thread workgroup fills a CU: one slab per CU
   pl->n_slabs = (int)(tiles < cap ? tiles : cap);
   pl->total = (long long)pl->n_slabs * md.n_nets * pl->net.n_params;
   return MBPO_OK;
@@ -173,16 +162,13 @@ extern "C" int mbpo_mlp_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n,
                "mlp_vjp: dw is laid out [net][params]: net_stride must equal the parameters per net (%d)", pl.net.n_params);
   VjpArgs A;
   A.net = pl.net;
-  A.sh = NetShape{mlp->dims[0], mlp->n_layers, mlp->dims[mlp->n_layers], mlp->activation};
+  A.sh = net_shape(pl.net);
   A.X = mlp->dims[0]; A.N_out = mlp->dims[mlp->n_layers]; A.n_nets = mlp->n_nets; A.want_dw = dw ? 1 : 0;
   A.x = x; A.mean = norm_mean; A.std = norm_std; A.dy = dy; A.y = y; A.dx = dx; A.slabs = dw ? workspace : nullptr;
   A.n = n; A.ld_x = pl.ld_x; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
-  const bool wide = net_is_wide(A.sh);
-  rc = wide ? mbpo_ensure_lds<k_mlp_vjp<64, 4, true>>(pl.lds, "mlp_vjp") : mbpo_ensure_lds<k_mlp_vjp<64, 4, false>>(pl.lds, "mlp_vjp");
-  if (rc != MBPO_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (wide) hipLaunchKernelGGL((k_mlp_vjp<64, 4, true>), dim3(pl.n_slabs), dim3(1024), pl.lds, st, A);
-  else hipLaunchKernelGGL((k_mlp_vjp<64, 4, false>), dim3(pl.n_slabs), dim3(1024), pl.lds, st, A);
+  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_mlp_vjp<64, 4, W.value>>(pl.n_slabs, 1024, pl.lds, st, "mlp_vjp", A); });
+  if (rc != MBPO_OK) return rc;
   if (dw) {
     const int NW = mlp->n_nets * pl.net.n_params;
     hipLaunchKernelGGL(k_vjp_reduce, dim3((NW + 63) / 64), dim3(256), 0, st, (const float *)workspace, pl.n_slabs, NW, dw);

@@ -686,35 +686,13 @@ struct PpoPlan {
 
 // Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_ppo_fwd_bwd, 1 = k_ppo_lean where it applies,
 // -1 = the MBPO_PPO_LEAN environment default (on).
-static int g_ppo_lean = -1;
 static unsigned long long *g_ppo_stamps = nullptr;
 // measurement hook: device buffer of >= 64 uint64 that k_ppo_lean fills with s_memtime stamps (workgroup 0, 12 per tile); NULL = off
 extern "C" int mbpo_debug_set_ppo_stamps(void *buf) {
   g_ppo_stamps = (unsigned long long *)buf;
   return MBPO_OK;
 }
-extern "C" int mbpo_debug_set_ppo_lean(int mode) {
-  g_ppo_lean = mode;
-  return MBPO_OK;
-}
-
-static int ppo_same_hidden(const int *dims, int n_layers) {
-  if (n_layers < 2) return -1;
-  for (int l = 2; l < n_layers; ++l)
-    if (dims[l] != dims[1]) return -1;
-  return dims[1];
-}
-
-static int ppo_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
+extern "C" int mbpo_debug_set_ppo_lean(int mode) { return mbpo_knob_set_override(KNOB_PPO_LEAN, mode); }
 
 static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "ppo: null descriptor");
@@ -728,23 +706,12 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(!d->non_equidistant_time || d->env_dt > 0.f, MBPO_ERR_ARG, "ppo: non_equidistant_time needs env_dt > 0");
   pl->neq = d->non_equidistant_time != 0;
   pl->clip = d->max_grad_norm > 0.f;
-  const int Hp = ppo_same_hidden(d->policy_dims, d->policy_layers), Hv = ppo_same_hidden(d->value_dims, d->value_layers);
-  static const int layered_env = getenv("MBPO_PPO_LAYERED") ? atoi(getenv("MBPO_PPO_LAYERED")) : 0;    // 1: force the layered path (tests)
-  pl->layered = layered_env != 0 || !(Hp == Hv && (Hp == 64 || Hp == 128));
-  mbpo_mlp_desc md;
-  md.net_stride = 0;
-  md.n_nets = 1;
-  md.params = d->params ? d->params : (const float *)16;
-  md.n_layers = d->policy_layers;
-  for (int l = 0; l <= d->policy_layers; ++l) md.dims[l] = d->policy_dims[l];
-  md.activation = d->policy_activation;
-  int rc = mbpo_make_mlp_dev(&md, &pl->pi, "ppo.policy");
+  const int Hp = same_hidden(d->policy_dims, d->policy_layers), Hv = same_hidden(d->value_dims, d->value_layers);
+  pl->layered = mbpo_knob(KNOB_PPO_LAYERED) != 0 || !(Hp == Hv && (Hp == 64 || Hp == 128));
+  int rc = mbpo_make_mlp_dev_from(d->policy_dims, d->policy_layers, d->policy_activation, d->params, 1, "ppo.policy", &pl->pi);
   if (rc != MBPO_OK) return rc;
   pl->P = pl->pi.n_params;
-  md.n_layers = d->value_layers;
-  for (int l = 0; l <= d->value_layers; ++l) md.dims[l] = d->value_dims[l];
-  md.activation = d->value_activation;
-  rc = mbpo_make_mlp_dev(&md, &pl->v, "ppo.value");
+  rc = mbpo_make_mlp_dev_from(d->value_dims, d->value_layers, d->value_activation, d->params, 1, "ppo.value", &pl->v);
   if (rc != MBPO_OK) return rc;
   pl->V = pl->v.n_params;
   pl->v.params = d->params ? d->params + pl->P : nullptr;
@@ -753,7 +720,6 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   const int lhp = d->policy_layers - 1, lhv = d->value_layers - 1;
   pl->LH = lhp > lhv ? lhp : lhv;
   pl->M = (long long)d->batch_size * d->unroll_length;
-  auto up4 = [](int v) { return (v + 3) & ~3; };
   pl->ld_x = up4(d->x_dim) + 4;
   pl->ld_h = Hp + 4;
   pl->ld_y = up4(2 * d->u_dim) + 4;
@@ -766,18 +732,17 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   // T = 40: 22 us of a 158 us minibatch_step, rocprofv3 round 3).  The 512-thread / 128-VGPR launch (sp2) holds two per CU.
   {
     const NetShape sp_ = NetShape{d->x_dim, d->policy_layers, 2 * d->u_dim, 0}, sv_ = NetShape{d->x_dim, d->value_layers, 1, 0};
-    static const int sp2_env = getenv("MBPO_PPO_SP2") ? atoi(getenv("MBPO_PPO_SP2")) : -1;
-    pl->sp2 = (Hp == 64 && !net_is_wide(sp_) && !net_is_wide(sv_) && tiles > ppo_num_cus() && sp2_env != 0) ? 1 : 0;
+    pl->sp2 = (Hp == 64 && !net_is_wide(sp_) && !net_is_wide(sv_) && tiles > mbpo_num_cus() && mbpo_knob(KNOB_PPO_SP2) != 0) ? 1 : 0;
   }
-  long long cap = (pl->sp2 ? 2LL : 1LL) * ppo_num_cus();
+  long long cap = (pl->sp2 ? 2LL : 1LL) * mbpo_num_cus();
   {
-    static const int lean_env = getenv("MBPO_PPO_LEAN") ? atoi(getenv("MBPO_PPO_LEAN")) : 1;
-    pl->lean = (g_ppo_lean >= 0 ? g_ppo_lean : lean_env) != 0 && !pl->layered &&
+    const bool want_lean = mbpo_knob(KNOB_PPO_LEAN) != 0;
+    pl->lean = want_lean && !pl->layered &&
                ppo_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->value_dims, d->value_layers,
                                  d->value_activation);
-    if (pl->lean) cap = ppo_num_cus();
+    if (pl->lean) cap = mbpo_num_cus();
     // the values + GAE launch has its own specialised form: the value network alone decides (64 x 2 or 64 x 3)
-    pl->vg_lean = (g_ppo_lean >= 0 ? g_ppo_lean : lean_env) != 0 && !pl->layered && d->u_dim == 1 &&      // (the kernel's row offsets assume u = 1)
+    pl->vg_lean = want_lean && !pl->layered && d->u_dim == 1 &&      // (the kernel's row offsets assume u = 1)
                   ppo_vg_lean_supports(d->x_dim, d->value_dims, d->value_layers, d->value_activation);
   }
   pl->n_slabs = (int)(tiles < cap ? tiles : cap);
@@ -796,17 +761,16 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   {
     // G = 1 while that does not oversubscribe the chip (a tile with a few rows of one trajectory wastes MFMA lanes nobody else wants:
     // the launch is a latency chain per workgroup); beyond 4 workgroups per CU, more trajectories per workgroup
-    static const int vg_env = getenv("MBPO_PPO_VALUES_GAE") ? atoi(getenv("MBPO_PPO_VALUES_GAE")) : -1;
     // at most 1024 workgroups: k_ppo_moments_combine reads NPT * 256 = 1024 {n, mean, M2} partials (4 x 256 CUs sits exactly at
     // that limit; a device with more CUs must not drop partials silently: ADVICE r3)
-    const long long cap_wg = 4LL * ppo_num_cus() < 1024 ? 4LL * ppo_num_cus() : 1024;
+    const long long cap_wg = 4LL * mbpo_num_cus() < 1024 ? 4LL * mbpo_num_cus() : 1024;
     long long G = (d->batch_size + cap_wg - 1) / cap_wg;
     if (G < 1) G = 1;
     const long long R = (long long)d->unroll_length + 1;
     // the [G][R] / [G][T] LDS arrays: values, truncation, termination, reward, advantages (+ the per-sample discount with neq), each
     // at most 1024 floats' worth of the constant-discount launch's five
     const int n_arr = pl->neq ? 6 : 5;
-    pl->vg_G = (!pl->layered && vg_env != 0 && n_arr * G * R <= 5 * 1024) ? (int)G : 0;
+    pl->vg_G = (!pl->layered && mbpo_knob(KNOB_PPO_VALUES_GAE) != 0 && n_arr * G * R <= 5 * 1024) ? (int)G : 0;
     pl->n_vg = pl->vg_G ? (int)((d->batch_size + pl->vg_G - 1) / pl->vg_G) : 0;
     const long long GT = (long long)pl->vg_G * d->unroll_length;
     pl->lds_vg = pl->lds_values + sizeof(float) * (size_t)(((pl->vg_G * R + 3) & ~3LL) + (n_arr - 1) * ((GT + 3) & ~3LL));
@@ -837,8 +801,21 @@ static void ppo_clip_apply_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, hip
   C.ss_part = d->workspace + pl.off_sspart; C.NPV = pl.NPV; C.n_parts = pl.n_ss;
   C.lr = d->lr; C.wd = d->wd; C.grad_scale = d->grad_scale; C.max_norm = d->max_grad_norm;
   // a few elements per thread: every workgroup re-adds all n_ss partials, so the grid is kept to at most 4 per CU
-  const int want = (pl.NPV + 255) / 256, cap = 4 * ppo_num_cus();
+  const int want = (pl.NPV + 255) / 256, cap = 4 * mbpo_num_cus();
   hipLaunchKernelGGL(k_ppo_clip_apply, dim3(want < cap ? want : cap), dim3(256), 0, st, C);
+}
+
+// k_ppo_values_gae<H, NC, NEQ>: NC = the workgroup's value chains (1..4), NEQ = per-sample discounts
+template <int H, int NC>
+static int values_gae_launch(const PpoPlan &pl, size_t lds, hipStream_t st, const PpoArgs &A) {
+  return mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values_gae<H, NC, Q.value>>(pl.n_vg, 256 * NC, lds, st, "ppo_grads", A); });
+}
+template <int H>
+static int values_gae_launch(int NC, const PpoPlan &pl, size_t lds, hipStream_t st, const PpoArgs &A) {
+  if (NC == 1) return values_gae_launch<H, 1>(pl, lds, st, A);
+  if (NC == 2) return values_gae_launch<H, 2>(pl, lds, st, A);
+  if (NC == 3) return values_gae_launch<H, 3>(pl, lds, st, A);
+  return values_gae_launch<H, 4>(pl, lds, st, A);
 }
 
 static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply) {
@@ -850,8 +827,8 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
   float *ws = d->workspace;
   PpoArgs A;
   A.pi = pl.pi; A.v = pl.v;
-  A.sh_pi = NetShape{pl.pi.dims[0], pl.pi.n_layers, pl.pi.dims[pl.pi.n_layers], pl.pi.act};
-  A.sh_v = NetShape{pl.v.dims[0], pl.v.n_layers, pl.v.dims[pl.v.n_layers], pl.v.act};
+  A.sh_pi = net_shape(pl.pi);
+  A.sh_v = net_shape(pl.v);
   A.X = d->x_dim; A.U = d->u_dim; A.B = d->batch_size; A.T = d->unroll_length; A.D = d->row_len;
   A.data = d->data; A.norm_mean = d->norm_mean; A.norm_std = d->norm_std; A.ent_noise = d->entropy_noise;
   A.step_count_rw = d->step_count;
@@ -870,7 +847,7 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
   hipStream_t st = (hipStream_t)stream;
   // 1. values pre-pass
   long long vt = (pl.M + d->batch_size + 15) / 16;
-  int vgrid = (int)(vt < 4LL * ppo_num_cus() ? vt : 4LL * ppo_num_cus());
+  int vgrid = (int)(vt < 4LL * mbpo_num_cus() ? vt : 4LL * mbpo_num_cus());
   if (pl.layered) {
     float *values = nullptr;
     rc = ppo_layered_values(d, pl.pi, pl.v, ws + pl.off_layered, A.trunc, A.term, A.rew, A.disc, &values, st);
@@ -895,38 +872,17 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
     const int tiles_wg = (int)(((long long)pl.vg_G * (d->unroll_length + 1) + 15) / 16);
     const int NCv = tiles_wg >= 4 ? 4 : tiles_wg;
     const size_t lds = pl.lds_vg + (size_t)(NCv - 1) * pl.lds_values;
-#define LVG_(H_, N_, Q_)                                                                             \
-  {                                                                                                  \
-    rc = mbpo_ensure_lds<k_ppo_values_gae<H_, N_, Q_>>(lds, "ppo_grads");                            \
-    if (rc != MBPO_OK) return rc;                                                                    \
-    hipLaunchKernelGGL((k_ppo_values_gae<H_, N_, Q_>), dim3(pl.n_vg), dim3(256 * N_), lds, st, A);    \
-  }
-#define LVG(H_, N_)                                                                                  \
-  {                                                                                                  \
-    if (pl.neq) LVG_(H_, N_, true) else LVG_(H_, N_, false)                                          \
-  }
-    if (pl.H == 64) {
-      if (NCv == 1) LVG(64, 1) else if (NCv == 2) LVG(64, 2) else if (NCv == 3) LVG(64, 3) else LVG(64, 4)
-    } else {
-      if (NCv == 1) LVG(128, 1) else if (NCv == 2) LVG(128, 2) else if (NCv == 3) LVG(128, 3) else LVG(128, 4)
-    }
-#undef LVG
-#undef LVG_
+    rc = pl.H == 64 ? values_gae_launch<64>(NCv, pl, lds, st, A) : values_gae_launch<128>(NCv, pl, lds, st, A);
+    if (rc != MBPO_OK) return rc;
     if (d->normalize_advantage)
       hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.n_vg, (float)pl.M, A.mom);
   } else {
-#define LV(H_, Q_)                                                                                   \
-  {                                                                                                  \
-    rc = mbpo_ensure_lds<k_ppo_values<H_, Q_>>(pl.lds_values, "ppo_grads");                          \
-    if (rc != MBPO_OK) return rc;                                                                    \
-    hipLaunchKernelGGL((k_ppo_values<H_, Q_>), dim3(vgrid), dim3(256), pl.lds_values, st, A);        \
-  }
     if (pl.H == 64) {
-      if (pl.neq) LV(64, true) else LV(64, false)
+      rc = mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values<64, Q.value>>(vgrid, 256, pl.lds_values, st, "ppo_grads", A); });
     } else {
-      if (pl.neq) LV(128, true) else LV(128, false)
+      rc = mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values<128, Q.value>>(vgrid, 256, pl.lds_values, st, "ppo_grads", A); });
     }
-#undef LV
+    if (rc != MBPO_OK) return rc;
   }
   // 2. GAE on [B,T] (batch-major: the data's native layout, no transpose)   losses.py:94-99,128-184 (losses_new.py:181-226 with neq)
   if (!pl.vg_G) {
@@ -969,18 +925,14 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
     if (rc != MBPO_OK) return rc;
   } else if (pl.H == 64) {
     const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_v);
-    rc = wide ? mbpo_ensure_lds<k_ppo_fwd_bwd<64, 4, true>>(pl.lds_fb, "ppo_grads") : mbpo_ensure_lds<k_ppo_fwd_bwd<64, 4, false>>(pl.lds_fb, "ppo_grads");
+    // (sp2 is only ever planned for networks that are not wide)
+    if (wide && !pl.sp2) rc = mbpo_launch<k_ppo_fwd_bwd<64, 4, true>>(pl.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
+    else if (!pl.sp2) rc = mbpo_launch<k_ppo_fwd_bwd<64, 4, false>>(pl.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
+    else rc = mbpo_launch<k_ppo_fwd_bwd<64, 2, false>>(pl.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);
     if (rc != MBPO_OK) return rc;
-    if (pl.sp2) {
-      rc = mbpo_ensure_lds<k_ppo_fwd_bwd<64, 2, false>>(pl.lds_fb, "ppo_grads");
-      if (rc != MBPO_OK) return rc;
-      hipLaunchKernelGGL((k_ppo_fwd_bwd<64, 2, false>), dim3(pl.n_slabs), dim3(512), pl.lds_fb, st, A);
-    } else if (wide) hipLaunchKernelGGL((k_ppo_fwd_bwd<64, 4, true>), dim3(pl.n_slabs), dim3(1024), pl.lds_fb, st, A);
-    else hipLaunchKernelGGL((k_ppo_fwd_bwd<64, 4, false>), dim3(pl.n_slabs), dim3(1024), pl.lds_fb, st, A);
   } else {
-    rc = mbpo_ensure_lds<k_ppo_fwd_bwd<128, 2, false>>(pl.lds_fb, "ppo_grads");
+    rc = mbpo_launch<k_ppo_fwd_bwd<128, 2, false>>(pl.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);
     if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL((k_ppo_fwd_bwd<128, 2, false>), dim3(pl.n_slabs), dim3(512), pl.lds_fb, st, A);
   }
   // 5. reduce
   PpoReduceArgs R;

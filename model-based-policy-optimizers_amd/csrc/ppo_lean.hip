@@ -558,13 +558,9 @@ __global__ void __launch_bounds__(512) k_ppo_vg_lean(const PpoVgLeanArgs A) {
 int ppo_vg_lean_launch(const PpoVgLeanArgs &A, int x_dim, int n_wgs, size_t arr_floats, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)(VG_ARR + arr_floats) * sizeof(float);
-  int rc;
 #define VG_XQ_(X_, Q_)                                                                  \
   if (x_dim == X_ && (A.neq != 0) == Q_) {                                              \
-    rc = mbpo_ensure_lds<k_ppo_vg_lean<X_, Q_>>(lds, "ppo_vg_lean");                    \
-    if (rc != MBPO_OK) return rc;                                                       \
-    hipLaunchKernelGGL((k_ppo_vg_lean<X_, Q_>), dim3(n_wgs), dim3(512), lds, st, A);    \
-    return MBPO_OK;                                                                     \
+    return mbpo_launch<k_ppo_vg_lean<X_, Q_>>(n_wgs, 512, lds, st, "ppo_vg_lean", A);   \
   }
 #define VG_X_(X_) VG_XQ_(X_, false) VG_XQ_(X_, true)
   VG_X_(2) VG_X_(3) VG_X_(4) VG_X_(5) VG_X_(6)
@@ -595,19 +591,12 @@ bool ppo_lean_supports(int x_dim, int u_dim, const int *policy_dims, int policy_
 
 int ppo_lean_launch(const PpoLeanArgs &A, int x_dim, int n_hid, int n_wgs, void *stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc;
 #define PL_X_(X_)                                                                                        \
   if (x_dim == X_ && n_hid == 2) {                                                                       \
-    rc = mbpo_ensure_lds<k_ppo_lean<X_, 2>>(PPO_LEAN_LDS_BYTES, "ppo_lean");                             \
-    if (rc != MBPO_OK) return rc;                                                                        \
-    hipLaunchKernelGGL((k_ppo_lean<X_, 2>), dim3(n_wgs), dim3(512), PPO_LEAN_LDS_BYTES, st, A);          \
-    return MBPO_OK;                                                                                      \
+    return mbpo_launch<k_ppo_lean<X_, 2>>(n_wgs, 512, PPO_LEAN_LDS_BYTES, st, "ppo_lean", A);            \
   }                                                                                                      \
   if (x_dim == X_ && n_hid == 1) {                                                                       \
-    rc = mbpo_ensure_lds<k_ppo_lean<X_, 1>>(PPO_LEAN_LDS_BYTES, "ppo_lean");                             \
-    if (rc != MBPO_OK) return rc;                                                                        \
-    hipLaunchKernelGGL((k_ppo_lean<X_, 1>), dim3(n_wgs), dim3(512), PPO_LEAN_LDS_BYTES, st, A);          \
-    return MBPO_OK;                                                                                      \
+    return mbpo_launch<k_ppo_lean<X_, 1>>(n_wgs, 512, PPO_LEAN_LDS_BYTES, st, "ppo_lean", A);            \
   }
   PL_X_(2) PL_X_(3) PL_X_(4) PL_X_(5) PL_X_(6)
 #undef PL_X_

@@ -541,11 +541,10 @@ extern "C" int mbpo_philox_permutation(uint64_t seed, uint64_t offset, const uin
     int np = 2;
     while (np < n) np <<= 1;
     const size_t lds = (size_t)np * sizeof(unsigned long long);
-    int rc = mbpo_ensure_lds<k_perm_sort_lds>(lds, "philox_permutation");
+    int rc = mbpo_ensure_lds<k_perm_sort_lds>(lds, "philox_permutation");      // (before the pre-sort launch: nothing is issued when it fails)
     if (rc != MBPO_OK) return rc;
-    static const int bucket_env = getenv("MBPO_PERM_BUCKETS") ? atoi(getenv("MBPO_PERM_BUCKETS")) : 1;
     unsigned int *flag = nullptr;
-    if (n > 1024 && bucket_env != 0) {
+    if (n > 1024 && mbpo_knob(KNOB_PERM_BUCKETS) != 0) {
       int lb = 1;
       while ((n >> lb) > 64 && lb < 8) ++lb;          // ~64 keys per bucket, at most 256 buckets
       flag = workspace;

@@ -78,8 +78,6 @@ static int hidden_width(const MlpDev &m) {
   return H;
 }
 
-static int up4(int v) { return (v + 3) & ~3; }
-
 // how many chains (waves) a workgroup runs side by side: one per member, capped at 8 waves (512 threads: two waves per
 // SIMD keep 256 VGPRs each) and by the LDS that the per-chain ping-pong tiles need next to `fixed_floats` of other
 // buffers; larger ensembles run in rounds of n_chains members
@@ -89,24 +87,9 @@ static int pick_chains(int n_members, size_t fixed_floats, int ld_h) {
   return c;
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_ensemble_forward, 1 = k_ens_fwd_lean where it applies,
 // -1 = the MBPO_ENS_LEAN environment default (on).
-static int g_ens_lean = -1;
-extern "C" int mbpo_debug_set_ens_lean(int mode) {
-  g_ens_lean = mode;
-  return MBPO_OK;
-}
+extern "C" int mbpo_debug_set_ens_lean(int mode) { return mbpo_knob_set_override(KNOB_ENS_LEAN, mode); }
 
 extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t shared_input, float *y,
                                          int64_t n_rows, void *stream) {
@@ -119,18 +102,17 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
   {
     // 64-wide member networks with 4 or 5 inputs: the throughput kernel (ens_lean.hip) — weights resident per workgroup, two tiles in
     // flight per workgroup, two workgroups per CU.  MBPO_ENS_LEAN=0 / mbpo_debug_set_ens_lean(0) keeps the generic kernel.
-    static const int lean_env = getenv("MBPO_ENS_LEAN") ? atoi(getenv("MBPO_ENS_LEAN")) : 1;
-    if ((g_ens_lean >= 0 ? g_ens_lean : lean_env) != 0 && ens_lean_supports(A.mlp.dims, A.mlp.n_layers, A.mlp.act)) {
+    if (mbpo_knob(KNOB_ENS_LEAN) != 0 && ens_lean_supports(A.mlp.dims, A.mlp.n_layers, A.mlp.act)) {
       EnsLeanArgs L;
       L.params = mlp->params; L.net_stride = mlp->n_nets > 1 ? mlp->net_stride : A.mlp.n_params;
       L.x = x; L.y = y; L.n_rows = n_rows; L.E = mlp->n_nets; L.N = A.mlp.dims[A.mlp.n_layers]; L.shared_input = shared_input ? 1 : 0;
       const long long pairs = (((n_rows + 15) >> 4) + 1) >> 1;
-      long long wpm = (2LL * num_cus()) / L.E;
+      long long wpm = (2LL * mbpo_num_cus()) / L.E;
       if (wpm < 1) wpm = 1;
       if (wpm > pairs) wpm = pairs;
       L.wgs_per_member = (int)wpm;
       L.n_hid = A.mlp.n_layers - 2;
-      rc = ens_lean_launch(L, A.mlp.dims[0], num_cus(), stream);
+      rc = ens_lean_launch(L, A.mlp.dims[0], mbpo_num_cus(), stream);
       if (rc != MBPO_OK) return rc;
       MBPO_CHECK_LAUNCH("ensemble_mlp_forward");
       return MBPO_OK;
@@ -152,16 +134,13 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
   MBPO_REQUIRE(A.n_chains >= 1, MBPO_ERR_UNSUPPORTED, "ensemble_mlp_forward: shapes do not fit 160 KiB of LDS");
   size_t lds = sizeof(float) * (fixed_f + 2ull * A.n_chains * 16 * A.ld_h);
   long long n_tiles = (n_rows + 15) >> 4;
-  int grid = (int)(n_tiles < 8LL * num_cus() ? n_tiles : 8LL * num_cus());
+  int grid = (int)(n_tiles < 8LL * mbpo_num_cus() ? n_tiles : 8LL * mbpo_num_cus());
   hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_ENS(HH)                                                          \
-  {                                                                             \
-    rc = mbpo_ensure_lds<k_ensemble_forward<HH>>(lds, "ensemble_mlp_forward");          \
-    if (rc != MBPO_OK) return rc;                                               \
-    hipLaunchKernelGGL(k_ensemble_forward<HH>, dim3(grid), dim3(A.n_chains * 64), lds, st, A); \
-  }
-  if (H == 64) LAUNCH_ENS(64) else if (H == 128) LAUNCH_ENS(128) else LAUNCH_ENS(256)
-#undef LAUNCH_ENS
+  const dim3 block(A.n_chains * 64);
+  if (H == 64) rc = mbpo_launch<k_ensemble_forward<64>>(grid, block, lds, st, "ensemble_mlp_forward", A);
+  else if (H == 128) rc = mbpo_launch<k_ensemble_forward<128>>(grid, block, lds, st, "ensemble_mlp_forward", A);
+  else rc = mbpo_launch<k_ensemble_forward<256>>(grid, block, lds, st, "ensemble_mlp_forward", A);
+  if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("ensemble_mlp_forward");
   return MBPO_OK;
 }
@@ -437,13 +416,9 @@ struct RolloutArgs64 {
 };
 
 static unsigned long long *g_ro_stamps = nullptr;
-static int g_ro_lean = -1;
 // Diagnostic switch (not part of include/mbpo_hip.h): 0 the generic 64-wide rollout kernel, 1 the specialised one, 2 / 3 the specialised one
 // with two tiles in flight per workgroup forced on / off, -1 = default.
-extern "C" int mbpo_debug_set_rollout_lean(int mode) {
-  g_ro_lean = mode;
-  return MBPO_OK;
-}
+extern "C" int mbpo_debug_set_rollout_lean(int mode) { return mbpo_knob_set_override(KNOB_ROLLOUT_LEAN, mode); }
 extern "C" int mbpo_debug_set_rollout_stamps(void *buf) {
   g_ro_stamps = (unsigned long long *)buf;
   return MBPO_OK;
@@ -907,29 +882,19 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   size_t lds = (fixed_f + 2ull * A.n_chains * 16 * A.ld_h) * sizeof(float);
   const int n_waves = A.n_chains > 4 ? A.n_chains : 4;  // the policy chain is shared by waves 0..3
   long long n_tiles = (d->n_envs + 15) >> 4;
-  int grid = (int)(n_tiles < 4LL * num_cus() ? n_tiles : 4LL * num_cus());
+  int grid = (int)(n_tiles < 4LL * mbpo_num_cus() ? n_tiles : 4LL * mbpo_num_cus());
   hipStream_t st = (hipStream_t)stream;
   if (!has_policy && d->system_kind == MBPO_SYS_PENDULUM && d->reward_kind == MBPO_REWARD_PENDULUM && !d->ppo_extras &&
-      !(g_ro_lean == 0)) {      // (mbpo_debug_set_rollout_lean(0): the tile kernel, for the A/B test)
+      mbpo_knob_override(KNOB_ROLLOUT_LEAN) != 0) {      // (mbpo_debug_set_rollout_lean(0), not the environment: the tile kernel, for the A/B test)
     hipLaunchKernelGGL(k_openloop_pendulum, dim3((unsigned)((d->n_envs + 255) / 256)), dim3(256), 0, st, A);
     MBPO_CHECK_LAUNCH("model_rollout");
     return MBPO_OK;
   }
-#define LAUNCH_RO_LR(HH, LR_)                                                                  \
-  {                                                                                            \
-    rc = mbpo_ensure_lds<k_model_rollout<HH, LR_>>(lds, "model_rollout");                      \
-    if (rc != MBPO_OK) return rc;                                                              \
-    hipLaunchKernelGGL((k_model_rollout<HH, LR_>), dim3(grid), dim3(n_waves * 64), lds, st, A); \
-  }
-#define LAUNCH_RO(HH)                                                        \
-  {                                                                          \
-    if (d->reward_kind == MBPO_REWARD_LEARNED) LAUNCH_RO_LR(HH, true) else LAUNCH_RO_LR(HH, false) \
-  }
+  const bool lr = d->reward_kind == MBPO_REWARD_LEARNED;
   if (H == 64) {
     // the kernel specialised for the benchmark networks (rollout_lean.hip): MBPO_ROLLOUT_LEAN=0 / mbpo_debug_set_rollout_lean(0) keep the
     // generic one
-    static const int env_lean = getenv("MBPO_ROLLOUT_LEAN") ? atoi(getenv("MBPO_ROLLOUT_LEAN")) : 1;
-    const int lean_mode = g_ro_lean >= 0 ? g_ro_lean : env_lean;      // 0 generic, 1 lean, 2 lean + two tiles in flight forced, 3 lean without
+    const int lean_mode = (int)mbpo_knob(KNOB_ROLLOUT_LEAN);      // 0 generic, 1 lean, 2 lean + two tiles in flight forced, 3 lean without
     if (lean_mode && rollout_lean_supports(A, has_policy, E)) {
       RoLeanArgs L;
       L.a = A;
@@ -937,11 +902,10 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
       L.n_dyn_out = dyn_out;
       L.stamps = g_ro_stamps;
       // two tiles in flight per workgroup once every CU has at least two (MBPO_ROLLOUT_PIPE=0/1 forces it off / on)
-      static const int env_pipe = getenv("MBPO_ROLLOUT_PIPE") ? atoi(getenv("MBPO_ROLLOUT_PIPE")) : -1;
-      const int pipe_force = lean_mode == 2 ? 1 : (lean_mode == 3 ? 0 : env_pipe);
-      const bool pipe = E > 0 && (pipe_force >= 0 ? pipe_force != 0 : n_tiles >= 2LL * num_cus());
+      const int pipe_force = lean_mode == 2 ? 1 : (lean_mode == 3 ? 0 : (int)mbpo_knob(KNOB_ROLLOUT_PIPE));
+      const bool pipe = E > 0 && (pipe_force >= 0 ? pipe_force != 0 : n_tiles >= 2LL * mbpo_num_cus());
       const long long units = pipe ? (n_tiles + 1) / 2 : n_tiles;
-      const int lgrid = (int)(units < (long long)num_cus() ? units : (long long)num_cus());
+      const int lgrid = (int)(units < (long long)mbpo_num_cus() ? units : (long long)mbpo_num_cus());
       rc = rollout_lean_launch(L, lgrid, pipe, stream);
       if (rc != MBPO_OK) return rc;
       MBPO_CHECK_LAUNCH("model_rollout");
@@ -950,30 +914,25 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     RolloutArgs64 AA;
     AA.a = A;
     AA.stamps = g_ro_stamps;
-    if (has_policy) AA.sh_pi = NetShape{A.policy.dims[0], A.policy.n_layers, A.policy.dims[A.policy.n_layers], A.policy.act};
+    if (has_policy) AA.sh_pi = net_shape(A.policy);
     else AA.sh_pi = NetShape{X, 0, 2 * U, 0};
-    if (E > 0) AA.sh_dyn = NetShape{A.dyn.dims[0], A.dyn.n_layers, A.dyn.dims[A.dyn.n_layers], A.dyn.act};
+    if (E > 0) AA.sh_dyn = net_shape(A.dyn);
     else AA.sh_dyn = NetShape{X + U, 0, X, 0};
     if (AA.a.n_chains > RO64_WAVES / 2) AA.a.n_chains = RO64_WAVES / 2;   // member chains of 2 waves side by side
     if (AA.a.n_chains < 1) AA.a.n_chains = 1;
     lds = (fixed_f + 2ull * (AA.a.n_chains > 1 ? AA.a.n_chains : 1) * 16 * A.ld_h) * sizeof(float);
     const bool wide = net_is_wide(AA.sh_pi) || net_is_wide(AA.sh_dyn);
-    const bool lr = d->reward_kind == MBPO_REWARD_LEARNED;
-#define LAUNCH_RO64(W_, LR_)                                                                      \
-  {                                                                                               \
-    rc = mbpo_ensure_lds<k_model_rollout64<W_, LR_>>(lds, "model_rollout");                       \
-    if (rc != MBPO_OK) return rc;                                                                 \
-    hipLaunchKernelGGL((k_model_rollout64<W_, LR_>), dim3(grid), dim3(64 * RO64_WAVES), lds, st, AA); \
+    rc = mbpo_with_bool(lr, [&](auto LR) {
+      return mbpo_with_bool(wide, [&](auto W) {
+        return mbpo_launch<k_model_rollout64<W.value, LR.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+      });
+    });
+  } else if (H == 128) {
+    rc = mbpo_with_bool(lr, [&](auto LR) { return mbpo_launch<k_model_rollout<128, LR.value>>(grid, n_waves * 64, lds, st, "model_rollout", A); });
+  } else {
+    rc = mbpo_with_bool(lr, [&](auto LR) { return mbpo_launch<k_model_rollout<256, LR.value>>(grid, n_waves * 64, lds, st, "model_rollout", A); });
   }
-    if (lr) {
-      if (wide) LAUNCH_RO64(true, true) else LAUNCH_RO64(false, true)
-    } else {
-      if (wide) LAUNCH_RO64(true, false) else LAUNCH_RO64(false, false)
-    }
-#undef LAUNCH_RO64
-  } else if (H == 128) LAUNCH_RO(128) else LAUNCH_RO(256)
-#undef LAUNCH_RO
-#undef LAUNCH_RO_LR
+  if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("model_rollout");
   return MBPO_OK;
 }

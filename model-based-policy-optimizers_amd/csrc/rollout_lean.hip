@@ -507,9 +507,8 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   const bool lr = A.a.reward_kind == MBPO_REWARD_LEARNED;      // (an ensemble: never with pend)
 #define RL_LAUNCH_LR(X_, P_, PP_, LR_)                                                                              \
   {                                                                                                                 \
-    rc = mbpo_ensure_lds<k_rollout_lean<X_, P_, PP_, LR_>>(RL_LDS_BYTES, "rollout_lean");                           \
+    rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
     if (rc != MBPO_OK) return rc;                                                                                   \
-    hipLaunchKernelGGL((k_rollout_lean<X_, P_, PP_, LR_>), dim3(grid), dim3(RL_THREADS), RL_LDS_BYTES, st, A);      \
   }
 #define RL_LAUNCH(X_, P_, PP_) RL_LAUNCH_LR(X_, P_, PP_, false)
   if (lr) {

@@ -81,11 +81,7 @@ struct SacArgs {
 static unsigned long long *g_sac_stamps = nullptr;
 // Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_sac_fwd_bwd, 1 = the specialised k_sac_lean
 // where it applies, -1 = the MBPO_SAC_LEAN environment default (on).  tests/test_gpu_sac_lean.py flips it inside one process.
-static int g_sac_lean = -1;
-extern "C" int mbpo_debug_set_sac_lean(int mode) {
-  g_sac_lean = mode;
-  return MBPO_OK;
-}
+extern "C" int mbpo_debug_set_sac_lean(int mode) { return mbpo_knob_set_override(KNOB_SAC_LEAN, mode); }
 // Measurement hook (not part of include/mbpo_hip.h): device buffer of >= 32 uint64 that k_sac_fwd_bwd fills with
 // s_memtime stamps at its phase boundaries (tile 0, both roles); NULL switches the stamps off.
 extern "C" int mbpo_debug_set_stamps(void *buf) {
@@ -877,13 +873,6 @@ struct SacPlan {
   bool layered;
 };
 
-static int same_hidden(const int *dims, int n_layers) {
-  if (n_layers < 2) return -1;
-  for (int l = 2; l < n_layers; ++l)
-    if (dims[l] != dims[1]) return -1;
-  return dims[1];
-}
-
 static int sac_plan(const mbpo_sac_desc *d, SacPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "sac: null descriptor");
   MBPO_REQUIRE(d->x_dim > 0 && d->u_dim > 0 && d->batch_size > 0, MBPO_ERR_ARG, "sac: x_dim/u_dim/batch_size must be positive");
@@ -895,25 +884,11 @@ static int sac_plan(const mbpo_sac_desc *d, SacPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d->q_dims[0] == d->x_dim + d->u_dim && d->q_dims[d->q_layers] == 1, MBPO_ERR_ARG,
                "sac: critic must map [x_dim+u_dim] -> [1]");
   const int Hp = same_hidden(d->policy_dims, d->policy_layers), Hq = same_hidden(d->q_dims, d->q_layers);
-  static const int layered_env = getenv("MBPO_SAC_LAYERED") ? atoi(getenv("MBPO_SAC_LAYERED")) : 0;    // 1: force the layered path (tests)
-  pl->layered = layered_env != 0 || !(Hp == Hq && (Hp == 64 || Hp == 128));
-  mbpo_mlp_desc md;
-  md.net_stride = 0;
-  // policy
-  md.params = d->params ? d->params : (const float *)16;  // placeholder for size queries
-  md.n_nets = 1;
-  md.n_layers = d->policy_layers;
-  for (int l = 0; l <= d->policy_layers; ++l) md.dims[l] = d->policy_dims[l];
-  md.activation = d->policy_activation;
-  int rc = mbpo_make_mlp_dev(&md, &pl->pi, "sac.policy");
+  pl->layered = mbpo_knob(KNOB_SAC_LAYERED) != 0 || !(Hp == Hq && (Hp == 64 || Hp == 128));
+  int rc = mbpo_make_mlp_dev_from(d->policy_dims, d->policy_layers, d->policy_activation, d->params, 1, "sac.policy", &pl->pi);
   if (rc != MBPO_OK) return rc;
   pl->P = pl->pi.n_params;
-  // critics
-  md.n_layers = d->q_layers;
-  for (int l = 0; l <= d->q_layers; ++l) md.dims[l] = d->q_dims[l];
-  md.activation = d->q_activation;
-  md.n_nets = 1;
-  rc = mbpo_make_mlp_dev(&md, &pl->q, "sac.q");
+  rc = mbpo_make_mlp_dev_from(d->q_dims, d->q_layers, d->q_activation, d->params, 1, "sac.q", &pl->q);
   if (rc != MBPO_OK) return rc;
   pl->Q = pl->q.n_params;
   pl->q.n_nets = 2;
@@ -928,7 +903,6 @@ static int sac_plan(const mbpo_sac_desc *d, SacPlan *pl, bool need_ptrs) {
   pl->n_tiles = (d->batch_size + 15) / 16;
   pl->n_red = (pl->NP + 255) / 256;
   pl->off_layered = 0;
-  auto up4 = [](int v) { return (v + 3) & ~3; };
   pl->ld_x = up4(d->x_dim) + 4;
   pl->ld_xu = up4(d->x_dim + d->u_dim) + 4;
   pl->ld_h = Hp + 4;
@@ -1090,29 +1064,24 @@ static int sac_grads_impl(const mbpo_sac_desc *d, int phase_mask, void *stream, 
   MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG, "sac_grads: norm_mean/norm_std mismatch");
   SacArgs A;
   A.pi = pl.pi; A.q = pl.q; A.qt = pl.qt;
-  A.sh_pi = NetShape{pl.pi.dims[0], pl.pi.n_layers, pl.pi.dims[pl.pi.n_layers], pl.pi.act};
-  A.sh_q = NetShape{pl.q.dims[0], pl.q.n_layers, pl.q.dims[pl.q.n_layers], pl.q.act};
+  A.sh_pi = net_shape(pl.pi);
+  A.sh_q = net_shape(pl.q);
   // three workgroups per tile (one critic each): at hidden width 128 a phase is MFMA-bound on its CU, at 64 the two critic
   // workgroups finish before the actor role does and 8-wave workgroups have cheaper barriers (26.9 -> 24.0 us with the forward-mode
   // actor role).  The WIDE kernels keep two workgroups per tile.  MBPO_SAC_SPLIT=0/1 overrides (measurement).
-  static const int split_env = getenv("MBPO_SAC_SPLIT") ? atoi(getenv("MBPO_SAC_SPLIT")) : -1;
+  const long long split_env = mbpo_knob(KNOB_SAC_SPLIT);
   const bool wide_any = net_is_wide(A.sh_pi) || net_is_wide(A.sh_q);
   const bool split = split_env >= 0 ? split_env != 0 : !wide_any;
   A.split = split ? 1 : 0;
   const int wg_per_tile = split ? 3 : 2;
   // forward-mode dQ/da in the actor role: one action dimension (one tangent), register-image kernels with one-tile network ends
-  static const int jvp_env = getenv("MBPO_SAC_JVP") ? atoi(getenv("MBPO_SAC_JVP")) : -1;
-  const bool reg_path = (pl.H == 64 || split) && !(net_is_wide(A.sh_pi) || net_is_wide(A.sh_q)) && pl.LH >= 2;
-  const bool jvp = d->u_dim == 1 && reg_path && (jvp_env < 0 || jvp_env != 0);
+  const bool reg_path = (pl.H == 64 || split) && !wide_any && pl.LH >= 2;
+  const bool jvp = d->u_dim == 1 && reg_path && mbpo_knob(KNOB_SAC_JVP) != 0;
   A.jvp = jvp ? 1 : 0;
   // thin layers: the three-workgroup launch at H = 64 with forward-mode actor (no input-gradient chains), small input / output
   // layers and at least one H x H layer in each network
-  {
-    const char *e = getenv("MBPO_SAC_THIN");
-    const bool want = e ? atoi(e) != 0 : true;
-    A.thin = (want && split && jvp && pl.H == 64 && A.sh_pi.K_in <= THIN_KMAX && A.sh_q.K_in <= THIN_KMAX && A.sh_pi.N_out <= THIN_NMAX &&
-              A.sh_q.N_out <= THIN_NMAX && A.sh_pi.L >= 3 && A.sh_q.L >= 3) ? 1 : 0;
-  }
+  A.thin = (mbpo_knob(KNOB_SAC_THIN) != 0 && split && jvp && pl.H == 64 && A.sh_pi.K_in <= THIN_KMAX && A.sh_q.K_in <= THIN_KMAX &&
+            A.sh_pi.N_out <= THIN_NMAX && A.sh_q.N_out <= THIN_NMAX && A.sh_pi.L >= 3 && A.sh_q.L >= 3) ? 1 : 0;
   if (!pl.layered) sac_chain_table(pl, d->row_len, &A, split, jvp);
   A.X = d->x_dim; A.U = d->u_dim; A.B = d->batch_size; A.D = d->row_len;
   A.batch = d->batch; A.norm_mean = d->norm_mean; A.norm_std = d->norm_std;
@@ -1141,8 +1110,7 @@ static int sac_grads_impl(const mbpo_sac_desc *d, int phase_mask, void *stream, 
   A.ld_x = pl.ld_x; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
   hipStream_t st = (hipStream_t)stream;
   // MBPO_SAC_LEAN=0 keeps the generic kernel on the benchmark networks too (A/B runs, the bit-identity test)
-  static const int lean_env = getenv("MBPO_SAC_LEAN") ? atoi(getenv("MBPO_SAC_LEAN")) : 1;
-  const bool lean = (g_sac_lean >= 0 ? g_sac_lean : lean_env) != 0 && !pl.layered && A.thin &&
+  const bool lean = mbpo_knob(KNOB_SAC_LEAN) != 0 && !pl.layered && A.thin &&
                     sac_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->q_dims, d->q_layers,
                                       d->q_activation);
   if (pl.layered) {
@@ -1167,35 +1135,18 @@ static int sac_grads_impl(const mbpo_sac_desc *d, int phase_mask, void *stream, 
     rc = sac_lean_launch(L, d->x_dim, pl.n_tiles, stream);
     if (rc != MBPO_OK) return rc;
   } else if (phase_mask & 1) {
+    const dim3 grid(wg_per_tile * pl.n_tiles);
     if (pl.H == 64) {
-      if (net_is_wide(A.sh_pi) || net_is_wide(A.sh_q)) {
-        rc = mbpo_ensure_lds<k_sac_fwd_bwd<64, SP64, true>>(pl.lds, "sac_grads");
-        if (rc != MBPO_OK) return rc;
-        hipLaunchKernelGGL((k_sac_fwd_bwd<64, SP64, true>), dim3(wg_per_tile * pl.n_tiles), dim3(256 * SP64), pl.lds, st, A);
-      } else if (split) {
-        if (A.thin) {
-          rc = mbpo_ensure_lds<k_sac_fwd_bwd<64, SP64, false, 2, true>>(pl.lds, "sac_grads");
-          if (rc != MBPO_OK) return rc;
-          hipLaunchKernelGGL((k_sac_fwd_bwd<64, SP64, false, 2, true>), dim3(wg_per_tile * pl.n_tiles), dim3(128 * SP64), pl.lds, st, A);
-        } else {
-          rc = mbpo_ensure_lds<k_sac_fwd_bwd<64, SP64, false, 2>>(pl.lds, "sac_grads");
-          if (rc != MBPO_OK) return rc;
-          hipLaunchKernelGGL((k_sac_fwd_bwd<64, SP64, false, 2>), dim3(wg_per_tile * pl.n_tiles), dim3(128 * SP64), pl.lds, st, A);
-        }
-      } else {
-        rc = mbpo_ensure_lds<k_sac_fwd_bwd<64, SP64, false>>(pl.lds, "sac_grads");
-        if (rc != MBPO_OK) return rc;
-        hipLaunchKernelGGL((k_sac_fwd_bwd<64, SP64, false>), dim3(wg_per_tile * pl.n_tiles), dim3(256 * SP64), pl.lds, st, A);
-      }
-    } else if (split && !(net_is_wide(A.sh_pi) || net_is_wide(A.sh_q))) {
-      rc = mbpo_ensure_lds<k_sac_fwd_bwd<128, 4, false, 2>>(pl.lds, "sac_grads");
-      if (rc != MBPO_OK) return rc;
-      hipLaunchKernelGGL((k_sac_fwd_bwd<128, 4, false, 2>), dim3(wg_per_tile * pl.n_tiles), dim3(512), pl.lds, st, A);
+      if (wide_any) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, true>>(grid, 256 * SP64, pl.lds, st, "sac_grads", A);
+      else if (split && A.thin) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2, true>>(grid, 128 * SP64, pl.lds, st, "sac_grads", A);
+      else if (split) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2>>(grid, 128 * SP64, pl.lds, st, "sac_grads", A);
+      else rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false>>(grid, 256 * SP64, pl.lds, st, "sac_grads", A);
+    } else if (split && !wide_any) {
+      rc = mbpo_launch<k_sac_fwd_bwd<128, 4, false, 2>>(grid, 512, pl.lds, st, "sac_grads", A);
     } else {
-      rc = mbpo_ensure_lds<k_sac_fwd_bwd<128, 2, false>>(pl.lds, "sac_grads");
-      if (rc != MBPO_OK) return rc;
-      hipLaunchKernelGGL((k_sac_fwd_bwd<128, 2, false>), dim3(wg_per_tile * pl.n_tiles), dim3(512), pl.lds, st, A);
+      rc = mbpo_launch<k_sac_fwd_bwd<128, 2, false>>(grid, 512, pl.lds, st, "sac_grads", A);
     }
+    if (rc != MBPO_OK) return rc;
   }
   if (!(phase_mask & 2)) {
     MBPO_CHECK_LAUNCH("sac_grads");

@@ -585,17 +585,9 @@ namespace {
 
 template <int X>
 int launch_x(const SacLeanArgs &A, int n_tiles, hipStream_t st) {
-  int rc;
-  if (A.stamps) {
-    rc = mbpo_ensure_lds<k_sac_lean<X, true>>(LEAN_LDS_BYTES, "sac_lean");
-    if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL((k_sac_lean<X, true>), dim3(3 * n_tiles), dim3(LEAN_THREADS), LEAN_LDS_BYTES, st, A);
-  } else {
-    rc = mbpo_ensure_lds<k_sac_lean<X, false>>(LEAN_LDS_BYTES, "sac_lean");
-    if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL((k_sac_lean<X, false>), dim3(3 * n_tiles), dim3(LEAN_THREADS), LEAN_LDS_BYTES, st, A);
-  }
-  return MBPO_OK;
+  return mbpo_with_bool(A.stamps != nullptr, [&](auto STAMP) {
+    return mbpo_launch<k_sac_lean<X, STAMP.value>>(3 * n_tiles, LEAN_THREADS, LEAN_LDS_BYTES, st, "sac_lean", A);
+  });
 }
 
 }  // namespace
@@ -613,15 +605,9 @@ int sac_lean_launch(const SacLeanArgs &A, int x_dim, int n_tiles, void *stream) 
   if (x_dim == 3) return launch_x<3>(A, n_tiles, st);
   if (x_dim == 4) return launch_x<4>(A, n_tiles, st);
   // other observation widths: the plain instantiation only (no in-kernel timeline)
-#define LEAN_X(X_)                                                                                                    \
-  if (x_dim == X_) {                                                                                                  \
-    int rc = mbpo_ensure_lds<k_sac_lean<X_, false>>(LEAN_LDS_BYTES, "sac_lean");                                      \
-    if (rc != MBPO_OK) return rc;                                                                                     \
-    hipLaunchKernelGGL((k_sac_lean<X_, false>), dim3(3 * n_tiles), dim3(LEAN_THREADS), LEAN_LDS_BYTES, st, A);        \
-    return MBPO_OK;                                                                                                   \
-  }
-  LEAN_X(2) LEAN_X(5) LEAN_X(6)
-#undef LEAN_X
+  if (x_dim == 2) return mbpo_launch<k_sac_lean<2, false>>(3 * n_tiles, LEAN_THREADS, LEAN_LDS_BYTES, st, "sac_lean", A);
+  if (x_dim == 5) return mbpo_launch<k_sac_lean<5, false>>(3 * n_tiles, LEAN_THREADS, LEAN_LDS_BYTES, st, "sac_lean", A);
+  if (x_dim == 6) return mbpo_launch<k_sac_lean<6, false>>(3 * n_tiles, LEAN_THREADS, LEAN_LDS_BYTES, st, "sac_lean", A);
   mbpo_set_error("sac_lean: x_dim %d has no instantiation", x_dim);
   return MBPO_ERR_UNSUPPORTED;
 }
