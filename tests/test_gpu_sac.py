@@ -525,7 +525,8 @@ torch.save({"g": up.grads.cpu(), "p": up.params.cpu(), "m": up.metrics.cpu()}, s
     for t2_min in ("1", "1000000000"):
         f = tmp_path / f"out_{t2_min}.pt"
         env = dict(os.environ, MBPO_LAYERED_T2_MIN=t2_min)
-        r = subprocess.run([sys.executable, "-c", code, str(f)], env=env, capture_output=True, text=True, cwd=str(__import__("pathlib").Path(__file__).resolve().parents[1]))
+        r = subprocess.run([sys.executable, "-c", code, str(f)], env=env, capture_output=True, text=True, timeout=600,
+                           cwd=str(__import__("pathlib").Path(__file__).resolve().parents[1]))
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append(torch.load(f, weights_only=True))
     scale = float(outs[0]["g"].abs().max())
