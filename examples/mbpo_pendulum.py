@@ -5,10 +5,12 @@
                       ->  SACOptimizer on EnsembleSystem (short model rollouts branched from true states + SAC updates)
                       ->  the policy acts on the TRUE PendulumSystem.
 
-    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward]
+    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
+--elites: MBPO's model selection — 7 members, a 20 % holdout, per-member early stopping with --model-steps as the cap, and rollouts
+through the 5 members of lowest held-out error (fit(holdout_ratio=0.2, n_elites=5)).
 """
 from __future__ import annotations
 
@@ -43,7 +45,7 @@ def true_return(system, optimizer, opt_state, steps=200):
     return total
 
 
-def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False):
+def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -56,7 +58,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                        discount=torch.tensor(0.99, device=dev), next_observation=s0.x_next)
     true_buffer = UniformSamplingQueue(max_replay_size=iters * n_true, dummy_data_sample=dummy, sample_batch_size=1, device=dev)
     tbs = true_buffer.init(seed)
-    dyn = EnsembleDynamics(3, 1, n_members=5, learn_reward=learn_reward)
+    dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
     model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), mode="mean", predict_delta=True)
     dyn_params = dyn.init_params(seed + 1)
     history = []
@@ -66,7 +68,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         tbs = true_buffer.insert(tbs, Transition(observation=x, action=u, reward=r, discount=torch.ones(n_true, device=dev), next_observation=xn))
         n_rows = true_buffer.size(tbs)
         dyn_params, losses = dyn.fit(dyn_params, true_buffer.logical_data(tbs), num_steps=model_steps, batch_size=256, learning_rate=3e-3,
-                                     key=seed + 10 * it, n_rows=n_rows)
+                                     key=seed + 10 * it, n_rows=n_rows, **(dict(holdout_ratio=0.2, n_elites=5) if elites else {}))
         optimizer = SACOptimizer(system=model, true_buffer=true_buffer, num_timesteps=sac_steps, num_evals=2, reward_scaling=1,
                                  episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
                                  lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
@@ -81,6 +83,9 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         ret = true_return(true_system, optimizer, out.optimizer_state)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
                             seconds=time.time() - t0))
+        if elites:
+            history[-1].update(steps_run=int(losses.shape[0]), elite_idx=dyn_params.elite_idx.tolist(),
+                               holdout_mse=[round(float(v), 6) for v in dyn_params.holdout[1]])
         if verbose:
             print(history[-1], flush=True)
     return history
@@ -93,5 +98,6 @@ if __name__ == "__main__":
     ap.add_argument("--sac-steps", type=int, default=40_000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--learn-reward", action="store_true")
+    ap.add_argument("--elites", action="store_true")
     a = ap.parse_args()
-    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward)
+    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites)

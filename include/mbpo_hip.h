@@ -552,6 +552,48 @@ typedef struct mbpo_ens_train_desc {
 int64_t mbpo_ens_nll_workspace_floats(const mbpo_ens_train_desc *d);
 int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream);
 
+/* ---- N3b: ensemble model selection (MBPO's model-training procedure — Janner et al. 2019, "When to Trust Your Model" — not the
+ * reference's, which has no learned model): held-out loss of every member, per-member best snapshot, elite members.
+ * mbpo_ens_eval: forward only, every member on the SAME rows idx[0..n):
+ *   metrics[0][e] = mbpo_ens_nll_grads's loss_e on those rows (the same per-element terms; a row's state terms summed first, the
+ *                   reward term last);
+ *   metrics[1][e] = mean_b [ sum_d (t_d - mu_d)^2 (+ (r - mu_r)^2 when reward_off >= 0) ], t the regression target (delta-encoded
+ *                   when predict_delta): MBPO's selection metric, non-negative and independent of the std head.
+ * The two paths of mbpo_ens_nll_grads, selected the same way: fused (hidden layers all 64 wide: one workgroup = (member, slot)
+ * walks 16-row tiles through the forward chain, two partials per (member, slot), fixed-order reduce — no atomics, deterministic
+ * for a fixed slot count) or layered (the shared [x, u] and target gathered once, one GEMM launch per Dense layer over the E nets,
+ * a head kernel).  Rows beyond n in the last tile contribute zero.  The shape checks are mbpo_ens_nll_grads's; n > 0; idx,
+ * metrics and workspace must not be NULL.  mbpo_ens_eval_workspace_floats needs no device. */
+typedef struct mbpo_ens_eval_desc {
+  int32_t x_dim, u_dim;
+  mbpo_mlp_desc dynamics;              /* [x+u] -> [2x] or [2x+2], as mbpo_ens_train_desc */
+  const float *rows;
+  int32_t row_len, next_obs_off, reward_off;   /* reward_off -1: no reward term */
+  const int32_t *idx;                  /* ONE index list [n], shared by all members */
+  int64_t n;
+  int32_t predict_delta;
+  float min_std;
+  float *metrics;                      /* [2][E]: row 0 mean NLL, row 1 mean squared error */
+  float *workspace;
+} mbpo_ens_eval_desc;
+int64_t mbpo_ens_eval_workspace_floats(const mbpo_ens_eval_desc *d);
+int mbpo_ens_eval(const mbpo_ens_eval_desc *d, void *stream);
+
+/* Per-member best snapshot (MBPO's early stopping), decided and copied on the device: params / best_params [n_members][n_params].
+ *   improved_e = isfinite(score_e) && score_e < best_score_e * (1 - rel_tol)      (best_score starts at +inf; scores are >= 0)
+ *   improved members: best_params[e] <- params[e] (bit copy), best_score_e <- score_e; the others are untouched.
+ *   state (device int32[2]): state[0] <- any improved ? 0 : state[0] + 1 (evaluations since an improvement);  state[1] += 1.
+ * Two launches: the decision (it stages the copy map in workspace, int32[n_members]) and the member copy, which reads the map
+ * only — nothing reads best_score after it was overwritten. */
+int mbpo_ens_keep_best(const float *params, float *best_params, int64_t n_params, int32_t n_members, const float *score,
+                       float *best_score, float rel_tol, int32_t *state, int32_t *workspace, void *stream);
+/* elite_idx[j] = the member of rank j under the total order (score ascending, NaN last, ties by lower index) — the order
+ * mbpo_icem_update ranks by;  elite_params[j] <- params[elite_idx[j]] (bit copy), j < n_elites <= n_members.  Two launches (rank,
+ * member copy).  The member copy of both calls: destination member j takes source member map[j], 16-byte accesses where source
+ * and destination are equally aligned; n_params need not be a multiple of 4. */
+int mbpo_ens_pick_elites(const float *params, int64_t n_params, int32_t n_members, const float *score, int32_t n_elites,
+                         int32_t *elite_idx, float *elite_params, void *stream);
+
 /* ---- N4: iCEM trajectory optimizer, device side (trajectory_optimizers/icem_optimizer.py:135-252) ---------------------
  * One iteration = mbpo_icem_sample -> mbpo_model_rollout(actions = the sampled sequences) -> mbpo_icem_update.
  * mbpo_icem_sample: coloured noise (utils/general_utils.py:81-208, powerlaw_psd_gaussian, as a direct inverse real DFT; Philox

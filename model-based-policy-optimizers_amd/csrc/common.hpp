@@ -310,6 +310,16 @@ __device__ __forceinline__ void slab_group16_sum(float *slab, long long stride, 
     if (ok[k]) slab[(long long)t0 * stride + c0 + 256 * k] = acc[k];
 }
 
+// Element (w, j) sorts before element (v, c): the total order of np.argsort(kind="stable") — NaN after every number (+inf
+// included), NaNs tied with each other, ties broken by index.  A plain `w < v || (w == v && j < c)` gives every NaN rank 0:
+// the ranks stop being a permutation and the indices the consumers read (iCEM's elites, the ensemble's elite members) are never
+// written.
+__device__ __forceinline__ bool rank_before(float w, int j, float v, int c) {
+  const bool wn = w != w, vn = v != v;
+  if (wn != vn) return vn;
+  return w < v || (!(v < w) && j < c);      // both numbers: w < v, or equal (-0 == +0); both NaN: neither is less
+}
+
 // jnp.floor_divide for floats ([3P] jax.numpy: remainder-based, then rounded): x1 // x2
 __device__ __forceinline__ float floor_divide_f(float x1, float x2) {
   const float mod = fmodf(x1, x2);

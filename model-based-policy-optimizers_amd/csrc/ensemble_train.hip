@@ -202,37 +202,52 @@ struct EnsPlan {
   long long off_xu, off_t, off_z[MBPO_MAX_LAYERS + 1], off_h[MBPO_MAX_LAYERS + 1], off_y, off_dy, off_tmp0, off_tmp1, off_part;
 };
 
-static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
-  MBPO_REQUIRE(d, MBPO_ERR_ARG, "ens_nll: null descriptor");
-  MBPO_REQUIRE(d->x_dim > 0 && d->u_dim > 0 && d->batch > 0, MBPO_ERR_ARG, "ens_nll: x_dim/u_dim/batch must be positive");
-  mbpo_mlp_desc md = d->dynamics;
+// What the training and the evaluation plans share: the shape checks, the tile geometry and the choice of path.  `what` prefixes the
+// messages; batch = rows per member.
+static int ens_plan_shape(const char *what, int X, int U, const mbpo_mlp_desc &dynamics, int row_len, int noff, int roff, long long batch,
+                          EnsPlan *pl) {
+  MBPO_REQUIRE(X > 0 && U > 0 && batch > 0, MBPO_ERR_ARG, "%s: x_dim/u_dim/batch must be positive", what);
+  mbpo_mlp_desc md = dynamics;
   if (!md.params) md.params = (const float *)16;
-  int rc = mbpo_make_mlp_dev(&md, &pl->dyn, "ens_nll.dynamics");
+  char name[48];
+  snprintf(name, sizeof name, "%s.dynamics", what);
+  int rc = mbpo_make_mlp_dev(&md, &pl->dyn, name);
   if (rc != MBPO_OK) return rc;
-  const int X = d->x_dim, U = d->u_dim, L = pl->dyn.n_layers;
+  const int L = pl->dyn.n_layers;
   MBPO_REQUIRE(pl->dyn.dims[0] == X + U && (pl->dyn.dims[L] == 2 * X || pl->dyn.dims[L] == 2 * X + 2), MBPO_ERR_ARG,
-               "ens_nll: dynamics must map [x+u] -> [2x] (mean, raw std) or [2x+2] (+ reward mean, raw std)");
-  MBPO_REQUIRE(d->reward_off >= -1 && d->reward_off < d->row_len, MBPO_ERR_ARG, "ens_nll: reward_off %d outside the row", d->reward_off);
-  MBPO_REQUIRE(d->reward_off < 0 || pl->dyn.dims[L] == 2 * X + 2, MBPO_ERR_ARG, "ens_nll: reward_off needs a [x+u] -> [2x+2] ensemble");
-  MBPO_REQUIRE(L >= 2, MBPO_ERR_ARG, "ens_nll: the member networks need at least one hidden layer");
-  MBPO_REQUIRE(d->row_len >= d->next_obs_off + X && d->next_obs_off >= X + U, MBPO_ERR_ARG, "ens_nll: bad row_len / next_obs_off");
+               "%s: dynamics must map [x+u] -> [2x] (mean, raw std) or [2x+2] (+ reward mean, raw std)", what);
+  MBPO_REQUIRE(roff >= -1 && roff < row_len, MBPO_ERR_ARG, "%s: reward_off %d outside the row", what, roff);
+  MBPO_REQUIRE(roff < 0 || pl->dyn.dims[L] == 2 * X + 2, MBPO_ERR_ARG, "%s: reward_off needs a [x+u] -> [2x+2] ensemble", what);
+  MBPO_REQUIRE(L >= 2, MBPO_ERR_ARG, "%s: the member networks need at least one hidden layer", what);
+  MBPO_REQUIRE(row_len >= noff + X && noff >= X + U, MBPO_ERR_ARG, "%s: bad row_len / next_obs_off", what);
   bool all64 = true;
   for (int l = 1; l < L; ++l) all64 = all64 && pl->dyn.dims[l] == 64;
   pl->LH = L - 1;
   pl->ld_xu = up4(X + U) + 4;
   pl->ld_h = 68;
   pl->ld_y = up4(pl->dyn.dims[L]) + 4;
+  // (the training tile decides for both: one shape, one path)
   pl->lds = sizeof(float) * (16ull * pl->ld_xu + 3ull * 16 * pl->ld_y + (size_t)(2 * pl->LH + 2) * 16 * pl->ld_h + 16);
-  const int E = pl->dyn.n_nets;
   pl->layered = !all64 || pl->lds > 160 * 1024;
   if (!pl->layered) {
-    const long long tiles = (d->batch + 15) / 16;
-    long long cap = (2LL * mbpo_num_cus() + E - 1) / E;
+    const long long tiles = (batch + 15) / 16;
+    long long cap = (2LL * mbpo_num_cus() + pl->dyn.n_nets - 1) / pl->dyn.n_nets;
     if (cap < 1) cap = 1;
     pl->n_slots = (int)(tiles < cap ? tiles : cap);
+  } else {
+    MBPO_REQUIRE(batch < (1LL << 24), MBPO_ERR_ARG, "%s: batch must be below 2^24 on the layered path", what);
+  }
+  return MBPO_OK;
+}
+
+static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
+  MBPO_REQUIRE(d, MBPO_ERR_ARG, "ens_nll: null descriptor");
+  int rc = ens_plan_shape("ens_nll", d->x_dim, d->u_dim, d->dynamics, d->row_len, d->next_obs_off, d->reward_off, d->batch, pl);
+  if (rc != MBPO_OK) return rc;
+  const int X = d->x_dim, U = d->u_dim, L = pl->dyn.n_layers, E = pl->dyn.n_nets;
+  if (!pl->layered) {
     pl->total = (long long)E * pl->n_slots * pl->dyn.n_params + (((long long)E * pl->n_slots + 3) & ~3LL);
   } else {
-    MBPO_REQUIRE(d->batch < (1LL << 24), MBPO_ERR_ARG, "ens_nll: batch must be below 2^24 on the layered path");
     const long long EB = (long long)E * d->batch;
     const LayeredNet net = layered_net(pl->dyn, nullptr, pl->dyn.n_params, E);
     long long off = 0;
@@ -309,4 +324,323 @@ extern "C" int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream) {
                      pl.n_slots, pl.dyn.n_params, (long long)d->batch, d->grads, d->metrics);
   MBPO_CHECK_LAUNCH("ens_nll_grads");
   return MBPO_OK;
+}
+
+// ================================================================================================ model selection
+// MBPO's model-training procedure (held-out loss per member, per-member best snapshot, elite members) — not the reference's, which
+// has no learned model.  mbpo_ens_eval is the forward half of the step above on ONE index list shared by the members: the same
+// per-element terms, the row's state terms summed first and the reward last, plus the squared error of the mean head.
+struct EnsEvalArgs {
+  NetShape sh;
+  const float *params;
+  long long net_stride;
+  int E, X, U, D, noff, roff;
+  const float *rows;
+  const int *idx;
+  long long n;
+  int predict_delta;
+  float min_std;
+  float *part;      // [2][E][n_slots]
+  int n_slots, ld_xu, ld_h, ld_y;
+};
+
+// 0.5 q^2 + log sigma and (t - mu)^2 of one output element: k_ens_nll_fwd_bwd's loss term, written the same way
+__device__ __forceinline__ void ens_eval_terms(float t, float mu, float raw, float min_std, float *nll, float *se) {
+  const float sg = softplus_f(raw) + min_std;
+  const float q = (t - mu) / sg;
+  *nll = 0.5f * q * q + logf(sg);
+  const float d = t - mu;
+  *se = d * d;
+}
+
+// One workgroup = (member, slot), four waves = one forward chain; hidden activations ping-pong through two tiles (nothing is kept
+// for a backward pass).
+template <bool WIDE>
+__global__ void __launch_bounds__(256) k_ens_eval(EnsEvalArgs A) {
+  extern __shared__ __align__(16) float smem[];
+  constexpr int HT = 4, SP = 4;
+  const int tid_ = threadIdx.x, nthreads = 256;
+  const int sub = __builtin_amdgcn_readfirstlane(tid_ >> 6);
+  const int e = blockIdx.x / A.n_slots, slot = blockIdx.x - e * A.n_slots;
+  const int X = A.X, U = A.U, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y;
+  const int T = 16 * ld_h;
+  float *s_xu = smem;                       // [16][ld_xu]  [x, u]
+  float *s_t = s_xu + 16 * ld_xu;           // [16][ld_y]   regression target: X state columns, then the reward
+  float *s_y = s_t + 16 * ld_y;             // [16][ld_y]   (mu, raw)
+  float *s_el = s_y + 16 * ld_y;            // [16][ld_y]   per-element NLL terms at [0, X], squared errors at [X + 1, 2X + 1]
+  float *s_pp = s_el + 16 * ld_y;           // 2 hidden tiles
+  float *s_ls = s_pp + 2 * T;               // [2][16] row sums
+  const float *params = A.params + (long long)e * A.net_stride;
+  const int L = A.sh.L;
+  float loss = 0.f, sqe = 0.f;
+  const long long n_tiles = (A.n + 15) >> 4;
+#pragma nounroll
+  for (long long tile = slot; tile < n_tiles; tile += A.n_slots) {
+    const int tid = opaque(tid_), lane = tid & 63;
+    const long long j0 = tile * 16;
+    WSet<HT, SP> R;
+    chain_fwd_prefetch<HT, SP, WIDE>(R, A.sh, params, sub, lane);
+    for (int i2 = tid; i2 < 16 * (X + U); i2 += nthreads) {
+      const int r = i2 & 15, c = i2 >> 4;
+      const long long j = j0 + r;
+      s_xu[r * ld_xu + c] = (j < A.n) ? A.rows[(long long)A.idx[j] * A.D + c] : 0.f;
+    }
+    for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
+      const int r = i2 & 15, c = i2 >> 4;
+      const long long j = j0 + r;
+      float t = 0.f;
+      if (j < A.n) {
+        const float *row = A.rows + (long long)A.idx[j] * A.D;
+        t = row[A.noff + c] - (A.predict_delta ? row[c] : 0.f);
+      }
+      s_t[r * ld_y + c] = t;
+    }
+    if (A.roff >= 0 && tid < 16) {
+      const long long j = j0 + tid;
+      s_t[tid * ld_y + X] = (j < A.n) ? A.rows[(long long)A.idx[j] * A.D + A.roff] : 0.f;
+    }
+    __syncthreads();
+    chain_fwd_run<HT, SP, WIDE>(A.sh, params, s_xu, ld_xu, s_pp, s_pp + T, nullptr, nullptr, s_y, ld_y, ld_h, L, sub, lane, R);
+    for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
+      const int r = i2 & 15, c = i2 >> 4;
+      const bool ok = j0 + r < A.n;
+      float nll, se;
+      ens_eval_terms(s_t[r * ld_y + c], s_y[r * ld_y + c], s_y[r * ld_y + X + c], A.min_std, &nll, &se);
+      s_el[r * ld_y + c] = ok ? nll : 0.f;
+      s_el[r * ld_y + X + 1 + c] = ok ? se : 0.f;
+    }
+    if (A.roff >= 0 && tid < 16) {
+      const int r = tid;
+      const bool ok = j0 + r < A.n;
+      float nll, se;
+      ens_eval_terms(s_t[r * ld_y + X], s_y[r * ld_y + 2 * X], s_y[r * ld_y + 2 * X + 1], A.min_std, &nll, &se);
+      s_el[r * ld_y + X] = ok ? nll : 0.f;
+      s_el[r * ld_y + 2 * X + 1] = ok ? se : 0.f;
+    }
+    __syncthreads();
+    if (tid < 32) {                          // threads 0..15: the rows' NLL, 16..31: their squared error
+      const int r = tid & 15;
+      const float *el = s_el + r * ld_y + (tid < 16 ? 0 : X + 1);
+      float a = 0.f;
+      for (int c = 0; c < X; ++c) a += el[c];
+      if (A.roff >= 0) a += el[X];
+      s_ls[tid] = a;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int i = 0; i < 16; ++i) {
+        loss += s_ls[i];
+        sqe += s_ls[16 + i];
+      }
+  }
+  if (tid_ == 0) {
+    A.part[(long long)e * A.n_slots + slot] = loss;
+    A.part[((long long)A.E + e) * A.n_slots + slot] = sqe;
+  }
+}
+
+// metrics[m][e] = (sum over slots, in slot order) / n
+__global__ void __launch_bounds__(64) k_ens_eval_reduce(const float *part, int n_slots, int n_out, long long n, float *metrics) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n_out) metrics[i] = slab_sum<16>(part + (long long)i * n_slots, 1, n_slots, 0) / (float)n;
+}
+
+// Layered path's head, one workgroup per member over the shared targets t [n][X + 1]: k_ens_nll_head's loss and summation order
+// (a thread adds its rows b = tid, tid + 256, ... in order, then a fixed tree over the threads), without the output gradient.
+__global__ void __launch_bounds__(256) k_ens_eval_head(const float *y, const float *t, int X, int dout, int roff, int n, int E,
+                                                       float min_std, float *metrics) {
+  __shared__ float s_red[2][256];
+  const int e = blockIdx.x, tid = threadIdx.x;
+  float acc = 0.f, acc2 = 0.f;
+  for (int b = tid; b < n; b += 256) {
+    const float *yr = y + ((long long)e * n + b) * dout, *tr = t + (long long)b * (X + 1);
+    float a = 0.f, a2 = 0.f, nll, se;
+    for (int c = 0; c < X; ++c) {
+      ens_eval_terms(tr[c], yr[c], yr[X + c], min_std, &nll, &se);
+      a += nll;
+      a2 += se;
+    }
+    if (roff >= 0) {
+      ens_eval_terms(tr[X], yr[2 * X], yr[2 * X + 1], min_std, &nll, &se);
+      a += nll;
+      a2 += se;
+    }
+    acc += a;
+    acc2 += a2;
+  }
+  s_red[0][tid] = acc;
+  s_red[1][tid] = acc2;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) {
+      s_red[0][tid] += s_red[0][tid + h];
+      s_red[1][tid] += s_red[1][tid + h];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    metrics[e] = s_red[0][0] / (float)n;
+    metrics[E + e] = s_red[1][0] / (float)n;
+  }
+}
+
+struct EnsEvalPlan {
+  EnsPlan p;
+  size_t lds;                                   // fused
+  long long off_xu, off_t, off_h0, off_h1, off_y;   // layered
+  long long total;
+};
+
+static int ens_eval_plan(const mbpo_ens_eval_desc *d, EnsEvalPlan *pl, bool need_ptrs) {
+  MBPO_REQUIRE(d, MBPO_ERR_ARG, "ens_eval: null descriptor");
+  int rc = ens_plan_shape("ens_eval", d->x_dim, d->u_dim, d->dynamics, d->row_len, d->next_obs_off, d->reward_off, d->n, &pl->p);
+  if (rc != MBPO_OK) return rc;
+  const EnsPlan &p = pl->p;
+  const int X = d->x_dim, U = d->u_dim, L = p.dyn.n_layers, E = p.dyn.n_nets;
+  if (!p.layered) {
+    pl->lds = sizeof(float) * (16ull * p.ld_xu + 3ull * 16 * p.ld_y + 2ull * 16 * p.ld_h + 32);
+    pl->total = (2LL * E * p.n_slots + 3) & ~3LL;
+  } else {
+    const LayeredNet net = layered_net(p.dyn, nullptr, p.dyn.n_params, E);
+    const long long mh = layered_max_hidden(net);
+    long long off = 0;
+    auto take = [&](long long n) { const long long o = off; off += (n + 3) & ~3LL; return o; };
+    pl->off_xu = take(d->n * (X + U));
+    pl->off_t = take(d->n * (X + 1));
+    pl->off_h0 = take((long long)E * d->n * mh);
+    pl->off_h1 = take((long long)E * d->n * mh);
+    pl->off_y = take((long long)E * d->n * p.dyn.dims[L]);
+    pl->total = off;
+  }
+  if (need_ptrs)
+    MBPO_REQUIRE(d->dynamics.params && d->rows && d->idx && d->metrics && d->workspace, MBPO_ERR_ARG, "ens_eval: null pointer");
+  return MBPO_OK;
+}
+
+extern "C" int64_t mbpo_ens_eval_workspace_floats(const mbpo_ens_eval_desc *d) {
+  EnsEvalPlan pl;
+  int rc = ens_eval_plan(d, &pl, false);
+  if (rc != MBPO_OK) return rc;
+  return pl.total;
+}
+
+extern "C" int mbpo_ens_eval(const mbpo_ens_eval_desc *d, void *stream) {
+  EnsEvalPlan pl;
+  int rc = ens_eval_plan(d, &pl, true);
+  if (rc != MBPO_OK) return rc;
+  const EnsPlan &p = pl.p;
+  const int L = p.dyn.n_layers, E = p.dyn.n_nets, X = d->x_dim, U = d->u_dim;
+  hipStream_t st = (hipStream_t)stream;
+  if (p.layered) {
+    const int n = (int)d->n;
+    float *ws = d->workspace;
+    float *xu = ws + pl.off_xu, *t = ws + pl.off_t, *y = ws + pl.off_y;
+    float *H[MBPO_MAX_LAYERS + 1];
+    for (int l = 0; l <= MBPO_MAX_LAYERS; ++l) H[l] = ws + ((l & 1) ? pl.off_h1 : pl.off_h0);     // layer l reads H[l], writes H[l + 1]
+    // the members share the rows: one gather (k_ens_gather with a single "member")
+    hipLaunchKernelGGL(k_ens_gather, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, st, d->rows, d->idx, d->row_len, X, U,
+                       d->next_obs_off, d->reward_off, d->predict_delta, (long long)d->n, xu, t);
+    MBPO_CHECK_LAUNCH("ens_eval.gather");
+    const LayeredNet net = layered_net(p.dyn, d->dynamics.params, p.dyn.net_stride, E);
+    rc = layered_forward(net, xu, 0, n, nullptr, H, y, st);
+    if (rc != MBPO_OK) return rc;
+    hipLaunchKernelGGL(k_ens_eval_head, dim3(E), dim3(256), 0, st, (const float *)y, (const float *)t, X, p.dyn.dims[L], d->reward_off, n,
+                       E, d->min_std, d->metrics);
+    MBPO_CHECK_LAUNCH("ens_eval.head");
+    return MBPO_OK;
+  }
+  EnsEvalArgs A;
+  A.sh = net_shape(p.dyn);
+  A.params = d->dynamics.params; A.net_stride = p.dyn.net_stride; A.E = E;
+  A.X = X; A.U = U; A.D = d->row_len; A.noff = d->next_obs_off; A.roff = d->reward_off;
+  A.rows = d->rows; A.idx = d->idx; A.n = d->n; A.predict_delta = d->predict_delta; A.min_std = d->min_std;
+  A.part = d->workspace;
+  A.n_slots = p.n_slots; A.ld_xu = p.ld_xu; A.ld_h = p.ld_h; A.ld_y = p.ld_y;
+  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_ens_eval<W.value>>(E * p.n_slots, 256, pl.lds, st, "ens_eval", A); });
+  if (rc != MBPO_OK) return rc;
+  hipLaunchKernelGGL(k_ens_eval_reduce, dim3((2 * E + 63) / 64), dim3(64), 0, st, (const float *)A.part, p.n_slots, 2 * E, (long long)d->n,
+                     d->metrics);
+  MBPO_CHECK_LAUNCH("ens_eval");
+  return MBPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ snapshot and elites
+// The member copy both calls end in: destination member j = blockIdx.y takes source member map[j], or is skipped when map[j] < 0.
+// Bit copy (integer words).  16-byte accesses over the part of the member where source and destination are equally aligned (members
+// are n_params floats apart, not necessarily a multiple of 4: the aligned part starts up to 3 words in), single words elsewhere.
+__global__ void __launch_bounds__(256) k_ens_member_copy(const uint32_t *src, uint32_t *dst, long long n_params, const int *map) {
+  const int j = blockIdx.y, m = map[j];
+  if (m < 0) return;
+  const uint32_t *s = src + (long long)m * n_params;
+  uint32_t *d = dst + (long long)j * n_params;
+  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  if ((((uintptr_t)s ^ (uintptr_t)d) & 15) != 0) {
+    for (long long i = i0; i < n_params; i += stride) d[i] = s[i];
+    return;
+  }
+  long long head = (long long)(((16 - ((uintptr_t)d & 15)) & 15) >> 2);
+  if (head > n_params) head = n_params;
+  const long long n_vec = (n_params - head) >> 2, tail = head + 4 * n_vec;
+  const uint4 *s4 = reinterpret_cast<const uint4 *>(s + head);
+  uint4 *d4 = reinterpret_cast<uint4 *>(d + head);
+  for (long long v = i0; v < n_vec; v += stride) d4[v] = s4[v];
+  if (i0 < head) d[i0] = s[i0];
+  if (tail + i0 < n_params) d[tail + i0] = s[tail + i0];      // (at most 3 words; i0 < 256 reaches them in workgroup 0)
+}
+
+static int ens_member_copy(const float *src, float *dst, long long n_params, const int *map, int n_dst, hipStream_t st, const char *what) {
+  long long bx = (n_params / 4 + 255) / 256;
+  bx = bx < 1 ? 1 : (bx > 1024 ? 1024 : bx);
+  hipLaunchKernelGGL(k_ens_member_copy, dim3((unsigned)bx, (unsigned)n_dst), dim3(256), 0, st, reinterpret_cast<const uint32_t *>(src),
+                     reinterpret_cast<uint32_t *>(dst), n_params, map);
+  MBPO_CHECK_LAUNCH(what);
+  return MBPO_OK;
+}
+
+// One workgroup: the decision of mbpo_ens_keep_best.  Every member's test reads its own best_score entry before writing it.
+__global__ void __launch_bounds__(64) k_ens_keep_decide(const float *score, float *best_score, int E, float rel_tol, int *state, int *map) {
+  int any = 0;
+  for (int e = threadIdx.x; e < E; e += 64) {
+    const float s = score[e];
+    const bool improved = isfinite(s) && s < best_score[e] * (1.0f - rel_tol);
+    map[e] = improved ? e : -1;
+    if (improved) best_score[e] = s;
+    any |= improved ? 1 : 0;
+  }
+  any = __syncthreads_or(any);
+  if (threadIdx.x == 0) {
+    state[0] = any ? 0 : state[0] + 1;
+    state[1] += 1;
+  }
+}
+
+extern "C" int mbpo_ens_keep_best(const float *params, float *best_params, int64_t n_params, int32_t n_members, const float *score,
+                                  float *best_score, float rel_tol, int32_t *state, int32_t *workspace, void *stream) {
+  MBPO_REQUIRE(n_members > 0 && n_members <= 65535 && n_params > 0, MBPO_ERR_ARG, "ens_keep_best: n_members must be in [1, 65535], n_params positive");
+  MBPO_REQUIRE(params && best_params && score && best_score && state && workspace, MBPO_ERR_ARG, "ens_keep_best: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ens_keep_decide, dim3(1), dim3(64), 0, st, score, best_score, n_members, rel_tol, state, workspace);
+  MBPO_CHECK_LAUNCH("ens_keep_best.decide");
+  return ens_member_copy(params, best_params, n_params, workspace, n_members, st, "ens_keep_best.copy");
+}
+
+// One workgroup: elite_idx[rank of member e] = e for the ranks below n_elites (the ranks are a permutation: rank_before is total)
+__global__ void __launch_bounds__(64) k_ens_rank(const float *score, int E, int n_elites, int *elite_idx) {
+  for (int e = threadIdx.x; e < E; e += 64) {
+    const float v = score[e];
+    int r = 0;
+    for (int j = 0; j < E; ++j) r += rank_before(score[j], j, v, e) ? 1 : 0;
+    if (r < n_elites) elite_idx[r] = e;
+  }
+}
+
+extern "C" int mbpo_ens_pick_elites(const float *params, int64_t n_params, int32_t n_members, const float *score, int32_t n_elites,
+                                    int32_t *elite_idx, float *elite_params, void *stream) {
+  MBPO_REQUIRE(n_members > 0 && n_members <= 65535 && n_params > 0, MBPO_ERR_ARG, "ens_pick_elites: n_members must be in [1, 65535], n_params positive");
+  MBPO_REQUIRE(n_elites > 0 && n_elites <= n_members, MBPO_ERR_ARG, "ens_pick_elites: n_elites %d outside [1, n_members = %d]", n_elites, n_members);
+  MBPO_REQUIRE(params && score && elite_idx && elite_params, MBPO_ERR_ARG, "ens_pick_elites: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ens_rank, dim3(1), dim3(64), 0, st, score, n_members, n_elites, elite_idx);
+  MBPO_CHECK_LAUNCH("ens_pick_elites.rank");
+  return ens_member_copy(params, elite_params, n_params, elite_idx, n_elites, st, "ens_pick_elites.copy");
 }

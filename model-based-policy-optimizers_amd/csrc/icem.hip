@@ -235,15 +235,6 @@ __global__ void __launch_bounds__(256) k_icem_values_wave(const float *rows, int
   values[c] = value;
 }
 
-// Candidate (w, j) sorts before candidate (v, c): the total order of np.argsort(kind="stable") — NaN after every number (+inf
-// included), NaNs tied with each other, ties broken by candidate index.  A plain `w < v || (w == v && j < c)` gives every NaN rank 0:
-// the ranks stop being a permutation and the elite / best indices the update kernels read are never written.
-__device__ __forceinline__ bool icem_before(float w, int j, float v, int c) {
-  const bool wn = w != w, vn = v != v;
-  if (wn != vn) return vn;
-  return w < v || (!(v < w) && j < c);      // both numbers: w < v, or equal (-0 == +0); both NaN: neither is less
-}
-
 struct IcemUpdateArgs {
   const float *values, *candidates;
   int NC, H, U, n_elites, n_prev;
@@ -279,7 +270,7 @@ __global__ void __launch_bounds__(1024) k_icem_update(IcemUpdateArgs A) {
     const float v = A.values[c];
     int r = 0;
     for (int j = 0; j < NC; ++j) {
-      r += icem_before(A.values[j], j, v, c) ? 1 : 0;
+      r += rank_before(A.values[j], j, v, c) ? 1 : 0;
     }
     A.rank[c] = r;
   }
@@ -347,7 +338,7 @@ __global__ void __launch_bounds__(1024) k_icem_update_lds(IcemUpdateArgs A) {
     const float v = s_val[c];
     int r = 0;
     for (int j = 0; j < NC; ++j) {
-      r += icem_before(s_val[j], j, v, c) ? 1 : 0;
+      r += rank_before(s_val[j], j, v, c) ? 1 : 0;
     }
     s_rank[c] = r;
     A.rank[c] = r;

@@ -101,6 +101,13 @@ class EnsTrainDesc(C.Structure):
                 ("reward_off", C.c_int32)]
 
 
+class EnsEvalDesc(C.Structure):
+    """mbpo_ens_eval_desc"""
+    _fields_ = [("x_dim", C.c_int32), ("u_dim", C.c_int32), ("dynamics", MlpDesc), ("rows", C.c_void_p), ("row_len", C.c_int32),
+                ("next_obs_off", C.c_int32), ("reward_off", C.c_int32), ("idx", C.c_void_p), ("n", C.c_int64),
+                ("predict_delta", C.c_int32), ("min_std", C.c_float), ("metrics", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class SacDesc(C.Structure):
     _fields_ = [
         ("x_dim", C.c_int32), ("u_dim", C.c_int32),
@@ -265,6 +272,14 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_ens_nll_workspace_floats.argtypes = [C.POINTER(EnsTrainDesc)]
     lib.mbpo_ens_nll_grads.restype = C.c_int
     lib.mbpo_ens_nll_grads.argtypes = [C.POINTER(EnsTrainDesc), vp]
+    lib.mbpo_ens_eval_workspace_floats.restype = C.c_int64
+    lib.mbpo_ens_eval_workspace_floats.argtypes = [C.POINTER(EnsEvalDesc)]
+    lib.mbpo_ens_eval.restype = C.c_int
+    lib.mbpo_ens_eval.argtypes = [C.POINTER(EnsEvalDesc), vp]
+    lib.mbpo_ens_keep_best.restype = C.c_int
+    lib.mbpo_ens_keep_best.argtypes = [vp, vp, i64, i32, vp, vp, f32, vp, vp, vp]
+    lib.mbpo_ens_pick_elites.restype = C.c_int
+    lib.mbpo_ens_pick_elites.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
     u64 = C.c_uint64
     lib.mbpo_icem_sample.restype = C.c_int
     lib.mbpo_icem_sample.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, u64, u64, vp, vp, vp, vp]

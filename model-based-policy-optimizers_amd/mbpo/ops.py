@@ -1249,3 +1249,91 @@ class EnsembleNllGrad:
         d.workspace = self.workspace.data_ptr()
         check(self.lib.mbpo_ens_nll_grads(C.byref(d), current_stream_ptr()), "mbpo_ens_nll_grads")
         return self.grads
+
+
+class EnsembleEval:
+    """Drives mbpo_ens_eval: every member's mean NLL (row 0) and mean squared error (row 1) on ONE shared list of rows, forward only —
+    the held-out loss of MBPO's model selection.  reward_off as in EnsembleNllGrad.  Returns `metrics` [2, E] (reused across calls)."""
+
+    def __init__(self, *, x_dim: int, u_dim: int, spec: MlpSpec, device, predict_delta: bool = True, min_std: float = 1e-3):
+        self.lib = load()
+        self.x_dim, self.u_dim, self.spec = x_dim, u_dim, spec
+        self.device = torch.device(device)
+        self.E, self.n_params = spec.n_nets, spec.n_params
+        d = _hip.EnsEvalDesc()
+        d.x_dim, d.u_dim = x_dim, u_dim
+        d.predict_delta, d.min_std = int(predict_delta), min_std
+        d.reward_off = -1
+        self.desc = d
+        self.metrics = torch.zeros(2, self.E, device=self.device, dtype=torch.float32)
+        self.workspace, self._ws_key = None, None
+
+    def __call__(self, params: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor, next_obs_off: Optional[int] = None,
+                 reward_off: Optional[int] = None) -> torch.Tensor:
+        _req(params, "params"); _req(rows, "rows"); _req(idx, "idx", torch.int32)
+        if params.numel() != self.E * self.n_params:
+            raise ValueError("params must hold E * n_params floats")
+        if rows.dim() != 2 or idx.dim() != 1:
+            raise ValueError("rows must be [R, D] and idx [n]")
+        d = self.desc
+        d.dynamics = self.spec.desc(params)
+        d.rows, d.row_len = rows.data_ptr(), rows.shape[1]
+        d.next_obs_off = self.x_dim + self.u_dim + 2 if next_obs_off is None else next_obs_off
+        d.reward_off = -1 if reward_off is None else int(reward_off)
+        d.idx, d.n = idx.data_ptr(), idx.numel()
+        d.metrics = self.metrics.data_ptr()
+        key = (int(d.n), int(d.row_len), int(d.next_obs_off), int(d.reward_off))
+        if self._ws_key != key:
+            nws = self.lib.mbpo_ens_eval_workspace_floats(C.byref(d))
+            if nws < 0:
+                check(int(nws), "mbpo_ens_eval_workspace_floats")
+            if self.workspace is None or self.workspace.numel() < int(nws):
+                self.workspace = torch.zeros(int(nws), device=self.device, dtype=torch.float32)
+            self._ws_key = key
+        d.workspace = self.workspace.data_ptr()
+        check(self.lib.mbpo_ens_eval(C.byref(d), current_stream_ptr()), "mbpo_ens_eval")
+        return self.metrics
+
+
+def ens_keep_best(params: torch.Tensor, best_params: torch.Tensor, n_members: int, score: torch.Tensor, best_score: torch.Tensor,
+                  rel_tol: float, state: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
+    """mbpo_ens_keep_best: members whose score improved on best_score by the relative margin are snapshotted into best_params; state
+    (int32[2]) = [evaluations since any member improved, evaluations so far].  All on the device."""
+    lib = load()
+    _req(params, "params"); _req(best_params, "best_params"); _req(score, "score"); _req(best_score, "best_score")
+    _req(state, "state", torch.int32)
+    if params.numel() % n_members or best_params.numel() != params.numel():
+        raise ValueError("params / best_params must hold n_members equal members")
+    if score.numel() != n_members or best_score.numel() != n_members or state.numel() != 2:
+        raise ValueError("score / best_score must be [n_members] and state int32[2]")
+    if workspace is None:
+        workspace = torch.empty(n_members, device=params.device, dtype=torch.int32)
+    _req(workspace, "workspace", torch.int32)
+    if workspace.numel() < n_members:
+        raise ValueError("workspace must hold n_members int32")
+    check(lib.mbpo_ens_keep_best(params.data_ptr(), best_params.data_ptr(), params.numel() // n_members, n_members, score.data_ptr(),
+                                 best_score.data_ptr(), rel_tol, state.data_ptr(), workspace.data_ptr(), current_stream_ptr()),
+          "mbpo_ens_keep_best")
+
+
+def ens_pick_elites(params: torch.Tensor, n_members: int, score: torch.Tensor, n_elites: int,
+                    elite_idx: Optional[torch.Tensor] = None, elite_params: Optional[torch.Tensor] = None):
+    """mbpo_ens_pick_elites: (elite_idx int32 [n_elites], elite_params [n_elites * P]) — the n_elites members of lowest score (NaN
+    last, ties by lower index) and a bit copy of their parameters."""
+    lib = load()
+    _req(params, "params"); _req(score, "score")
+    if n_members <= 0 or params.numel() % n_members or score.numel() != n_members:
+        raise ValueError("params must hold n_members equal members and score be [n_members]")
+    if not 0 < n_elites <= n_members:
+        raise ValueError(f"n_elites must be in [1, {n_members}]")
+    P = params.numel() // n_members
+    if elite_idx is None:
+        elite_idx = torch.empty(n_elites, device=params.device, dtype=torch.int32)
+    if elite_params is None:
+        elite_params = torch.empty(n_elites * P, device=params.device, dtype=torch.float32)
+    _req(elite_idx, "elite_idx", torch.int32); _req(elite_params, "elite_params")
+    if elite_idx.numel() != n_elites or elite_params.numel() != n_elites * P:
+        raise ValueError("elite_idx must be [n_elites] and elite_params [n_elites * P]")
+    check(lib.mbpo_ens_pick_elites(params.data_ptr(), P, n_members, score.data_ptr(), n_elites, elite_idx.data_ptr(),
+                                   elite_params.data_ptr(), current_stream_ptr()), "mbpo_ens_pick_elites")
+    return elite_idx, elite_params

@@ -16,6 +16,13 @@ Learned reward (EnsembleDynamics(learn_reward=True) + LearnedReward): the member
     out_e = [mu_e (x_dim), raw_std_e (x_dim), mu_r,e, raw_r,e]
 and the reward of a step is the head at the pre-step (x, u): 'mean' r = mean_e mu_r,e; 'ts1' / 'tsinf' r = mu_r,m with the member m
 the state takes.  sample_noise perturbs the state only.  `fit` adds the reward's Gaussian NLL (target: the rows' reward column).
+
+Model selection (MBPO's model-training procedure, Janner et al. 2019 — not the reference's, which has no model): `fit(holdout_ratio=)`
+holds rows out, evaluates every member on them once per epoch (mbpo_ens_eval), keeps each member's best parameters on the device
+(mbpo_ens_keep_best) and stops when no member improved for a few evaluations; `fit(n_elites=)` / `select_elites` pick the members
+of lowest held-out squared error (mbpo_ens_pick_elites).  EnsembleDynamicsParams.elite_params, when set, is what every rollout
+consumer runs: the kernels see an ensemble of n_elites members, so 'mean' averages the elites, 'ts1' draws among them and 'tsinf'
+binds env i to elite i % n_elites.
 """
 from __future__ import annotations
 
@@ -35,9 +42,18 @@ from mbpo.utils import keys as K
 _MODES = {"mean": _hip.ENS_MEAN, "ts1": _hip.ENS_TS1, "tsinf": _hip.ENS_TSINF}
 
 
+FIT_SITE_HOLDOUT = 1            # high word of the Philox offset of fit's holdout permutation (the sampler draws at offsets 0, 1, ...)
+
+
 @dataclass
 class EnsembleDynamicsParams:
+    """elite_params is a COPY of the elite members' parameters (in elite_idx order), taken when they were selected: a later `fit`
+    without re-selection leaves it stale (the rollouts then still run the old elites); `fit(..., n_elites=)` always refreshes it, and
+    `select_elites` does on request.  Set both elite fields to None to roll out through all members again."""
     params: torch.Tensor          # flat [E * P] device tensor (layout: include/mbpo_hip.h)
+    elite_idx: Optional[torch.Tensor] = None       # int32 [n_elites]: the members the rollouts use, best first
+    elite_params: Optional[torch.Tensor] = None    # [n_elites * P]
+    holdout: Optional[torch.Tensor] = None         # [2, E]: held-out (NLL, squared error) of the members fit(holdout_ratio=) kept
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -104,22 +120,43 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
     def fit(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, num_steps: int, batch_size: int = 256,
             learning_rate: float = 1e-3, weight_decay: float = 0.0, key: int = 0, predict_delta: bool = True,
             min_std: float = 1e-3, n_rows: Optional[int] = None, next_obs_off: Optional[int] = None,
-            reward_off: Optional[int] = None):
+            reward_off: Optional[int] = None, holdout_ratio: float = 0.0, max_holdout: int = 5000, eval_every: Optional[int] = None,
+            max_evals_since_improvement: int = 5, rel_tol: float = 0.01, n_elites: Optional[int] = None):
         """Model learning (N3 — not in the reference, whose model would come from `bsm`): `num_steps` AdamW steps on the
         members' Gaussian negative log-likelihood, each member on its own bootstrapped minibatch (sampling with replacement
         from rows[:n_rows]; Philox randint on the device).  `rows` are true-buffer transition rows (obs, action, reward,
         discount, next_obs, ...).  With learn_reward the reward head is fitted to column `reward_off` (default x_dim + u_dim, the
-        Transition's reward).  Updates dynamics_params.params in place; returns (dynamics_params, losses [num_steps, E])."""
+        Transition's reward).  Updates dynamics_params.params in place; returns (dynamics_params, losses [steps run, E]).
+
+        holdout_ratio > 0 (MBPO's model selection): rows[:n_rows] are permuted (device Philox permutation keyed by `key`); the first
+        min(max_holdout, floor(holdout_ratio * R)) are held out, the rest are copied once into the training matrix the sampler draws
+        from.  Every `eval_every` steps (default: one epoch, ceil(R_train / batch_size)) the members are evaluated on the holdout and
+        each member whose squared error improved by the relative margin `rel_tol` is snapshotted; the fit stops when no member improved
+        for more than `max_evals_since_improvement` evaluations, or at `num_steps` (then after one last evaluation).  The snapshots are
+        copied back into dynamics_params.params in place; dynamics_params.holdout = their held-out [NLL; squared error] ([2, E]).
+        n_elites: dynamics_params.elite_idx / elite_params = the n_elites members of lowest held-out squared error."""
         dev = self.device
         if reward_off is not None and not self.learn_reward:
             raise ValueError("reward_off needs EnsembleDynamics(learn_reward=True)")
         if self.learn_reward and reward_off is None:
             reward_off = self.x_dim + self.u_dim
+        if n_elites is not None and not holdout_ratio > 0:
+            raise ValueError("n_elites needs a holdout (holdout_ratio > 0): the elites are picked by held-out error")
         rows = rows.to(dev, torch.float32).contiguous()
         R = int(rows.shape[0] if n_rows is None else n_rows)
         if R <= 0:
             raise ValueError("no transitions to fit on")
         E = self.n_members
+        seed = K.PRNGKey(key)
+        train, hold_idx = rows, None
+        if holdout_ratio > 0:
+            n_hold = min(int(max_holdout), int(math.floor(holdout_ratio * R)))
+            if n_hold <= 0 or n_hold >= R:
+                raise ValueError(f"holdout_ratio {holdout_ratio} of {R} rows leaves an empty holdout or training set")
+            perm = ops.philox_permutation(R, seed=seed, offset=FIT_SITE_HOLDOUT << 32)
+            hold_idx = perm[:n_hold]
+            train = ops.replay_gather(rows, torch.tensor([R, 0, 0, R], device=dev, dtype=torch.int32), perm[n_hold:])
+            R = R - n_hold
         if getattr(self, "_fit_cfg", None) != (batch_size, predict_delta, min_std, learning_rate, weight_decay):
             self._nll = ops.EnsembleNllGrad(x_dim=self.x_dim, u_dim=self.u_dim, spec=self.spec, batch=batch_size, device=dev,
                                             predict_delta=predict_delta, min_std=min_std)
@@ -131,24 +168,101 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         self._fit_state[0] = R
         self._fit_state[3] = R
         losses = torch.zeros(num_steps, E, device=dev, dtype=torch.float32)
-        seed = K.PRNGKey(key)
-        col0 = rows[:, :1].contiguous()          # the sampler gathers something; one column keeps that cheap
+        col0 = train[:, :1].contiguous()         # the sampler gathers something; one column keeps that cheap
+        if hold_idx is not None:
+            every = int(eval_every) if eval_every is not None else -(-R // batch_size)
+            if every <= 0:
+                raise ValueError("eval_every must be positive")
+            ev = self._evaluator(predict_delta, min_std)
+            best_params = dynamics_params.params.clone()
+            best_score = torch.full((E,), float("inf"), device=dev, dtype=torch.float32)
+            sel_state = torch.zeros(2, device=dev, dtype=torch.int32)
+            sel_ws = torch.zeros(E, device=dev, dtype=torch.int32)
+
+            def evaluate_and_keep() -> int:
+                m = ev(dynamics_params.params, rows, hold_idx, next_obs_off=next_obs_off, reward_off=reward_off)
+                ops.ens_keep_best(dynamics_params.params, best_params, E, m[1], best_score, rel_tol, sel_state, sel_ws)
+                return int(sel_state[0])         # the epoch's one read-back: evaluations since any member improved
+        steps_run, evaluated_at = num_steps, -1
         for it in range(num_steps):
             ops.replay_sample(col0, self._fit_state, E * batch_size, seed=seed, offset=it, out=self._fit_scratch, idx_out=self._fit_idx)
-            g = self._nll(dynamics_params.params, rows, self._fit_idx.view(E, batch_size), next_obs_off=next_obs_off,
+            g = self._nll(dynamics_params.params, train, self._fit_idx.view(E, batch_size), next_obs_off=next_obs_off,
                           reward_off=reward_off)
             self._opt.step(dynamics_params.params, g)
             losses[it].copy_(self._nll.metrics)
-        return dynamics_params, losses
+            if hold_idx is not None and (it + 1) % every == 0:
+                evaluated_at = it + 1
+                if evaluate_and_keep() > max_evals_since_improvement:
+                    steps_run = it + 1
+                    break
+        if hold_idx is None:
+            return dynamics_params, losses
+        if steps_run == num_steps and evaluated_at != num_steps:
+            evaluate_and_keep()                  # num_steps ended the fit: the last steps can still be snapshotted
+        dynamics_params.params.copy_(best_params)
+        # the snapshots' metrics: their squared error as it was scored, their NLL from one more evaluation of the restored parameters
+        holdout = ev(dynamics_params.params, rows, hold_idx, next_obs_off=next_obs_off, reward_off=reward_off).clone()
+        holdout[1].copy_(best_score)
+        dynamics_params.holdout = holdout
+        if n_elites is not None:
+            dynamics_params.elite_idx, dynamics_params.elite_params = ops.ens_pick_elites(dynamics_params.params, E, holdout[1], n_elites)
+        return dynamics_params, losses[:steps_run]
 
-    def member_outputs(self, x: torch.Tensor, u: torch.Tensor, dynamics_params: EnsembleDynamicsParams) -> torch.Tensor:
-        """[E, N, 2*x_dim] raw member outputs (+ [mu_r, raw_r] with learn_reward) — mbpo_ensemble_mlp_forward."""
+    def _evaluator(self, predict_delta: bool, min_std: float) -> "ops.EnsembleEval":
+        if getattr(self, "_eval_cfg", None) != (predict_delta, min_std):
+            self._eval = ops.EnsembleEval(x_dim=self.x_dim, u_dim=self.u_dim, spec=self.spec, device=self.device,
+                                          predict_delta=predict_delta, min_std=min_std)
+            self._eval_cfg = (predict_delta, min_std)
+        return self._eval
+
+    def evaluate(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                 next_obs_off: Optional[int] = None, reward_off: Optional[int] = None, predict_delta: bool = True,
+                 min_std: float = 1e-3) -> torch.Tensor:
+        """[2, E]: every member's mean Gaussian NLL (row 0, `fit`'s loss) and mean squared error of its mean prediction (row 1, MBPO's
+        selection metric) on rows[idx] (idx int32, shared by the members; None: all rows) — mbpo_ens_eval, forward only.  reward_off
+        defaults as in `fit`."""
+        if reward_off is not None and not self.learn_reward:
+            raise ValueError("reward_off needs EnsembleDynamics(learn_reward=True)")
+        if self.learn_reward and reward_off is None:
+            reward_off = self.x_dim + self.u_dim
+        rows = rows.to(self.device, torch.float32).contiguous()
+        if idx is None:
+            idx = torch.arange(rows.shape[0], device=self.device, dtype=torch.int32)
+        idx = idx.to(self.device, torch.int32).contiguous()
+        return self._evaluator(predict_delta, min_std)(dynamics_params.params, rows, idx, next_obs_off=next_obs_off,
+                                                       reward_off=reward_off).clone()
+
+    def select_elites(self, dynamics_params: EnsembleDynamicsParams, score: torch.Tensor, n_elites: int) -> EnsembleDynamicsParams:
+        """The n_elites members of lowest `score` ([E]; NaN last, ties by lower index) become the members every rollout consumer runs:
+        returns the params with elite_idx / elite_params set (mbpo_ens_pick_elites; elite_params is a copy, see EnsembleDynamicsParams)."""
+        score = score.to(self.device, torch.float32).contiguous()
+        elite_idx, elite_params = ops.ens_pick_elites(dynamics_params.params, self.n_members, score, int(n_elites))
+        return dynamics_params.replace(elite_idx=elite_idx, elite_params=elite_params)
+
+    def elite_spec(self, n_elites: int) -> "ops.MlpSpec":
+        """The kernel shapes of an ensemble of n_elites of these members (cached per n_elites)."""
+        cache = self.__dict__.setdefault("_elite_specs", {})
+        if n_elites not in cache:
+            cache[n_elites] = ops.MlpSpec(self.dims, self.spec.activation, int(n_elites))
+        return cache[n_elites]
+
+    def _rollout_members(self, dynamics_params: EnsembleDynamicsParams):
+        """(params, spec) of the members the rollouts use: the elites when selected, else all."""
+        if dynamics_params.elite_params is None:
+            return dynamics_params.params, self.spec
+        return dynamics_params.elite_params, self.elite_spec(int(dynamics_params.elite_idx.numel()))
+
+    def member_outputs(self, x: torch.Tensor, u: torch.Tensor, dynamics_params: EnsembleDynamicsParams,
+                       elites: bool = False) -> torch.Tensor:
+        """[E, N, 2*x_dim] raw member outputs (+ [mu_r, raw_r] with learn_reward) — mbpo_ensemble_mlp_forward.  All members, also
+        when elites are selected; elites=True: the members the rollouts use ([n_elites, N, ...] when selected)."""
         xu = torch.cat([x.reshape(-1, self.x_dim), u.reshape(-1, self.u_dim)], dim=1).to(self.device, torch.float32).contiguous()
-        return ops.ensemble_mlp_forward(dynamics_params.params, self.spec, xu)
+        params, spec = self._rollout_members(dynamics_params) if elites else (dynamics_params.params, self.spec)
+        return ops.ensemble_mlp_forward(params, spec, xu)
 
     def next_state(self, x, u, dynamics_params, predict_delta: bool = True, min_std: float = 1e-3):
-        """Mixture moments over members: mean = E_e[mu_e], std = sqrt(E_e[sigma_e^2] + Var_e[mu_e])."""
-        y = self.member_outputs(x, u, dynamics_params)
+        """Mixture moments over members (the elites when selected): mean = E_e[mu_e], std = sqrt(E_e[sigma_e^2] + Var_e[mu_e])."""
+        y = self.member_outputs(x, u, dynamics_params, elites=True)
         X = self.x_dim
         mu = y[..., :X] + (x.reshape(-1, X) if predict_delta else 0.0)
         sig = torch.nn.functional.softplus(y[..., X:2 * X]) + min_std
@@ -159,10 +273,11 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         return Normal(mean, std), dynamics_params
 
     def reward(self, x, u, dynamics_params, min_std: float = 1e-3) -> Normal:
-        """The reward head's mixture moments over members at (x, u): mean = E_e[mu_r,e], std = sqrt(E_e[sigma_r,e^2] + Var_e[mu_r,e])."""
+        """The reward head's mixture moments over members (the elites when selected) at (x, u): mean = E_e[mu_r,e],
+        std = sqrt(E_e[sigma_r,e^2] + Var_e[mu_r,e])."""
         if not self.learn_reward:
             raise ValueError("this ensemble has no reward head (EnsembleDynamics(learn_reward=True))")
-        y = self.member_outputs(x, u, dynamics_params)
+        y = self.member_outputs(x, u, dynamics_params, elites=True)
         X = self.x_dim
         mu = y[..., 2 * X]
         sig = torch.nn.functional.softplus(y[..., 2 * X + 1]) + min_std
@@ -225,6 +340,8 @@ class EnsembleSystem(System):
             self._rspec = self.reward.kernel_spec(rp, device)
             self._rspec_key = ck
         kind, rvec = self._rspec
-        return dict(system_kind=_hip.SYS_ENSEMBLE, dyn_params=system_params.dynamics_params.params, dyn_spec=self.dynamics.spec,
+        # the elites, when selected, ARE the ensemble the kernels see (every consumer takes E from dyn_spec.n_nets)
+        dyn_params, dyn_spec = self.dynamics._rollout_members(system_params.dynamics_params)
+        return dict(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dyn_params, dyn_spec=dyn_spec,
                     ens_mode=_MODES[self.mode], ens_predict_delta=self.predict_delta, ens_sample_noise=self.sample_noise,
                     ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec)

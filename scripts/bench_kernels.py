@@ -353,6 +353,27 @@ def main():
 
     if want("fit_case"): attempt(fit_case, 4, 1, 7, (200, 200, 200, 200), 256, 50)
 
+    # held-out loss of every member (mbpo_ens_eval, forward only) on n shared rows, next to mbpo_ensemble_mlp_forward on the same
+    # [E, n] rows in the same run: the eval drops the y write and adds the row gather and the loss head.  The forward row's roof.
+    def ens_eval_case(X, U, E, hid, n, reps):
+        from mbpo.systems import EnsembleDynamics
+        dyn = EnsembleDynamics(X, U, n_members=E, hidden_layer_sizes=hid, device=dev)
+        p = dyn.init_params(0)
+        rows = torch.randn(8192, 2 * X + U + 2, generator=g).to(dev)
+        idx = torch.randperm(8192, generator=g)[:n].to(torch.int32).to(dev)
+        ev = ops.EnsembleEval(x_dim=X, u_dim=U, spec=dyn.spec, device=dev)
+        xu = rows[idx.long(), :X + U].contiguous()
+        t, te = both(lambda: ev(p.params, rows, idx), reps)
+        tf, _ = both(lambda: ops.ensemble_mlp_forward(p.params, dyn.spec, xu), reps)
+        out.append(mfma_entry("k_ens_eval + k_ens_eval_reduce" if dyn.dims[1:-1] == [64] * len(hid) else "k_ens_gather + layered forward + k_ens_eval_head",
+                              "mbpo_ens_eval", {"n": n, "x": X, "u": U, "E": E, "member": list(hid), "stored": dyn.dims[1:-1]}, t,
+                              n * 2 * E * mlp_macs(dyn.dims_logical), "2*E*M FLOP per row (shared rows), logical shapes",
+                              {"eager_us": te * 1e6, "forward_device_us": tf * 1e6, "eval_over_forward": t / tf}))
+        log(f"ensemble eval n={n} E={E} {hid}: {t * 1e6:.1f} us (eager {te * 1e6:.1f} us); forward of the same rows {tf * 1e6:.1f} us; ratio {t / tf:.2f}")
+
+    if want("ens_eval_case"): attempt(ens_eval_case, 4, 1, 7, (64, 64, 64), 5000, 100)
+    if want("ens_eval_case"): attempt(ens_eval_case, 4, 1, 7, (200, 200, 200, 200), 5000, 50)
+
     # ---------------------------------------------------------------- N4: iCEM planner at the reference's defaults (icem_optimizer.py:25-50)
     def icem_case(H, reps):
         from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
