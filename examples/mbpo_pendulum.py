@@ -5,12 +5,15 @@
                       ->  SACOptimizer on EnsembleSystem (short model rollouts branched from true states + SAC updates)
                       ->  the policy acts on the TRUE PendulumSystem.
 
-    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites]
+    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
 --elites: MBPO's model selection — 7 members, a 20 % holdout, per-member early stopping with --model-steps as the cap, and rollouts
 through the 5 members of lowest held-out error (fit(holdout_ratio=0.2, n_elites=5)).
+--terminate-speed V: the MODEL system (not the true one) gets a termination function, BoxTermination on |thetadot| <= V: a model episode
+ends where the predicted speed leaves the interval (discount 0, truncation 0, restart from the env's first state).  After every SAC
+epoch the share of the last collection's model transitions that ended this way is printed.
 """
 from __future__ import annotations
 
@@ -45,10 +48,41 @@ def true_return(system, optimizer, opt_state, steps=200):
     return total
 
 
-def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False):
+def train_reporting_terminations(optimizer, opt_state, verbose=True):
+    """SACOptimizer.train (a new trainer per call) with a progress_fn: after every epoch, the share of the last collection's model
+    transitions with discount == 0 and truncation == 0 — the ones the termination function ended.  Returns (output, shares).
+    KEEP IN STEP with BraxOptimizer.train (mbpo/optimizers/policy_optimizers/brax_optimizers.py), whose body this repeats because the
+    progress_fn needs the trainer: the rows of its last collection are the trainer's `_rollout_rows` (what tests/ read too)."""
+    from mbpo.optimizers.policy_optimizers.brax_optimizers import BraxOutput
+    from mbpo.systems.brax_wrapper import BraxWrapper
+    from mbpo.utils import keys as K
+    env = BraxWrapper(system=optimizer.system, system_params=opt_state.system_params, sample_buffer_state=opt_state.true_buffer_state,
+                      sample_buffer=optimizer.true_buffer)
+    trainer = optimizer.agent_class(environment=env, **optimizer.agent_kwargs)
+    X, U = optimizer.system.x_dim, optimizer.system.u_dim
+    shares = []
+
+    def progress(env_steps, metrics):
+        if env_steps == 0:
+            return
+        rows = trainer._rollout_rows                  # the last get_experience's rows: [..., reward, discount, next_obs, truncation]
+        shares.append(float(((rows[:, X + U + 1] == 0) & (rows[:, -1] == 0)).float().mean()))
+        if verbose:
+            print(f"  env_steps {env_steps}: {100 * shares[-1]:.1f} % of the model transitions terminated", flush=True)
+
+    key, new_key = K.split(opt_state.key)
+    try:
+        policy_params, metrics = trainer.run_training(key=new_key, progress_fn=progress)
+    finally:
+        trainer.close()
+    return BraxOutput(optimizer_state=opt_state.replace(policy_params=policy_params, key=new_key), summary=metrics), shares
+
+
+def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
+        terminate_speed=None):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
-    from mbpo.systems import EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
+    from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
     from mbpo.types import Transition
     dev = torch.device("cuda", torch.cuda.current_device())
     gen = torch.Generator().manual_seed(seed)
@@ -59,7 +93,9 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
     true_buffer = UniformSamplingQueue(max_replay_size=iters * n_true, dummy_data_sample=dummy, sample_batch_size=1, device=dev)
     tbs = true_buffer.init(seed)
     dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
-    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), mode="mean", predict_delta=True)
+    termination = None if terminate_speed is None else BoxTermination.from_intervals(3, {2: (-terminate_speed, terminate_speed)})
+    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), mode="mean", predict_delta=True,
+                           termination=termination)
     dyn_params = dyn.init_params(seed + 1)
     history = []
     for it in range(iters):
@@ -79,13 +115,18 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         if learn_reward:
             sp = sp.replace(reward_params=dyn_params)      # the learned reward's parameters are the model's
         state = state.replace(system_params=sp)
-        out = optimizer.train(opt_state=state)
+        if termination is None:
+            out, shares = optimizer.train(opt_state=state), None
+        else:
+            out, shares = train_reporting_terminations(optimizer, state, verbose)
         ret = true_return(true_system, optimizer, out.optimizer_state)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
                             seconds=time.time() - t0))
         if elites:
             history[-1].update(steps_run=int(losses.shape[0]), elite_idx=dyn_params.elite_idx.tolist(),
                                holdout_mse=[round(float(v), 6) for v in dyn_params.holdout[1]])
+        if shares is not None:
+            history[-1].update(terminated_share=[round(s, 4) for s in shares])
         if verbose:
             print(history[-1], flush=True)
     return history
@@ -99,5 +140,8 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--learn-reward", action="store_true")
     ap.add_argument("--elites", action="store_true")
+    ap.add_argument("--terminate-speed", type=float, default=None, metavar="V",
+                    help="end a MODEL episode where the predicted |thetadot| exceeds V (BoxTermination on the model system only)")
     a = ap.parse_args()
-    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites)
+    run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
+        terminate_speed=a.terminate_speed)

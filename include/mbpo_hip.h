@@ -117,6 +117,17 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
  * The analytic rewards accept a 2x + 2 ensemble too and ignore its reward head. */
 #define MBPO_REWARD_LEARNED 2
 
+/* Termination (SystemState.done of the fused systems, base_systems.py:25; MBPO's termination functions): a box on the step's
+ * pre-auto-reset next state x', term_low / term_high [x_dim] (unbounded dimensions carry -inf / +inf; the bounds are closed):
+ *   violated_d = !(low_d <= x'_d && x'_d <= high_d) || isinf(x'_d)        (NaN fails the compares, so it is violated)
+ *   sys_done   = any_d violated_d ? 1 : 0
+ *   over = steps >= episode_length;  done = over ? 1 : sys_done;  truncation = over ? 1 - sys_done : 0
+ *   obs <- first_obs where done;  discount = 1 - done;  next_observation = the post-reset obs
+ * (EpisodeWrapper / AutoReset, brax_utils/training.py:98-107, 126-137, given a System that reports done.)  Both system kinds, every
+ * ensemble mode and reward kind, with a policy or open-loop `actions`.  With action_repeat > 1 sys_done comes from the LAST inner
+ * step: the inner steps keep stepping and the reward is summed over all of them.  The reward is unchanged (evaluated at the
+ * pre-step (x, u)).  With a termination set a non-finite next state is done = 1 and a reset to first_obs: it never reaches
+ * next_observation or the carried obs.  Without one (both pointers NULL) sys_done = 0 and every kernel runs as before. */
 typedef struct mbpo_rollout_desc {
   mbpo_mlp_desc policy;   /* [x_dim] -> [2*u_dim] */
   mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std) or [2*x_dim+2] (+ reward mean, raw std: MBPO_REWARD_LEARNED);
@@ -157,6 +168,8 @@ typedef struct mbpo_rollout_desc {
    *   [obs(x), action(u), reward, discount, next_obs(x), {log_prob, raw_action(u)}, truncation] */
   float *transitions;     /* [S*N, row_len] */
   int32_t row_len;        /* 2x+u+3 (+1+u with ppo_extras) */
+  /* termination (see above): each [x_dim], both NULL = none (a zero-initialised descriptor), exactly one NULL = MBPO_ERR_ARG */
+  const float *term_low, *term_high;
 } mbpo_rollout_desc;
 
 int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream);

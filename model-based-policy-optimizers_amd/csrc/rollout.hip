@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
       if (tid < 16) {
         const int r = tid;
         float st = s_steps[r] + (float)AR;
-        float sys_done = 0.f;  // SystemState.done default (base_systems.py:25)
+        float sys_done = term_row_done(A, s_xu + r * A.ld_xu, X);  // SystemState.done: 0 (base_systems.py:25) or the termination box
         float dn = (st >= (float)A.episode_length) ? 1.f : sys_done;
         float trunc = (st >= (float)A.episode_length) ? (1.f - sys_done) : 0.f;
         s_steps[r] = st;
@@ -447,7 +447,9 @@ __device__ __forceinline__ int ro_tid_now(int wave) {
 
 // LR: MBPO_REWARD_LEARNED (section C reads the reward from the members' outputs; a flag of its own so the other instantiations stay
 // as they were)
-template <bool WIDE, bool LR>
+// TERM: a termination box is set (a flag of its own for the same reason: the run-time test cost the plain instantiation two spilled
+// registers in the step loop; with it the step gains one barrier)
+template <bool WIDE, bool LR, bool TERM>
 __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64 AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -669,12 +671,18 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
         }
       }
 
+      // TERM: the rows' SystemState.done, once per row by 16 threads (the 16 floats behind the log-prob scratch), read by section D
+      float *s_sd = s_scr + 16 * (X + U);
+      if (TERM) {
+        if (tid < 16) s_sd[tid] = term_row_done(A, s_scr + tid * X, X);
+        __syncthreads();
+      }
       RO_STAMP(5);
       // ---- section D: EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137) + Transition (acting.py:46-55) ----
       for (int idx = tid; idx < 16 * X; idx += nthreads) {
         const int r = idx & 15, c = idx >> 4;
         const float st = steps_cur[r] + (float)AR;
-        const bool dn = st >= (float)A.episode_length;
+        const bool dn = st >= (float)A.episode_length || (TERM && s_sd[r] != 0.f);
         const float v = dn ? s_first[r * ld_x + c] : s_scr[r * X + c];
         s_obs[r * ld_x + c] = v;
         s_row[r * D + X + U + 2 + c] = v;  // next_observation = nstate.obs (post auto-reset)
@@ -682,7 +690,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
       if (tid < 16) {
         const int r = tid;
         const float st = steps_cur[r] + (float)AR;
-        const float sys_done = 0.f;  // SystemState.done default (base_systems.py:25)
+        const float sys_done = TERM ? s_sd[r] : 0.f;  // SystemState.done: 0 (base_systems.py:25) or the termination box
         const float dn = (st >= (float)A.episode_length) ? 1.f : sys_done;
         const float trunc = (st >= (float)A.episode_length) ? (1.f - sys_done) : 0.f;
         steps_nxt[r] = st;
@@ -772,7 +780,9 @@ __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
       xu[0] = xn[0]; xu[1] = xn[1]; xu[2] = xn[2];
     }
     const float st = steps + (float)AR;
-    const bool dn = st >= (float)A.episode_length;
+    const bool over = st >= (float)A.episode_length;
+    const float sys_done = term_row_done(A, xu, X);      // SystemState.done: 0 (base_systems.py:25) or the termination box
+    const bool dn = over || sys_done != 0.f;
 #pragma unroll
     for (int c = 0; c < X; ++c) {
       const float v = dn ? f[c] : xu[c];
@@ -781,7 +791,7 @@ __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
     }
     row[X + U] = rew;
     row[X + U + 1] = 1.f - (dn ? 1.f : 0.f);
-    row[D - 1] = dn ? 1.f : 0.f;       // truncation
+    row[D - 1] = over ? 1.f - sys_done : 0.f;      // truncation
     steps = st;
     done = dn ? 1.f : 0.f;
   }
@@ -802,6 +812,8 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
                "model_rollout: null state/output pointer");
   MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG,
                "model_rollout: norm_mean and norm_std must both be set or both NULL");
+  MBPO_REQUIRE((d->term_low == nullptr) == (d->term_high == nullptr), MBPO_ERR_ARG,
+               "model_rollout: term_low and term_high must both be set or both NULL");
   MBPO_REQUIRE(d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED, MBPO_ERR_ARG, "model_rollout: reward_params is NULL");
   const int X = d->x_dim, U = d->u_dim;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
@@ -868,6 +880,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   A.seed = d->seed; A.offset = d->offset; A.rng_dev = (const unsigned long long *)d->rng_dev;
   A.obs = d->obs; A.first_obs = d->first_obs; A.steps = d->steps; A.done = d->done;
   A.transitions = d->transitions; A.row_len = d->row_len;
+  A.term_low = d->term_low; A.term_high = d->term_high;
   A.n_out = E > 1 ? E : 1;
   A.ld_x = up4(X) + 4;
   A.ld_xu = up4(X + U) + 4;
@@ -924,7 +937,9 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     const bool wide = net_is_wide(AA.sh_pi) || net_is_wide(AA.sh_dyn);
     rc = mbpo_with_bool(lr, [&](auto LR) {
       return mbpo_with_bool(wide, [&](auto W) {
-        return mbpo_launch<k_model_rollout64<W.value, LR.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+        return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
+          return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+        });
       });
     });
   } else if (H == 128) {

@@ -44,7 +44,8 @@ constexpr int R_TILES = R_BIAS + 6 * RL_NB;         // [6 chains][2] hidden tile
 constexpr int R_SLOT1 = R_TILES + 12 * LT;          // PIPE: the second tile's [pin | xu | eps | lp | rows]: 128 + 128 + 16 + 16 + 256
 constexpr int S_PIN = 0, S_XU = 128, S_EPS = 256, S_LP = 272, S_ROW = 288, RL_SLOT_F = 544;
 constexpr int R_SLOT0 = R_SLOT1 + RL_SLOT_F;
-constexpr size_t RL_LDS_BYTES = (size_t)(R_SLOT0 + RL_SLOT_F) * sizeof(float);
+constexpr int R_TERM = R_SLOT0 + RL_SLOT_F;         // TERM: [2][4] the termination box, low then high
+constexpr size_t RL_LDS_BYTES = (size_t)(R_TERM + 8) * sizeof(float);
 constexpr int SW = 3;                               // the wave that holds the tile's env state
 constexpr int NW = 4;                               // the wave that draws the policy noise
 
@@ -87,7 +88,9 @@ __device__ __forceinline__ void rl_sample(const RolloutArgs &A, const f32x4 acc,
 // step s + 1, or NULL after the last step).
 // LR (MBPO_REWARD_LEARNED): the reward is the members' reward head (output column 2X) at the pre-step (x, u) — the mean over members,
 // or in the TS modes the member the row's state takes (the lanes of column 0 hold the row's member already); no reward parameters.
-template <int X, bool PEND, bool LR>
+// TERM: a termination box is set (include/mbpo_hip.h "termination"): a row's SystemState.done is the OR of term_violated over the lanes
+// that hold its elements — one wave-wide ballot that all 64 lanes reach (lanes with sc >= X vote "not violated"), folded by 16.
+template <int X, bool PEND, bool LR, bool TERM>
 __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, long long env0, int lane, float *smem, float *s_pin, float *s_xu,
                                          const float *s_lp, float *s_row, float *n_row, float &o, float fo, float &steps, float &done,
                                          unsigned long long rng_seed, unsigned long long rng_off) {
@@ -152,14 +155,22 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
     }
   }
   const float st = steps + 1.0f;
-  const bool dnb = st >= (float)A.episode_length;
+  const bool over = st >= (float)A.episode_length;
+  bool sys_done = false;                             // SystemState.done defaults to 0 (base_systems.py:25)
+  if (TERM) {
+    const bool bad = s_ok && term_violated(v, smem[R_TERM + (sc & 3)], smem[R_TERM + 4 + (sc & 3)]);
+    const unsigned long long b = __ballot(bad);      // bit (r + 16 c): element c of row r
+    const unsigned int rows_bad = (unsigned int)(b | (b >> 16) | (b >> 32) | (b >> 48)) & 0xffffu;
+    sys_done = (rows_bad >> sr) & 1u;
+  }
+  const bool dnb = over || sys_done;
   const float v2 = dnb ? fo : v;
   if (s_ok) s_row[sr * D + X + U + 2 + sc] = v2;      // next_observation = nstate.obs (post auto-reset)
   if (lane < 16) {
-    const float dn = dnb ? 1.f : 0.f;                // SystemState.done defaults to 0 (base_systems.py:25)
+    const float dn = dnb ? 1.f : 0.f;
     s_row[sr * D + X + U] = rew;
     s_row[sr * D + X + U + 1] = 1.f - dn;
-    s_row[sr * D + D - 1] = dnb ? 1.f : 0.f;         // truncation
+    s_row[sr * D + D - 1] = (over && !sys_done) ? 1.f : 0.f;      // truncation
     if (A.ppo_extras) s_row[sr * D + 2 * X + U + 2] = s_lp[sr];
   }
   steps = st;
@@ -184,7 +195,8 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
 // the resident weights leave; the ensemble + quadratic-reward instantiation — the benchmark's — carries neither)
 // PIPE: two tiles in flight per workgroup — the policy phase of one beside the member phase of the other (see the pipelined loop below)
 // LR: MBPO_REWARD_LEARNED (the reward read from the members' outputs; a flag of its own so the other instantiations stay as they were)
-template <int X, bool PEND, bool PIPE, bool LR>
+// TERM: a termination box is set (a flag of its own, for the same reason: without one the kernel is the code it was)
+template <int X, bool PEND, bool PIPE, bool LR, bool TERM>
 __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -260,6 +272,10 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
   if (tid < X) {
     smem[R_NORM + tid] = A.norm_mean ? A.norm_mean[tid] : 0.f;
     smem[R_NORM + 4 + tid] = A.norm_mean ? A.norm_std[tid] : 1.f;
+    if (TERM) {
+      smem[R_TERM + tid] = A.term_low[tid];
+      smem[R_TERM + 4 + tid] = A.term_high[tid];
+    }
   }
   __syncthreads();
 
@@ -332,7 +348,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
         __syncthreads();
         if (is_sw && my_slot == ms && mv) {
           float *const row = my_base + S_ROW;
-          rl_fused<X, PEND, LR>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo, steps, done,
+          rl_fused<X, PEND, LR, TERM>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo, steps, done,
                             rng_seed, rng_off);
           // the finished rows of step sm leave from here (this wave's own LDS writes and reads stay in order); then the next step's inputs
           if (A.env_major) {
@@ -444,7 +460,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
       // ---- one section on the state wave: AutoReset pre-step (training.py:119-124), reward on the pre-step (x, u), next state,
       //      EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137), Transition (acting.py:46-55), next step's inputs ----
       if (wave == SW)
-        rl_fused<X, PEND, LR>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
+        rl_fused<X, PEND, LR, TERM>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
                           s + 1 < A.n_steps ? smem + R_ROWS + ((s + 1) & 1) * 16 * D4 : nullptr, o, fo, steps, done, rng_seed, rng_off);
       __syncthreads();
       RL_STAMP(9);
@@ -505,10 +521,15 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   int rc;
   const bool pend = A.a.system_kind == MBPO_SYS_PENDULUM || A.a.reward_kind == MBPO_REWARD_PENDULUM;
   const bool lr = A.a.reward_kind == MBPO_REWARD_LEARNED;      // (an ensemble: never with pend)
-#define RL_LAUNCH_LR(X_, P_, PP_, LR_)                                                                              \
-  {                                                                                                                 \
-    rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
-    if (rc != MBPO_OK) return rc;                                                                                   \
+  const bool term = A.a.term_low != nullptr;
+#define RL_LAUNCH_T(X_, P_, PP_, LR_, T_)                                                                                \
+  {                                                                                                                      \
+    rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_, T_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
+    if (rc != MBPO_OK) return rc;                                                                                        \
+  }
+#define RL_LAUNCH_LR(X_, P_, PP_, LR_)                                                       \
+  {                                                                                          \
+    if (term) RL_LAUNCH_T(X_, P_, PP_, LR_, true) else RL_LAUNCH_T(X_, P_, PP_, LR_, false)  \
   }
 #define RL_LAUNCH(X_, P_, PP_) RL_LAUNCH_LR(X_, P_, PP_, false)
   if (lr) {
@@ -538,5 +559,6 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   }
 #undef RL_LAUNCH
 #undef RL_LAUNCH_LR
+#undef RL_LAUNCH_T
   return MBPO_OK;
 }

@@ -26,7 +26,22 @@ struct RolloutArgs {
   int row_len;
   // LDS geometry
   int ld_x, ld_xu, ld_h, ld_y, n_chains, n_out;
+  const float *term_low, *term_high;      // [x_dim] each, or both NULL: no termination
 };
+
+// Termination (include/mbpo_hip.h): one element of the next state against its closed interval.  NaN fails both compares and an
+// infinity is violated whatever the bounds (an unbounded dimension carries -inf / +inf, which +-inf would pass).
+__device__ __forceinline__ bool term_violated(float v, float lo, float hi) {
+  return !(lo <= v && v <= hi) || fabsf(v) == __builtin_inff();
+}
+
+// SystemState.done of row r from its next state xn[0..X): 1 if any element is violated; 0 without a termination.
+__device__ __forceinline__ float term_row_done(const RolloutArgs &A, const float *xn, int X) {
+  if (!A.term_low) return 0.f;
+  bool bad = false;
+  for (int c = 0; c < X; ++c) bad |= term_violated(xn[c], A.term_low[c], A.term_high[c]);
+  return bad ? 1.f : 0.f;
+}
 
 // PendulumDynamics.next_state (dynamics/pendulum_dynamics.py:29-63), fp32, same operation order.
 __device__ __forceinline__ void pendulum_step(const float *x, float u, const float *sp, float *xn) {

@@ -81,6 +81,8 @@ class RolloutDesc(C.Structure):
         ("done", C.c_void_p),
         ("transitions", C.c_void_p),
         ("row_len", C.c_int32),
+        ("term_low", C.c_void_p),
+        ("term_high", C.c_void_p),
     ]
 
 

@@ -268,10 +268,14 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
                   policy_noise: Optional[torch.Tensor] = None, model_noise: Optional[torch.Tensor] = None,
                   member_idx: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
                   rng_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                  system=None, system_params=None, system_params_out: Optional[list] = None) -> torch.Tensor:
+                  system=None, system_params=None, system_params_out: Optional[list] = None,
+                  term_low: Optional[torch.Tensor] = None, term_high: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused S-step model rollout for N envs (R1-R8).  Updates obs/steps/done in place; returns rows [S*N, D].
-    system_kind == SYS_GENERIC (a user-defined `system`): the same contract through generic_rollout below."""
+    system_kind == SYS_GENERIC (a user-defined `system`): the same contract through generic_rollout below.
+    term_low / term_high ([x_dim] each, both or neither): the box termination of include/mbpo_hip.h (BoxTermination.kernel_spec)."""
     if system_kind == _hip.SYS_GENERIC:
+        if term_low is not None or term_high is not None:
+            raise ValueError("term_low / term_high belong to the fused systems; a user-defined System reports SystemState.done itself")
         if model_noise is not None or member_idx is not None:
             raise ValueError("model_noise / member_idx belong to the fused ensemble; a user-defined System draws its own randomness")
         return generic_rollout(system=system, system_params=system_params, system_params_out=system_params_out,
@@ -339,6 +343,10 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
     d.rng_dev = rng_ptr(rng_dev)
     d.obs, d.first_obs, d.steps, d.done = obs.data_ptr(), first_obs.data_ptr(), steps.data_ptr(), done.data_ptr()
     d.transitions, d.row_len = out.data_ptr(), D
+    for t, nm in ((term_low, "term_low"), (term_high, "term_high")):
+        if t is not None and _req(t, nm).numel() != x_dim:
+            raise ValueError(f"{nm} must be [x_dim]")
+    d.term_low, d.term_high = ptr(term_low), ptr(term_high)
     check(lib.mbpo_model_rollout(C.byref(d), current_stream_ptr()), "mbpo_model_rollout")
     return out
 

@@ -28,6 +28,7 @@ from mbpo.optimizers.base_optimizer import BaseOptimizer
 from mbpo.replay import ReplayBufferState, UniformSamplingQueue
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
 from mbpo.systems.rewards.base_rewards import RewardParams
+from mbpo.systems.termination import without_termination
 from mbpo.types import Transition
 from mbpo.utils import keys as K
 from mbpo.utils.type_aliases import OptimizerState, OptimizerTrainingOutPut
@@ -348,7 +349,8 @@ class BPTTOptimizer(BaseOptimizer):
 
     # -- one train step on the working buffers ----------------------------------------------------------------------
     def _system_kwargs(self, system_params):
-        spec = self.system.rollout_spec(system_params, self.device)
+        # (rollout_policy's scan ignores SystemState.done, utils/optimizer_utils.py:85-93: no termination in the gradient or the evaluation)
+        spec = without_termination(self.system.rollout_spec(system_params, self.device))
         if spec["system_kind"] == _hip.SYS_GENERIC:
             # a user-defined System (the reference's plug-in seam, base_systems.py:40-52): rollout_policy's scan
             # (utils/optimizer_utils.py:62-116) is walked on the host — ops.BpttActorGradGeneric: the networks' forward and VJP in HIP

@@ -35,6 +35,7 @@ from mbpo.replay import ReplayBufferState
 from mbpo.systems.base_systems import System
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
 from mbpo.systems.rewards.base_rewards import RewardParams
+from mbpo.systems.termination import without_termination
 from mbpo.utils import keys as K
 from mbpo.utils.type_aliases import OptimizerState, OptimizerTrainingOutPut
 
@@ -161,7 +162,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         b["best_seq"].copy_(b["mean"])
         b["prev"].zero_()
         optimizer_key, key = K.split(opt_state.key, 2)
-        spec = self.system.rollout_spec(opt_state.system_params, dev)
+        spec = without_termination(self.system.rollout_spec(opt_state.system_params, dev))      # (rollout_actions ignores done)
         st = _hip.current_stream_ptr()
         lib = self.lib
         carry_key = optimizer_key
@@ -222,7 +223,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             seeds[it, 0], seeds[it, 1] = sk[:, 0], sk[:, 1]
             carry = K.split_many(sk[:, 0], 2)[:, 0]
         seeds_dev = torch.from_numpy(seeds.view(np.int64)).to(dev)
-        spec = self.system.rollout_spec(opt_state.system_params, dev)
+        spec = without_termination(self.system.rollout_spec(opt_state.system_params, dev))      # (rollout_actions ignores done)
         draw = self._batched_ensemble_draws(spec, b)
         st = _hip.current_stream_ptr()
         lib = self.lib

@@ -53,8 +53,16 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
         """Systems that exist as device code (PendulumSystem, EnsembleSystem): one fused launch of the rollout kernel with
         open-loop actions and S=1 (csrc/rollout.hip).  A user-defined System overrides this with its own BATCHED torch code
         (x [N, x_dim], u [N, u_dim] on the device -> SystemState with x_next [N, x_dim], reward [N]); the trainers then step it
-        between the HIP policy and bookkeeping kernels (ops.generic_rollout)."""
+        between the HIP policy and bookkeeping kernels (ops.generic_rollout).
+        With a termination set (PendulumSystem / EnsembleSystem(termination=)) SystemState.done is the box's verdict on the next state;
+        where done is 1 the kernel's auto-reset has already run, so x_next is the state the env restarts from — here x itself — and a
+        non-finite next state never leaves the kernel."""
+        return self._fused_step(x, u, system_params, terminate=True)
+
+    def _fused_step(self, x: torch.Tensor, u: torch.Tensor, system_params: SystemParams, terminate: bool) -> SystemState:
+        """`step` of a fused system; terminate=False drops the termination (rollout_policy's scan ignores SystemState.done)."""
         from mbpo import ops
+        from mbpo.systems.termination import without_termination
         if not self.fused:
             raise NotImplementedError(f"{type(self).__name__} must define step(x, u, system_params) itself (batched torch code)")
         dev = _device_of(x)
@@ -63,15 +71,21 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
         ub = u.reshape(-1, self.u_dim).to(dev, torch.float32).contiguous()
         n = xb.shape[0]
         key, sub = K.split(system_params.key)
+        spec = self.rollout_spec(system_params, dev)
+        if not terminate:
+            spec = without_termination(spec)
         rows = ops.model_rollout(x_dim=self.x_dim, u_dim=self.u_dim, actions=ub.reshape(1, n, self.u_dim), obs=xb,
                                  first_obs=xb.clone(), steps=torch.zeros(n, device=dev), done=torch.zeros(n, device=dev),
-                                 n_steps=1, episode_length=2 ** 30, seed=sub, **self.rollout_spec(system_params, dev))
+                                 n_steps=1, episode_length=2 ** 30, seed=sub, **spec)
         X, U = self.x_dim, self.u_dim
         x_next, reward = rows[:, X + U + 2:2 * X + U + 2], rows[:, X + U]
+        # the episode cannot run out here (episode_length 2**30): done = 1 - discount is the system's own
+        done = 1.0 - rows[:, X + U + 1] if "term_low" in spec else 0.0      # (no termination: SystemState's default)
         if single:
             x_next, reward = x_next[0], reward[0]
+            done = done[0] if "term_low" in spec else done
         # a stochastic System must split-and-return its key; the reference's Pendulum drops it (:38)
-        return SystemState(x_next=x_next, reward=reward, system_params=system_params.replace(key=key))
+        return SystemState(x_next=x_next, reward=reward, system_params=system_params.replace(key=key), done=done)
 
     def init_params(self, key: int) -> SystemParams:
         keys = K.split(key, 3)

@@ -37,6 +37,7 @@ from mbpo import _hip, ops
 from mbpo.systems.base_systems import System, SystemParams
 from mbpo.systems.dynamics.base_dynamics import Dynamics, Normal
 from mbpo.systems.rewards.base_rewards import Reward
+from mbpo.systems.termination import BoxTermination, termination_spec
 from mbpo.utils import keys as K
 
 _MODES = {"mean": _hip.ENS_MEAN, "ts1": _hip.ENS_TS1, "tsinf": _hip.ENS_TSINF}
@@ -311,9 +312,17 @@ class LearnedReward(Reward[EnsembleDynamicsParams]):
 
 
 class EnsembleSystem(System):
+    """termination: a BoxTermination on the next state (mbpo/systems/termination.py) — the model episodes of the SAC / PPO trainers
+    and of the evaluators then end where the box is left or the state stops being finite (discount 0, truncation 0, reset to the
+    env's first obs), and `step` reports SystemState.done.  iCEM, BPTT and rollout_actions / rollout_policy IGNORE it, as the
+    reference's scans ignore SystemState.done (utils/optimizer_utils.py:31-47, 85-93): their trajectories run on through the box."""
+
     def __init__(self, dynamics: EnsembleDynamics, reward: Reward, mode: str = "mean", predict_delta: bool = True,
-                 sample_noise: bool = False, min_std: float = 1e-3):
+                 sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None):
         super().__init__(dynamics=dynamics, reward=reward)
+        if termination is not None and termination.x_dim != dynamics.x_dim:
+            raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {dynamics.x_dim}")
+        self.termination = termination
         if mode not in _MODES:
             raise ValueError(f"mode must be one of {sorted(_MODES)}")
         if isinstance(reward, LearnedReward):
@@ -335,7 +344,10 @@ class EnsembleSystem(System):
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         rp = system_params.reward_params
         # (the learned reward has no parameter vector: its params hold a device tensor, whose repr would copy it to the host)
-        ck = ("learned" if isinstance(self.reward, LearnedReward) else repr(rp), str(device))
+        # (the termination's device tensors are cached per device by BoxTermination.kernel_spec itself; its key here only makes the
+        # spec's cache key change with the bounds)
+        ck = ("learned" if isinstance(self.reward, LearnedReward) else repr(rp), str(device),
+              None if self.termination is None else self.termination.key)
         if getattr(self, "_rspec_key", None) != ck:    # cached: no H2D copy inside a captured graph
             self._rspec = self.reward.kernel_spec(rp, device)
             self._rspec_key = ck
@@ -344,4 +356,5 @@ class EnsembleSystem(System):
         dyn_params, dyn_spec = self.dynamics._rollout_members(system_params.dynamics_params)
         return dict(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dyn_params, dyn_spec=dyn_spec,
                     ens_mode=_MODES[self.mode], ens_predict_delta=self.predict_delta, ens_sample_noise=self.sample_noise,
-                    ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec)
+                    ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec,
+                    **termination_spec(self.termination, self.x_dim, device))

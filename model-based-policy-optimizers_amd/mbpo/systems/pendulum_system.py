@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import dataclasses
+from typing import Optional
 
 import torch
 
@@ -9,21 +10,27 @@ from mbpo import _hip
 from mbpo.systems.base_systems import System, SystemParams, SystemState, _device_of
 from mbpo.systems.dynamics.pendulum_dynamics import PendulumDynamics, PendulumDynamicsParams
 from mbpo.systems.rewards.pendulum_reward import PendulumReward, PendulumRewardParams
+from mbpo.systems.termination import BoxTermination, termination_spec
 
 
 class PendulumSystem(System[PendulumDynamicsParams, PendulumRewardParams]):
-    def __init__(self):
+    def __init__(self, termination: Optional[BoxTermination] = None):
+        """termination (not in the reference): a BoxTermination on the next state [cos, sin, thetadot]; see EnsembleSystem."""
         super().__init__(dynamics=PendulumDynamics(), reward=PendulumReward())
+        if termination is not None and termination.x_dim != self.x_dim:
+            raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {self.x_dim}")
+        self.termination = termination
         self.min_action = -1.0
         self.max_action = 1.0
 
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         dp = system_params.dynamics_params or PendulumDynamicsParams()
         rp = system_params.reward_params or PendulumRewardParams()
-        ck = (dataclasses.astuple(dp), dataclasses.astuple(rp), str(device))
+        ck = (dataclasses.astuple(dp), dataclasses.astuple(rp), str(device), None if self.termination is None else self.termination.key)
         if getattr(self, "_spec_key", None) != ck:     # device vectors are cached: no H2D copy inside a captured graph
             kind, rvec = self.reward.kernel_spec(rp, device)
-            self._spec = dict(system_kind=_hip.SYS_PENDULUM, sys_params=dp.vector(device), reward_kind=kind, reward_params=rvec)
+            self._spec = dict(system_kind=_hip.SYS_PENDULUM, sys_params=dp.vector(device), reward_kind=kind, reward_params=rvec,
+                              **termination_spec(self.termination, self.x_dim, device))
             self._spec_key = ck
         return dict(self._spec)
 

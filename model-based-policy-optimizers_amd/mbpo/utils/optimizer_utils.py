@@ -20,6 +20,7 @@ import torch
 
 from mbpo import _hip, ops
 from mbpo.systems.base_systems import System, SystemParams
+from mbpo.systems.termination import without_termination
 from mbpo.types import Transition
 
 
@@ -40,7 +41,7 @@ def rollout_actions(system: System, system_params: SystemParams, init_state: tor
     acts = actions.reshape(horizon, -1, U).to(dev, torch.float32)
     if acts.shape[1] != N:
         raise ValueError(f"actions must be [H,u] or [H,{N},u]")
-    spec = system.rollout_spec(system_params, dev)
+    spec = without_termination(system.rollout_spec(system_params, dev))      # (the scan ignores SystemState.done, see below)
     if spec["system_kind"] == _hip.SYS_GENERIC:
         # a user-defined System: the reference's scan (:31-47) is a plain loop over System.step — it ignores SystemState.done (no
         # Episode / AutoReset bookkeeping on this path: a terminating System keeps propagating x_next) and carries system_params
@@ -57,7 +58,8 @@ def rollout_actions(system: System, system_params: SystemParams, init_state: tor
             tr = Transition(observation=tr.observation[:, 0], action=tr.action[:, 0], reward=tr.reward[:, 0], discount=tr.discount[:, 0],
                             next_observation=tr.next_observation[:, 0])
         return tr
-    # fused systems (Pendulum, learned ensemble) never report done and the episode never ends: one launch for all steps
+    # fused systems (Pendulum, learned ensemble): their termination, if any, is dropped above and the episode never ends: one launch
+    # for all steps
     z = torch.zeros(N, device=dev)
     rows = ops.model_rollout(x_dim=X, u_dim=U, actions=acts.contiguous(), obs=obs, first_obs=obs.clone(), steps=z, done=z.clone(),
                              n_steps=horizon, episode_length=2 ** 30, seed=system_params.key, **spec)
@@ -88,7 +90,8 @@ def rollout_policy(system: System, system_params: SystemParams, init_state: torc
     for _ in range(horizon):
         acs, ps = policy(obs[0] if single else obs, ps)
         acs = acs.reshape(-1, U).to(dev, torch.float32)
-        out = system.step(x=obs, u=acs, system_params=sp)
+        # (:85-93 ignores SystemState.done: a fused system steps without its termination)
+        out = system._fused_step(obs, acs, sp, terminate=False) if system.fused else system.step(x=obs, u=acs, system_params=sp)
         o.append(obs); a.append(acs); r.append(out.reward.reshape(-1)); n.append(out.x_next.reshape(-1, X))
         obs, sp = n[-1], out.system_params
     tr = Transition(observation=torch.stack(o), action=torch.stack(a), reward=torch.stack(r), discount=torch.ones_like(torch.stack(r)),
