@@ -790,17 +790,16 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   long long tiles = (d->n + 15) / 16;
   long long cap = mbpo_num_cus();
   pl->n_slabs = (int)(tiles < cap ? tiles : cap);
-  long long o = 0;
-  auto take = [&](long long n) { long long at = o; o += (n + 3) & ~3LL; return at; };
-  pl->o_xs = take(d->n * (d->horizon + 1) * d->x_dim);
-  pl->o_as = take(d->n * d->horizon * d->u_dim);
-  pl->o_eps = take(d->n * d->horizon * d->u_dim);
-  pl->o_rs = take(d->n * d->horizon);
-  pl->o_vs = take(d->n * d->horizon);
-  pl->o_km = take(d->n * d->horizon);
+  Carve c;
+  pl->o_xs = c.take(d->n * (d->horizon + 1) * d->x_dim);
+  pl->o_as = c.take(d->n * d->horizon * d->u_dim);
+  pl->o_eps = c.take(d->n * d->horizon * d->u_dim);
+  pl->o_rs = c.take(d->n * d->horizon);
+  pl->o_vs = c.take(d->n * d->horizon);
+  pl->o_km = c.take(d->n * d->horizon);
   // trajectory sampling: the member of every (trajectory, step), and with noise eps and the selected member's raw std output, so the
   // backward sweep never redraws (and works the same on the z store and on recompute)
-  pl->o_ts = ts ? take(ts_noise ? ts_raw_off(d->n, d->horizon, d->x_dim) + d->n * d->horizon * d->x_dim : d->n * d->horizon) : -1;
+  pl->o_ts = ts ? c.take(ts_noise ? ts_raw_off(d->n, d->horizon, d->x_dim) + d->n * d->horizon * d->x_dim : d->n * d->horizon) : -1;
   // member pre-activations kept from the forward sweep (the backward sweep then skips the members' recompute): 4 KB per (trajectory
   // tile, step, member, hidden layer) — 1 GB at BASELINE config 5 (n = 4096, H = 32, E = 10); beyond MBPO_BPTT_ZSTORE_MAX_MB (default
   // 16384) the kernel recomputes instead
@@ -808,11 +807,11 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
   if (E > 0 && mbpo_knob(KNOB_BPTT_ZSTORE) != 0) {
     const long long max_mb = mbpo_knob(KNOB_BPTT_ZSTORE_MAX_MB);
     const long long zf = tiles * d->horizon * E * (pl->dyn.n_layers - 1) * 1024;
-    if (zf * 4 <= max_mb * (1LL << 20)) pl->o_z = take(zf);
+    if (zf * 4 <= max_mb * (1LL << 20)) pl->o_z = c.take(zf);
   }
-  pl->o_slabs = take((long long)pl->n_slabs * pl->P);
-  pl->o_extras = take((long long)pl->n_slabs * 2);
-  pl->total = o;
+  pl->o_slabs = c.take((long long)pl->n_slabs * pl->P);
+  pl->o_extras = c.take((long long)pl->n_slabs * 2);
+  pl->total = c.off;
   if (need_ptrs)
     MBPO_REQUIRE(d->actor_params && d->target_critic_params && (d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED) && d->state_mean && d->state_std && d->reward_mean_std &&
                      d->init_states && d->transitions && d->lambda_values && d->grads && d->metrics && d->workspace,

@@ -76,6 +76,22 @@ int mbpo_num_cus();
 
 static inline int up4(int v) { return (v + 3) & ~3; }
 
+// Workspace carve: take(n) returns the current offset (floats) and advances it by n rounded up to 4 floats, so every region starts
+// 16-byte aligned; ptr(n) is the same region as a pointer into `base` (nullptr without one: a size query).
+struct Carve {
+  float *base = nullptr;
+  long long off = 0;
+  long long take(long long n) {
+    const long long at = off;
+    off += (n + 3) & ~3LL;
+    return at;
+  }
+  float *ptr(long long n) {
+    const long long at = take(n);
+    return base ? base + at : nullptr;
+  }
+};
+
 // the one width all hidden layers share, or -1 (none, or mixed widths)
 static inline int same_hidden(const int *dims, int n_layers) {
   if (n_layers < 2) return -1;

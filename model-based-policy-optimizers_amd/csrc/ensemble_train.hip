@@ -19,29 +19,78 @@
 #include "chain_run.hpp"
 #include "layered.hpp"
 
-struct EnsTrainArgs {
+// Kernel arguments of both fused kernels (training step and evaluation).
+struct EnsArgs {
   NetShape sh;
   const float *params;
   long long net_stride;
   int n_params, E, X, U, D, noff, roff;   // roff: reward target column, or -1
   const float *rows;
-  const int *idx;
-  long long batch;
+  const int *idx;                         // training: [E][n], a minibatch per member; evaluation: [n], shared by the members
+  long long n;                            // rows per member
   int predict_delta;
   float min_std;
-  float *slabs, *extras;
+  float *slabs, *extras;                  // training: gradient slabs, loss partials [E][n_slots]; evaluation: extras = [2][E][n_slots]
   int n_slots, ld_xu, ld_h, ld_y, LH;
 };
 
+// One output element of the Gaussian NLL, the one place its terms are written: sigma = softplus(raw) + min_std, q = (t - mu) / sigma,
+// the loss term 0.5 q^2 + log sigma and the squared error (t - mu)^2.  Padded rows and an unfitted reward head are masked by the callers.
+struct NllTerm {
+  float sg, q, nll, se;
+};
+__device__ __forceinline__ NllTerm ens_nll_term(float t, float mu, float raw, float min_std) {
+  NllTerm o;
+  o.sg = softplus_f(raw) + min_std;
+  o.q = (t - mu) / o.sg;
+  o.nll = 0.5f * o.q * o.q + logf(o.sg);
+  const float d = t - mu;
+  o.se = d * d;
+  return o;
+}
+// ... and its gradient: d(nll * invB) / d mu and / d raw
+__device__ __forceinline__ NllTerm ens_nll_grad(float t, float mu, float raw, float min_std, float invB, float *dmu, float *draw) {
+  const NllTerm o = ens_nll_term(t, mu, raw, min_std);
+  *dmu = -(o.q / o.sg) * invB;
+  *draw = ((1.f - o.q * o.q) / o.sg) * sigmoid_f(raw) * invB;
+  return o;
+}
+
+// Stage rows j0 .. j0 + 15 of the index list `idx` ([n]; zeros beyond n): s_xu [16][ld_xu] = [x, u], s_t [16][ld_y] = the regression
+// target (X state columns, delta-encoded with predict_delta; then the reward at column X when roff >= 0).  No barrier.
+__device__ __forceinline__ void ens_stage_tile(const EnsArgs &A, const int *idx, long long j0, float *s_xu, float *s_t, int tid,
+                                               int nthreads) {
+  const int X = A.X, U = A.U, ld_xu = A.ld_xu, ld_y = A.ld_y;
+  for (int i2 = tid; i2 < 16 * (X + U); i2 += nthreads) {
+    const int r = i2 & 15, c = i2 >> 4;
+    const long long j = j0 + r;
+    s_xu[r * ld_xu + c] = (j < A.n) ? A.rows[(long long)idx[j] * A.D + c] : 0.f;
+  }
+  for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
+    const int r = i2 & 15, c = i2 >> 4;
+    const long long j = j0 + r;
+    float t = 0.f;
+    if (j < A.n) {
+      const float *row = A.rows + (long long)idx[j] * A.D;
+      t = row[A.noff + c] - (A.predict_delta ? row[c] : 0.f);
+    }
+    s_t[r * ld_y + c] = t;
+  }
+  if (A.roff >= 0 && tid < 16) {
+    const long long j = j0 + tid;
+    s_t[tid * ld_y + X] = (j < A.n) ? A.rows[(long long)idx[j] * A.D + A.roff] : 0.f;
+  }
+}
+
 template <int SP, bool WIDE>
-__global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
+__global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = 4;
   const int tid_ = threadIdx.x, nthreads = 128 * SP;
   const int wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
   const int chain = wave / SP, sub = wave % SP;    // chain 0: forward, then dgrad; chain 1: wgrad
   const int e = blockIdx.x / A.n_slots, slot = blockIdx.x - e * A.n_slots;
-  const int X = A.X, U = A.U, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y, LH = A.LH;
+  const int X = A.X, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y, LH = A.LH;
   const int T = 16 * ld_h;
   float *s_xu = smem;                       // [16][ld_xu]  [x, u]
   float *s_t = s_xu + 16 * ld_xu;           // [16][ld_y]   regression target (X state columns, then the reward), loss elements from X + 1
@@ -52,37 +101,19 @@ __global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
   float *s_ls = s_pp + 2 * T;               // [16] loss partials
   const float *params = A.params + (long long)e * A.net_stride;
   const int L = A.sh.L;
-  const float invB = 1.0f / (float)A.batch;
+  const float invB = 1.0f / (float)A.n;
   float *slab = A.slabs + ((long long)e * A.n_slots + slot) * A.n_params;
-  const int *idx = A.idx + (long long)e * A.batch;
+  const int *idx = A.idx + (long long)e * A.n;
   float loss = 0.f;
   bool first = true;
-  const long long n_tiles = (A.batch + 15) >> 4;
+  const long long n_tiles = (A.n + 15) >> 4;
 #pragma nounroll
   for (long long tile = slot; tile < n_tiles; tile += A.n_slots, first = false) {
     const int tid = opaque(tid_), lane = tid & 63;
     const long long j0 = tile * 16;
     WSet<HT, SP> R;
     if (chain == 0) chain_fwd_prefetch<HT, SP, WIDE>(R, A.sh, params, sub, lane);
-    for (int i2 = tid; i2 < 16 * (X + U); i2 += nthreads) {
-      const int r = i2 & 15, c = i2 >> 4;
-      const long long j = j0 + r;
-      s_xu[r * ld_xu + c] = (j < A.batch) ? A.rows[(long long)idx[j] * A.D + c] : 0.f;
-    }
-    for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
-      const int r = i2 & 15, c = i2 >> 4;
-      const long long j = j0 + r;
-      float t = 0.f;
-      if (j < A.batch) {
-        const float *row = A.rows + (long long)idx[j] * A.D;
-        t = row[A.noff + c] - (A.predict_delta ? row[c] : 0.f);
-      }
-      s_t[r * ld_y + c] = t;
-    }
-    if (A.roff >= 0 && tid < 16) {
-      const long long j = j0 + tid;
-      s_t[tid * ld_y + X] = (j < A.batch) ? A.rows[(long long)idx[j] * A.D + A.roff] : 0.f;
-    }
+    ens_stage_tile(A, idx, j0, s_xu, s_t, tid, nthreads);
     __syncthreads();
     if (chain == 0) chain_fwd_run<HT, SP, WIDE>(A.sh, params, s_xu, ld_xu, nullptr, nullptr, s_st, s_st + LH * T, s_y, ld_y, ld_h, L, sub, lane, R);
     else chain_idle_run(L);
@@ -90,23 +121,21 @@ __global__ void __launch_bounds__(128 * SP) k_ens_nll_fwd_bwd(EnsTrainArgs A) {
     // d loss / d(mu, raw) per element, loss partial per row
     for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
       const int r = i2 & 15, c = i2 >> 4;
-      const bool ok = j0 + r < A.batch;
-      const float mu = s_y[r * ld_y + c], raw = s_y[r * ld_y + X + c];
-      const float sg = softplus_f(raw) + A.min_std;
-      const float q = (s_t[r * ld_y + c] - mu) / sg;
-      s_dy[r * ld_y + c] = ok ? -(q / sg) * invB : 0.f;
-      s_dy[r * ld_y + X + c] = ok ? ((1.f - q * q) / sg) * sigmoid_f(raw) * invB : 0.f;
-      s_t[r * ld_y + X + 1 + c] = ok ? 0.5f * q * q + logf(sg) : 0.f;      // per-element loss, summed below
+      const bool ok = j0 + r < A.n;
+      float dmu, draw;
+      const NllTerm el = ens_nll_grad(s_t[r * ld_y + c], s_y[r * ld_y + c], s_y[r * ld_y + X + c], A.min_std, invB, &dmu, &draw);
+      s_dy[r * ld_y + c] = ok ? dmu : 0.f;
+      s_dy[r * ld_y + X + c] = ok ? draw : 0.f;
+      s_t[r * ld_y + X + 1 + c] = ok ? el.nll : 0.f;      // per-element loss, summed below
     }
     if (A.sh.N_out > 2 * X && tid < 16) {       // the reward head: its term, or zero gradient when it is not fitted
       const int r = tid;
-      const bool ok = j0 + r < A.batch && A.roff >= 0;
-      const float mu = s_y[r * ld_y + 2 * X], raw = s_y[r * ld_y + 2 * X + 1];
-      const float sg = softplus_f(raw) + A.min_std;
-      const float q = (s_t[r * ld_y + X] - mu) / sg;
-      s_dy[r * ld_y + 2 * X] = ok ? -(q / sg) * invB : 0.f;
-      s_dy[r * ld_y + 2 * X + 1] = ok ? ((1.f - q * q) / sg) * sigmoid_f(raw) * invB : 0.f;
-      s_t[r * ld_y + 2 * X + 1] = ok ? 0.5f * q * q + logf(sg) : 0.f;
+      const bool ok = j0 + r < A.n && A.roff >= 0;
+      float dmu, draw;
+      const NllTerm el = ens_nll_grad(s_t[r * ld_y + X], s_y[r * ld_y + 2 * X], s_y[r * ld_y + 2 * X + 1], A.min_std, invB, &dmu, &draw);
+      s_dy[r * ld_y + 2 * X] = ok ? dmu : 0.f;
+      s_dy[r * ld_y + 2 * X + 1] = ok ? draw : 0.f;
+      s_t[r * ld_y + 2 * X + 1] = ok ? el.nll : 0.f;
     }
     __syncthreads();
     if (tid < 16) {
@@ -150,46 +179,61 @@ __global__ void __launch_bounds__(256) k_ens_gather(const float *rows, const int
   tt[X] = roff >= 0 ? row[roff] : 0.f;
 }
 
-// One workgroup per member: dy [E][B][dout] and the member's loss.  The formulas are k_ens_nll_fwd_bwd's: the same per-element
-// terms, the row's state terms summed first and the reward last; a thread adds its rows b = tid, tid + 256, ... in order, then a
-// fixed tree over the threads.
-__global__ void __launch_bounds__(256) k_ens_nll_head(const float *y, const float *t, int X, int dout, int roff, int B, float min_std,
-                                                      float *dy, float *metrics) {
-  __shared__ float s_red[256];
+// The layered path's head, one workgroup per member over y [E][B][dout] and the targets t [B][X + 1] at t + e * t_stride (training:
+// a minibatch per member, t_stride = B * (X + 1); evaluation: shared, 0).  The terms and their order are the fused kernels': the row's
+// state terms summed first and the reward last; a thread adds its rows b = tid, tid + 256, ... in order, then a fixed tree over the
+// threads.  GRAD (training): dy [E][B][dout] and metrics[e] = the member's loss; otherwise (evaluation) metrics[e] and, at
+// metrics[E + e], the mean squared error.
+template <bool GRAD>
+__global__ void __launch_bounds__(256) k_ens_head(const float *y, const float *t, long long t_stride, int X, int dout, int roff, int B,
+                                                  int E, float min_std, float *dy, float *metrics) {
+  __shared__ float s_red[GRAD ? 1 : 2][256];
   const int e = blockIdx.x, tid = threadIdx.x;
   const float invB = 1.0f / (float)B;
-  float acc = 0.f;
+  float acc = 0.f, acc2 = 0.f;
   for (int b = tid; b < B; b += 256) {
     const long long r = (long long)e * B + b;
-    const float *yr = y + r * dout, *tr = t + r * (X + 1);
-    float *dr = dy + r * dout;
-    float a = 0.f;
+    const float *yr = y + r * dout, *tr = t + e * t_stride + (long long)b * (X + 1);
+    float *dr = GRAD ? dy + r * dout : nullptr;
+    float a = 0.f, a2 = 0.f, dmu, draw;
     for (int c = 0; c < X; ++c) {
-      const float mu = yr[c], raw = yr[X + c];
-      const float sg = softplus_f(raw) + min_std;
-      const float q = (tr[c] - mu) / sg;
-      dr[c] = -(q / sg) * invB;
-      dr[X + c] = ((1.f - q * q) / sg) * sigmoid_f(raw) * invB;
-      a += 0.5f * q * q + logf(sg);
+      const NllTerm el = ens_nll_grad(tr[c], yr[c], yr[X + c], min_std, invB, &dmu, &draw);
+      if constexpr (GRAD) {
+        dr[c] = dmu;
+        dr[X + c] = draw;
+      }
+      a += el.nll;
+      a2 += el.se;
     }
     if (dout > 2 * X) {                         // the reward head: its term, or zero gradient when it is not fitted
       const bool ok = roff >= 0;
-      const float mu = yr[2 * X], raw = yr[2 * X + 1];
-      const float sg = softplus_f(raw) + min_std;
-      const float q = (tr[X] - mu) / sg;
-      dr[2 * X] = ok ? -(q / sg) * invB : 0.f;
-      dr[2 * X + 1] = ok ? ((1.f - q * q) / sg) * sigmoid_f(raw) * invB : 0.f;
-      if (ok) a += 0.5f * q * q + logf(sg);
+      const NllTerm el = ens_nll_grad(tr[X], yr[2 * X], yr[2 * X + 1], min_std, invB, &dmu, &draw);
+      if constexpr (GRAD) {
+        dr[2 * X] = ok ? dmu : 0.f;
+        dr[2 * X + 1] = ok ? draw : 0.f;
+      }
+      if (ok) {
+        a += el.nll;
+        a2 += el.se;
+      }
     }
     acc += a;
+    acc2 += a2;
   }
-  s_red[tid] = acc;
+  s_red[0][tid] = acc;
+  if constexpr (!GRAD) s_red[1][tid] = acc2;
   __syncthreads();
   for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) s_red[tid] += s_red[tid + h];
+    if (tid < h) {
+      s_red[0][tid] += s_red[0][tid + h];
+      if constexpr (!GRAD) s_red[1][tid] += s_red[1][tid + h];
+    }
     __syncthreads();
   }
-  if (tid == 0) metrics[e] = s_red[0] / (float)B;
+  if (tid == 0) {
+    metrics[e] = s_red[0][0] / (float)B;
+    if constexpr (!GRAD) metrics[E + e] = s_red[1][0] / (float)B;
+  }
 }
 
 struct EnsPlan {
@@ -198,7 +242,7 @@ struct EnsPlan {
   int n_slots, ld_xu, ld_h, ld_y, LH;
   size_t lds;
   long long total;
-  // layered path: workspace offsets (floats)
+  // layered path: workspace offsets (floats); evaluation keeps no z / h / dy / part and ping-pongs its hidden layers through tmp0 / tmp1
   long long off_xu, off_t, off_z[MBPO_MAX_LAYERS + 1], off_h[MBPO_MAX_LAYERS + 1], off_y, off_dy, off_tmp0, off_tmp1, off_part;
 };
 
@@ -240,6 +284,20 @@ static int ens_plan_shape(const char *what, int X, int U, const mbpo_mlp_desc &d
   return MBPO_OK;
 }
 
+// The fused kernels' arguments that both entry points fill alike, from the members the two public descriptors share (n = rows per
+// member); slabs / extras are the caller's.
+static EnsArgs ens_args(const EnsPlan &pl, const mbpo_mlp_desc &dynamics, int X, int U, const float *rows, int row_len, int noff, int roff,
+                        const int *idx, long long n, int predict_delta, float min_std) {
+  EnsArgs A;
+  A.sh = net_shape(pl.dyn);
+  A.params = dynamics.params; A.net_stride = pl.dyn.net_stride; A.n_params = pl.dyn.n_params; A.E = pl.dyn.n_nets;
+  A.X = X; A.U = U; A.D = row_len; A.noff = noff; A.roff = roff;
+  A.rows = rows; A.idx = idx; A.n = n; A.predict_delta = predict_delta; A.min_std = min_std;
+  A.slabs = A.extras = nullptr;
+  A.n_slots = pl.n_slots; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
+  return A;
+}
+
 static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "ens_nll: null descriptor");
   int rc = ens_plan_shape("ens_nll", d->x_dim, d->u_dim, d->dynamics, d->row_len, d->next_obs_off, d->reward_off, d->batch, pl);
@@ -250,21 +308,20 @@ static int ens_plan(const mbpo_ens_train_desc *d, EnsPlan *pl, bool need_ptrs) {
   } else {
     const long long EB = (long long)E * d->batch;
     const LayeredNet net = layered_net(pl->dyn, nullptr, pl->dyn.n_params, E);
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 3) & ~3LL; return o; };
-    pl->off_xu = take(EB * (X + U));
-    pl->off_t = take(EB * (X + 1));
+    Carve c;
+    pl->off_xu = c.take(EB * (X + U));
+    pl->off_t = c.take(EB * (X + 1));
     for (int l = 1; l < L; ++l) {
-      pl->off_z[l] = take(EB * pl->dyn.dims[l]);
-      pl->off_h[l] = take(EB * pl->dyn.dims[l]);
+      pl->off_z[l] = c.take(EB * pl->dyn.dims[l]);
+      pl->off_h[l] = c.take(EB * pl->dyn.dims[l]);
     }
-    pl->off_y = take(EB * pl->dyn.dims[L]);
-    pl->off_dy = take(EB * pl->dyn.dims[L]);
+    pl->off_y = c.take(EB * pl->dyn.dims[L]);
+    pl->off_dy = c.take(EB * pl->dyn.dims[L]);
     const long long mh = layered_max_hidden(net);
-    pl->off_tmp0 = take(EB * mh);
-    pl->off_tmp1 = take(EB * mh);
-    pl->off_part = take(layered_part_floats(net, (int)d->batch));
-    pl->total = off;
+    pl->off_tmp0 = c.take(EB * mh);
+    pl->off_tmp1 = c.take(EB * mh);
+    pl->off_part = c.take(layered_part_floats(net, (int)d->batch));
+    pl->total = c.off;
   }
   if (need_ptrs)
     MBPO_REQUIRE(d->dynamics.params && d->rows && d->idx && d->grads && d->metrics && d->workspace, MBPO_ERR_ARG, "ens_nll: null pointer");
@@ -296,8 +353,8 @@ static int ens_nll_layered(const mbpo_ens_train_desc *d, const EnsPlan &pl, hipS
   const LayeredNet net = layered_net(pl.dyn, d->dynamics.params, pl.dyn.net_stride, E);
   int rc = layered_forward(net, xu, (long long)B * (X + U), B, Z, H, y, st);
   if (rc != MBPO_OK) return rc;
-  hipLaunchKernelGGL(k_ens_nll_head, dim3(E), dim3(256), 0, st, (const float *)y, (const float *)t, X, dout, d->reward_off, B, d->min_std,
-                     dy, d->metrics);
+  hipLaunchKernelGGL(k_ens_head<true>, dim3(E), dim3(256), 0, st, (const float *)y, (const float *)t, (long long)B * (X + 1), X, dout,
+                     d->reward_off, B, E, d->min_std, dy, d->metrics);
   MBPO_CHECK_LAUNCH("ens_nll_grads.head");
   // every weight and bias of every member is written: the bias gradient is the last row of its layer's [K + 1][N] block
   return layered_backward(net, xu, (long long)B * (X + U), B, Z, H, dy, d->grads, pl.dyn.n_params, nullptr, ws + pl.off_tmp0,
@@ -309,14 +366,10 @@ extern "C" int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream) {
   int rc = ens_plan(d, &pl, true);
   if (rc != MBPO_OK) return rc;
   if (pl.layered) return ens_nll_layered(d, pl, (hipStream_t)stream);
-  EnsTrainArgs A;
   const int E = pl.dyn.n_nets;
-  A.sh = net_shape(pl.dyn);
-  A.params = d->dynamics.params; A.net_stride = pl.dyn.net_stride; A.n_params = pl.dyn.n_params; A.E = E;
-  A.X = d->x_dim; A.U = d->u_dim; A.D = d->row_len; A.noff = d->next_obs_off; A.roff = d->reward_off;
-  A.rows = d->rows; A.idx = d->idx; A.batch = d->batch; A.predict_delta = d->predict_delta; A.min_std = d->min_std;
+  EnsArgs A = ens_args(pl, d->dynamics, d->x_dim, d->u_dim, d->rows, d->row_len, d->next_obs_off, d->reward_off, d->idx, d->batch,
+                       d->predict_delta, d->min_std);
   A.slabs = d->workspace; A.extras = d->workspace + (long long)E * pl.n_slots * pl.dyn.n_params;
-  A.n_slots = pl.n_slots; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
   hipStream_t st = (hipStream_t)stream;
   rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_ens_nll_fwd_bwd<4, W.value>>(E * pl.n_slots, 512, pl.lds, st, "ens_nll_grads", A); });
   if (rc != MBPO_OK) return rc;
@@ -329,40 +382,18 @@ extern "C" int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream) {
 // ================================================================================================ model selection
 // MBPO's model-training procedure (held-out loss per member, per-member best snapshot, elite members) — not the reference's, which
 // has no learned model.  mbpo_ens_eval is the forward half of the step above on ONE index list shared by the members: the same
-// per-element terms, the row's state terms summed first and the reward last, plus the squared error of the mean head.
-struct EnsEvalArgs {
-  NetShape sh;
-  const float *params;
-  long long net_stride;
-  int E, X, U, D, noff, roff;
-  const float *rows;
-  const int *idx;
-  long long n;
-  int predict_delta;
-  float min_std;
-  float *part;      // [2][E][n_slots]
-  int n_slots, ld_xu, ld_h, ld_y;
-};
-
-// 0.5 q^2 + log sigma and (t - mu)^2 of one output element: k_ens_nll_fwd_bwd's loss term, written the same way
-__device__ __forceinline__ void ens_eval_terms(float t, float mu, float raw, float min_std, float *nll, float *se) {
-  const float sg = softplus_f(raw) + min_std;
-  const float q = (t - mu) / sg;
-  *nll = 0.5f * q * q + logf(sg);
-  const float d = t - mu;
-  *se = d * d;
-}
+// per-element terms (ens_nll_term), the row's state terms summed first and the reward last, plus the squared error of the mean head.
 
 // One workgroup = (member, slot), four waves = one forward chain; hidden activations ping-pong through two tiles (nothing is kept
-// for a backward pass).
+// for a backward pass).  Partials to A.extras [2][E][n_slots].
 template <bool WIDE>
-__global__ void __launch_bounds__(256) k_ens_eval(EnsEvalArgs A) {
+__global__ void __launch_bounds__(256) k_ens_eval(EnsArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = 4, SP = 4;
   const int tid_ = threadIdx.x, nthreads = 256;
   const int sub = __builtin_amdgcn_readfirstlane(tid_ >> 6);
   const int e = blockIdx.x / A.n_slots, slot = blockIdx.x - e * A.n_slots;
-  const int X = A.X, U = A.U, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y;
+  const int X = A.X, ld_xu = A.ld_xu, ld_h = A.ld_h, ld_y = A.ld_y;
   const int T = 16 * ld_h;
   float *s_xu = smem;                       // [16][ld_xu]  [x, u]
   float *s_t = s_xu + 16 * ld_xu;           // [16][ld_y]   regression target: X state columns, then the reward
@@ -380,42 +411,22 @@ __global__ void __launch_bounds__(256) k_ens_eval(EnsEvalArgs A) {
     const long long j0 = tile * 16;
     WSet<HT, SP> R;
     chain_fwd_prefetch<HT, SP, WIDE>(R, A.sh, params, sub, lane);
-    for (int i2 = tid; i2 < 16 * (X + U); i2 += nthreads) {
-      const int r = i2 & 15, c = i2 >> 4;
-      const long long j = j0 + r;
-      s_xu[r * ld_xu + c] = (j < A.n) ? A.rows[(long long)A.idx[j] * A.D + c] : 0.f;
-    }
-    for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
-      const int r = i2 & 15, c = i2 >> 4;
-      const long long j = j0 + r;
-      float t = 0.f;
-      if (j < A.n) {
-        const float *row = A.rows + (long long)A.idx[j] * A.D;
-        t = row[A.noff + c] - (A.predict_delta ? row[c] : 0.f);
-      }
-      s_t[r * ld_y + c] = t;
-    }
-    if (A.roff >= 0 && tid < 16) {
-      const long long j = j0 + tid;
-      s_t[tid * ld_y + X] = (j < A.n) ? A.rows[(long long)A.idx[j] * A.D + A.roff] : 0.f;
-    }
+    ens_stage_tile(A, A.idx, j0, s_xu, s_t, tid, nthreads);
     __syncthreads();
     chain_fwd_run<HT, SP, WIDE>(A.sh, params, s_xu, ld_xu, s_pp, s_pp + T, nullptr, nullptr, s_y, ld_y, ld_h, L, sub, lane, R);
     for (int i2 = tid; i2 < 16 * X; i2 += nthreads) {
       const int r = i2 & 15, c = i2 >> 4;
       const bool ok = j0 + r < A.n;
-      float nll, se;
-      ens_eval_terms(s_t[r * ld_y + c], s_y[r * ld_y + c], s_y[r * ld_y + X + c], A.min_std, &nll, &se);
-      s_el[r * ld_y + c] = ok ? nll : 0.f;
-      s_el[r * ld_y + X + 1 + c] = ok ? se : 0.f;
+      const NllTerm el = ens_nll_term(s_t[r * ld_y + c], s_y[r * ld_y + c], s_y[r * ld_y + X + c], A.min_std);
+      s_el[r * ld_y + c] = ok ? el.nll : 0.f;
+      s_el[r * ld_y + X + 1 + c] = ok ? el.se : 0.f;
     }
     if (A.roff >= 0 && tid < 16) {
       const int r = tid;
       const bool ok = j0 + r < A.n;
-      float nll, se;
-      ens_eval_terms(s_t[r * ld_y + X], s_y[r * ld_y + 2 * X], s_y[r * ld_y + 2 * X + 1], A.min_std, &nll, &se);
-      s_el[r * ld_y + X] = ok ? nll : 0.f;
-      s_el[r * ld_y + 2 * X + 1] = ok ? se : 0.f;
+      const NllTerm el = ens_nll_term(s_t[r * ld_y + X], s_y[r * ld_y + 2 * X], s_y[r * ld_y + 2 * X + 1], A.min_std);
+      s_el[r * ld_y + X] = ok ? el.nll : 0.f;
+      s_el[r * ld_y + 2 * X + 1] = ok ? el.se : 0.f;
     }
     __syncthreads();
     if (tid < 32) {                          // threads 0..15: the rows' NLL, 16..31: their squared error
@@ -434,8 +445,8 @@ __global__ void __launch_bounds__(256) k_ens_eval(EnsEvalArgs A) {
       }
   }
   if (tid_ == 0) {
-    A.part[(long long)e * A.n_slots + slot] = loss;
-    A.part[((long long)A.E + e) * A.n_slots + slot] = sqe;
+    A.extras[(long long)e * A.n_slots + slot] = loss;
+    A.extras[((long long)A.E + e) * A.n_slots + slot] = sqe;
   }
 }
 
@@ -445,120 +456,67 @@ __global__ void __launch_bounds__(64) k_ens_eval_reduce(const float *part, int n
   if (i < n_out) metrics[i] = slab_sum<16>(part + (long long)i * n_slots, 1, n_slots, 0) / (float)n;
 }
 
-// Layered path's head, one workgroup per member over the shared targets t [n][X + 1]: k_ens_nll_head's loss and summation order
-// (a thread adds its rows b = tid, tid + 256, ... in order, then a fixed tree over the threads), without the output gradient.
-__global__ void __launch_bounds__(256) k_ens_eval_head(const float *y, const float *t, int X, int dout, int roff, int n, int E,
-                                                       float min_std, float *metrics) {
-  __shared__ float s_red[2][256];
-  const int e = blockIdx.x, tid = threadIdx.x;
-  float acc = 0.f, acc2 = 0.f;
-  for (int b = tid; b < n; b += 256) {
-    const float *yr = y + ((long long)e * n + b) * dout, *tr = t + (long long)b * (X + 1);
-    float a = 0.f, a2 = 0.f, nll, se;
-    for (int c = 0; c < X; ++c) {
-      ens_eval_terms(tr[c], yr[c], yr[X + c], min_std, &nll, &se);
-      a += nll;
-      a2 += se;
-    }
-    if (roff >= 0) {
-      ens_eval_terms(tr[X], yr[2 * X], yr[2 * X + 1], min_std, &nll, &se);
-      a += nll;
-      a2 += se;
-    }
-    acc += a;
-    acc2 += a2;
-  }
-  s_red[0][tid] = acc;
-  s_red[1][tid] = acc2;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) {
-      s_red[0][tid] += s_red[0][tid + h];
-      s_red[1][tid] += s_red[1][tid + h];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    metrics[e] = s_red[0][0] / (float)n;
-    metrics[E + e] = s_red[1][0] / (float)n;
-  }
-}
-
-struct EnsEvalPlan {
-  EnsPlan p;
-  size_t lds;                                   // fused
-  long long off_xu, off_t, off_h0, off_h1, off_y;   // layered
-  long long total;
-};
-
-static int ens_eval_plan(const mbpo_ens_eval_desc *d, EnsEvalPlan *pl, bool need_ptrs) {
+static int ens_eval_plan(const mbpo_ens_eval_desc *d, EnsPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "ens_eval: null descriptor");
-  int rc = ens_plan_shape("ens_eval", d->x_dim, d->u_dim, d->dynamics, d->row_len, d->next_obs_off, d->reward_off, d->n, &pl->p);
+  int rc = ens_plan_shape("ens_eval", d->x_dim, d->u_dim, d->dynamics, d->row_len, d->next_obs_off, d->reward_off, d->n, pl);
   if (rc != MBPO_OK) return rc;
-  const EnsPlan &p = pl->p;
-  const int X = d->x_dim, U = d->u_dim, L = p.dyn.n_layers, E = p.dyn.n_nets;
-  if (!p.layered) {
-    pl->lds = sizeof(float) * (16ull * p.ld_xu + 3ull * 16 * p.ld_y + 2ull * 16 * p.ld_h + 32);
-    pl->total = (2LL * E * p.n_slots + 3) & ~3LL;
+  const int X = d->x_dim, U = d->u_dim, L = pl->dyn.n_layers, E = pl->dyn.n_nets;
+  Carve c;
+  if (!pl->layered) {
+    pl->lds = sizeof(float) * (16ull * pl->ld_xu + 3ull * 16 * pl->ld_y + 2ull * 16 * pl->ld_h + 32);
+    c.take(2LL * E * pl->n_slots);
   } else {
-    const LayeredNet net = layered_net(p.dyn, nullptr, p.dyn.n_params, E);
+    const LayeredNet net = layered_net(pl->dyn, nullptr, pl->dyn.n_params, E);
     const long long mh = layered_max_hidden(net);
-    long long off = 0;
-    auto take = [&](long long n) { const long long o = off; off += (n + 3) & ~3LL; return o; };
-    pl->off_xu = take(d->n * (X + U));
-    pl->off_t = take(d->n * (X + 1));
-    pl->off_h0 = take((long long)E * d->n * mh);
-    pl->off_h1 = take((long long)E * d->n * mh);
-    pl->off_y = take((long long)E * d->n * p.dyn.dims[L]);
-    pl->total = off;
+    pl->off_xu = c.take(d->n * (X + U));
+    pl->off_t = c.take(d->n * (X + 1));
+    pl->off_tmp0 = c.take((long long)E * d->n * mh);
+    pl->off_tmp1 = c.take((long long)E * d->n * mh);
+    pl->off_y = c.take((long long)E * d->n * pl->dyn.dims[L]);
   }
+  pl->total = c.off;
   if (need_ptrs)
     MBPO_REQUIRE(d->dynamics.params && d->rows && d->idx && d->metrics && d->workspace, MBPO_ERR_ARG, "ens_eval: null pointer");
   return MBPO_OK;
 }
 
 extern "C" int64_t mbpo_ens_eval_workspace_floats(const mbpo_ens_eval_desc *d) {
-  EnsEvalPlan pl;
+  EnsPlan pl;
   int rc = ens_eval_plan(d, &pl, false);
   if (rc != MBPO_OK) return rc;
   return pl.total;
 }
 
 extern "C" int mbpo_ens_eval(const mbpo_ens_eval_desc *d, void *stream) {
-  EnsEvalPlan pl;
+  EnsPlan pl;
   int rc = ens_eval_plan(d, &pl, true);
   if (rc != MBPO_OK) return rc;
-  const EnsPlan &p = pl.p;
-  const int L = p.dyn.n_layers, E = p.dyn.n_nets, X = d->x_dim, U = d->u_dim;
+  const int L = pl.dyn.n_layers, E = pl.dyn.n_nets, X = d->x_dim, U = d->u_dim;
   hipStream_t st = (hipStream_t)stream;
-  if (p.layered) {
+  if (pl.layered) {
     const int n = (int)d->n;
     float *ws = d->workspace;
     float *xu = ws + pl.off_xu, *t = ws + pl.off_t, *y = ws + pl.off_y;
     float *H[MBPO_MAX_LAYERS + 1];
-    for (int l = 0; l <= MBPO_MAX_LAYERS; ++l) H[l] = ws + ((l & 1) ? pl.off_h1 : pl.off_h0);     // layer l reads H[l], writes H[l + 1]
+    for (int l = 0; l <= MBPO_MAX_LAYERS; ++l) H[l] = ws + ((l & 1) ? pl.off_tmp1 : pl.off_tmp0);     // layer l reads H[l], writes H[l + 1]
     // the members share the rows: one gather (k_ens_gather with a single "member")
     hipLaunchKernelGGL(k_ens_gather, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, st, d->rows, d->idx, d->row_len, X, U,
                        d->next_obs_off, d->reward_off, d->predict_delta, (long long)d->n, xu, t);
     MBPO_CHECK_LAUNCH("ens_eval.gather");
-    const LayeredNet net = layered_net(p.dyn, d->dynamics.params, p.dyn.net_stride, E);
+    const LayeredNet net = layered_net(pl.dyn, d->dynamics.params, pl.dyn.net_stride, E);
     rc = layered_forward(net, xu, 0, n, nullptr, H, y, st);
     if (rc != MBPO_OK) return rc;
-    hipLaunchKernelGGL(k_ens_eval_head, dim3(E), dim3(256), 0, st, (const float *)y, (const float *)t, X, p.dyn.dims[L], d->reward_off, n,
-                       E, d->min_std, d->metrics);
+    hipLaunchKernelGGL(k_ens_head<false>, dim3(E), dim3(256), 0, st, (const float *)y, (const float *)t, 0LL, X, pl.dyn.dims[L],
+                       d->reward_off, n, E, d->min_std, (float *)nullptr, d->metrics);
     MBPO_CHECK_LAUNCH("ens_eval.head");
     return MBPO_OK;
   }
-  EnsEvalArgs A;
-  A.sh = net_shape(p.dyn);
-  A.params = d->dynamics.params; A.net_stride = p.dyn.net_stride; A.E = E;
-  A.X = X; A.U = U; A.D = d->row_len; A.noff = d->next_obs_off; A.roff = d->reward_off;
-  A.rows = d->rows; A.idx = d->idx; A.n = d->n; A.predict_delta = d->predict_delta; A.min_std = d->min_std;
-  A.part = d->workspace;
-  A.n_slots = p.n_slots; A.ld_xu = p.ld_xu; A.ld_h = p.ld_h; A.ld_y = p.ld_y;
-  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_ens_eval<W.value>>(E * p.n_slots, 256, pl.lds, st, "ens_eval", A); });
+  EnsArgs A = ens_args(pl, d->dynamics, X, U, d->rows, d->row_len, d->next_obs_off, d->reward_off, d->idx, d->n, d->predict_delta,
+                       d->min_std);
+  A.extras = d->workspace;
+  rc = mbpo_with_bool(net_is_wide(A.sh), [&](auto W) { return mbpo_launch<k_ens_eval<W.value>>(E * pl.n_slots, 256, pl.lds, st, "ens_eval", A); });
   if (rc != MBPO_OK) return rc;
-  hipLaunchKernelGGL(k_ens_eval_reduce, dim3((2 * E + 63) / 64), dim3(64), 0, st, (const float *)A.part, p.n_slots, 2 * E, (long long)d->n,
+  hipLaunchKernelGGL(k_ens_eval_reduce, dim3((2 * E + 63) / 64), dim3(64), 0, st, (const float *)A.extras, pl.n_slots, 2 * E, (long long)d->n,
                      d->metrics);
   MBPO_CHECK_LAUNCH("ens_eval");
   return MBPO_OK;

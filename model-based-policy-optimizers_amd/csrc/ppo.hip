@@ -753,11 +753,10 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
     pl->lean = false;
     pl->vg_lean = false;
   }
-  long long o = 0;
-  auto take = [&](long long n) { long long at = o; o += (n + 3) & ~3LL; return at; };
-  pl->off_baseline = take(pl->M); pl->off_boot = take(d->batch_size); pl->off_trunc = take(pl->M); pl->off_term = take(pl->M);
-  pl->off_rew = take(pl->M); pl->off_vs = take(pl->M); pl->off_adv = take(pl->M); pl->off_mom = take(4); pl->off_part = take(PPO_MOM_WGS);
-  pl->off_slabs = take((long long)pl->n_slabs * pl->NPV); pl->off_extras = take((long long)pl->n_slabs * 4);
+  Carve c;
+  pl->off_baseline = c.take(pl->M); pl->off_boot = c.take(d->batch_size); pl->off_trunc = c.take(pl->M); pl->off_term = c.take(pl->M);
+  pl->off_rew = c.take(pl->M); pl->off_vs = c.take(pl->M); pl->off_adv = c.take(pl->M); pl->off_mom = c.take(4); pl->off_part = c.take(PPO_MOM_WGS);
+  pl->off_slabs = c.take((long long)pl->n_slabs * pl->NPV); pl->off_extras = c.take((long long)pl->n_slabs * 4);
   {
     // G = 1 while that does not oversubscribe the chip (a tile with a few rows of one trajectory wastes MFMA lanes nobody else wants:
     // the launch is a latency chain per workgroup); beyond 4 workgroups per CU, more trajectories per workgroup
@@ -774,14 +773,14 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
     pl->n_vg = pl->vg_G ? (int)((d->batch_size + pl->vg_G - 1) / pl->vg_G) : 0;
     const long long GT = (long long)pl->vg_G * d->unroll_length;
     pl->lds_vg = pl->lds_values + sizeof(float) * (size_t)(((pl->vg_G * R + 3) & ~3LL) + (n_arr - 1) * ((GT + 3) & ~3LL));
-    pl->off_mompart = take(4LL * (pl->n_vg > 0 ? pl->n_vg : 1));
+    pl->off_mompart = c.take(4LL * (pl->n_vg > 0 ? pl->n_vg : 1));
   }
-  pl->off_disc = take(pl->neq ? pl->M : 0);
+  pl->off_disc = c.take(pl->neq ? pl->M : 0);
   pl->n_ss = (pl->NPV + 63) / 64;
-  pl->off_sspart = take(pl->clip ? pl->n_ss : 0);
-  pl->off_layered = o;
-  if (pl->layered) o += ppo_layered_floats(d, pl->pi, pl->v);
-  pl->total = o;
+  pl->off_sspart = c.take(pl->clip ? pl->n_ss : 0);
+  pl->off_layered = c.off;
+  if (pl->layered) c.off += ppo_layered_floats(d, pl->pi, pl->v);
+  pl->total = c.off;
   if (need_ptrs)
     MBPO_REQUIRE(d->params && d->adam_m && d->adam_v && d->step_count && d->grads && d->workspace && d->metrics, MBPO_ERR_ARG,
                  "ppo: null state pointer");

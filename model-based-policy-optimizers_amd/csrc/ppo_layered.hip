@@ -115,15 +115,6 @@ __global__ void __launch_bounds__(256) k_ppol_heads(HeadArgs A) {
   if (tid < 3) A.extras[4 * blockIdx.x + tid] = s_red[tid][0];
 }
 
-struct Carve {
-  float *base;
-  long long off;
-  float *take(long long n) {
-    float *p = base ? base + off : nullptr;
-    off += (n + 3) & ~3LL;
-    return p;
-  }
-};
 struct Bufs {
   float *x_all, *values, *outp, *dy_pi, *dy_v, *pp[2], *pq[2], *part, *part2, *extras;   // pp/part: policy pass, pq/part2: value pass
   int n_heads;
@@ -132,18 +123,18 @@ struct Bufs {
 long long carve_all(float *base, const mbpo_ppo_desc *d, const LayeredNet &pi, const LayeredNet &v, Bufs *b) {
   Carve c{base, 0};
   const long long M = (long long)d->batch_size * d->unroll_length, R = M + d->batch_size, X = d->x_dim, U = d->u_dim;
-  b->x_all = c.take(R * X); b->values = c.take(R); b->outp = c.take(M * 2 * U); b->dy_pi = c.take(M * 2 * U); b->dy_v = c.take(R);
-  for (int l = 1; l < v.L; ++l) { b->Zv[l] = c.take(R * v.dims[l]); b->Hv[l] = c.take(R * v.dims[l]); }
-  for (int l = 1; l < pi.L; ++l) { b->Zp[l] = c.take(M * pi.dims[l]); b->Hp[l] = c.take(M * pi.dims[l]); }
+  b->x_all = c.ptr(R * X); b->values = c.ptr(R); b->outp = c.ptr(M * 2 * U); b->dy_pi = c.ptr(M * 2 * U); b->dy_v = c.ptr(R);
+  for (int l = 1; l < v.L; ++l) { b->Zv[l] = c.ptr(R * v.dims[l]); b->Hv[l] = c.ptr(R * v.dims[l]); }
+  for (int l = 1; l < pi.L; ++l) { b->Zp[l] = c.ptr(M * pi.dims[l]); b->Hp[l] = c.ptr(M * pi.dims[l]); }
   int mh = layered_max_hidden(pi);
   const int mv = layered_max_hidden(v);
   mh = mv > mh ? mv : mh;
-  b->pp[0] = c.take(M * mh); b->pp[1] = c.take(M * mh);
-  b->pq[0] = c.take(R * mh); b->pq[1] = c.take(R * mh);
-  b->part = c.take(layered_part_floats(pi, (int)M));
-  b->part2 = c.take(layered_part_floats(v, (int)R));
+  b->pp[0] = c.ptr(M * mh); b->pp[1] = c.ptr(M * mh);
+  b->pq[0] = c.ptr(R * mh); b->pq[1] = c.ptr(R * mh);
+  b->part = c.ptr(layered_part_floats(pi, (int)M));
+  b->part2 = c.ptr(layered_part_floats(v, (int)R));
   b->n_heads = (int)((R + 255) / 256);
-  b->extras = c.take(4LL * b->n_heads);
+  b->extras = c.ptr(4LL * b->n_heads);
   return c.off;
 }
 }  // namespace

@@ -180,15 +180,6 @@ __global__ void __launch_bounds__(256) k_sacl_actor_head(ActorHeadArgs A) {
   }
 }
 
-struct Carve {
-  float *base;
-  long long off;
-  float *take(long long n) {
-    float *p = base ? base + off : nullptr;
-    off += (n + 3) & ~3LL;
-    return p;
-  }
-};
 
 struct Bufs {
   float *xo, *xn, *qin_d, *qin_p, *qin_n, *outp, *outn;
@@ -201,25 +192,25 @@ struct Bufs {
 long long carve_all(float *base, const mbpo_sac_desc *d, const LayeredNet &pi, const LayeredNet &q, Bufs *b) {
   Carve c{base, 0};
   const long long B = d->batch_size, X = d->x_dim, U = d->u_dim, XU = X + U;
-  b->xo = c.take(B * X); b->xn = c.take(B * X);
-  b->qin_d = c.take(B * XU); b->qin_p = c.take(B * XU); b->qin_n = c.take(B * XU);
-  b->outp = c.take(B * 2 * U); b->outn = c.take(B * 2 * U);
-  for (int l = 1; l < pi.L; ++l) { b->Zp[l] = c.take(B * pi.dims[l]); b->Hp[l] = c.take(B * pi.dims[l]); }
+  b->xo = c.ptr(B * X); b->xn = c.ptr(B * X);
+  b->qin_d = c.ptr(B * XU); b->qin_p = c.ptr(B * XU); b->qin_n = c.ptr(B * XU);
+  b->outp = c.ptr(B * 2 * U); b->outn = c.ptr(B * 2 * U);
+  for (int l = 1; l < pi.L; ++l) { b->Zp[l] = c.ptr(B * pi.dims[l]); b->Hp[l] = c.ptr(B * pi.dims[l]); }
   for (int l = 1; l < q.L; ++l) {
-    b->Zqd[l] = c.take(2 * B * q.dims[l]); b->Hqd[l] = c.take(2 * B * q.dims[l]); b->Zqp[l] = c.take(2 * B * q.dims[l]);
+    b->Zqd[l] = c.ptr(2 * B * q.dims[l]); b->Hqd[l] = c.ptr(2 * B * q.dims[l]); b->Zqp[l] = c.ptr(2 * B * q.dims[l]);
   }
   int mh = layered_max_hidden(pi);
   const int mq = layered_max_hidden(q);
   mh = mq > mh ? mq : mh;
-  b->pp[0] = c.take(2 * B * mh); b->pp[1] = c.take(2 * B * mh);
-  b->pq[0] = c.take(2 * B * mh); b->pq[1] = c.take(2 * B * mh);
-  b->pr[0] = c.take(2 * B * mh); b->pr[1] = c.take(2 * B * mh);
-  b->qd = c.take(2 * B); b->qp = c.take(2 * B); b->qn = c.take(2 * B);
-  b->lp_alpha = c.take(B); b->lp_next = c.take(B); b->lp_actor = c.take(B); b->eps_actor = c.take(B * U);
-  b->dqd = c.take(2 * B); b->dqp = c.take(2 * B); b->dqin = c.take(2 * B * XU); b->doutp = c.take(B * 2 * U);
+  b->pp[0] = c.ptr(2 * B * mh); b->pp[1] = c.ptr(2 * B * mh);
+  b->pq[0] = c.ptr(2 * B * mh); b->pq[1] = c.ptr(2 * B * mh);
+  b->pr[0] = c.ptr(2 * B * mh); b->pr[1] = c.ptr(2 * B * mh);
+  b->qd = c.ptr(2 * B); b->qp = c.ptr(2 * B); b->qn = c.ptr(2 * B);
+  b->lp_alpha = c.ptr(B); b->lp_next = c.ptr(B); b->lp_actor = c.ptr(B); b->eps_actor = c.ptr(B * U);
+  b->dqd = c.ptr(2 * B); b->dqp = c.ptr(2 * B); b->dqin = c.ptr(2 * B * XU); b->doutp = c.ptr(B * 2 * U);
   const long long pa = layered_part_floats(pi, (int)B), pb = layered_part_floats(q, (int)B);
-  b->part = c.take(pa > pb ? pa : pb);
-  b->part2 = c.take(pb);
+  b->part = c.ptr(pa > pb ? pa : pb);
+  b->part2 = c.ptr(pb);
   return c.off;
 }
 }  // namespace

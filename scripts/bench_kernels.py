@@ -372,7 +372,7 @@ def main():
         xu = rows[idx.long(), :X + U].contiguous()
         t, te = both(lambda: ev(p.params, rows, idx), reps)
         tf, _ = both(lambda: ops.ensemble_mlp_forward(p.params, dyn.spec, xu), reps)
-        out.append(mfma_entry("k_ens_eval + k_ens_eval_reduce" if dyn.dims[1:-1] == [64] * len(hid) else "k_ens_gather + layered forward + k_ens_eval_head",
+        out.append(mfma_entry("k_ens_eval + k_ens_eval_reduce" if dyn.dims[1:-1] == [64] * len(hid) else "k_ens_gather + layered forward + k_ens_head<false>",
                               "mbpo_ens_eval", {"n": n, "x": X, "u": U, "E": E, "member": list(hid), "stored": dyn.dims[1:-1]}, t,
                               n * 2 * E * mlp_macs(dyn.dims_logical), "2*E*M FLOP per row (shared rows), logical shapes",
                               {"eager_us": te * 1e6, "forward_device_us": tf * 1e6, "eval_over_forward": t / tf}))

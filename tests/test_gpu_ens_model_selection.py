@@ -69,6 +69,24 @@ def test_ens_eval_parity(dev, X, U, E, n, hidden, reward):
     assert bool((got[1] >= 0).all())
 
 
+@pytest.mark.parametrize("hidden", [(64, 64, 64), (96, 32)])       # fused with a ragged last tile; layered
+def test_ens_eval_unfitted_reward_head(dev, hidden):
+    """reward_off=None on a [x+u] -> [2x+2] ensemble: the reward head's outputs enter neither metric."""
+    from mbpo import ops
+    X, U, E, n = 4, 1, 3, 70
+    g, dims, params, rows, R = _case_data(X, U, E, hidden, True, seed=len(hidden) + n)
+    idx = torch.randint(0, R, (n,), generator=g)
+    ref32 = sref.eval_metrics(params, dims, E, rows, idx, X, U, True, 1e-3, None)
+    ref64 = sref.eval_metrics(params.double(), dims, E, rows.double(), idx, X, U, True, 1e-3, None)
+    op = ops.EnsembleEval(x_dim=X, u_dim=U, spec=ops.MlpSpec(dims, "swish", E), device=dev)
+    got = op(params.to(dev), rows.to(dev), idx.to(torch.int32).to(dev), reward_off=None).cpu()
+    err = lambda a, b: float(((a.double() - b.double()).abs() / (2e-5 + 2e-5 * b.double().abs())).max())
+    print(f"ens_eval, unfitted reward head {hidden}: kernel vs fp64 {err(got, ref64):.3f}, kernel vs fp32 {err(got, ref32):.3f}, "
+          f"fp32 restatement vs fp64 {err(ref32, ref64):.3f} (units of the tolerance)")
+    np.testing.assert_allclose(got.numpy(), ref32.numpy(), **TOL)
+    np.testing.assert_allclose(got.double().numpy(), ref64.numpy(), **TOL)
+
+
 @pytest.mark.parametrize("X,U,E,B,hidden,reward", [
     (4, 1, 5, 256, (64, 64, 64), False),            # fused
     (4, 1, 3, 70, (64, 64, 64), True),              # fused, reward head
