@@ -6,6 +6,7 @@
                       ->  the policy acts on the TRUE PendulumSystem.
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
+                                     [--real-ratio R]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -14,6 +15,9 @@ through the 5 members of lowest held-out error (fit(holdout_ratio=0.2, n_elites=
 --terminate-speed V: the MODEL system (not the true one) gets a termination function, BoxTermination on |thetadot| <= V: a model episode
 ends where the predicted speed leaves the interval (discount 0, truncation 0, restart from the env's first state).  After every SAC
 epoch the share of the last collection's model transitions that ended this way is printed.
+--real-ratio R: MBPO's mixed minibatches — int(batch_size * R) rows of every SAC minibatch are true transitions from the environment
+buffer, the others model transitions (SACOptimizer(real_ratio=R); MBPO's published runs use 0.05).  0, the default, trains on model
+transitions only.
 """
 from __future__ import annotations
 
@@ -79,7 +83,7 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
 
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None):
+        terminate_speed=None, real_ratio=0.0):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -109,7 +113,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                  episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
                                  lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
                                  max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16, deterministic_eval=True, tau=0.005,
-                                 num_env_steps_between_updates=5)
+                                 num_env_steps_between_updates=5, real_ratio=real_ratio)
         state = optimizer.init(key=seed + 3, true_buffer_state=tbs)
         sp = state.system_params.replace(dynamics_params=dyn_params)
         if learn_reward:
@@ -142,6 +146,8 @@ if __name__ == "__main__":
     ap.add_argument("--elites", action="store_true")
     ap.add_argument("--terminate-speed", type=float, default=None, metavar="V",
                     help="end a MODEL episode where the predicted |thetadot| exceeds V (BoxTermination on the model system only)")
+    ap.add_argument("--real-ratio", type=float, default=0.0, metavar="R",
+                    help="share of true transitions in every SAC minibatch (MBPO's real_ratio; 0 = model transitions only)")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
-        terminate_speed=a.terminate_speed)
+        terminate_speed=a.terminate_speed, real_ratio=a.real_ratio)

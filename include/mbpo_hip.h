@@ -231,6 +231,23 @@ int mbpo_replay_gather(const float *data, int64_t max_size, int32_t row_len, con
  * Fused sample+gather: sac/sac.py:318 (UniformSamplingQueue.sample). */
 int mbpo_replay_sample(const float *data, int64_t max_size, int32_t row_len, const int32_t *state, uint64_t seed,
                        uint64_t offset, const uint64_t *rng_dev, int64_t n, int32_t *idx_out, float *out, void *stream);
+/* MBPO's mixed minibatches (its real_ratio; not in the reference tree, which has no model loop — restated from the MBPO paper's
+ * procedure, unverified against its code): ONE launch fills out [n, row_len], n = minibatch * G rows in the MODEL buffer's layout,
+ * from two rings.  replaces: the mbpo_replay_sample launch of a SAC training step (sac/sac.py:318) when real_ratio > 0.
+ * Row j is position p = j % minibatch of minibatch j / minibatch; real rows come first:
+ *   p <  n_real: idx[j] = randint(real sample_position, real insert_position) from Philox(seed, real_offset, stream=REPLAY, j),
+ *                out[j] = [real_logical[wrap(idx[j])][0 .. real_row_len) | 0.0f ...]   (real_row_len <= row_len: a real transition
+ *                [obs | action | reward | discount | next_obs] shares the model row's column prefix; the rest — truncation — is 0)
+ *   p >= n_real: idx[j] and out[j] are exactly mbpo_replay_sample's at the same j under (seed, offset): same draw, same row.
+ * The element index is j in both draws; positions, head and max_size are each buffer's own.  An empty range (insert_position ==
+ * sample_position) yields idx = sample_position, as mbpo_replay_sample does.  idx_out (may be NULL) receives the LOGICAL index in
+ * whichever buffer served row j.  rng_dev is added to (seed, offset) and to (seed, real_offset).  n == 0 launches nothing.
+ * MBPO_ERR_ARG: a null buffer/state (or out with n > 0), minibatch <= 0, n not a multiple of minibatch, n_real outside
+ * [0, minibatch], real_row_len outside (0, row_len], either max_size outside (0, 2^31 - 1). */
+int mbpo_replay_sample_mixed(const float *data, int64_t max_size, int32_t row_len, const int32_t *state, const float *real_data,
+                             int64_t real_max_size, int32_t real_row_len, const int32_t *real_state, uint64_t seed, uint64_t offset,
+                             uint64_t real_offset, const uint64_t *rng_dev, int64_t n, int32_t minibatch, int32_t n_real,
+                             int32_t *idx_out, float *out, void *stream);
 
 /* perm = stable argsort of key_i = Philox(seed, offset [+ rng_dev], stream PERM, i).word0, i in [0, n): the ONE shared
  * permutation of PPO.sgd_step (ppo/ppo.py:166-171: jr.permutation with the same key for every leaf); gather whole

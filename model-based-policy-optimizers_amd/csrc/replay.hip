@@ -181,6 +181,105 @@ extern "C" int mbpo_replay_sample(const float *data, int64_t max_size, int32_t r
   return MBPO_OK;
 }
 
+// MBPO's mixed minibatches (real_ratio): out is n = minibatch * G rows in the MODEL buffer's layout; inside every minibatch the
+// first n_real positions are drawn from the real (environment) ring, the others from the model ring.  Both draws are
+// k_replay_gather<true>'s — element index j, stream REPLAY, each buffer's own {sample_position, insert_position, head, max} — under
+// two offsets, so a model position gets bit for bit the row mbpo_replay_sample gives it.  The copy keeps that kernel's scheme: one
+// thread per row resolves the source (LDS: the row's physical ELEMENT offset, real rows stored as ~offset, i.e. negative), then the
+// RB rows are copied cooperatively.  A real row has RD <= D floats (no truncation column, usually): columns [RD, D) are written 0.
+// 16-byte pieces under k_replay_gather's condition (D a multiple of 4, out and data aligned); a REAL piece is loaded as 16 bytes
+// only when its own source allows it (RD a multiple of 4 and rdata aligned) — at x=4, u=1 (D=12, RD=11) it is four dword loads.
+__global__ void __launch_bounds__(256) k_replay_sample_mixed(const float *data, int max_size, int D, const int *state,
+                                                              const float *rdata, int rmax_size, int RD, const int *rstate,
+                                                              unsigned long long seed, unsigned long long offset,
+                                                              unsigned long long roffset, const unsigned long long *rng_dev, long long n,
+                                                              int minibatch, int n_real, int *idx_out, float *out, int RB) {
+  __shared__ long long s_src[256];
+  const RngKey rk = rng_resolve(seed, offset, rng_dev);
+  const unsigned long long roff = roffset + (rk.offset - offset);      // rng_resolve(seed, roffset, rng_dev).offset
+  const int head = state[2], lo = state[1], hi = state[0];
+  const int rhead = rstate[2], rlo = rstate[1], rhi = rstate[0];
+  const int tid = threadIdx.x;
+  // (as k_replay_gather: the 16-byte form needs D % 4 == 0 and both out and the model ring aligned; otherwise every row goes as dwords)
+  const bool vec_out = (D & 3) == 0 && ((((unsigned long long)data) | ((unsigned long long)out)) & 15ull) == 0;
+  const bool vec_real = (RD & 3) == 0 && (((unsigned long long)rdata) & 15ull) == 0;
+  for (long long row0 = (long long)blockIdx.x * RB; row0 < n; row0 += (long long)gridDim.x * RB) {
+    const long long j = row0 + tid;
+    if (tid < RB && j < n) {
+      const bool real = (int)(j % minibatch) < n_real;
+      // ONE Philox block per row, keyed and ranged by the buffer that serves it
+      const long long li = philox_randint(rk.seed, real ? roff : rk.offset, MBPO_STREAM_REPLAY, (unsigned long long)j,
+                                          real ? rlo : lo, real ? rhi : hi);
+      if (idx_out) idx_out[j] = (int)li;
+      const long long mx = real ? rmax_size : max_size;
+      long long w = li % mx;
+      if (w < 0) w += mx;
+      const long long el = ((w + (real ? rhead : head)) % mx) * (real ? RD : D);
+      s_src[tid] = real ? ~el : el;
+    }
+    __syncthreads();
+    const int rows_here = (int)((n - row0) < RB ? (n - row0) : RB);
+    if (vec_out) {
+      const int D4 = D >> 2, total = rows_here * D4;
+      f32x4 *dst = reinterpret_cast<f32x4 *>(out) + row0 * D4;
+      for (int e = tid; e < total; e += 256) {
+        const int r = e / D4, c = (e - r * D4) << 2;
+        const long long s = s_src[r];
+        f32x4 v;
+        if (s >= 0) {
+          v = *reinterpret_cast<const f32x4 *>(data + s + c);
+        } else {
+          const float *p = rdata + ~s + c;
+          if (vec_real) {
+            v = c < RD ? *reinterpret_cast<const f32x4 *>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
+          } else {
+            v.x = c < RD ? p[0] : 0.f;
+            v.y = c + 1 < RD ? p[1] : 0.f;
+            v.z = c + 2 < RD ? p[2] : 0.f;
+            v.w = c + 3 < RD ? p[3] : 0.f;
+          }
+        }
+        dst[e] = v;
+      }
+    } else {
+      const int total = rows_here * D;
+      float *dst = out + row0 * D;
+      for (int e = tid; e < total; e += 256) {
+        const int r = e / D, c = e - r * D;
+        const long long s = s_src[r];
+        dst[e] = s >= 0 ? data[s + c] : (c < RD ? rdata[~s + c] : 0.f);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" int mbpo_replay_sample_mixed(const float *data, int64_t max_size, int32_t row_len, const int32_t *state,
+                                        const float *real_data, int64_t real_max_size, int32_t real_row_len,
+                                        const int32_t *real_state, uint64_t seed, uint64_t offset, uint64_t real_offset,
+                                        const uint64_t *rng_dev, int64_t n, int32_t minibatch, int32_t n_real, int32_t *idx_out,
+                                        float *out, void *stream) {
+  MBPO_REQUIRE(data && state && real_data && real_state, MBPO_ERR_ARG, "replay_sample_mixed: null pointer");
+  MBPO_REQUIRE(max_size > 0 && max_size < (1LL << 31) - 1 && real_max_size > 0 && real_max_size < (1LL << 31) - 1, MBPO_ERR_ARG,
+               "replay_sample_mixed: bad max_size (%lld model, %lld real)", (long long)max_size, (long long)real_max_size);
+  MBPO_REQUIRE(row_len > 0 && real_row_len > 0 && real_row_len <= row_len, MBPO_ERR_ARG,
+               "replay_sample_mixed: real_row_len=%d must lie in (0, row_len=%d]", real_row_len, row_len);
+  MBPO_REQUIRE(minibatch > 0 && n >= 0 && n % minibatch == 0, MBPO_ERR_ARG,
+               "replay_sample_mixed: n=%lld is not a whole number of minibatches of %d rows", (long long)n, minibatch);
+  MBPO_REQUIRE(n_real >= 0 && n_real <= minibatch, MBPO_ERR_ARG, "replay_sample_mixed: n_real=%d outside [0, minibatch=%d]", n_real,
+               minibatch);
+  if (n == 0) return MBPO_OK;
+  MBPO_REQUIRE(out, MBPO_ERR_ARG, "replay_sample_mixed: null out");
+  const int RB = gather_rows_per_block(row_len);
+  int grid = (int)((n + RB - 1) / RB < 4096 ? (n + RB - 1) / RB : 4096);
+  hipLaunchKernelGGL(k_replay_sample_mixed, dim3(grid), dim3(256), 0, (hipStream_t)stream, data, (int)max_size, row_len, state,
+                     real_data, (int)real_max_size, real_row_len, real_state, (unsigned long long)seed,
+                     (unsigned long long)offset, (unsigned long long)real_offset, (const unsigned long long *)rng_dev, (long long)n,
+                     minibatch, n_real, idx_out, out, RB);
+  MBPO_CHECK_LAUNCH("replay_sample_mixed");
+  return MBPO_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // running_statistics.update, split into reduce (per-rank sums) and apply.
 // ------------------------------------------------------------------------------------------------

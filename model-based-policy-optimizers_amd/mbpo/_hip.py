@@ -211,6 +211,7 @@ def _bind_optional(lib: C.CDLL) -> None:
         "mbpo_replay_insert": [vp, i64, i32, vp, vp, i64, vp],
         "mbpo_replay_gather": [vp, i64, i32, vp, vp, i64, vp, vp],
         "mbpo_replay_sample": [vp, i64, i32, vp, u64, u64, vp, i64, vp, vp, vp],
+        "mbpo_replay_sample_mixed": [vp, i64, i32, vp, vp, i64, i32, vp, u64, u64, u64, vp, i64, i32, i32, vp, vp, vp],
         "mbpo_running_stats_reduce": [vp, i64, i32, i32, i32, vp, vp, vp, i32, vp],
         "mbpo_running_stats_apply": [vp, vp, i32, f32, f32, vp],
         "mbpo_running_stats_update": [vp, i64, i32, i32, i32, vp, vp, vp, f32, f32, vp],

@@ -503,6 +503,34 @@ def replay_sample(data: torch.Tensor, state: torch.Tensor, n: int, seed: int, of
     return (out, idx) if return_idx else out
 
 
+def replay_sample_mixed(data: torch.Tensor, state: torch.Tensor, real_data: torch.Tensor, real_state: torch.Tensor, n: int,
+                        minibatch: int, n_real: int, seed: int, offset: int, real_offset: int,
+                        out: Optional[torch.Tensor] = None, rng_dev: Optional[torch.Tensor] = None,
+                        idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MBPO's mixed minibatches in one launch: n = minibatch * G rows in `data`'s layout; in every minibatch the first n_real rows
+    are drawn from the real buffer (Philox offset `real_offset`, columns past its row length written 0), the others from `data`
+    exactly as replay_sample draws them at the same row (include/mbpo_hip.h: mbpo_replay_sample_mixed)."""
+    lib = load()
+    _req(data, "data"); _req(state, "state", torch.int32); _req(real_data, "real_data"); _req(real_state, "real_state", torch.int32)
+    if data.dim() != 2 or real_data.dim() != 2:
+        raise ValueError("data and real_data must be [max_size, row_len]")
+    if out is None:
+        out = torch.empty((n, data.shape[1]), device=data.device, dtype=torch.float32)
+    else:
+        _req(out, "out")
+        if out.numel() < n * data.shape[1]:
+            raise ValueError(f"out must hold {n} rows of {data.shape[1]} floats")
+    if idx_out is not None:
+        _req(idx_out, "idx_out", torch.int32)
+        if idx_out.numel() != n:
+            raise ValueError(f"idx_out must have {n} entries")
+    check(lib.mbpo_replay_sample_mixed(data.data_ptr(), data.shape[0], data.shape[1], state.data_ptr(), real_data.data_ptr(),
+                                       real_data.shape[0], real_data.shape[1], real_state.data_ptr(), seed, offset, real_offset,
+                                       rng_ptr(rng_dev), n, minibatch, n_real, ptr(idx_out), out.data_ptr(), current_stream_ptr()),
+          "mbpo_replay_sample_mixed")
+    return out
+
+
 def philox_permutation(n: int, seed: int, offset: int = 0, rng_dev: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Random permutation of range(n) as int32 (PPO.sgd_step's shared shuffle, ppo/ppo.py:166-171): stable argsort of Philox keys."""

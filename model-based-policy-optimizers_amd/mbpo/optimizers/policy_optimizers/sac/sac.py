@@ -5,6 +5,7 @@ Where the reference has                      this file issues
   lax.scan of actor_step (:283-296)      ->  ONE mbpo_model_rollout launch per get_experience
   running_statistics.update (:298-301)   ->  mbpo_running_stats_reduce x2 + _apply (two-pass, psum positions kept)
   replay_buffer.insert / .sample (:303,318) -> mbpo_replay_insert / mbpo_replay_sample (device-resident positions)
+  (MBPO's real_ratio, not in the reference) -> mbpo_replay_sample_mixed in the sample's place when real_ratio > 0
   lax.scan of sgd_step (:324)            ->  G x (mbpo_sac_grads [+ all-reduce] + mbpo_sac_apply)
   jit(training_epoch) (:347-361)         ->  one captured hipGraph of a training_step, replayed per step
 
@@ -36,7 +37,7 @@ from mbpo.utils import keys as K
 Metrics = Dict[str, Any]
 
 # Philox call-site ids (high 32 bits of the offset; the low 32 bits count training steps on the device)
-SITE_ROLLOUT, SITE_SAMPLE, SITE_SGD = 1, 2, 16
+SITE_ROLLOUT, SITE_SAMPLE, SITE_SAMPLE_REAL, SITE_SGD = 1, 2, 3, 16
 
 
 @dataclass
@@ -128,13 +129,25 @@ class SAC:
                  # --- MI355X-side knobs (not in the reference) ---
                  use_graph: bool = True,
                  process_group=None,
+                 real_ratio: float = 0.0,
                  ):
+        """real_ratio: MBPO's share of REAL transitions in every SGD minibatch (0.05 in its published runs; the arithmetic is MBPO's
+        as remembered, unverified against its code — the reference tree has no model loop): the first
+        n_real = int(batch_size * real_ratio) rows of each minibatch are drawn from the environment's true buffer
+        (`environment.sample_buffer`), zero-padded to the model row (truncation = 0), the others from this trainer's buffer of
+        model rollouts — one launch, in place of the plain sample.  0 (the default) issues exactly the plain sample.  The
+        observation normaliser keeps being updated from the model rollouts only (get_experience): MBPO normalises nothing, and
+        mixing does not change which stream feeds the statistics."""
         if min_replay_size >= num_timesteps:
             raise ValueError('No training will happen because min_replay_size >= num_timesteps')     # sac.py:100-102
         if non_equidistant_time and not env_dt > 0:
             raise ValueError("non_equidistant_time needs env_dt > 0 (sac/losses.py:95 floors the switch time to multiples of it)")
         if wandb_logging:
             raise NotImplementedError("wandb is not available in this environment")
+        if not 0.0 <= real_ratio <= 1.0:
+            raise ValueError(f"real_ratio={real_ratio} must lie in [0, 1]")
+        self.real_ratio = float(real_ratio)
+        self.n_real = int(batch_size * real_ratio)
         self.eval_key_fixed = eval_key_fixed
         self.return_best_model = return_best_model
         self.target_entropy = target_entropy
@@ -228,6 +241,8 @@ class SAC:
         self.replay_buffer = UniformSamplingQueue(max_replay_size=max_replay_size, dummy_data_sample=dummy_transition,
                                                   sample_batch_size=batch_size * grad_updates_per_step, device=self.device)
         self.row_len = self.replay_buffer.row_len
+        # real rows (the true buffer's transitions) must be a column prefix of the model rows: checked even when n_real == 0
+        self.replay_buffer.check_mixable(self.env.sample_buffer)
         # fixed device buffers (graph-replayable)
         S, N = num_env_steps_between_updates, num_envs
         self._rollout_rows = torch.empty(S * N, self.row_len, device=self.device)
@@ -334,8 +349,14 @@ class SAC:
             training_state.normalizer_params, training_state.policy_params, env_state, buffer_state)
         training_state = training_state.replace(
             env_steps=training_state.env_steps + self.env_steps_per_actor_step * self.num_env_steps_between_updates)
-        buffer_state, rows = self.replay_buffer.sample_rows(buffer_state, out=self._batch_rows, seed=0,
-                                                            offset=SITE_SAMPLE << 32, rng_dev=self._rng)   # :318
+        if self.n_real == 0:
+            buffer_state, rows = self.replay_buffer.sample_rows(buffer_state, out=self._batch_rows, seed=0,
+                                                                offset=SITE_SAMPLE << 32, rng_dev=self._rng)   # :318
+        else:
+            # MBPO's mixed minibatches: the same launch slot, the model draw unchanged, n_real real rows at the head of each minibatch
+            buffer_state, rows = self.replay_buffer.sample_rows_mixed(
+                buffer_state, self.env.sample_buffer, self.env.sample_buffer_state, self.n_real, self.batch_size,
+                out=self._batch_rows, seed=0, offset=SITE_SAMPLE << 32, real_offset=SITE_SAMPLE_REAL << 32, rng_dev=self._rng)
         B = self.batch_size
         for g in range(self.grad_updates_per_step):                                                # scan :324
             # each step's clip check is resolved by the next step's first launch; the last one by finalize (ops.SacUpdater)
@@ -438,8 +459,9 @@ class SAC:
         TrainingState must re-capture, not replay a graph that updates other tensors)."""
         spec = self.env.system.rollout_spec(env_state.system_params, self.device)
         u = self.updater
+        real = self.env.sample_buffer_state      # read by the mixed sample launch (real_ratio > 0)
         tensors = [env_state.obs, env_state.info['first_obs'], env_state.info['steps'], env_state.done, buffer_state.data,
-                   buffer_state.state, self._rollout_rows, self._batch_rows, self._stats_vec, self._rng,
+                   buffer_state.state, real.data, real.state, self._rollout_rows, self._batch_rows, self._stats_vec, self._rng,
                    training_state.policy_params, training_state.normalizer_params.vec, u.params, u.target_q, u.adam_m, u.adam_v,
                    u.step_count, u.workspace]
         tensors += [v for v in spec.values() if isinstance(v, torch.Tensor)]
@@ -471,6 +493,8 @@ class SAC:
 
     def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
         """sac.py:404-494 — same order of key splits and phases."""
+        if self.n_real > 0 and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
+            raise ValueError(f"real_ratio={self.real_ratio} draws {self.n_real} real rows per minibatch, but the true buffer is empty")
         key, subkey = K.split(key)
         training_state = self.init_training_state(subkey)
         key, rb_key, env_key, eval_key = K.split(key, 4)

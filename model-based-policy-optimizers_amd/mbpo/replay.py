@@ -97,6 +97,37 @@ class UniformSamplingQueue:
                                  rng_dev=rng_dev)
         return bs.replace(key=key, sample_count=bs.sample_count + 1), rows
 
+    def check_mixable(self, real_queue: "UniformSamplingQueue") -> None:
+        """A real row must be a column prefix of this queue's rows: same x_dim / u_dim, no PPO extras on either side (they sit
+        before truncation), and no column this queue lacks."""
+        if (real_queue.x_dim, real_queue.u_dim) != (self.x_dim, self.u_dim):
+            raise ValueError(f"cannot mix rows of a buffer with (x_dim, u_dim) = ({real_queue.x_dim}, {real_queue.u_dim}) into one with "
+                             f"({self.x_dim}, {self.u_dim})")
+        if real_queue.ppo_extras or self.ppo_extras:
+            raise ValueError("cannot mix rows that carry PPO policy extras (log_prob, raw_action)")
+        if real_queue.row_len > self.row_len:
+            raise ValueError(f"real rows of {real_queue.row_len} floats do not fit rows of {self.row_len}")
+
+    def sample_rows_mixed(self, bs: ReplayBufferState, real_queue: "UniformSamplingQueue", real_bs: ReplayBufferState, n_real: int,
+                          minibatch: int, n: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                          rng_dev: Optional[torch.Tensor] = None, seed: Optional[int] = None, offset: int = 0,
+                          real_offset: int = 0, idx_out: Optional[torch.Tensor] = None
+                          ) -> Tuple[ReplayBufferState, torch.Tensor]:
+        """sample_rows with MBPO's real_ratio: n rows in minibatches of `minibatch`, each starting with n_real rows of `real_queue`
+        (zero-padded to this queue's row length) followed by this queue's own draws — one launch (ops.replay_sample_mixed).  Key
+        split and sample_count move as in sample_rows; the real buffer's state object is only read."""
+        n = self.sample_batch_size if n is None else n
+        self.check_mixable(real_queue)
+        if self.size(bs) <= 0:
+            raise ValueError("cannot sample from an empty replay buffer")
+        if n_real > 0 and real_queue.size(real_bs) <= 0:
+            raise ValueError("cannot sample real rows from an empty replay buffer")
+        key, sample_key = K.split(bs.key)
+        rows = ops.replay_sample_mixed(bs.data, bs.state, real_bs.data, real_bs.state, n, minibatch, n_real,
+                                       seed=sample_key if seed is None else seed, offset=offset, real_offset=real_offset, out=out,
+                                       rng_dev=rng_dev, idx_out=idx_out)
+        return bs.replace(key=key, sample_count=bs.sample_count + 1), rows
+
     def logical_data(self, bs: ReplayBufferState) -> torch.Tensor:
         """The reference's `data` array (logical row order), materialised — for checkpoints/tests, not the hot path."""
         idx = (torch.arange(self.max_replay_size, device=bs.data.device) + bs.head) % self.max_replay_size

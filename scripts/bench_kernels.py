@@ -145,12 +145,24 @@ def main():
         out.append(hbm_entry("k_replay_insert", "mbpo_replay_insert", {"max_replay": mx, "rows": n, "D": D}, t, 2 * 48 * n,
                              "48 B read + 48 B write per row (SURVEY counts the 48 B write only)"))
         log(f"insert {n}: {t * 1e6:.1f} us")
-        for (ns, r2) in ([(256, 200)] if n == 20480 else [(1 << 20, 20)]):
+        # (256 x 64 = 16384 rows: the sampling launch of the benchmark's training step, plain and with MBPO's real_ratio)
+        for (ns, r2) in ([(256, 200), (256 * 64, 200)] if n == 20480 else [(1 << 20, 20)]):
             buf = torch.empty(ns, D, device=dev)
             t, te = both(lambda: ops.replay_sample(data, state, ns, 1, 0, out=buf), r2)
             out.append(hbm_entry("k_replay_sample", "mbpo_replay_sample", {"max_replay": mx, "rows": ns, "D": D}, t, 2 * 48 * ns,
                                  "48 B read + 48 B write per sampled row (random rows: 64 B sectors)"))
             log(f"sample {ns}: {t * 1e6:.1f} us")
+            if ns == 256 * 64:
+                mb, n_real, rmx, RD = 256, 12, 100_000, 11
+                rdata = torch.rand(rmx, RD, generator=g).to(dev)
+                rstate = torch.tensor([rmx, 0, 0, rmx], dtype=torch.int32, device=dev)          # a full real ring
+                t, te = both(lambda: ops.replay_sample_mixed(data, state, rdata, rstate, ns, mb, n_real, 1, 0, 1 << 32, out=buf), r2)
+                nb = 48 * ns + (ns // mb) * (n_real * 4 * RD + (mb - n_real) * 48)
+                out.append(hbm_entry("k_replay_sample_mixed", "mbpo_replay_sample_mixed",
+                                     {"max_replay": mx, "real_replay": rmx, "rows": ns, "minibatch": mb, "n_real": n_real, "D": D, "real_D": RD},
+                                     t, nb, "48 B write per row + 48 B (model) or 44 B (real) read"))
+                log(f"sample_mixed {ns} ({n_real} real of every {mb}): {t * 1e6:.1f} us")
+                del rdata
         del data, rows
     # ---------------------------------------------------------------- R8: running statistics (2 passes over x columns)
     for (n, reps) in [(20480, 200), (1 << 22, 10)]:
