@@ -6,7 +6,7 @@
                       ->  the policy acts on the TRUE PendulumSystem.
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
-                                     [--real-ratio R]
+                                     [--real-ratio R] [--normalize-inputs]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -18,6 +18,8 @@ epoch the share of the last collection's model transitions that ended this way i
 --real-ratio R: MBPO's mixed minibatches — int(batch_size * R) rows of every SAC minibatch are true transitions from the environment
 buffer, the others model transitions (SACOptimizer(real_ratio=R); MBPO's published runs use 0.05).  0, the default, trains on model
 transitions only.
+--normalize-inputs: MBPO's input scaler — fit(normalize_inputs=True) standardises the members' inputs [x, u] with the training rows'
+mean / std; the rollouts run the members with the scaler folded into their first layer.
 """
 from __future__ import annotations
 
@@ -83,7 +85,7 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
 
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None, real_ratio=0.0):
+        terminate_speed=None, real_ratio=0.0, normalize_inputs=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -108,7 +110,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         tbs = true_buffer.insert(tbs, Transition(observation=x, action=u, reward=r, discount=torch.ones(n_true, device=dev), next_observation=xn))
         n_rows = true_buffer.size(tbs)
         dyn_params, losses = dyn.fit(dyn_params, true_buffer.logical_data(tbs), num_steps=model_steps, batch_size=256, learning_rate=3e-3,
-                                     key=seed + 10 * it, n_rows=n_rows, **(dict(holdout_ratio=0.2, n_elites=5) if elites else {}))
+                                     key=seed + 10 * it, n_rows=n_rows, normalize_inputs=normalize_inputs,
+                                     **(dict(holdout_ratio=0.2, n_elites=5) if elites else {}))
         optimizer = SACOptimizer(system=model, true_buffer=true_buffer, num_timesteps=sac_steps, num_evals=2, reward_scaling=1,
                                  episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
                                  lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
@@ -148,6 +151,8 @@ if __name__ == "__main__":
                     help="end a MODEL episode where the predicted |thetadot| exceeds V (BoxTermination on the model system only)")
     ap.add_argument("--real-ratio", type=float, default=0.0, metavar="R",
                     help="share of true transitions in every SAC minibatch (MBPO's real_ratio; 0 = model transitions only)")
+    ap.add_argument("--normalize-inputs", action="store_true",
+                    help="standardise the model's inputs with the training rows' mean / std (MBPO's input scaler)")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
-        terminate_speed=a.terminate_speed, real_ratio=a.real_ratio)
+        terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs)

@@ -624,6 +624,47 @@ int mbpo_ens_keep_best(const float *params, float *best_params, int64_t n_params
 int mbpo_ens_pick_elites(const float *params, int64_t n_params, int32_t n_members, const float *score, int32_t n_elites,
                          int32_t *elite_idx, float *elite_params, void *stream);
 
+/* ---- N3c: input scaler of the ensemble (MBPO fits one on the training inputs [x, u]; restated from its procedure, unverified against
+ * its code; the reference has no model).  Only the inputs are scaled, never the targets.  No kernel above changes: training runs
+ * mbpo_ens_nll_grads / mbpo_ens_eval on a matrix prepared once per fit, and every consumer runs on parameters whose first Dense layer
+ * has the scaler folded in — ((v - m) / s) W + b == v (diag(1/s) W) + (b - (diag(1/s) W)^T m).
+ * Rows are selected the same way in both row calls: row k = rows[idx[k]], k < n, or rows[k] with idx == NULL (then n <= n_rows); an
+ * idx entry outside [0, n_rows) is clamped into it.  in_dim = x_dim + u_dim <= 256, else MBPO_ERR_UNSUPPORTED.
+ *
+ * mbpo_ens_scaler_fit: scaler[0][c] = mean_c, scaler[1][c] = std_c of column c < in_dim over the selected rows, two passes in fp64:
+ *   mean_c = (sum_k d_kc) / n;  var_c = (sum_k (d_kc - mean_c)^2) / n  (population variance);  std_c = (float)sqrt(var_c), and
+ *   std_c < std_floor -> exactly 1.0f (a constant column, or n = 1, stays unscaled).
+ * Three launches (partial sums per workgroup, partial squared deviations per workgroup — each workgroup adds the first pass's
+ * partials itself —, one workgroup that finishes).  No atomics; the number of workgroups and each one's rows depend on (n, in_dim)
+ * only and every sum runs in a fixed order, so two calls give the same bits.  workspace: mbpo_ens_scaler_workspace_floats(n, in_dim)
+ * floats (fp64 partials: 8-byte aligned), no device needed for the query.
+ * MBPO_ERR_ARG: a null rows / scaler / workspace, n_rows, row_len or n <= 0, in_dim outside [1, row_len], n > n_rows without idx,
+ * std_floor < 0 (or NaN), a misaligned workspace. */
+int64_t mbpo_ens_scaler_workspace_floats(int64_t n, int32_t in_dim);
+int mbpo_ens_scaler_fit(const float *rows, int64_t n_rows, int32_t row_len, const int32_t *idx, int64_t n, int32_t in_dim,
+                        float std_floor, float *scaler, float *workspace, void *stream);
+/* One launch: out[n][2 x_dim + u_dim + 1], the matrix mbpo_ens_nll_grads / mbpo_ens_eval then read with predict_delta = 0,
+ * reward_off = x_dim + u_dim (or -1) and next_obs_off = x_dim + u_dim + 1:
+ *   out[k][c]               = (row[c] - mean_c) * inv_c,  c < in_dim,  inv_c = 1.0f / std_c (fp32, once per column)
+ *   out[k][in_dim]          = row[reward_off], or 0.0f when reward_off < 0
+ *   out[k][in_dim + 1 + d]  = row[next_obs_off + d] - row[d] when predict_delta, else row[next_obs_off + d]   (raw values), d < x_dim
+ * The output is written 16 bytes per lane when `out` is 16-byte aligned, as dwords otherwise; the source rows are read as dwords.
+ * MBPO_ERR_ARG: as above, and a null scaler / out, x_dim <= 0, u_dim < 0, next_obs_off < 0 or next_obs_off + x_dim > row_len,
+ * reward_off >= row_len. */
+int mbpo_ens_scaler_prepare(const float *rows, int64_t n_rows, int32_t row_len, const int32_t *idx, int64_t n, int32_t x_dim,
+                            int32_t u_dim, int32_t next_obs_off, int32_t reward_off, int32_t predict_delta, const float *scaler,
+                            float *out, void *stream);
+/* One launch: out_params[e] = params[e] with the scaler folded into the first Dense layer, e < n_members (members n_params apart, the
+ * stored — padded — layout: W_0[dims0][dims1] row-major, then b_0[dims1]; dims0 = in_dim):
+ *   W'[i][j] = W[i][j] * inv_i,  inv_i = 1.0f / std_i
+ *   b'[j]    = b[j] - s_j,  s_j = fma(W'[i][j], mean_i, s_j) over i ascending from 0.0f
+ * every other float is a bit copy.  A zero-padded hidden column j (W[.][j] = b[j] = +0) comes out exactly +0.  16-byte accesses when
+ * n_params and dims1 are multiples of 4 and both vectors are 16-byte aligned, dwords otherwise.
+ * MBPO_ERR_ARG: a null pointer, n_members outside [1, 65535], n_params <= 0, a first layer that does not fit n_params, out_params
+ * overlapping params (the bias sum reads the unfolded weights). */
+int mbpo_ens_fold_scaler(const float *params, int64_t n_params, int32_t n_members, int32_t dims0, int32_t dims1, const float *scaler,
+                         float *out_params, void *stream);
+
 /* ---- N4: iCEM trajectory optimizer, device side (trajectory_optimizers/icem_optimizer.py:135-252) ---------------------
  * One iteration = mbpo_icem_sample -> mbpo_model_rollout(actions = the sampled sequences) -> mbpo_icem_update.
  * mbpo_icem_sample: coloured noise (utils/general_utils.py:81-208, powerlaw_psd_gaussian, as a direct inverse real DFT; Philox

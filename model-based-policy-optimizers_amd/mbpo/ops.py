@@ -1373,3 +1373,97 @@ def ens_pick_elites(params: torch.Tensor, n_members: int, score: torch.Tensor, n
     check(lib.mbpo_ens_pick_elites(params.data_ptr(), P, n_members, score.data_ptr(), n_elites, elite_idx.data_ptr(),
                                    elite_params.data_ptr(), current_stream_ptr()), "mbpo_ens_pick_elites")
     return elite_idx, elite_params
+
+
+# ---- input scaler of the dynamics ensemble (N3c; csrc/ens_scaler.hip) -------------------------------------------------------
+SCALER_STD_FLOOR = 1e-12
+
+
+def prepared_row_len(x_dim: int, u_dim: int) -> int:
+    """Row length of ens_scaler_prepare's matrix: [normalised x, u | reward | target]."""
+    return 2 * x_dim + u_dim + 1
+
+
+def prepared_reward_off(x_dim: int, u_dim: int) -> int:
+    return x_dim + u_dim
+
+
+def prepared_next_obs_off(x_dim: int, u_dim: int) -> int:
+    return x_dim + u_dim + 1
+
+
+def _scaler_rows(rows: torch.Tensor, idx: Optional[torch.Tensor], n: Optional[int]) -> int:
+    _req(rows, "rows")
+    if rows.dim() != 2:
+        raise ValueError("rows must be [R, D]")
+    if idx is not None:
+        _req(idx, "idx", torch.int32)
+        if idx.dim() != 1:
+            raise ValueError("idx must be [n]")
+        if n is not None and n != idx.numel():
+            raise ValueError("n must be idx's length (or None)")
+        return int(idx.numel())
+    return int(rows.shape[0] if n is None else n)
+
+
+def ens_scaler_fit(rows: torch.Tensor, in_dim: int, idx: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                   std_floor: float = SCALER_STD_FLOOR, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_ens_scaler_fit: scaler [2, in_dim] = per-column (mean; std) of rows[idx[k]][:in_dim], k < n (idx None: rows[:n], n None:
+    every row); fp64 two-pass, population variance, std below std_floor -> exactly 1.  Deterministic."""
+    lib = load()
+    n = _scaler_rows(rows, idx, n)
+    if out is None:
+        out = torch.empty(2, in_dim, device=rows.device, dtype=torch.float32)
+    _req(out, "out")
+    if out.numel() != 2 * in_dim:
+        raise ValueError("out must be [2, in_dim]")
+    nws = lib.mbpo_ens_scaler_workspace_floats(n, in_dim)
+    if nws < 0:
+        check(int(nws), "mbpo_ens_scaler_workspace_floats")
+    workspace = torch.empty(int(nws), device=rows.device, dtype=torch.float32)
+    check(lib.mbpo_ens_scaler_fit(rows.data_ptr(), rows.shape[0], rows.shape[1], ptr(idx), n, in_dim, std_floor, out.data_ptr(),
+                                  workspace.data_ptr(), current_stream_ptr()), "mbpo_ens_scaler_fit")
+    return out
+
+
+def ens_scaler_prepare(rows: torch.Tensor, scaler: torch.Tensor, x_dim: int, u_dim: int, idx: Optional[torch.Tensor] = None,
+                       n: Optional[int] = None, next_obs_off: Optional[int] = None, reward_off: Optional[int] = None,
+                       predict_delta: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_ens_scaler_prepare: [n, 2x+u+1] rows [ (x,u - mean) * (1/std) | reward (0 without reward_off) | target ], target =
+    next_obs - x when predict_delta else next_obs — what EnsembleNllGrad / EnsembleEval read with predict_delta=False,
+    reward_off=prepared_reward_off (or None) and next_obs_off=prepared_next_obs_off."""
+    lib = load()
+    n = _scaler_rows(rows, idx, n)
+    _req(scaler, "scaler")
+    if scaler.numel() != 2 * (x_dim + u_dim):
+        raise ValueError("scaler must be [2, x_dim + u_dim]")
+    if out is None:
+        out = torch.empty(n, prepared_row_len(x_dim, u_dim), device=rows.device, dtype=torch.float32)
+    _req(out, "out")
+    if out.numel() != n * prepared_row_len(x_dim, u_dim):
+        raise ValueError("out must be [n, 2 * x_dim + u_dim + 1]")
+    check(lib.mbpo_ens_scaler_prepare(rows.data_ptr(), rows.shape[0], rows.shape[1], ptr(idx), n, x_dim, u_dim,
+                                      x_dim + u_dim + 2 if next_obs_off is None else int(next_obs_off),
+                                      -1 if reward_off is None else int(reward_off), int(bool(predict_delta)), scaler.data_ptr(),
+                                      out.data_ptr(), current_stream_ptr()), "mbpo_ens_scaler_prepare")
+    return out
+
+
+def ens_fold_scaler(params: torch.Tensor, n_members: int, dims0: int, dims1: int, scaler: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_ens_fold_scaler: the members' parameters with the scaler folded into the first Dense layer (W' = diag(1/std) W,
+    b' = b - W'^T mean), everything else a bit copy.  `out` must not overlap `params`."""
+    lib = load()
+    _req(params, "params"); _req(scaler, "scaler")
+    if n_members <= 0 or params.numel() % n_members:
+        raise ValueError("params must hold n_members equal members")
+    if scaler.numel() != 2 * dims0:
+        raise ValueError("scaler must be [2, dims0]")
+    if out is None:
+        out = torch.empty_like(params)
+    _req(out, "out")
+    if out.numel() != params.numel():
+        raise ValueError("out must have params' size")
+    check(lib.mbpo_ens_fold_scaler(params.data_ptr(), params.numel() // n_members, n_members, dims0, dims1, scaler.data_ptr(),
+                                   out.data_ptr(), current_stream_ptr()), "mbpo_ens_fold_scaler")
+    return out

@@ -23,6 +23,12 @@ holds rows out, evaluates every member on them once per epoch (mbpo_ens_eval), k
 of lowest held-out squared error (mbpo_ens_pick_elites).  EnsembleDynamicsParams.elite_params, when set, is what every rollout
 consumer runs: the kernels see an ensemble of n_elites members, so 'mean' averages the elites, 'ts1' draws among them and 'tsinf'
 binds env i to elite i % n_elites.
+
+Input scaler (MBPO's, fitted on the training inputs; only the inputs are scaled): `fit(normalize_inputs=True)` fits per-column mean / std
+of [x, u] on the training rows (mbpo_ens_scaler_fit), trains on a matrix prepared once — inputs normalised, target encoded
+(mbpo_ens_scaler_prepare) — and leaves EnsembleDynamicsParams.params in NORMALISED coordinates.  Consumers never normalise: they run
+folded_params, the same members with the scaler folded into the first Dense layer (mbpo_ens_fold_scaler; W' = diag(1/std) W,
+b' = b - W'^T mean), on raw inputs — the same affine map, so no rollout, planning or BPTT kernel knows about the scaler.
 """
 from __future__ import annotations
 
@@ -50,11 +56,18 @@ FIT_SITE_HOLDOUT = 1            # high word of the Philox offset of fit's holdou
 class EnsembleDynamicsParams:
     """elite_params is a COPY of the elite members' parameters (in elite_idx order), taken when they were selected: a later `fit`
     without re-selection leaves it stale (the rollouts then still run the old elites); `fit(..., n_elites=)` always refreshes it, and
-    `select_elites` does on request.  Set both elite fields to None to roll out through all members again."""
+    `select_elites` does on request.  Set both elite fields to None to roll out through all members again.
+
+    scaler, when set, says that `params` live in normalised input coordinates (they are what `fit` trains and `evaluate` scores) and
+    that every consumer runs folded_params instead: a COPY of params with the scaler folded into layer one, taken at the end of
+    `fit(normalize_inputs=True)` and by `select_elites` / `EnsembleDynamics.fold`.  Changing params or scaler by hand leaves it stale
+    until `fold` is called; elite_params of a scaler-bearing object are picked from folded_params and go stale the same way."""
     params: torch.Tensor          # flat [E * P] device tensor (layout: include/mbpo_hip.h)
     elite_idx: Optional[torch.Tensor] = None       # int32 [n_elites]: the members the rollouts use, best first
     elite_params: Optional[torch.Tensor] = None    # [n_elites * P]
     holdout: Optional[torch.Tensor] = None         # [2, E]: held-out (NLL, squared error) of the members fit(holdout_ratio=) kept
+    scaler: Optional[torch.Tensor] = None          # [2, x+u]: (mean; std) of the training inputs, fit(normalize_inputs=True)
+    folded_params: Optional[torch.Tensor] = None   # [E * P]: params with the scaler folded into layer one (what consumers run)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -122,7 +135,8 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             learning_rate: float = 1e-3, weight_decay: float = 0.0, key: int = 0, predict_delta: bool = True,
             min_std: float = 1e-3, n_rows: Optional[int] = None, next_obs_off: Optional[int] = None,
             reward_off: Optional[int] = None, holdout_ratio: float = 0.0, max_holdout: int = 5000, eval_every: Optional[int] = None,
-            max_evals_since_improvement: int = 5, rel_tol: float = 0.01, n_elites: Optional[int] = None):
+            max_evals_since_improvement: int = 5, rel_tol: float = 0.01, n_elites: Optional[int] = None,
+            normalize_inputs: bool = False, scaler_std_floor: float = ops.SCALER_STD_FLOOR):
         """Model learning (N3 — not in the reference, whose model would come from `bsm`): `num_steps` AdamW steps on the
         members' Gaussian negative log-likelihood, each member on its own bootstrapped minibatch (sampling with replacement
         from rows[:n_rows]; Philox randint on the device).  `rows` are true-buffer transition rows (obs, action, reward,
@@ -135,8 +149,17 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         each member whose squared error improved by the relative margin `rel_tol` is snapshotted; the fit stops when no member improved
         for more than `max_evals_since_improvement` evaluations, or at `num_steps` (then after one last evaluation).  The snapshots are
         copied back into dynamics_params.params in place; dynamics_params.holdout = their held-out [NLL; squared error] ([2, E]).
-        n_elites: dynamics_params.elite_idx / elite_params = the n_elites members of lowest held-out squared error."""
+        n_elites: dynamics_params.elite_idx / elite_params = the n_elites members of lowest held-out squared error.
+
+        normalize_inputs (MBPO's input scaler): the per-column mean / std of [x, u] are fitted on the TRAINING rows (after the holdout
+        split; a std below scaler_std_floor counts as 1) and the training and holdout rows are prepared once — inputs normalised,
+        target delta-encoded as `predict_delta` says, columns [x, u | reward | target] — so the steps above run unchanged on the
+        prepared matrices and the scaler costs nothing per step.  dynamics_params.params are then in normalised coordinates;
+        dynamics_params.scaler = the scaler and dynamics_params.folded_params = the members every consumer runs on raw inputs (`fold`);
+        the elites are picked from folded_params.  A refit refits the scaler on the new rows and continues from the same weights."""
         dev = self.device
+        if dynamics_params.scaler is not None and not normalize_inputs:
+            raise ValueError("these parameters were fitted on normalised inputs (scaler is set): refit with normalize_inputs=True")
         if reward_off is not None and not self.learn_reward:
             raise ValueError("reward_off needs EnsembleDynamics(learn_reward=True)")
         if self.learn_reward and reward_off is None:
@@ -150,19 +173,38 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         E = self.n_members
         seed = K.PRNGKey(key)
         train, hold_idx = rows, None
+        # what the NLL / eval kernels are told: the caller's row layout, or the prepared one (target already encoded)
+        X, U = self.x_dim, self.u_dim
+        k_delta, k_next, k_rew, hold_rows, scaler = predict_delta, next_obs_off, reward_off, rows, None
+        if normalize_inputs:
+            k_delta, k_next = False, ops.prepared_next_obs_off(X, U)
+            k_rew = ops.prepared_reward_off(X, U) if self.learn_reward else None
         if holdout_ratio > 0:
             n_hold = min(int(max_holdout), int(math.floor(holdout_ratio * R)))
             if n_hold <= 0 or n_hold >= R:
                 raise ValueError(f"holdout_ratio {holdout_ratio} of {R} rows leaves an empty holdout or training set")
             perm = ops.philox_permutation(R, seed=seed, offset=FIT_SITE_HOLDOUT << 32)
             hold_idx = perm[:n_hold]
-            train = ops.replay_gather(rows, torch.tensor([R, 0, 0, R], device=dev, dtype=torch.int32), perm[n_hold:])
+            if normalize_inputs:
+                train_idx = perm[n_hold:].contiguous()
+                scaler = ops.ens_scaler_fit(rows, X + U, idx=train_idx, std_floor=scaler_std_floor)
+                train = ops.ens_scaler_prepare(rows, scaler, X, U, idx=train_idx, next_obs_off=next_obs_off, reward_off=reward_off,
+                                               predict_delta=predict_delta)
+                hold_rows = ops.ens_scaler_prepare(rows, scaler, X, U, idx=hold_idx.contiguous(), next_obs_off=next_obs_off,
+                                                   reward_off=reward_off, predict_delta=predict_delta)
+                hold_idx = torch.arange(n_hold, device=dev, dtype=torch.int32)
+            else:
+                train = ops.replay_gather(rows, torch.tensor([R, 0, 0, R], device=dev, dtype=torch.int32), perm[n_hold:])
             R = R - n_hold
-        if getattr(self, "_fit_cfg", None) != (batch_size, predict_delta, min_std, learning_rate, weight_decay):
+        elif normalize_inputs:
+            scaler = ops.ens_scaler_fit(rows, X + U, n=R, std_floor=scaler_std_floor)
+            train = ops.ens_scaler_prepare(rows, scaler, X, U, n=R, next_obs_off=next_obs_off, reward_off=reward_off,
+                                           predict_delta=predict_delta)
+        if getattr(self, "_fit_cfg", None) != (batch_size, k_delta, min_std, learning_rate, weight_decay):
             self._nll = ops.EnsembleNllGrad(x_dim=self.x_dim, u_dim=self.u_dim, spec=self.spec, batch=batch_size, device=dev,
-                                            predict_delta=predict_delta, min_std=min_std)
+                                            predict_delta=k_delta, min_std=min_std)
             self._opt = ops.AdamW(E * self.spec.n_params, dev, learning_rate, weight_decay, apply_if_finite=True)
-            self._fit_cfg = (batch_size, predict_delta, min_std, learning_rate, weight_decay)
+            self._fit_cfg = (batch_size, k_delta, min_std, learning_rate, weight_decay)
             self._fit_state = torch.tensor([R, 0, 0, R], device=dev, dtype=torch.int32)
             self._fit_idx = torch.zeros(E * batch_size, device=dev, dtype=torch.int32)
             self._fit_scratch = torch.zeros(E * batch_size, 1, device=dev, dtype=torch.float32)
@@ -174,21 +216,20 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             every = int(eval_every) if eval_every is not None else -(-R // batch_size)
             if every <= 0:
                 raise ValueError("eval_every must be positive")
-            ev = self._evaluator(predict_delta, min_std)
+            ev = self._evaluator(k_delta, min_std)
             best_params = dynamics_params.params.clone()
             best_score = torch.full((E,), float("inf"), device=dev, dtype=torch.float32)
             sel_state = torch.zeros(2, device=dev, dtype=torch.int32)
             sel_ws = torch.zeros(E, device=dev, dtype=torch.int32)
 
             def evaluate_and_keep() -> int:
-                m = ev(dynamics_params.params, rows, hold_idx, next_obs_off=next_obs_off, reward_off=reward_off)
+                m = ev(dynamics_params.params, hold_rows, hold_idx, next_obs_off=k_next, reward_off=k_rew)
                 ops.ens_keep_best(dynamics_params.params, best_params, E, m[1], best_score, rel_tol, sel_state, sel_ws)
                 return int(sel_state[0])         # the epoch's one read-back: evaluations since any member improved
         steps_run, evaluated_at = num_steps, -1
         for it in range(num_steps):
             ops.replay_sample(col0, self._fit_state, E * batch_size, seed=seed, offset=it, out=self._fit_scratch, idx_out=self._fit_idx)
-            g = self._nll(dynamics_params.params, train, self._fit_idx.view(E, batch_size), next_obs_off=next_obs_off,
-                          reward_off=reward_off)
+            g = self._nll(dynamics_params.params, train, self._fit_idx.view(E, batch_size), next_obs_off=k_next, reward_off=k_rew)
             self._opt.step(dynamics_params.params, g)
             losses[it].copy_(self._nll.metrics)
             if hold_idx is not None and (it + 1) % every == 0:
@@ -197,17 +238,45 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
                     steps_run = it + 1
                     break
         if hold_idx is None:
+            if scaler is not None:
+                dynamics_params.scaler = scaler
+                self.fold(dynamics_params)
             return dynamics_params, losses
         if steps_run == num_steps and evaluated_at != num_steps:
             evaluate_and_keep()                  # num_steps ended the fit: the last steps can still be snapshotted
         dynamics_params.params.copy_(best_params)
         # the snapshots' metrics: their squared error as it was scored, their NLL from one more evaluation of the restored parameters
-        holdout = ev(dynamics_params.params, rows, hold_idx, next_obs_off=next_obs_off, reward_off=reward_off).clone()
+        holdout = ev(dynamics_params.params, hold_rows, hold_idx, next_obs_off=k_next, reward_off=k_rew).clone()
         holdout[1].copy_(best_score)
         dynamics_params.holdout = holdout
+        members = dynamics_params.params
+        if scaler is not None:
+            dynamics_params.scaler = scaler
+            members = self.fold(dynamics_params).folded_params
         if n_elites is not None:
-            dynamics_params.elite_idx, dynamics_params.elite_params = ops.ens_pick_elites(dynamics_params.params, E, holdout[1], n_elites)
+            dynamics_params.elite_idx, dynamics_params.elite_params = ops.ens_pick_elites(members, E, holdout[1], n_elites)
         return dynamics_params, losses[:steps_run]
+
+    def fold(self, dynamics_params: EnsembleDynamicsParams) -> EnsembleDynamicsParams:
+        """Refresh dynamics_params.folded_params from its params and scaler (mbpo_ens_fold_scaler, in place when the buffer exists);
+        without a scaler folded_params is cleared.  Returns dynamics_params."""
+        if dynamics_params.scaler is None:
+            dynamics_params.folded_params = None
+            return dynamics_params
+        out = dynamics_params.folded_params
+        if out is not None and out.shape != dynamics_params.params.shape:
+            out = None
+        dynamics_params.folded_params = ops.ens_fold_scaler(dynamics_params.params, self.n_members, self.dims[0], self.dims[1],
+                                                            dynamics_params.scaler.to(self.device, torch.float32).contiguous(), out=out)
+        return dynamics_params
+
+    def _consumer_params(self, dynamics_params: EnsembleDynamicsParams) -> torch.Tensor:
+        """All members as a consumer of raw inputs must see them: folded when a scaler is set (folded on first use if nobody has)."""
+        if dynamics_params.scaler is None:
+            return dynamics_params.params
+        if dynamics_params.folded_params is None:
+            self.fold(dynamics_params)
+        return dynamics_params.folded_params
 
     def _evaluator(self, predict_delta: bool, min_std: float) -> "ops.EnsembleEval":
         if getattr(self, "_eval_cfg", None) != (predict_delta, min_std):
@@ -221,7 +290,8 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
                  min_std: float = 1e-3) -> torch.Tensor:
         """[2, E]: every member's mean Gaussian NLL (row 0, `fit`'s loss) and mean squared error of its mean prediction (row 1, MBPO's
         selection metric) on rows[idx] (idx int32, shared by the members; None: all rows) — mbpo_ens_eval, forward only.  reward_off
-        defaults as in `fit`."""
+        defaults as in `fit`.  With a scaler, rows[idx] are prepared with it first (as `fit` prepares its holdout) and the stored
+        params — normalised coordinates — are evaluated on them: the figures `fit` reports for the same rows."""
         if reward_off is not None and not self.learn_reward:
             raise ValueError("reward_off needs EnsembleDynamics(learn_reward=True)")
         if self.learn_reward and reward_off is None:
@@ -230,14 +300,23 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         if idx is None:
             idx = torch.arange(rows.shape[0], device=self.device, dtype=torch.int32)
         idx = idx.to(self.device, torch.int32).contiguous()
+        if dynamics_params.scaler is not None:
+            X, U = self.x_dim, self.u_dim
+            rows = ops.ens_scaler_prepare(rows, dynamics_params.scaler, X, U, idx=idx, next_obs_off=next_obs_off, reward_off=reward_off,
+                                          predict_delta=predict_delta)
+            idx = torch.arange(rows.shape[0], device=self.device, dtype=torch.int32)
+            predict_delta, next_obs_off = False, ops.prepared_next_obs_off(X, U)
+            reward_off = ops.prepared_reward_off(X, U) if self.learn_reward else None
         return self._evaluator(predict_delta, min_std)(dynamics_params.params, rows, idx, next_obs_off=next_obs_off,
                                                        reward_off=reward_off).clone()
 
     def select_elites(self, dynamics_params: EnsembleDynamicsParams, score: torch.Tensor, n_elites: int) -> EnsembleDynamicsParams:
         """The n_elites members of lowest `score` ([E]; NaN last, ties by lower index) become the members every rollout consumer runs:
-        returns the params with elite_idx / elite_params set (mbpo_ens_pick_elites; elite_params is a copy, see EnsembleDynamicsParams)."""
+        returns the params with elite_idx / elite_params set (mbpo_ens_pick_elites; elite_params is a copy, see EnsembleDynamicsParams).
+        With a scaler the fold is refreshed first and the elites are copies of folded_params."""
         score = score.to(self.device, torch.float32).contiguous()
-        elite_idx, elite_params = ops.ens_pick_elites(dynamics_params.params, self.n_members, score, int(n_elites))
+        members = self._consumer_params(self.fold(dynamics_params))
+        elite_idx, elite_params = ops.ens_pick_elites(members, self.n_members, score, int(n_elites))
         return dynamics_params.replace(elite_idx=elite_idx, elite_params=elite_params)
 
     def elite_spec(self, n_elites: int) -> "ops.MlpSpec":
@@ -248,17 +327,18 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         return cache[n_elites]
 
     def _rollout_members(self, dynamics_params: EnsembleDynamicsParams):
-        """(params, spec) of the members the rollouts use: the elites when selected, else all."""
+        """(params, spec) of the members the rollouts use: the elites when selected, else all — with a scaler, the folded members."""
         if dynamics_params.elite_params is None:
-            return dynamics_params.params, self.spec
+            return self._consumer_params(dynamics_params), self.spec
         return dynamics_params.elite_params, self.elite_spec(int(dynamics_params.elite_idx.numel()))
 
     def member_outputs(self, x: torch.Tensor, u: torch.Tensor, dynamics_params: EnsembleDynamicsParams,
                        elites: bool = False) -> torch.Tensor:
         """[E, N, 2*x_dim] raw member outputs (+ [mu_r, raw_r] with learn_reward) — mbpo_ensemble_mlp_forward.  All members, also
-        when elites are selected; elites=True: the members the rollouts use ([n_elites, N, ...] when selected)."""
+        when elites are selected; elites=True: the members the rollouts use ([n_elites, N, ...] when selected).  x, u are RAW: with a
+        scaler the folded members run."""
         xu = torch.cat([x.reshape(-1, self.x_dim), u.reshape(-1, self.u_dim)], dim=1).to(self.device, torch.float32).contiguous()
-        params, spec = self._rollout_members(dynamics_params) if elites else (dynamics_params.params, self.spec)
+        params, spec = self._rollout_members(dynamics_params) if elites else (self._consumer_params(dynamics_params), self.spec)
         return ops.ensemble_mlp_forward(params, spec, xu)
 
     def next_state(self, x, u, dynamics_params, predict_delta: bool = True, min_std: float = 1e-3):

@@ -393,6 +393,82 @@ def main():
     if want("ens_eval_case"): attempt(ens_eval_case, 4, 1, 7, (64, 64, 64), 5000, 100)
     if want("ens_eval_case"): attempt(ens_eval_case, 4, 1, 7, (200, 200, 200, 200), 5000, 50)
 
+    # ---------------------------------------------------------------- N3c: the ensemble's input scaler (three one-shot calls per fit)
+    # Statistics and prepare on 100 000 true-buffer rows of 12 floats, next to mbpo_replay_gather of the same rows (the launch
+    # prepare replaces in fit); the fold of 7 members next to mbpo_ens_pick_elites copying the same 7 members.  All HBM / latency bound.
+    def ens_scaler_case(n, reps):
+        X, U, D = 4, 1, 12
+        rows = torch.randn(n, D, generator=g).to(dev)
+        perm = torch.randperm(n, generator=g).to(torch.int32).to(dev)
+        state = torch.tensor([n, 0, 0, n], device=dev, dtype=torch.int32)
+        scaler = torch.empty(2, X + U, device=dev)
+        L = ops.prepared_row_len(X, U)
+        prep, gath = torch.empty(n, L, device=dev), torch.empty(n, D, device=dev)
+        for tag, idx in (("rows in order", None), ("permuted rows", perm)):
+            cfg = {"rows": n, "row_len": D, "x": X, "u": U, "selection": tag, "group": "ens_scaler"}
+            t, te = both(lambda: ops.ens_scaler_fit(rows, X + U, idx=idx, out=scaler), reps)
+            out.append(hbm_entry("k_ens_scaler_partial<0> + <1> + k_ens_scaler_finish", "mbpo_ens_scaler_fit", cfg, t, 2 * 4 * (X + U) * n,
+                                 "2 passes x 4(x+u) B per row (rows are 48 B apart: sectors fetch more)"))
+            log(f"scaler fit {n} ({tag}): {t * 1e6:.1f} us (eager {te * 1e6:.1f} us; 3 launches)")
+            t, te = both(lambda: ops.ens_scaler_prepare(rows, scaler, X, U, idx=idx, next_obs_off=X + U + 2, predict_delta=True, out=prep), reps)
+            out.append(hbm_entry("k_ens_scaler_prepare", "mbpo_ens_scaler_prepare", cfg, t, (4 * D + 4 * L) * n,
+                                 f"{4 * D} B row read + {4 * L} B written per row"))
+            log(f"scaler prepare {n} ({tag}): {t * 1e6:.1f} us (eager {te * 1e6:.1f} us)")
+        t, te = both(lambda: ops.replay_gather(rows, state, perm, out=gath), reps)
+        out.append(hbm_entry("k_replay_gather", "mbpo_replay_gather", {"rows": n, "row_len": D, "selection": "permuted rows", "group": "ens_scaler"},
+                             t, 2 * 4 * D * n, "48 B read + 48 B write per row (the comparison for prepare)"))
+        log(f"replay_gather {n} (permuted rows): {t * 1e6:.1f} us")
+
+    def ens_fold_case(E, hid, reps):
+        from mbpo.systems import EnsembleDynamics
+        X, U = 4, 1
+        dyn = EnsembleDynamics(X, U, n_members=E, hidden_layer_sizes=hid, device=dev)
+        p = dyn.init_params(0)
+        scaler = torch.stack([torch.randn(X + U, generator=g), torch.rand(X + U, generator=g) + 0.5]).to(dev)
+        folded, copy = torch.empty_like(p.params), torch.empty_like(p.params)
+        score, eidx = torch.rand(E, generator=g).to(dev), torch.empty(E, device=dev, dtype=torch.int32)
+        cfg = {"E": E, "member": list(hid), "stored": dyn.dims[1:-1], "params_per_member": dyn.spec.n_params, "group": "ens_scaler"}
+        t, te = both(lambda: ops.ens_fold_scaler(p.params, E, dyn.dims[0], dyn.dims[1], scaler, out=folded), reps)
+        out.append(hbm_entry("k_ens_fold_scaler", "mbpo_ens_fold_scaler", cfg, t, 8 * p.params.numel(), "4 B read + 4 B written per parameter"))
+        t2, _ = both(lambda: ops.ens_pick_elites(p.params, E, score, E, elite_idx=eidx, elite_params=copy), reps)
+        out.append(hbm_entry("k_ens_rank + k_ens_member_copy", "mbpo_ens_pick_elites", dict(cfg, n_elites=E), t2, 8 * p.params.numel(),
+                             "4 B read + 4 B written per parameter (the comparison for the fold; two launches)"))
+        log(f"fold E={E} {hid}: {t * 1e6:.1f} us (eager {te * 1e6:.1f} us); pick_elites copying the same members {t2 * 1e6:.1f} us")
+
+    # Evidence, not a test: Pendulum transitions with the speed in other units (* 1000 + 500, state and next state alike), 4000
+    # training and 1000 held-out rows, 5 members, 500 steps, same seeds; held-out squared error of the ensemble-mean prediction in
+    # target units, with and without normalize_inputs.
+    def ens_scaler_mse_case(steps):
+        from mbpo.systems import EnsembleDynamics, PendulumSystem
+        system = PendulumSystem()
+        n = 5000
+        th = (torch.rand(n, generator=g) * 2 - 1) * math.pi
+        x = torch.stack([torch.cos(th), torch.sin(th), (torch.rand(n, generator=g) * 2 - 1) * 8], 1).to(dev)
+        u = (torch.rand(n, 1, generator=g) * 2 - 1).to(dev)
+        nxt = system.step(x, u, system.reset().system_params)
+        rows = torch.cat([x, u, nxt.reward[:, None], torch.ones(n, 1, device=dev), nxt.x_next], 1)
+        rows[:, 2] = rows[:, 2] * 1000 + 500
+        rows[:, 8] = rows[:, 8] * 1000 + 500
+        train, held = rows[:4000].contiguous(), rows[4000:].contiguous()
+        res = {}
+        for norm in (False, True):
+            dyn = EnsembleDynamics(3, 1, n_members=5, device=dev)
+            p, losses = dyn.fit(dyn.init_params(1), train, num_steps=steps, batch_size=256, learning_rate=3e-3, key=3, normalize_inputs=norm)
+            y = dyn.member_outputs(held[:, :3], held[:, 3:4], p)
+            err = (held[:, :3] + y[..., :3].mean(0) - held[:, 6:9]) ** 2
+            res["normalize_inputs" if norm else "raw_inputs"] = {
+                "heldout_mse_sum_over_dims": float(err.sum(1).mean()), "heldout_mse_per_dim": [float(v) for v in err.mean(0)],
+                "final_train_nll": float(losses[-20:].mean())}
+            log(f"scaler evidence, normalize_inputs={norm}: {res['normalize_inputs' if norm else 'raw_inputs']}")
+        out.append({"kernel": "EnsembleDynamics.fit with / without normalize_inputs (evidence, unasserted)", "entry": "mbpo_ens_scaler_*",
+                    "config": {"rows_train": 4000, "rows_heldout": 1000, "E": 5, "steps": steps, "batch": 256, "lr": 3e-3,
+                               "data": "Pendulum, speed column * 1000 + 500", "group": "ens_scaler"}, **res})
+
+    if want("ens_scaler_case"): attempt(ens_scaler_case, 100_000, 100)
+    if want("ens_scaler_case"): attempt(ens_fold_case, 7, (64, 64, 64), 100)
+    if want("ens_scaler_case"): attempt(ens_fold_case, 7, (200, 200, 200, 200), 100)
+    if want("ens_scaler_case"): attempt(ens_scaler_mse_case, 500)
+
     # ---------------------------------------------------------------- N4: iCEM planner at the reference's defaults (icem_optimizer.py:25-50)
     def icem_case(H, reps):
         from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
