@@ -742,6 +742,52 @@ __global__ void __launch_bounds__(256) k_sac_apply(SacOptArgs A) {
 // ------------------------------------------------------------------------------------------------ host side
 
 // ------------------------------------------------------------------------------------------------
+// One batch of up to NB slab terms of one column, t0 <= t < min(t0 + NB, n_tiles).  Every load of the batch is issued without a
+// branch: a term past the end re-reads the last tile (in bounds) and is never added.  The additions are those of slab_sum
+// (g += v[t], t ascending): bit-identical.
+template <int NB>
+__device__ __forceinline__ void slab_batch_load(float (&v)[NB], const float *col, long long stride, int t0, int n_tiles) {
+  if (t0 + NB <= n_tiles) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) v[k] = col[(long long)(t0 + k) * stride];
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const int t = (t0 + k < n_tiles) ? t0 + k : n_tiles - 1;
+      v[k] = col[(long long)t * stride];
+    }
+  }
+}
+template <int NB>
+__device__ __forceinline__ float slab_batch_add(float g, const float (&v)[NB], int t0, int n_tiles) {
+  if (t0 + NB <= n_tiles) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) g += v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+      if (t0 + k < n_tiles) g += v[k];
+  }
+  return g;
+}
+// The four extras sums (slab_ex[t * 4 + c]) of the wave that owns log_alpha: NB tiles are 4 NB contiguous words, ONE load
+// instruction of the wave (lane l holds word l of the batch); the sums then read the lanes in t order — per sum the additions of
+// slab_sum.  (As four slab_sum<16> calls these were eight dependent batches of scalar loads in the launch's last wave.)
+__device__ __forceinline__ float slab_ex_load(const float *slab_ex, int t0, int n_tiles, int lane) {
+  const int w = t0 * 4 + lane, w_end = n_tiles * 4 - 1;
+  return slab_ex[w < w_end ? w : w_end];
+}
+__device__ __forceinline__ void slab_ex_add(float (&s)[4], float exv, int t0, int n_tiles) {
+  const int xi = __float_as_int(exv);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (t0 + k < n_tiles) {        // (uniform)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s[c] += __int_as_float(__builtin_amdgcn_readlane(xi, 4 * k + c));
+    }
+  }
+}
+
 // k_sac_reduce_apply: k_sac_reduce (+ the peer exchange when EXCHANGE) and the optimizer step in ONE launch, without a device-wide
 // meeting point: the step is applied UNCLIPPED and the previous (params, m, v, target) go to the undo log; whoever reads the
 // parameters next (k_sac_fwd_bwd's prologue, k_sac_finalize) sums the clip-norm partials this kernel leaves and, if a group's
@@ -750,94 +796,141 @@ __global__ void __launch_bounds__(256) k_sac_apply(SacOptArgs A) {
 template <bool EXCHANGE>
 __global__ void __launch_bounds__(256) k_sac_reduce_apply(SacReduceArgs A, SacOptArgs O, P2pDev X) {
   __shared__ float s_corr[2];
-  const int NP = A.P + A.Q2 + 1;
-  const int tid = threadIdx.x;
+  constexpr int NB = 16;
+  typedef __attribute__((address_space(1))) float GF;
+  typedef __attribute__((address_space(1))) unsigned int GU;
+  // The argument block: every field this kernel uses, fetched in ONE burst of scalar loads and pinned in SGPRs here (sac_lean.hip
+  // does the same).  Left to itself hipcc fetched each field next to its use, inside the branch that uses it, every piece behind
+  // a full wait: seven dependent round trips before the first data load, and lr / wd as per-lane loads from the argument segment
+  // behind the barrier.  (A and O carry the same grads, metrics, metrics_accum, ss_part, P, Q2: one copy is read.)
+  // (pinned as global-address-space pointers: a generic pointer out of an asm statement would make every access a flat one)
+  GF *g_slab_pi = (GF *)A.slab_pi, *g_slab_q = (GF *)A.slab_q, *g_slab_ex = (GF *)A.slab_ex, *g_grads = (GF *)A.grads,
+     *g_metrics = (GF *)A.metrics, *g_metrics_accum = (GF *)A.metrics_accum, *g_ss_part = (GF *)A.ss_part, *g_params = (GF *)O.params,
+     *g_target_q = (GF *)O.target_q, *g_adam_m = (GF *)O.adam_m, *g_adam_v = (GF *)O.adam_v, *g_undo = (GF *)O.undo,
+     *g_undo_count = (GF *)O.undo_count, *g_step_count = (GF *)O.step_count;
+  GU *g_seq = (GU *)O.seq, *g_slot_word = (GU *)O.slot_word, *g_epoch = EXCHANGE ? (GU *)X.epoch : nullptr;
+  int n_tiles = A.n_tiles, P = A.P, Q2 = A.Q2, B = A.B, n_parts = O.n_parts;
+  float lr0 = O.lr[0], lr1 = O.lr[1], lr2 = O.lr[2], wd0 = O.wd[0], wd1 = O.wd[1], wd2 = O.wd[2];
+  float max_norm = O.max_norm, grad_scale = O.grad_scale, tau = O.tau, one_minus_tau = O.one_minus_tau;
+  asm("" : "+s"(g_slab_pi), "+s"(g_slab_q), "+s"(g_slab_ex), "+s"(n_tiles), "+s"(P), "+s"(Q2), "+s"(B), "+s"(g_grads),
+               "+s"(g_metrics), "+s"(g_metrics_accum), "+s"(g_ss_part), "+s"(g_params), "+s"(g_target_q), "+s"(g_adam_m), "+s"(g_adam_v));
+  asm("" : "+s"(g_undo), "+s"(g_undo_count), "+s"(g_step_count), "+s"(g_seq), "+s"(g_slot_word), "+s"(g_epoch), "+s"(n_parts),
+               "+s"(lr0), "+s"(lr1), "+s"(lr2), "+s"(wd0), "+s"(wd1), "+s"(wd2), "+s"(max_norm), "+s"(grad_scale));
+  asm("" : "+s"(tau), "+s"(one_minus_tau));
+  const float *slab_pi = (const float *)g_slab_pi, *slab_q = (const float *)g_slab_q, *slab_ex = (const float *)g_slab_ex,
+              *step_count = (const float *)g_step_count;
+  float *grads = (float *)g_grads, *metrics = (float *)g_metrics, *metrics_accum = (float *)g_metrics_accum, *ss_part = (float *)g_ss_part,
+        *params = (float *)g_params, *target_q = (float *)g_target_q, *adam_m = (float *)g_adam_m, *adam_v = (float *)g_adam_v,
+        *undo = (float *)g_undo, *undo_count = (float *)g_undo_count;
+  unsigned int *seq = (unsigned int *)g_seq, *slot_word = (unsigned int *)g_slot_word, *x_epoch = (unsigned int *)g_epoch;
+  const int NP = P + Q2 + 1;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int i = blockIdx.x * 256 + tid;
-  const bool in = i < NP;
-  // the element's own optimizer operands are requested first: their latency overlaps the slab sums
-  const float m_in = in ? O.adam_m[i] : 0.f, v_in = in ? O.adam_v[i] : 0.f, p_in = in ? O.params[i] : 0.f;
-  const bool crit = in && i >= A.P && i < A.P + A.Q2;
-  const float tq_in = crit ? O.target_q[i - A.P] : 0.f;
-  const float count = O.step_count[0];
-  // the launch's last element (log_alpha) also keeps the running metric sums and the sequence word: everything it will
-  // read-modify-write is requested HERE, beside its slab sums — one after the other behind them (a load of what it had just
-  // stored among them) these round trips were the tail of the launch: 0.45 us per update
-  const bool last = (i == NP - 1);
-  float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f, acc4 = 0.f;
-  unsigned int seq0 = 0u;
-  if (last) {
-    seq0 = O.seq[0];
-    if (A.metrics_accum) {
-      acc0 = A.metrics_accum[0];
-      acc1 = A.metrics_accum[1];
-      acc2 = A.metrics_accum[2];
-      acc3 = A.metrics_accum[3];
-      acc4 = A.metrics_accum[4];
-    }
-  }
+  const bool in = i < NP, last = (i == NP - 1);
+  const int grp = (i < P) ? 0 : (i < P + Q2 ? 1 : 2);
+  const bool crit = in && grp == 1;
+  // the wave that holds the launch's last element (log_alpha): uniform, so what only that element needs costs the others nothing
+  const bool last_wave = __builtin_amdgcn_readfirstlane(i >> 6) == ((NP - 1) >> 6);
+
+  // ---- ONE burst: every load this thread will ever need, no wait in between.
+  // The uniform words first (scalar loads, a queue of their own): step_count heads the launch's longest chain, count -> powf.
+  // (step_count was bumped and slot_word published by this step's fwd/bwd launch: stable during this launch)
+  const float count = step_count[0];
+  const unsigned int slot = slot_word[0];
+  // the last element also keeps the running metric sums and the sequence word: everything it will read-modify-write.  Uniform
+  // addresses: scalar loads, issued by every wave rather than behind a branch (without running sums the five words come from
+  // params, in bounds, and are dropped)
+  const unsigned int seq0 = seq[0];
+  const float *ma = metrics_accum ? metrics_accum : params;
+  const float ma0 = ma[0], ma1 = ma[1], ma2 = ma[2], ma3 = ma[3], ma4 = ma[4];
   unsigned epoch = 0, want = 0;
   if (EXCHANGE) {
-    epoch = X.epoch[0];
-    want = X.epoch[1];
+    epoch = x_epoch[0];
+    want = x_epoch[1];
   }
-  if (tid == 0) {
-    s_corr[0] = 1.f - powf(0.9f, count);
-    s_corr[1] = 1.f - powf(0.999f, count);
+  asm volatile("" ::: "memory");          // (keeps the scalar loads here, as the one at the end of the burst does)
+  // Lanes without a weight gradient (past the end, log_alpha) read column 0 of the policy slab and element NP - 1 of the state:
+  // in bounds, unused, and no branch in the burst.
+  const bool wl = in && !last;
+  const float *col = !wl ? slab_pi : (grp == 0 ? slab_pi + i : slab_q + (i - P));
+  const long long stride = (wl && grp == 1) ? Q2 : P;
+  float exv = 0.f;
+  if (last_wave) exv = slab_ex_load(slab_ex, 0, n_tiles, lane);        // ahead of the wave's vector path
+  float v[NB];
+  slab_batch_load<NB>(v, col, stride, 0, n_tiles);
+  // the element's own optimizer operands
+  const int ic = in ? i : NP - 1, jc = crit ? i - P : 0;
+  const float p_in = params[ic], m_in = adam_m[ic], v_in = adam_v[ic], tq_in = target_q[jc];
+  // (a compiler-level store barrier: without one behind them in their block, scalar loads are sunk past the powf branches to
+  // their first uses)
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  // The Adam bias corrections run in the shadow of that burst, and they wait for step_count alone (scalar loads count apart from
+  // the vector ones).  count -> powf stays the longest chain of the launch, every wave meets its end at group_sumsq's barrier:
+  // hence step_count at the head of the burst, and the two powf calls (~160 instructions each on a lone lane) on the first
+  // lanes of two waves, side by side on two SIMDs, instead of one after the other on thread 0.
+  if (tid == 0) s_corr[0] = 1.f - powf(0.9f, count);
+  if (tid == 64) s_corr[1] = 1.f - powf(0.999f, count);
+  __builtin_amdgcn_sched_barrier(0);
+
+  const float acc0 = ma0, acc1 = ma1, acc2 = ma2, acc3 = metrics_accum ? ma3 : 0.f, acc4 = ma4;
+  float g = slab_batch_add<NB>(0.f, v, 0, n_tiles);
+  float ex[4] = {0.f, 0.f, 0.f, 0.f};
+  if (last_wave) slab_ex_add(ex, exv, 0, n_tiles);
+  for (int t0 = NB; t0 < n_tiles; t0 += NB) {          // more than NB tiles (batch_size > 256): further bursts
+    if (last_wave) exv = slab_ex_load(slab_ex, t0, n_tiles, lane);
+    slab_batch_load<NB>(v, col, stride, t0, n_tiles);
+    g = slab_batch_add<NB>(g, v, t0, n_tiles);
+    if (last_wave) slab_ex_add(ex, exv, t0, n_tiles);
   }
-  float g = 0.f;
-  if (i < A.P) {
-    g = slab_sum<16>(A.slab_pi, A.P, A.n_tiles, i);
-  } else if (i < A.P + A.Q2) {
-    const int j = i - A.P;
-    g = slab_sum<16>(A.slab_q, A.Q2, A.n_tiles, j);
-  } else if (i == NP - 1) {
-    const float ce = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 0) + slab_sum<16>(A.slab_ex, 4, A.n_tiles, 3), ac = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 1),
-                al = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 2);
-    const float invB = 1.0f / (float)A.B;
+  if (!wl) g = 0.f;
+  if (last) {
+    const float ce = ex[0] + ex[3], ac = ex[1], al = ex[2];
+    const float invB = 1.0f / (float)B;
     g = al * invB;
     const float m0 = 0.5f * ce * (0.5f * invB), m1 = ac * invB, m2 = al * invB;
-    A.metrics[0] = m0;
-    A.metrics[1] = m1;
-    A.metrics[2] = m2;
-    if (A.metrics_accum) {
-      A.metrics_accum[0] = acc0 + m0;
-      A.metrics_accum[1] = acc1 + m1;
-      A.metrics_accum[2] = acc2 + m2;
-      A.metrics_accum[4] = acc4 + 1.0f;
+    metrics[0] = m0;
+    metrics[1] = m1;
+    metrics[2] = m2;
+    if (metrics_accum) {
+      metrics_accum[0] = acc0 + m0;
+      metrics_accum[1] = acc1 + m1;
+      metrics_accum[2] = acc2 + m2;
+      metrics_accum[4] = acc4 + 1.0f;
     }
-    O.undo_count[0] = count;
-    O.undo_count[1] = acc3;          // metrics_accum[3] before this step adds its 'alpha' (0 without running sums)
-    O.seq[1] = seq0;                 // everything before this step was resolved by this step's fwd/bwd launch ...
-    O.seq[0] = seq0 + 1u;            // ... and this one speculative step is pending now
+    undo_count[0] = count;
+    undo_count[1] = acc3;          // metrics_accum[3] before this step adds its 'alpha' (0 without running sums)
+    seq[1] = seq0;                 // everything before this step was resolved by this step's fwd/bwd launch ...
+    seq[0] = seq0 + 1u;            // ... and this one speculative step is pending now
   }
   if (EXCHANGE) {
     p2p_push(X, epoch, i, NP, g);
     const bool ok = p2p_wait(X, want);
     g = in ? (ok ? p2p_sum(X, epoch, i) : NAN) : 0.f;
   }
-  if (in) A.grads[i] = g;
-  // (slot_word was published by this step's fwd/bwd launch: stable during this launch)
-  group_sumsq(g, i, A.P, A.Q2, NP, A.ss_part, reinterpret_cast<float *>(O.seq) + 2 + 3 * (O.slot_word[0] & 1u),
-              (O.max_norm / O.grad_scale) * (O.max_norm / O.grad_scale) * 0.9998f / (float)O.n_parts);   // ends in a __syncthreads
+  if (in) grads[i] = g;
+  group_sumsq(g, i, P, Q2, NP, ss_part, reinterpret_cast<float *>(seq) + 2 + 3 * (slot & 1u),
+              (max_norm / grad_scale) * (max_norm / grad_scale) * 0.9998f / (float)n_parts);   // ends in a __syncthreads
   if (!in) return;
-  const int grp = (i < A.P) ? 0 : (i < A.P + A.Q2 ? 1 : 2);
-  float *u_p = O.undo, *u_m = O.undo + NP, *u_v = O.undo + 2 * NP, *u_tq = O.undo + 3 * NP;
+  float *u_p = undo, *u_m = undo + NP, *u_v = undo + 2 * NP, *u_tq = undo + 3 * NP;
   u_p[i] = p_in;
   u_m[i] = m_in;
   u_v[i] = v_in;
-  const AdamOut o = sac_adam(p_in, m_in, v_in, g * O.grad_scale, s_corr[0], s_corr[1], O.lr[grp], O.wd[grp]);
-  O.params[i] = o.p;
-  O.adam_m[i] = o.m;
-  O.adam_v[i] = o.v;
+  // lr / wd arrive as scalars and are selected by group
+  const float lr = grp == 0 ? lr0 : (grp == 1 ? lr1 : lr2), wd = grp == 0 ? wd0 : (grp == 1 ? wd1 : wd2);
+  const AdamOut o = sac_adam(p_in, m_in, v_in, g * grad_scale, s_corr[0], s_corr[1], lr, wd);
+  params[i] = o.p;
+  adam_m[i] = o.m;
+  adam_v[i] = o.v;
   if (grp == 1) {
-    u_tq[i - A.P] = tq_in;
-    O.target_q[i - A.P] = tq_in * O.one_minus_tau + o.p * O.tau;       // sac.py:260-261
+    u_tq[i - P] = tq_in;
+    target_q[i - P] = tq_in * one_minus_tau + o.p * tau;       // sac.py:260-261
   } else if (grp == 2) {
-    O.undo_count[2] = s_corr[0];
-    O.undo_count[3] = s_corr[1];
+    undo_count[2] = s_corr[0];
+    undo_count[3] = s_corr[1];
     const float al = expf(o.p);                                        // 'alpha' (sac.py:267); repaired by the fix-up if the group clips
-    O.metrics[3] = al;
-    if (O.metrics_accum) O.metrics_accum[3] = acc3 + al;
+    metrics[3] = al;
+    if (metrics_accum) metrics_accum[3] = acc3 + al;
   }
 }
 
