@@ -6,7 +6,7 @@
                       ->  the policy acts on the TRUE PendulumSystem.
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
-                                     [--real-ratio R] [--normalize-inputs]
+                                     [--real-ratio R] [--normalize-inputs] [--resample-starts]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -20,6 +20,9 @@ buffer, the others model transitions (SACOptimizer(real_ratio=R); MBPO's publish
 transitions only.
 --normalize-inputs: MBPO's input scaler — fit(normalize_inputs=True) standardises the members' inputs [x, u] with the training rows'
 mean / std; the rollouts run the members with the scaler folded into their first layer.
+--resample-starts: MBPO's branched rollouts — SACOptimizer(resample_starts=True): every reset inside the fused model rollout is followed
+by a fresh draw from the true buffer, so an env's consecutive model episodes start at different real states instead of the one state
+its first reset chose.
 """
 from __future__ import annotations
 
@@ -85,7 +88,7 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
 
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None, real_ratio=0.0, normalize_inputs=False):
+        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -116,7 +119,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                  episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
                                  lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
                                  max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16, deterministic_eval=True, tau=0.005,
-                                 num_env_steps_between_updates=5, real_ratio=real_ratio)
+                                 num_env_steps_between_updates=5, real_ratio=real_ratio,
+                                 **(dict(resample_starts=True) if resample_starts else {}))
         state = optimizer.init(key=seed + 3, true_buffer_state=tbs)
         sp = state.system_params.replace(dynamics_params=dyn_params)
         if learn_reward:
@@ -153,6 +157,10 @@ if __name__ == "__main__":
                     help="share of true transitions in every SAC minibatch (MBPO's real_ratio; 0 = model transitions only)")
     ap.add_argument("--normalize-inputs", action="store_true",
                     help="standardise the model's inputs with the training rows' mean / std (MBPO's input scaler)")
+    ap.add_argument("--resample-starts", action="store_true",
+                    help="after every reset inside the model rollouts draw the env's next start state from the true buffer (MBPO's "
+                         "branched rollouts) instead of returning to the same state every time")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
-        terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs)
+        terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
+        resample_starts=a.resample_starts)

@@ -127,7 +127,24 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
  * ensemble mode and reward kind, with a policy or open-loop `actions`.  With action_repeat > 1 sys_done comes from the LAST inner
  * step: the inner steps keep stepping and the reward is summed over all of them.  The reward is unchanged (evaluated at the
  * pre-step (x, u)).  With a termination set a non-finite next state is done = 1 and a reset to first_obs: it never reaches
- * next_observation or the carried obs.  Without one (both pointers NULL) sys_done = 0 and every kernel runs as before. */
+ * next_observation or the carried obs.  Without one (both pointers NULL) sys_done = 0 and every kernel runs as before.
+ *
+ * Fresh starts (MBPO's branched rollouts: every round of k-step model rollouts starts from a new batch of real states.  Not in the
+ * reference tree, whose AutoReset returns to the same first_obs every time — restated from the MBPO paper's procedure as remembered,
+ * unverified against its code).  first_obs[env] is the state the env's next reset goes to.  With a start buffer set (start_rows,
+ * start_max_size, start_row_len, start_state: a ring of mbpo_replay_insert, normally the true buffer, with its device state
+ * {insert_position, sample_position, head, ...}), when env's step s of this launch ends with done = 1:
+ *   the reset uses the current first_obs[env], exactly as above;  immediately after it
+ *   idx = randint(sample_position, insert_position) from Philox(seed_eff, offset_eff, stream START = 11, element s * n_envs + env)
+ *   first_obs[env] <- start_logical[wrap(idx)][0 .. x_dim)     (a bit copy through the ring's head, as mbpo_replay_gather reads it)
+ * The draw shares the launch's (seed, offset, rng_dev) and, having a stream id of its own, collides with no other consumer.  An empty
+ * range (insert_position == sample_position) yields idx = sample_position, as mbpo_replay_sample does.  One draw per env step
+ * whatever action_repeat is.  The updated first_obs is written back at the end of the launch (the field is in/out with a start
+ * buffer, read-only without), so across launches and hipGraph replays an env walks one chain of start states.  Everything else
+ * about the row — discount, truncation, next_observation = the post-reset obs, the termination rules, the reward — is unchanged.
+ * Both system kinds, every ensemble mode and reward kind, with or without a termination box, with a policy or open-loop `actions`.
+ * All four start_* fields zero (a zero-initialised descriptor): off, every kernel runs what it ran before.  MBPO_ERR_ARG, checked
+ * before any device use: rows without state or state without rows, start_row_len < x_dim, start_max_size outside (0, 2^31 - 1). */
 typedef struct mbpo_rollout_desc {
   mbpo_mlp_desc policy;   /* [x_dim] -> [2*u_dim] */
   mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std) or [2*x_dim+2] (+ reward mean, raw std: MBPO_REWARD_LEARNED);
@@ -161,13 +178,18 @@ typedef struct mbpo_rollout_desc {
   const uint64_t *rng_dev;     /* optional device uint64[2] {seed word, step counter} added to (seed, offset): see "randomness" */
   /* env state, updated in place (brax State.obs / info['steps'] / done / info['first_obs']) */
   float *obs;             /* [N, x_dim] */
-  const float *first_obs; /* [N, x_dim] */
+  float *first_obs;       /* [N, x_dim]; in/out with a start buffer (see "fresh starts"), read-only without */
   float *steps;           /* [N] (float flags, as in the reference) */
   float *done;            /* [N] */
   /* output: flattened Transition rows (brax UniformSamplingQueue ravel order)
    *   [obs(x), action(u), reward, discount, next_obs(x), {log_prob, raw_action(u)}, truncation] */
   float *transitions;     /* [S*N, row_len] */
   int32_t row_len;        /* 2x+u+3 (+1+u with ppo_extras) */
+  /* fresh starts (see above): all four zero = off.  (They sit in front of the termination pair, which closes the descriptor.) */
+  const float *start_rows;     /* [start_max_size, start_row_len] ring storage; the start state is columns 0 .. x_dim of a row */
+  int64_t start_max_size;
+  int32_t start_row_len;       /* >= x_dim */
+  const int32_t *start_state;  /* device int32[>= 3] {insert_position, sample_position, head, ...} */
   /* termination (see above): each [x_dim], both NULL = none (a zero-initialised descriptor), exactly one NULL = MBPO_ERR_ARG */
   const float *term_low, *term_high;
 } mbpo_rollout_desc;
@@ -187,7 +209,10 @@ int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream);
  * mbpo_episode_step : EpisodeWrapper.step + AutoResetWrapper.step bookkeeping (brax_utils/training.py:91-137) and the
  *                     Transition row of actor_step (sac/acting.py:46-55) for step `step_index` of an unroll of `n_steps`;
  *                     `reward` is already summed over action_repeat, `sys_done` (optional) is SystemState.done.
- *                     Updates obs/steps/done in place, exactly like mbpo_model_rollout. */
+ *                     Updates obs/steps/done in place, exactly like mbpo_model_rollout.  With a start buffer (the start_* fields,
+ *                     "fresh starts" above) an env that comes out done has its first_obs replaced by the draw of element
+ *                     step_index * n_envs + env of stream START under (seed, offset [+ rng_dev]): a host loop over the steps draws
+ *                     bit for bit what the fused launch draws. */
 int mbpo_policy_act(const mbpo_mlp_desc *policy, const float *obs, int64_t n, const float *norm_mean, const float *norm_std,
                     int32_t deterministic, float action_clip, const float *noise, uint64_t seed, uint64_t offset,
                     const uint64_t *rng_dev, uint64_t elem_base, float *action, float *raw_action, float *log_prob,
@@ -205,10 +230,17 @@ typedef struct mbpo_episode_step_desc {
   const float *reward;             /* [N] */
   const float *x_next;             /* [N, x] */
   const float *sys_done;           /* [N] or NULL (= 0) */
-  const float *first_obs;          /* [N, x] */
+  float *first_obs;                /* [N, x]; in/out with a start buffer */
   float *obs, *steps, *done;       /* env state, updated in place */
   float *transitions;              /* [S*N, row_len] */
   int32_t row_len;
+  /* fresh starts: all four start_* zero = off (seed, offset, rng_dev are then unused) */
+  const float *start_rows;
+  int64_t start_max_size;
+  int32_t start_row_len;
+  const int32_t *start_state;
+  uint64_t seed, offset;
+  const uint64_t *rng_dev;         /* optional device uint64[2], see "randomness" */
 } mbpo_episode_step_desc;
 
 int mbpo_episode_step(const mbpo_episode_step_desc *d, void *stream);

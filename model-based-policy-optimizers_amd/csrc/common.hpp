@@ -219,6 +219,7 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
 #define MBPO_STREAM_PERM 8u
 #define MBPO_STREAM_ENTROPY 9u
 #define MBPO_STREAM_ICEM 10u
+#define MBPO_STREAM_START 11u
 
 // Device-resident RNG control (optional on every Philox-drawing entry point): rng_dev = uint64[2] {seed word, step counter}.
 // The effective key is (seed + rng_dev[0], offset + rng_dev[1]): a captured hipGraph whose host-side seed/offset are baked

@@ -8,6 +8,7 @@
 // with the SAME random stream as the fused kernel (Philox element index (s*N + env)*U + d of stream POLICY_NOISE), so a System
 // that exists in both forms produces the same rows either way (tests/test_gpu_generic_system.py).
 #include "common.hpp"
+#include "rollout_shared.hpp"
 
 #define LOG_SQRT_2PI_G 0.91893853320467274178f
 #define LOG_2_G 0.69314718055994530942f
@@ -89,8 +90,12 @@ struct EpisodeArgs {
   int X, U, D;
   long long N;
   int episode_length, action_repeat, ppo_extras, env_major, s, S;
-  const float *action, *raw_action, *log_prob, *reward, *x_next, *sys_done, *first_obs;
+  const float *action, *raw_action, *log_prob, *reward, *x_next, *sys_done;
+  float *first_obs;      // in/out with a start buffer
   float *obs, *steps, *done, *rows;
+  StartBuf start;        // rows == NULL: none
+  unsigned long long seed, offset;
+  const unsigned long long *rng_dev;
 };
 
 // AutoResetWrapper.step(EpisodeWrapper.step(...)) around an ALREADY evaluated System.step (brax_utils/training.py:91-137) and the
@@ -121,6 +126,14 @@ __global__ void __launch_bounds__(256) k_episode_step(EpisodeArgs A) {
     for (int d = 0; d < U; ++d) r[2 * X + U + 3 + d] = A.raw_action[env * U + d];
   }
   r[D - 1] = trunc;
+  if (A.start.rows && done != 0.f) {
+    // fresh starts (include/mbpo_hip.h): the reset consumed first_obs[env]; its next start state is the fused launch's draw for
+    // (step s, env): element s * N + env of stream START
+    const RngKey rk = rng_resolve(A.seed, A.offset, A.rng_dev);
+    const float *nf = A.start.rows + start_draw_row(A.start, A.start.state[1], A.start.state[0], A.start.state[2], rk.seed, rk.offset,
+                                                    (long long)A.s * A.N + env);
+    for (int c = 0; c < X; ++c) A.first_obs[env * X + c] = nf[c];
+  }
   A.steps[env] = steps;
   A.done[env] = done;
 }
@@ -132,13 +145,17 @@ extern "C" int mbpo_episode_step(const mbpo_episode_step_desc *d, void *stream) 
   MBPO_REQUIRE(d->step_index >= 0 && d->step_index < d->n_steps, MBPO_ERR_ARG, "episode_step: step_index %d outside [0, %d)", d->step_index, d->n_steps);
   const int want = 2 * d->x_dim + d->u_dim + 3 + (d->ppo_extras ? 1 + d->u_dim : 0);
   MBPO_REQUIRE(d->row_len == want, MBPO_ERR_ARG, "episode_step: row_len %d != expected %d", d->row_len, want);
+  const int rc = mbpo_check_start_buffer(d->start_rows, d->start_max_size, d->start_row_len, d->start_state, d->x_dim, "episode_step");
+  if (rc != MBPO_OK) return rc;
   if (d->n_envs == 0) return MBPO_OK;
   MBPO_REQUIRE(d->action && d->reward && d->x_next && d->first_obs && d->obs && d->steps && d->done && d->transitions, MBPO_ERR_ARG,
                "episode_step: null pointer");
   MBPO_REQUIRE(!d->ppo_extras || (d->raw_action && d->log_prob), MBPO_ERR_ARG, "episode_step: ppo_extras needs raw_action and log_prob");
   EpisodeArgs A{d->x_dim, d->u_dim, d->row_len, (long long)d->n_envs, d->episode_length, d->action_repeat, d->ppo_extras, d->env_major,
                 d->step_index, d->n_steps, d->action, d->raw_action, d->log_prob, d->reward, d->x_next, d->sys_done, d->first_obs,
-                d->obs, d->steps, d->done, d->transitions};
+                d->obs, d->steps, d->done, d->transitions,
+                StartBuf{d->start_rows, (long long)d->start_max_size, d->start_row_len, d->start_state},
+                (unsigned long long)d->seed, (unsigned long long)d->offset, (const unsigned long long *)d->rng_dev};
   hipLaunchKernelGGL(k_episode_step, dim3((unsigned)((d->n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
   MBPO_CHECK_LAUNCH("episode_step");
   return MBPO_OK;

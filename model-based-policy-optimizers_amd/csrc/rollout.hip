@@ -149,7 +149,9 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 // R1-R8 fused rollout.
 // ------------------------------------------------------------------------------------------------
 // LR: MBPO_REWARD_LEARNED (a flag of its own, as in k_model_rollout64)
-template <int H, bool LR>
+// START: a start buffer is set (include/mbpo_hip.h "fresh starts").  A flag of its own: as a run-time test on start.rows it added 32 to
+// 40 bytes of scratch per lane to every instantiation and two spilled registers to <128, false> (profiles/r09_fresh_starts_registers.txt)
+template <int H, bool LR, bool START>
 __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -175,6 +177,8 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
+  // START: the true buffer's {sample_position, insert_position, head}
+  const int sb_lo = START ? A.start.state[1] : 0, sb_hi = START ? A.start.state[0] : 0, sb_head = START ? A.start.state[2] : 0;
   const long long n_tiles = (N + 15) >> 4;
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const long long env0 = tile * 16;
@@ -366,6 +370,8 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
         float v = (s_done[r] != 0.f) ? s_first[r * A.ld_x + c] : s_xu[r * A.ld_xu + c];
         s_obs[r * A.ld_x + c] = v;
         s_row[r * D + X + U + 2 + c] = v;  // next_observation = nstate.obs (post auto-reset)
+        if (START && s_done[r] != 0.f && env0 + r < N)      // the reset consumed the start state: the row's next one
+          s_first[r * A.ld_x + c] = A.start.rows[start_draw_row(A.start, sb_lo, sb_hi, sb_head, rng_seed, rng_off, (long long)s * N + env0 + r) + c];
       }
       __syncthreads();
       // ---- write the tile's 16 rows ----
@@ -385,6 +391,7 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
       int r = idx / X, c = idx - r * X;
       long long env = env0 + r;
       if (env < N) A.obs[env * X + c] = s_obs[r * A.ld_x + c];
+      if (START && env < N) A.first_obs[env * X + c] = s_first[r * A.ld_x + c];
     }
     if (tid < 16) {
       long long env = env0 + tid;
@@ -449,7 +456,8 @@ __device__ __forceinline__ int ro_tid_now(int wave) {
 // as they were)
 // TERM: a termination box is set (a flag of its own for the same reason: the run-time test cost the plain instantiation two spilled
 // registers in the step loop; with it the step gains one barrier)
-template <bool WIDE, bool LR, bool TERM>
+// START: a start buffer is set (a flag of its own, likewise): section D replaces the first_obs element it has just consumed
+template <bool WIDE, bool LR, bool TERM, bool START>
 __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64 AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -491,6 +499,8 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
   const long long n_tiles = (N + 15) >> 4;
   const int mchain = wave >> 1, msub = wave & 1;   // member-phase role of this wave
+  // START: the true buffer's {sample_position, insert_position, head}
+  const int sb_lo = START ? A.start.state[1] : 0, sb_hi = START ? A.start.state[0] : 0, sb_head = START ? A.start.state[2] : 0;
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const long long env0 = tile * 16;
     {
@@ -686,6 +696,8 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
         const float v = dn ? s_first[r * ld_x + c] : s_scr[r * X + c];
         s_obs[r * ld_x + c] = v;
         s_row[r * D + X + U + 2 + c] = v;  // next_observation = nstate.obs (post auto-reset)
+        if (START && dn && env0 + r < N)     // the reset consumed the start state: the row's next one (read at its next reset)
+          s_first[r * ld_x + c] = A.start.rows[start_draw_row(A.start, sb_lo, sb_hi, sb_head, rng_seed, rng_off, (long long)s * N + env0 + r) + c];
       }
       if (tid < 16) {
         const int r = tid;
@@ -729,6 +741,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
         const int r = idx & 15, c = idx >> 4;
         const long long env = env0 + r;
         if (env < N) A.obs[env * X + c] = s_obs[r * ld_x + c];
+        if (START && env < N) A.first_obs[env * X + c] = s_first[r * ld_x + c];
       }
       if (tid < 16) {
         const long long env = env0 + tid;
@@ -749,6 +762,8 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
 // reward on the pre-step (x, u), the step, EpisodeWrapper / AutoReset bookkeeping, the Transition row — with the same device functions
 // in the same order: the same rows bit for bit (tests/test_gpu_icem.py).
 // ------------------------------------------------------------------------------------------------
+// START: a start buffer is set (a compile-time flag: the run-time test cost the plain kernel two registers)
+template <bool START>
 __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
   const long long env = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long N = A.n_envs;
@@ -763,6 +778,9 @@ __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
   }
   float steps = A.steps[env], done = A.done[env];
   const float rp[3] = {A.reward_params[0], A.reward_params[1], A.reward_params[2]};
+  // START (fresh starts, include/mbpo_hip.h): the key of the draw and the true buffer's {sample_position, insert_position, head}
+  const RngKey rk = START ? rng_resolve(A.seed, A.offset, A.rng_dev) : RngKey{0ull, 0ull};
+  const int sb_lo = START ? A.start.state[1] : 0, sb_hi = START ? A.start.state[0] : 0, sb_head = START ? A.start.state[2] : 0;
   for (int s = 0; s < A.n_steps; ++s) {
     float *row = A.transitions + (A.env_major ? (env * A.n_steps + s) : ((long long)s * N + env)) * D;
     const float a = A.actions[((long long)s * N + env) * U];
@@ -789,6 +807,11 @@ __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
       o[c] = v;
       row[X + U + 2 + c] = v;          // next_observation = nstate.obs (post auto-reset)
     }
+    if (START && dn) {                 // the reset consumed the start state: the env's next one
+      const float *nf = A.start.rows + start_draw_row(A.start, sb_lo, sb_hi, sb_head, rk.seed, rk.offset, (long long)s * N + env);
+#pragma unroll
+      for (int c = 0; c < X; ++c) f[c] = nf[c];
+    }
     row[X + U] = rew;
     row[X + U + 1] = 1.f - (dn ? 1.f : 0.f);
     row[D - 1] = over ? 1.f - sys_done : 0.f;      // truncation
@@ -797,6 +820,10 @@ __global__ void __launch_bounds__(256) k_openloop_pendulum(RolloutArgs A) {
   }
 #pragma unroll
   for (int c = 0; c < X; ++c) A.obs[env * X + c] = o[c];
+  if (START) {
+#pragma unroll
+    for (int c = 0; c < X; ++c) A.first_obs[env * X + c] = f[c];
+  }
   A.steps[env] = steps;
   A.done[env] = done;
 }
@@ -816,6 +843,8 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
                "model_rollout: term_low and term_high must both be set or both NULL");
   MBPO_REQUIRE(d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED, MBPO_ERR_ARG, "model_rollout: reward_params is NULL");
   const int X = d->x_dim, U = d->u_dim;
+  int rc = mbpo_check_start_buffer(d->start_rows, d->start_max_size, d->start_row_len, d->start_state, X, "model_rollout");
+  if (rc != MBPO_OK) return rc;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
   MBPO_REQUIRE(d->row_len == want_row, MBPO_ERR_ARG, "model_rollout: row_len %d != expected %d", d->row_len, want_row);
   MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_PENDULUM || d->reward_kind == MBPO_REWARD_QUADRATIC || d->reward_kind == MBPO_REWARD_LEARNED,
@@ -825,7 +854,6 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && U == 1), MBPO_ERR_ARG,
                "model_rollout: pendulum reward needs x_dim=3,u_dim=1");
   RolloutArgs A;
-  int rc;
   int H = 64;
   const bool has_policy = (d->actions == nullptr);
   MBPO_REQUIRE(has_policy || !d->ppo_extras, MBPO_ERR_ARG, "model_rollout: ppo_extras needs a policy (actions must be NULL)");
@@ -881,6 +909,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   A.obs = d->obs; A.first_obs = d->first_obs; A.steps = d->steps; A.done = d->done;
   A.transitions = d->transitions; A.row_len = d->row_len;
   A.term_low = d->term_low; A.term_high = d->term_high;
+  A.start = StartBuf{d->start_rows, (long long)d->start_max_size, d->start_row_len, d->start_state};
   A.n_out = E > 1 ? E : 1;
   A.ld_x = up4(X) + 4;
   A.ld_xu = up4(X + U) + 4;
@@ -899,11 +928,14 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!has_policy && d->system_kind == MBPO_SYS_PENDULUM && d->reward_kind == MBPO_REWARD_PENDULUM && !d->ppo_extras &&
       mbpo_knob_override(KNOB_ROLLOUT_LEAN) != 0) {      // (mbpo_debug_set_rollout_lean(0), not the environment: the tile kernel, for the A/B test)
-    hipLaunchKernelGGL(k_openloop_pendulum, dim3((unsigned)((d->n_envs + 255) / 256)), dim3(256), 0, st, A);
+    const dim3 ogrid((unsigned)((d->n_envs + 255) / 256));
+    if (A.start.rows) hipLaunchKernelGGL(k_openloop_pendulum<true>, ogrid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(k_openloop_pendulum<false>, ogrid, dim3(256), 0, st, A);
     MBPO_CHECK_LAUNCH("model_rollout");
     return MBPO_OK;
   }
   const bool lr = d->reward_kind == MBPO_REWARD_LEARNED;
+  const bool fresh = A.start.rows != nullptr;
   if (H == 64) {
     // the kernel specialised for the benchmark networks (rollout_lean.hip): MBPO_ROLLOUT_LEAN=0 / mbpo_debug_set_rollout_lean(0) keep the
     // generic one
@@ -938,14 +970,24 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     rc = mbpo_with_bool(lr, [&](auto LR) {
       return mbpo_with_bool(wide, [&](auto W) {
         return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
-          return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+          return mbpo_with_bool(A.start.rows != nullptr, [&](auto SB) {
+            return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value, SB.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+          });
         });
       });
     });
   } else if (H == 128) {
-    rc = mbpo_with_bool(lr, [&](auto LR) { return mbpo_launch<k_model_rollout<128, LR.value>>(grid, n_waves * 64, lds, st, "model_rollout", A); });
+    rc = mbpo_with_bool(lr, [&](auto LR) {
+      return mbpo_with_bool(fresh, [&](auto SB) {
+        return mbpo_launch<k_model_rollout<128, LR.value, SB.value>>(grid, n_waves * 64, lds, st, "model_rollout", A);
+      });
+    });
   } else {
-    rc = mbpo_with_bool(lr, [&](auto LR) { return mbpo_launch<k_model_rollout<256, LR.value>>(grid, n_waves * 64, lds, st, "model_rollout", A); });
+    rc = mbpo_with_bool(lr, [&](auto LR) {
+      return mbpo_with_bool(fresh, [&](auto SB) {
+        return mbpo_launch<k_model_rollout<256, LR.value, SB.value>>(grid, n_waves * 64, lds, st, "model_rollout", A);
+      });
+    });
   }
   if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("model_rollout");

@@ -90,10 +90,13 @@ __device__ __forceinline__ void rl_sample(const RolloutArgs &A, const f32x4 acc,
 // or in the TS modes the member the row's state takes (the lanes of column 0 hold the row's member already); no reward parameters.
 // TERM: a termination box is set (include/mbpo_hip.h "termination"): a row's SystemState.done is the OR of term_violated over the lanes
 // that hold its elements — one wave-wide ballot that all 64 lanes reach (lanes with sc >= X vote "not violated"), folded by 16.
-template <int X, bool PEND, bool LR, bool TERM>
+// START: a start buffer is set (include/mbpo_hip.h "fresh starts"): once the reset has consumed fo, the lane requests its element of the
+// row's next start state into fo; nothing reads it before the row's next reset, at least one step later (sb: the buffer's
+// {sample_position, insert_position, head}, read once at the top of the kernel).
+template <int X, bool PEND, bool LR, bool TERM, bool START>
 __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, long long env0, int lane, float *smem, float *s_pin, float *s_xu,
-                                         const float *s_lp, float *s_row, float *n_row, float &o, float fo, float &steps, float &done,
-                                         unsigned long long rng_seed, unsigned long long rng_off) {
+                                         const float *s_lp, float *s_row, float *n_row, float &o, float &fo, float &steps, float &done,
+                                         unsigned long long rng_seed, unsigned long long rng_off, const int (&sb)[3]) {
   constexpr int U = 1;
   const int sr = lane & 15, sc = lane >> 4, D = A.row_len;
   const long long N = A.n_envs;
@@ -176,6 +179,11 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
   steps = st;
   done = dnb ? 1.f : 0.f;
   o = v2;
+  if (START) {
+    const long long env = env0 + sr;
+    if (dnb && s_ok && env < N)
+      fo = A.start.rows[start_draw_row(A.start, sb[0], sb[1], sb[2], rng_seed, rng_off, (long long)s * N + env) + sc];
+  }
   if (n_row && s_ok) {                               // section A of the next step
     s_pin[sr * LDX + sc] = A.norm_mean ? (o - smem[R_NORM + sc]) / smem[R_NORM + 4 + sc] : o;      // running_statistics.normalize
     s_xu[sr * LDX + sc] = o;
@@ -196,7 +204,8 @@ __device__ __forceinline__ void rl_fused(const RolloutArgs &A, int E, int s, lon
 // PIPE: two tiles in flight per workgroup — the policy phase of one beside the member phase of the other (see the pipelined loop below)
 // LR: MBPO_REWARD_LEARNED (the reward read from the members' outputs; a flag of its own so the other instantiations stay as they were)
 // TERM: a termination box is set (a flag of its own, for the same reason: without one the kernel is the code it was)
-template <int X, bool PEND, bool PIPE, bool LR, bool TERM>
+// START: a start buffer is set (likewise: the draw's Philox rounds and the write-back of first_obs exist only in its instantiations)
+template <int X, bool PEND, bool PIPE, bool LR, bool TERM, bool START>
 __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -269,6 +278,12 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
   // the state wave: lane (r, c) = (lane & 15, lane >> 4) holds element c of env r's observation; every lane of a row its steps / done
   const int sr = lane & 15, sc = lane >> 4;
   const bool s_ok = sc < X;
+  int sb[3] = {0, 0, 0};      // START: the true buffer's {sample_position, insert_position, head}
+  if (START) {
+    sb[0] = A.start.state[1];
+    sb[1] = A.start.state[0];
+    sb[2] = A.start.state[2];
+  }
   if (tid < X) {
     smem[R_NORM + tid] = A.norm_mean ? A.norm_mean[tid] : 0.f;
     smem[R_NORM + 4 + tid] = A.norm_mean ? A.norm_std[tid] : 1.f;
@@ -348,8 +363,8 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
         __syncthreads();
         if (is_sw && my_slot == ms && mv) {
           float *const row = my_base + S_ROW;
-          rl_fused<X, PEND, LR, TERM>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo, steps, done,
-                            rng_seed, rng_off);
+          rl_fused<X, PEND, LR, TERM, START>(A, E, sm, my_env0, lane, smem, my_base + S_PIN, my_base + S_XU, my_base + S_LP, row, nullptr, o, fo,
+                                             steps, done, rng_seed, rng_off, sb);
           // the finished rows of step sm leave from here (this wave's own LDS writes and reads stay in order); then the next step's inputs
           if (A.env_major) {
             for (int r = 0; r < 16; ++r) {
@@ -373,6 +388,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
         const long long env = my_env0 + sr;
         if (env < N) {
           if (s_ok) A.obs[env * X + sc] = o;
+          if (START && s_ok) A.first_obs[env * X + sc] = fo;
           if (lane < 16) {
             A.steps[env] = steps;
             A.done[env] = done;
@@ -460,8 +476,9 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
       // ---- one section on the state wave: AutoReset pre-step (training.py:119-124), reward on the pre-step (x, u), next state,
       //      EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137), Transition (acting.py:46-55), next step's inputs ----
       if (wave == SW)
-        rl_fused<X, PEND, LR, TERM>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
-                          s + 1 < A.n_steps ? smem + R_ROWS + ((s + 1) & 1) * 16 * D4 : nullptr, o, fo, steps, done, rng_seed, rng_off);
+        rl_fused<X, PEND, LR, TERM, START>(A, E, s, env0, opaque(lane_), smem, smem + R_PIN, smem + R_XU, smem + R_LP, s_row,
+                                           s + 1 < A.n_steps ? smem + R_ROWS + ((s + 1) & 1) * 16 * D4 : nullptr, o, fo, steps, done, rng_seed,
+                                           rng_off, sb);
       __syncthreads();
       RL_STAMP(9);
     }
@@ -485,6 +502,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
       const long long env = env0 + sr;
       if (env < N) {
         if (s_ok) A.obs[env * X + sc] = o;
+        if (START && s_ok) A.first_obs[env * X + sc] = fo;
         if (lane < 16) {
           A.steps[env] = steps;
           A.done[env] = done;
@@ -522,10 +540,15 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   const bool pend = A.a.system_kind == MBPO_SYS_PENDULUM || A.a.reward_kind == MBPO_REWARD_PENDULUM;
   const bool lr = A.a.reward_kind == MBPO_REWARD_LEARNED;      // (an ensemble: never with pend)
   const bool term = A.a.term_low != nullptr;
-#define RL_LAUNCH_T(X_, P_, PP_, LR_, T_)                                                                                \
-  {                                                                                                                      \
-    rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_, T_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
-    if (rc != MBPO_OK) return rc;                                                                                        \
+  const bool start = A.a.start.rows != nullptr;
+#define RL_LAUNCH_S(X_, P_, PP_, LR_, T_, S_)                                                                               \
+  {                                                                                                                         \
+    rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_, T_, S_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
+    if (rc != MBPO_OK) return rc;                                                                                           \
+  }
+#define RL_LAUNCH_T(X_, P_, PP_, LR_, T_)                                                              \
+  {                                                                                                    \
+    if (start) RL_LAUNCH_S(X_, P_, PP_, LR_, T_, true) else RL_LAUNCH_S(X_, P_, PP_, LR_, T_, false)   \
   }
 #define RL_LAUNCH_LR(X_, P_, PP_, LR_)                                                       \
   {                                                                                          \
@@ -560,5 +583,6 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
 #undef RL_LAUNCH
 #undef RL_LAUNCH_LR
 #undef RL_LAUNCH_T
+#undef RL_LAUNCH_S
   return MBPO_OK;
 }

@@ -3,6 +3,23 @@
 #pragma once
 #include "common.hpp"
 
+// The true buffer a reset draws its next start state from (mbpo_rollout_desc.start_*): the ring of mbpo_replay_insert.
+struct StartBuf {
+  const float *rows;       // [max_size][row_len], the start state in columns 0 .. x_dim
+  long long max_size;
+  int row_len;
+  const int *state;        // {insert_position, sample_position, head, ...}
+};
+
+// host: the start_* fields of a descriptor — all zero (off), or a well-formed ring whose rows hold at least x_dim columns
+static inline int mbpo_check_start_buffer(const float *rows, long long max_size, int row_len, const int *state, int x_dim, const char *who) {
+  if (!rows && !state && max_size == 0 && row_len == 0) return MBPO_OK;
+  MBPO_REQUIRE(rows && state, MBPO_ERR_ARG, "%s: start_rows and start_state must both be set or both NULL", who);
+  MBPO_REQUIRE(row_len >= x_dim, MBPO_ERR_ARG, "%s: start_row_len %d < x_dim %d", who, row_len, x_dim);
+  MBPO_REQUIRE(max_size > 0 && max_size < 2147483647LL, MBPO_ERR_ARG, "%s: start_max_size outside (0, 2^31 - 1)", who);
+  return MBPO_OK;
+}
+
 struct RolloutArgs {
   MlpDev policy, dyn;
   int x_dim, u_dim;
@@ -20,14 +37,26 @@ struct RolloutArgs {
   unsigned long long seed, offset;
   const unsigned long long *rng_dev;
   float *obs;
-  const float *first_obs;
+  float *first_obs;                       // in/out with a start buffer (written back at the end of the launch), read-only without
   float *steps, *done;
   float *transitions;
   int row_len;
   // LDS geometry
   int ld_x, ld_xu, ld_h, ld_y, n_chains, n_out;
   const float *term_low, *term_high;      // [x_dim] each, or both NULL: no termination
+  StartBuf start;                         // rows == NULL: no start buffer (first_obs stays what the caller set)
 };
+
+// Fresh starts (include/mbpo_hip.h): the physical row of the true buffer that env `env` takes as its next start state after a reset at
+// the launch's step s: idx = randint(sample_position, insert_position) of element s * N + env of stream START, wrapped and moved
+// through the ring's head as k_replay_gather does.  An empty range yields sample_position (span 0), as mbpo_replay_sample does.
+__device__ __forceinline__ long long start_draw_row(const StartBuf &B, int lo, int hi, int head, unsigned long long rng_seed,
+                                                    unsigned long long rng_off, long long elem) {
+  const long long li = philox_randint(rng_seed, rng_off, MBPO_STREAM_START, (unsigned long long)elem, lo, hi);
+  long long w = li % B.max_size;      // jnp.take(mode='wrap'): python-style modulo
+  if (w < 0) w += B.max_size;
+  return ((w + head) % B.max_size) * B.row_len;
+}
 
 // Termination (include/mbpo_hip.h): one element of the next state against its closed interval.  NaN fails both compares and an
 // infinity is violated whatever the bounds (an unbounded dimension carries -inf / +inf, which +-inf would pass).

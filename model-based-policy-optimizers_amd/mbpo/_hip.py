@@ -81,6 +81,10 @@ class RolloutDesc(C.Structure):
         ("done", C.c_void_p),
         ("transitions", C.c_void_p),
         ("row_len", C.c_int32),
+        ("start_rows", C.c_void_p),
+        ("start_max_size", C.c_int64),
+        ("start_row_len", C.c_int32),
+        ("start_state", C.c_void_p),
         ("term_low", C.c_void_p),
         ("term_high", C.c_void_p),
     ]
@@ -92,7 +96,9 @@ class EpisodeStepDesc(C.Structure):
                 ("action_repeat", C.c_int32), ("ppo_extras", C.c_int32), ("env_major", C.c_int32), ("step_index", C.c_int32),
                 ("n_steps", C.c_int32), ("action", C.c_void_p), ("raw_action", C.c_void_p), ("log_prob", C.c_void_p),
                 ("reward", C.c_void_p), ("x_next", C.c_void_p), ("sys_done", C.c_void_p), ("first_obs", C.c_void_p),
-                ("obs", C.c_void_p), ("steps", C.c_void_p), ("done", C.c_void_p), ("transitions", C.c_void_p), ("row_len", C.c_int32)]
+                ("obs", C.c_void_p), ("steps", C.c_void_p), ("done", C.c_void_p), ("transitions", C.c_void_p), ("row_len", C.c_int32),
+                ("start_rows", C.c_void_p), ("start_max_size", C.c_int64), ("start_row_len", C.c_int32), ("start_state", C.c_void_p),
+                ("seed", C.c_uint64), ("offset", C.c_uint64), ("rng_dev", C.c_void_p)]
 
 
 class EnsTrainDesc(C.Structure):

@@ -250,6 +250,23 @@ def rng_ptr(rng: Optional[torch.Tensor]) -> Optional[int]:
     return rng.data_ptr()
 
 
+def _set_start_buffer(d, x_dim: int, start_rows, start_state) -> None:
+    """The start_* fields of a rollout / episode-step descriptor (include/mbpo_hip.h, "fresh starts"): start_rows [max_size, row_len]
+    is a replay ring's storage, start_state its int32 device state.  Both None: the fields stay zero and never reach the library."""
+    if start_rows is None and start_state is None:
+        return
+    if start_rows is None or start_state is None:
+        raise ValueError("start_rows and start_state must both be given or both None")
+    _req(start_rows, "start_rows")
+    _req(start_state, "start_state", torch.int32)
+    if start_rows.dim() != 2 or start_rows.shape[1] < x_dim:
+        raise ValueError(f"start_rows must be [max_size, row_len >= {x_dim}], got {tuple(start_rows.shape)}")
+    if start_state.numel() < 3:
+        raise ValueError("start_state must hold {insert_position, sample_position, head}")
+    d.start_rows, d.start_max_size, d.start_row_len = start_rows.data_ptr(), start_rows.shape[0], start_rows.shape[1]
+    d.start_state = start_state.data_ptr()
+
+
 def transition_row_len(x_dim: int, u_dim: int, ppo_extras: bool = False) -> int:
     return 2 * x_dim + u_dim + 3 + ((1 + u_dim) if ppo_extras else 0)
 
@@ -269,10 +286,13 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
                   member_idx: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
                   rng_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                   system=None, system_params=None, system_params_out: Optional[list] = None,
-                  term_low: Optional[torch.Tensor] = None, term_high: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  term_low: Optional[torch.Tensor] = None, term_high: Optional[torch.Tensor] = None,
+                  start_rows: Optional[torch.Tensor] = None, start_state: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused S-step model rollout for N envs (R1-R8).  Updates obs/steps/done in place; returns rows [S*N, D].
     system_kind == SYS_GENERIC (a user-defined `system`): the same contract through generic_rollout below.
-    term_low / term_high ([x_dim] each, both or neither): the box termination of include/mbpo_hip.h (BoxTermination.kernel_spec)."""
+    term_low / term_high ([x_dim] each, both or neither): the box termination of include/mbpo_hip.h (BoxTermination.kernel_spec).
+    start_rows / start_state (both or neither): a replay ring's storage [max_size, row_len] and int32 device state — the fresh starts
+    of include/mbpo_hip.h: every reset is followed by a new draw into first_obs, which is then updated in place too."""
     if system_kind == _hip.SYS_GENERIC:
         if term_low is not None or term_high is not None:
             raise ValueError("term_low / term_high belong to the fused systems; a user-defined System reports SystemState.done itself")
@@ -283,7 +303,8 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
                                obs=obs, first_obs=first_obs, steps=steps, done=done, n_steps=n_steps,
                                episode_length=episode_length, action_repeat=action_repeat, norm_mean=norm_mean, norm_std=norm_std,
                                deterministic=deterministic, ppo_extras=ppo_extras, env_major=env_major, action_clip=action_clip,
-                               policy_noise=policy_noise, seed=seed, offset=offset, rng_dev=rng_dev, out=out)
+                               policy_noise=policy_noise, seed=seed, offset=offset, rng_dev=rng_dev, out=out,
+                               start_rows=start_rows, start_state=start_state)
     lib = load()
     n_envs = obs.shape[0]
     D = transition_row_len(x_dim, u_dim, ppo_extras)
@@ -347,6 +368,7 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
         if t is not None and _req(t, nm).numel() != x_dim:
             raise ValueError(f"{nm} must be [x_dim]")
     d.term_low, d.term_high = ptr(term_low), ptr(term_high)
+    _set_start_buffer(d, x_dim, start_rows, start_state)
     check(lib.mbpo_model_rollout(C.byref(d), current_stream_ptr()), "mbpo_model_rollout")
     return out
 
@@ -382,8 +404,9 @@ def policy_act(policy_params: torch.Tensor, policy_spec: MlpSpec, obs: torch.Ten
 
 def episode_step(*, x_dim: int, u_dim: int, episode_length: int, action_repeat: int, ppo_extras: bool, env_major: bool,
                  step_index: int, n_steps: int, action, reward, x_next, first_obs, obs, steps, done, rows, raw_action=None,
-                 log_prob=None, sys_done=None) -> None:
-    """mbpo_episode_step: Episode/AutoReset bookkeeping + the Transition row of env step `step_index`."""
+                 log_prob=None, sys_done=None, start_rows=None, start_state=None, seed: int = 0, offset: int = 0, rng_dev=None) -> None:
+    """mbpo_episode_step: Episode/AutoReset bookkeeping + the Transition row of env step `step_index`.  With start_rows / start_state
+    (fresh starts, include/mbpo_hip.h) the envs that come out done get a new first_obs, drawn under (seed, offset, rng_dev)."""
     lib = load()
     for t, nm in ((action, "action"), (reward, "reward"), (x_next, "x_next"), (first_obs, "first_obs"), (obs, "obs"), (steps, "steps"),
                   (done, "done"), (rows, "rows")):
@@ -398,6 +421,9 @@ def episode_step(*, x_dim: int, u_dim: int, episode_length: int, action_repeat: 
     d.action, d.raw_action, d.log_prob = action.data_ptr(), ptr(raw_action), ptr(log_prob)
     d.reward, d.x_next, d.sys_done, d.first_obs = reward.data_ptr(), x_next.data_ptr(), ptr(sys_done), first_obs.data_ptr()
     d.obs, d.steps, d.done, d.transitions, d.row_len = obs.data_ptr(), steps.data_ptr(), done.data_ptr(), rows.data_ptr(), rows.shape[1]
+    if start_rows is not None or start_state is not None:
+        _set_start_buffer(d, x_dim, start_rows, start_state)
+        d.seed, d.offset, d.rng_dev = seed, offset, rng_ptr(rng_dev)
     check(lib.mbpo_episode_step(C.byref(d), current_stream_ptr()), "mbpo_episode_step")
 
 
@@ -405,7 +431,7 @@ def generic_rollout(*, system, system_params, system_params_out: Optional[list] 
                     x_dim: int, u_dim: int, actions=None, obs, first_obs, steps, done, n_steps: int, episode_length: int,
                     action_repeat: int = 1, norm_mean=None, norm_std=None, deterministic: bool = False, ppo_extras: bool = False,
                     env_major: bool = False, action_clip: float = 0.0, policy_noise=None, seed: int = 0, offset: int = 0,
-                    rng_dev=None, out=None) -> torch.Tensor:
+                    rng_dev=None, out=None, start_rows=None, start_state=None) -> torch.Tensor:
     """The contract of model_rollout for a USER-DEFINED System (the reference's plug-in seam, base_systems.py:40-52): per env step
     mbpo_policy_act (HIP) -> system.step(obs [N,x], action [N,u], system_params) x action_repeat (the user's batched torch code on
     the device; rewards summed, brax_utils/training.py:92-97) -> mbpo_episode_step (HIP).  Same Philox stream as the fused kernel.
@@ -452,7 +478,8 @@ def generic_rollout(*, system, system_params, system_params_out: Optional[list] 
         episode_step(x_dim=x_dim, u_dim=u_dim, episode_length=episode_length, action_repeat=action_repeat, ppo_extras=ppo_extras,
                      env_major=env_major, step_index=s, n_steps=n_steps, action=act, reward=reward.contiguous(),
                      x_next=x.to(torch.float32).contiguous(), first_obs=first_obs, obs=obs, steps=steps, done=done, rows=out,
-                     raw_action=raw, log_prob=lp, sys_done=sys_done)
+                     raw_action=raw, log_prob=lp, sys_done=sys_done, start_rows=start_rows, start_state=start_state, seed=seed,
+                     offset=offset, rng_dev=rng_dev)
     if system_params_out is not None:
         system_params_out.append(sp)
     return out

@@ -98,8 +98,12 @@ class PPO:
                  # --- MI355X-side knobs (not in the reference) ---
                  use_graph: bool = True,
                  process_group=None,
+                 resample_starts: bool = False,
                  ):
-        """max_grad_norm: None (ppo.py) -> plain adamw; > 0 -> optax.chain(clip_by_global_norm(max_grad_norm), adamw), the
+        """resample_starts: as SAC's — every reset inside an unroll is followed by a fresh draw from the environment's true buffer
+        into info['first_obs'] (include/mbpo_hip.h, "fresh starts"; MBPO's branched rollouts as remembered, unverified against its
+        code), so the episodes one unroll holds per env start at different real states.  False: no start buffer is passed.
+        max_grad_norm: None (ppo.py) -> plain adamw; > 0 -> optax.chain(clip_by_global_norm(max_grad_norm), adamw), the
         ppo_brax_env.py form (:137-141).  return_best_model: run_training returns the snapshot of the evaluation with the highest
         eval/episode_reward (:315-367).  non_equidistant_time: compute_gae discounts each sample by exp(-continuous_discounting * t),
         t = the switch time the last action component encodes, mapped to [min, max]_time_between_switches and floored to a multiple
@@ -111,6 +115,7 @@ class PPO:
         if non_equidistant_time and not env_dt > 0:
             raise ValueError("non_equidistant_time needs env_dt > 0 (losses_new.py:110 floors the switch time to multiples of it)")
         self.return_best_model = return_best_model
+        self.resample_starts = bool(resample_starts)
         self.episode_length = episode_length
         self.action_repeat = action_repeat
         self.num_timesteps = num_timesteps
@@ -264,13 +269,18 @@ class PPO:
         n_unrolls = self.batch_size * self.num_minibatches // self.num_envs
         N, T = self.num_envs, self.unroll_length
         sp_out: list = []
+        start = {}
+        if self.resample_starts:      # the true buffer's ring and device state (read, never written)
+            real = self.env.sample_buffer_state
+            start = dict(start_rows=real.data, start_state=real.state)
         for k in range(n_unrolls):                                                               # scan :194-208
             ops.model_rollout(policy_params=training_state.params.policy, policy_spec=self.policy_spec, x_dim=self.x_dim,
                               u_dim=self.u_dim, obs=state.obs, first_obs=state.info['first_obs'], steps=state.info['steps'],
                               done=state.done, n_steps=T, episode_length=self.episode_length, action_repeat=self.action_repeat,
                               norm_mean=nm, norm_std=ns, ppo_extras=True, env_major=True, seed=0,
                               offset=(SITE_UNROLL + k) << 32, rng_dev=self._rng,
-                              out=self._data[k * N:(k + 1) * N].reshape(N * T, self.row_len), system_params_out=sp_out, **spec)
+                              out=self._data[k * N:(k + 1) * N].reshape(N * T, self.row_len), system_params_out=sp_out, **spec,
+                              **start)
             if sp_out:
                 state = state.replace(system_params=sp_out[-1])
                 spec = self.env.system.rollout_spec(state.system_params, self.device)
@@ -343,6 +353,8 @@ class PPO:
                    self._rng, self._perm, self._perm_ws, training_state.params.policy, training_state.params.value,
                    training_state.normalizer_params.vec, u.params, u.adam_m, u.adam_v, u.step_count, u.workspace]
         tensors += [v for v in spec.values() if isinstance(v, torch.Tensor)]
+        if self.resample_starts:      # read by the rollout launches
+            tensors += [self.env.sample_buffer_state.data, self.env.sample_buffer_state.state]
         return tuple(t.data_ptr() for t in tensors), tensors
 
     def training_epoch_with_timing(self, training_state, env_state, key):
@@ -358,11 +370,16 @@ class PPO:
 
     def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
         """ppo.py:279-339 (ppo_brax_env.py:315-367 with return_best_model)."""
+        if self.resample_starts and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
+            raise ValueError("resample_starts=True draws every reset's start state from the true buffer, but it is empty")
         key, subkey = K.split(key)
         training_state = self.init_training_state(subkey)
         key, rb_key, env_key, eval_key = K.split(key, 4)
         rk = self.dp.rank_key      # data-generating keys differ per rank; the init key above is shared (parameters are broadcast)
-        env_state = self.env.reset(K.split(rk(env_key), self.num_envs))
+        if self.resample_starts:
+            env_state = self.env.reset(K.split(rk(env_key), self.num_envs), resample_first_obs=True)
+        else:
+            env_state = self.env.reset(K.split(rk(env_key), self.num_envs))
         evaluator = Evaluator(self, self.env, num_eval_envs=self.num_eval_envs, episode_length=self.episode_length,
                               action_repeat=self.action_repeat, key=eval_key)
         all_metrics: List[Metrics] = []

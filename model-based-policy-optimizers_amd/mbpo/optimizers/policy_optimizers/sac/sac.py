@@ -130,8 +130,13 @@ class SAC:
                  use_graph: bool = True,
                  process_group=None,
                  real_ratio: float = 0.0,
+                 resample_starts: bool = False,
                  ):
-        """real_ratio: MBPO's share of REAL transitions in every SGD minibatch (0.05 in its published runs; the arithmetic is MBPO's
+        """resample_starts: MBPO's branched rollouts (the procedure as remembered, unverified against its code — the reference's
+        AutoReset returns to the same first_obs every time): every reset inside the fused rollout is followed by a fresh draw from
+        the environment's true buffer into info['first_obs'] (include/mbpo_hip.h, "fresh starts"), so consecutive model episodes
+        of an env start at different real states.  False (the default) passes no start buffer: the launch is the one it was.
+        real_ratio: MBPO's share of REAL transitions in every SGD minibatch (0.05 in its published runs; the arithmetic is MBPO's
         as remembered, unverified against its code — the reference tree has no model loop): the first
         n_real = int(batch_size * real_ratio) rows of each minibatch are drawn from the environment's true buffer
         (`environment.sample_buffer`), zero-padded to the model row (truncation = 0), the others from this trainer's buffer of
@@ -147,6 +152,7 @@ class SAC:
         if not 0.0 <= real_ratio <= 1.0:
             raise ValueError(f"real_ratio={real_ratio} must lie in [0, 1]")
         self.real_ratio = float(real_ratio)
+        self.resample_starts = bool(resample_starts)
         self.n_real = int(batch_size * real_ratio)
         self.eval_key_fixed = eval_key_fixed
         self.return_best_model = return_best_model
@@ -320,7 +326,7 @@ class SAC:
                                  done=env_state.done, n_steps=self.num_env_steps_between_updates,
                                  episode_length=self.episode_length, action_repeat=self.action_repeat, norm_mean=nm,
                                  norm_std=ns, seed=0, offset=SITE_ROLLOUT << 32, rng_dev=self._rng,
-                                 out=self._rollout_rows, system_params_out=sp_out, **spec)
+                                 out=self._rollout_rows, system_params_out=sp_out, **spec, **self._start_buffer())
         if sp_out:      # a user-defined System returns its (possibly updated) parameters: carried in the env State, as upstream
             env_state = env_state.replace(system_params=sp_out[-1])
         # running_statistics.update(normalizer_params, transitions.observation, pmap_axis_name)   (:298-301)
@@ -328,6 +334,13 @@ class SAC:
                                  sums=self._stats_sums, workspace=self._stats_ws)
         buffer_state = self.replay_buffer.insert_rows(buffer_state, rows)                       # :303
         return normalizer_params, env_state, buffer_state
+
+    def _start_buffer(self) -> dict:
+        """The rollout launch's start buffer with resample_starts: the true buffer's ring and device state (read, never written)."""
+        if not self.resample_starts:
+            return {}
+        real = self.env.sample_buffer_state
+        return dict(start_rows=real.data, start_state=real.state)
 
     def sgd_step(self, transitions_rows: torch.Tensor, normalizer_params: RunningStatisticsState, key: Optional[int] = None,
                  g: int = 0, defer_clip_check: bool = False) -> None:
@@ -459,13 +472,13 @@ class SAC:
         TrainingState must re-capture, not replay a graph that updates other tensors)."""
         spec = self.env.system.rollout_spec(env_state.system_params, self.device)
         u = self.updater
-        real = self.env.sample_buffer_state      # read by the mixed sample launch (real_ratio > 0)
+        real = self.env.sample_buffer_state      # read by the mixed sample launch (real_ratio > 0) and the rollout (resample_starts)
         tensors = [env_state.obs, env_state.info['first_obs'], env_state.info['steps'], env_state.done, buffer_state.data,
                    buffer_state.state, real.data, real.state, self._rollout_rows, self._batch_rows, self._stats_vec, self._rng,
                    training_state.policy_params, training_state.normalizer_params.vec, u.params, u.target_q, u.adam_m, u.adam_v,
                    u.step_count, u.workspace]
         tensors += [v for v in spec.values() if isinstance(v, torch.Tensor)]
-        return tuple(t.data_ptr() for t in tensors) + (bool(self.updater.two_launch),), tensors
+        return tuple(t.data_ptr() for t in tensors) + (bool(self.updater.two_launch), self.resample_starts), tensors
 
     def close(self) -> None:
         """Release the graph and the peer-memory regions (one P2PExchange per trainer: BraxOptimizer.train builds a trainer
@@ -489,12 +502,16 @@ class SAC:
 
     # ------------------------------------------------------------------------------------------------ driver
     def reset_envs(self, env: BraxWrapper, key: int, n: int) -> State:
+        if self.resample_starts:
+            return env.reset(K.split(key, n), resample_first_obs=True)
         return env.reset(K.split(key, n))
 
     def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
         """sac.py:404-494 — same order of key splits and phases."""
         if self.n_real > 0 and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
             raise ValueError(f"real_ratio={self.real_ratio} draws {self.n_real} real rows per minibatch, but the true buffer is empty")
+        if self.resample_starts and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
+            raise ValueError("resample_starts=True draws every reset's start state from the true buffer, but it is empty")
         key, subkey = K.split(key)
         training_state = self.init_training_state(subkey)
         key, rb_key, env_key, eval_key = K.split(key, 4)

@@ -26,9 +26,11 @@ class BraxWrapper:
         self.sample_buffer = sample_buffer
         self.init_system_params = system_params
 
-    def reset(self, rng: Sequence[int]) -> State:
+    def reset(self, rng: Sequence[int], resample_first_obs: bool = False) -> State:
         """One state per key, each drawn uniformly from the TRUE buffer (brax_wrapper.py:25-38).  The reference vmaps a
-        batch-size-1 sample over the keys; here one launch draws all N rows (Philox index = env id)."""
+        batch-size-1 sample over the keys; here one launch draws all N rows (Philox index = env id).
+        resample_first_obs (the trainers' resample_starts; not in the reference): info['first_obs'] — where the first reset goes —
+        is a second, independent draw (the same key at offset 1) instead of a copy of obs."""
         from mbpo.optimizers.policy_optimizers.brax_utils.base import State
         keys = list(rng) if isinstance(rng, (list, tuple)) else [rng]
         n = len(keys)
@@ -44,9 +46,12 @@ class BraxWrapper:
         reward = rows[:, X + self.system.u_dim].contiguous()
         dev = obs.device
         z = lambda: torch.zeros(n, device=dev)
+        first_obs = obs.clone()
+        if resample_first_obs and self.sample_buffer.size(bs) > 0:
+            first_obs = ops.replay_sample(bs.data, bs.state, n, seed=k0, offset=1)[:, :X].contiguous()
         return State(pipeline_state=None, obs=obs, reward=reward, done=z(),
                      system_params=self.init_system_params.replace(key=k1),
-                     info={"steps": z(), "truncation": z(), "first_obs": obs.clone()})
+                     info={"steps": z(), "truncation": z(), "first_obs": first_obs})
 
     def step(self, state: State, action: torch.Tensor) -> State:
         """brax_wrapper.py:40-50 (no episode bookkeeping — that is the wrappers' job)."""

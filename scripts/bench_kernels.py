@@ -188,7 +188,9 @@ def main():
         del p, gr, tgt, opt
 
     # ---------------------------------------------------------------- R1-R7: fused model rollout
-    def rollout_case(N, X, U, E, S, hid_pi, hid_dyn, reps, learned_reward=False, terminate=False):
+    def rollout_case(N, X, U, E, S, hid_pi, hid_dyn, reps, learned_reward=False, terminate=False, start_buffer=False):
+        # start_buffer: a full 100 000-row true buffer (mbpo_rollout_desc.start_*): every reset — each env's last step of every launch,
+        # the horizon being S — is followed by a fresh draw into first_obs (the trainers' resample_starts)
         # terminate: a termination box |x0| <= 1 (mbpo_rollout_desc.term_low / term_high; envs that leave it restart from first_obs)
         # learned_reward: the members carry the reward head (2X + 2 outputs) and the rollout reads it (MBPO_REWARD_LEARNED)
         pd, dd = [X, *hid_pi, 2 * U], [X + U, *hid_dyn, 2 * X + (2 if learned_reward else 0)]
@@ -212,6 +214,10 @@ def main():
             lo, hi = torch.full((X,), float("-inf")), torch.full((X,), float("inf"))
             lo[0], hi[0] = -1.0, 1.0
             term = dict(term_low=lo.to(dev), term_high=hi.to(dev))
+        if start_buffer:
+            smx = 100_000
+            term.update(start_rows=torch.randn(smx, 2 * X + U + 2, generator=g).to(dev),
+                        start_state=torch.tensor([smx, 0, 0, smx], dtype=torch.int32, device=dev))
 
         def run():
             ops.model_rollout(policy_params=pp, policy_spec=ops.MlpSpec(pd_k), x_dim=X, u_dim=U, obs=obs, first_obs=first, steps=steps,
@@ -222,10 +228,11 @@ def main():
         flop = N * S * (2 * E * mlp_macs(dd) + 2 * mlp_macs(pd))
         e = mfma_entry("k_model_rollout", "mbpo_model_rollout",
                        {"N": N, "x": X, "u": U, "E": E, "S": S, "policy": list(hid_pi), "member": list(hid_dyn),
-                        "reward": "learned" if learned_reward else "quadratic", **({"termination": "|x0| <= 1"} if terminate else {})}, t, flop,
+                        "reward": "learned" if learned_reward else "quadratic", **({"termination": "|x0| <= 1"} if terminate else {}),
+                        **({"start_buffer_rows": 100_000} if start_buffer else {})}, t, flop,
                        "2*E*M + 2*P FLOP per transition", {"transitions_per_s": N * S / t})
         out.append(e)
-        log(f"rollout N={N} x={X} E={E} {hid_dyn}{' learned reward' if learned_reward else ''}{' termination' if terminate else ''}: {t * 1e6:.1f} us  "
+        log(f"rollout N={N} x={X} E={E} {hid_dyn}{' learned reward' if learned_reward else ''}{' termination' if terminate else ''}{' start buffer' if start_buffer else ''}: {t * 1e6:.1f} us  "
             f"{N * S / t / 1e6:.1f} M transitions/s")
 
     def attempt(fn, *a):
@@ -238,6 +245,7 @@ def main():
     if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50)       # C2
     if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50, learned_reward=True)   # C2, learned reward
     if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50, terminate=True)        # C2, termination box
+    if want("rollout_case"): rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50, start_buffer=True)     # C2, fresh starts
     if want("rollout_case"): rollout_case(32768, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 20)      # C4's global env count on one GPU
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (64, 64, 64), (256, 256), 20)   # "also report 256x2" members
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 5, 5, (256, 256), (256, 256), 20)
