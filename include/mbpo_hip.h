@@ -13,6 +13,11 @@
  *   - return value: MBPO_OK (0) or a negative MBPO_ERR_*; mbpo_last_error() gives text;
  *   - all floating point is IEEE fp32 (the reference's dtype: sac/sac.py:379,389);
  *     indices and positions are int32/int64 and bit-exact.
+ *   - a `workspace` is caller-owned scratch of the stated size: unless its entry point says otherwise its content on entry does not
+ *     matter (every word that is read was written earlier in the same call), it carries nothing from one call to the next, may be
+ *     shared by calls that do not overlap in time, and nothing is written past the stated size.  INTEGRATION.md, "Scratch
+ *     contract", lists every buffer of these entry points: outputs are overwritten in full (no element has to be zeroed first),
+ *     while state, running sums and in/out buffers are read before they are written and must hold their documented initial values.
  *
  * Parameter layout of an MLP ("flat params"): for layer l = 0..n_layers-1
  *   W_l[dims[l]][dims[l+1]] row-major (flax Dense kernel layout [in,out]), then b_l[dims[l+1]].
@@ -205,7 +210,7 @@ int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream);
  *                     NormalTanh sample / mode (sac/parametric_distribution.py:66-124); raw_action [n,u] and log_prob [n] are
  *                     optional (PPO's policy extras).  Noise: explicit [n,u] or Philox(seed, offset [+ rng_dev], stream 1,
  *                     element elem_base + i*u + d) — with elem_base = s*N*u this IS the fused kernel's stream at step s.
- *                     workspace: n * (x_dim + 2*u_dim) floats.
+ *                     workspace: n * (x_dim + 2*u_dim) floats (normalised obs, logits); need not be initialised.
  * mbpo_episode_step : EpisodeWrapper.step + AutoResetWrapper.step bookkeeping (brax_utils/training.py:91-137) and the
  *                     Transition row of actor_step (sac/acting.py:46-55) for step `step_index` of an unroll of `n_steps`;
  *                     `reward` is already summed over action_repeat, `sys_done` (optional) is SystemState.done.
@@ -284,7 +289,7 @@ int mbpo_replay_sample_mixed(const float *data, int64_t max_size, int32_t row_le
 /* perm = stable argsort of key_i = Philox(seed, offset [+ rng_dev], stream PERM, i).word0, i in [0, n): the ONE shared
  * permutation of PPO.sgd_step (ppo/ppo.py:166-171: jr.permutation with the same key for every leaf); gather whole
  * trajectories with mbpo_replay_gather(idx = perm).  workspace: n uint32 of scratch (keys for n > 16384; word 0 is an overflow flag of
- * the bucketed sort for 1024 < n <= 16384 — its initial value does not matter, it is left at 0).  n <= 2^20. */
+ * the bucketed sort for 1024 < n <= 16384 — its initial value does not matter, it is left at 0).  The whole workspace need not be initialised; perm is written in full.  n <= 2^20. */
 int mbpo_philox_permutation(uint64_t seed, uint64_t offset, const uint64_t *rng_dev, int64_t n, int32_t *perm,
                             uint32_t *workspace, void *stream);
 
@@ -298,7 +303,9 @@ int mbpo_philox_permutation(uint64_t seed, uint64_t offset, const uint64_t *rng_
  * The same update IS BPTT's Normalizer.update (bptt_optimizer.py:52-67) with summed_variance = std^2 * size:
  *   sum (x - new_mean)^2 + size*(mean - new_mean)^2 == sum d*(d - upd); its floor is std_min = 1e-8, no ceiling.
  * stats (device, fp32) = [count, mean[x], summed_variance[x], std[x]];
- * workspace >= mbpo_running_stats_workspace_floats(x_dim) floats (one partial per workgroup, column and pass).
+ * workspace >= mbpo_running_stats_workspace_floats(x_dim) floats (one partial per workgroup, column and pass); need not be initialised.
+ * `sums` [1 + 2 x_dim]: pass 0 writes [0, 1 + x_dim) and pass 1 reads those and writes the rest; mbpo_running_stats_update writes all of it.
+ * `stats` is state (read and updated).
  */
 int64_t mbpo_running_stats_workspace_floats(int32_t x_dim);
 int mbpo_running_stats_reduce(const float *rows, int64_t n_rows, int32_t row_len, int32_t col_off, int32_t x_dim,
@@ -444,9 +451,11 @@ typedef struct mbpo_ppo_desc {
   int32_t value_dims[MBPO_MAX_LAYERS + 1];   /* [x_dim, hidden..., 1] */
   int32_t policy_activation, value_activation;
   float *params, *adam_m, *adam_v, *step_count, *grads;
-  float *workspace;                          /* >= mbpo_ppo_workspace_floats() floats */
-  float *metrics;                            /* [4] */
-  float *metrics_accum;                      /* optional [5]: running sums of the four metrics + count */
+  float *workspace;                          /* >= mbpo_ppo_workspace_floats() floats; need not be initialised (every region — values,
+                                                GAE arrays, moments, per-sample discounts, slabs, norm partials, the layer-by-layer
+                                                buffers — is written before it is read in each mbpo_ppo_grads / _apply / _step) */
+  float *metrics;                            /* [4], overwritten (as `grads` is, in full, by mbpo_ppo_grads and mbpo_ppo_step) */
+  float *metrics_accum;                      /* optional [5]: running sums of the four metrics + count (state: start it at zero) */
   const float *data;
   int32_t batch_size, unroll_length, row_len;
   const float *norm_mean, *norm_std;         /* [x_dim] or NULL */
@@ -518,7 +527,10 @@ typedef struct mbpo_bptt_desc {
   const uint64_t *rng_dev;                   /* optional device uint64[2], see "randomness" */
   float discount, lambda_, ent_coef;
   float *transitions, *lambda_values, *grads, *metrics;
-  float *workspace;                          /* >= mbpo_bptt_workspace_floats() floats */
+  float *workspace;                          /* >= mbpo_bptt_workspace_floats() floats; need not be initialised (the forward sweep writes
+                                                every checkpoint — states, actions, noise, rewards, values, the drawn members, the z store —
+                                                before the reverse sweep reads it); transitions, lambda_values, grads and metrics are
+                                                overwritten in full */
   int32_t ens_mode;                          /* MBPO_ENS_*; TS1 / TSINF need MBPO_SYS_ENSEMBLE */
   int32_t ens_sample_noise;                  /* 1 (TS modes): x' += sigma_m * eps; needs dynamics outputs >= 2*x_dim */
   float ens_min_std;                         /* sigma = softplus(raw) + ens_min_std */
@@ -533,7 +545,8 @@ int mbpo_bptt_actor_grads(const mbpo_bptt_desc *d, void *stream);
  * replaces: value_and_grad(critic_loss_fn) of update_critic: loss = 0.5*(mean l2(v1, lamb) + mean l2(v2, lamb)), l2 = 0.5(.)^2,
  *           on a minibatch gathered (with replacement) from the flattened simulated transitions:
  *           obs_j = transitions[idx[j], 0:x_dim] (normalised with the state normaliser), target_j = lambda_values[idx[j]].
- * grads [2*C] in the [critic_1 | critic_2] layout; metrics[0] = critic loss.  workspace >= mbpo_critic_workspace_floats().
+ * grads [2*C] in the [critic_1 | critic_2] layout; metrics[0] = critic loss (both overwritten).  workspace >=
+ * mbpo_critic_workspace_floats() floats (gradient slabs and loss partials); need not be initialised.
  */
 int64_t mbpo_critic_workspace_floats(int32_t x_dim, int32_t critic_layers, const int32_t *critic_dims, int64_t batch);
 int mbpo_critic_grads(const float *critic_params, int32_t x_dim, int32_t critic_layers, const int32_t *critic_dims,
@@ -551,7 +564,8 @@ int mbpo_critic_grads(const float *critic_params, int32_t x_dim, int32_t critic_
  *   dw[k][:]    = sum_j d <dy[k][j], y_k[j]> / d params_k   (optional, [n_nets][params per net]; needs net_stride == params per net)
  *   y[k][j][:]  = the recomputed outputs (optional, [n_nets][n][dims[n_layers]])
  * dy: [n_nets][n][dims[n_layers]].  Hidden layers 64 wide, input / output width <= 32.  workspace (only for dw)
- * >= mbpo_mlp_vjp_workspace_floats(mlp, n) floats.  Fixed-order reductions: bit-reproducible.
+ * >= mbpo_mlp_vjp_workspace_floats(mlp, n) floats (weight-gradient slabs); need not be initialised.  y, dx and dw are overwritten
+ * in full.  Fixed-order reductions: bit-reproducible.
  */
 int64_t mbpo_mlp_vjp_workspace_floats(const mbpo_mlp_desc *mlp, int64_t n);
 int mbpo_mlp_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n, const float *norm_mean, const float *norm_std,
@@ -562,7 +576,8 @@ int mbpo_mlp_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n, const floa
  * forward recomputed with its pre-activations kept in `workspace`, then input and weight gradients layer by layer.
  *   x: [n][dims[0]], ALREADY normalised (shared by the nets);  dy: [n_nets][n][dims[n_layers]] or NULL (forward only -> y);
  *   y (optional with dy): [n_nets][n][dims[n_layers]];  dx (optional): [n_nets][n][dims[0]] with respect to the x given;
- *   dw (optional): [n_nets][params per net].  workspace >= mbpo_mlp_layered_workspace_floats(mlp, n) floats.  Fixed-order sums. */
+ *   dw (optional): [n_nets][params per net].  workspace >= mbpo_mlp_layered_workspace_floats(mlp, n) floats (activations, ping-pong
+ *   deltas, the split row ranges' partials beyond 1024 rows); need not be initialised.  Fixed-order sums. */
 int64_t mbpo_mlp_layered_workspace_floats(const mbpo_mlp_desc *mlp, int64_t n);
 int mbpo_mlp_layered_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n, const float *dy, float *y, float *dx, float *dw,
                          float *workspace, void *stream);
@@ -572,7 +587,8 @@ int mbpo_mlp_layered_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n, co
  *           (:406-410; utils/optimizer_utils.py:155-161).
  * grads *= grad_scale; if apply_if_finite and any gradient is non-finite the whole update (params, moments, count) is
  * skipped; count (device scalar) advances by one otherwise; grad_norm_out (optional) = optax.global_norm(grads);
- * target (optional) <- (1 - tau) * target + tau * new_params.   workspace >= 2 * ceil(n / 256) + 4 floats.
+ * target (optional) <- (1 - tau) * target + tau * new_params.   workspace >= 2 * ceil(n / 256) + 4 floats (sum-of-squares and
+ * non-finite counts per block); need not be initialised.  grad_norm_out is overwritten; params, moments, count and target are state.
  */
 int mbpo_adamw_step(float *params, const float *grads, float *adam_m, float *adam_v, float *step_count, int64_t n, float lr,
                     float wd, float grad_scale, int32_t apply_if_finite, float *target, float tau, float *grad_norm_out,
@@ -595,7 +611,8 @@ int mbpo_soft_update(const float *target, const float *online, float *out, int64
  * Any hidden sizes.  Hidden layers all 64 wide whose 16-row tile fits 160 KiB of LDS: the fused kernel (two launches).  Any other
  * shape (other widths, unequal widths, deeper or wider-output 64 stacks): a layer-by-layer path (gather, one GEMM launch per Dense
  * layer, NLL head, backward GEMM levels writing grads directly), the same loss and gradient, deterministic.  The workspace size
- * depends on the path; mbpo_ens_nll_workspace_floats needs no device. */
+ * depends on the path; mbpo_ens_nll_workspace_floats needs no device.  The workspace need not be initialised on either path; grads
+ * (every parameter of every member, an unfitted reward head's as zeros) and metrics are overwritten in full. */
 typedef struct mbpo_ens_train_desc {
   int32_t x_dim, u_dim;
   mbpo_mlp_desc dynamics;
@@ -625,7 +642,8 @@ int mbpo_ens_nll_grads(const mbpo_ens_train_desc *d, void *stream);
  * walks 16-row tiles through the forward chain, two partials per (member, slot), fixed-order reduce — no atomics, deterministic
  * for a fixed slot count) or layered (the shared [x, u] and target gathered once, one GEMM launch per Dense layer over the E nets,
  * a head kernel).  Rows beyond n in the last tile contribute zero.  The shape checks are mbpo_ens_nll_grads's; n > 0; idx,
- * metrics and workspace must not be NULL.  mbpo_ens_eval_workspace_floats needs no device. */
+ * metrics and workspace must not be NULL.  mbpo_ens_eval_workspace_floats needs no device.  The workspace need not be initialised
+ * (a larger one left by another shape or path serves as well); metrics [2][E] is overwritten in full. */
 typedef struct mbpo_ens_eval_desc {
   int32_t x_dim, u_dim;
   mbpo_mlp_desc dynamics;              /* [x+u] -> [2x] or [2x+2], as mbpo_ens_train_desc */
@@ -646,13 +664,15 @@ int mbpo_ens_eval(const mbpo_ens_eval_desc *d, void *stream);
  *   improved members: best_params[e] <- params[e] (bit copy), best_score_e <- score_e; the others are untouched.
  *   state (device int32[2]): state[0] <- any improved ? 0 : state[0] + 1 (evaluations since an improvement);  state[1] += 1.
  * Two launches: the decision (it stages the copy map in workspace, int32[n_members]) and the member copy, which reads the map
- * only — nothing reads best_score after it was overwritten. */
+ * only — nothing reads best_score after it was overwritten.  The workspace need not be initialised: the decision writes all
+ * n_members entries of the map before the copy reads them.  best_params, best_score and state are state. */
 int mbpo_ens_keep_best(const float *params, float *best_params, int64_t n_params, int32_t n_members, const float *score,
                        float *best_score, float rel_tol, int32_t *state, int32_t *workspace, void *stream);
 /* elite_idx[j] = the member of rank j under the total order (score ascending, NaN last, ties by lower index) — the order
  * mbpo_icem_update ranks by;  elite_params[j] <- params[elite_idx[j]] (bit copy), j < n_elites <= n_members.  Two launches (rank,
  * member copy).  The member copy of both calls: destination member j takes source member map[j], 16-byte accesses where source
- * and destination are equally aligned; n_params need not be a multiple of 4. */
+ * and destination are equally aligned; n_params need not be a multiple of 4.  elite_idx and elite_params are overwritten in full
+ * (no workspace: the ranks are a permutation, so every elite_idx entry is written before the copy reads it). */
 int mbpo_ens_pick_elites(const float *params, int64_t n_params, int32_t n_members, const float *score, int32_t n_elites,
                          int32_t *elite_idx, float *elite_params, void *stream);
 
@@ -669,7 +689,7 @@ int mbpo_ens_pick_elites(const float *params, int64_t n_params, int32_t n_member
  * Three launches (partial sums per workgroup, partial squared deviations per workgroup — each workgroup adds the first pass's
  * partials itself —, one workgroup that finishes).  No atomics; the number of workgroups and each one's rows depend on (n, in_dim)
  * only and every sum runs in a fixed order, so two calls give the same bits.  workspace: mbpo_ens_scaler_workspace_floats(n, in_dim)
- * floats (fp64 partials: 8-byte aligned), no device needed for the query.
+ * floats (fp64 partials: 8-byte aligned), no device needed for the query; need not be initialised.  scaler [2][in_dim] is overwritten.
  * MBPO_ERR_ARG: a null rows / scaler / workspace, n_rows, row_len or n <= 0, in_dim outside [1, row_len], n > n_rows without idx,
  * std_floor < 0 (or NaN), a misaligned workspace. */
 int64_t mbpo_ens_scaler_workspace_floats(int64_t n, int32_t in_dim);
@@ -707,7 +727,9 @@ int mbpo_ens_fold_scaler(const float *params, int64_t n_params, int32_t n_member
  * mbpo_icem_update: values[c] = mean (use_max: max) over particles of mean_t reward (:146-163) from the rollout's step-major
  *   transition rows; elites = the n_elites best in np.argsort order; mean <- alpha*mean + (1-alpha)*elite mean, std likewise on
  *   the population variance (:199-209); best_value/best_sequence keep the best elite seen (:212-221); the n_prev best elites
- *   go to prev_elites (:227).  workspace: n_candidates int32.  State vectors are [horizon*u_dim] device floats. */
+ *   go to prev_elites (:227).  workspace: n_candidates int32 (every candidate's rank, written before any is read); need not be
+ *   initialised.  values [n_candidates] and prev_elites [n_prev][horizon*u_dim] are overwritten in full; mean, std, best_value and
+ *   best_sequence are state.  State vectors are [horizon*u_dim] device floats. */
 int mbpo_icem_sample(const float *mean, const float *std, const float *prev_elites, const float *u_min, const float *u_max,
                      int32_t n_samples, int32_t n_prev, int32_t horizon, int32_t u_dim, int32_t n_particles, float exponent,
                      uint64_t seed, uint64_t offset, const uint64_t *rng_dev, float *actions, float *candidates, void *stream);
@@ -732,7 +754,7 @@ int mbpo_icem_update_constrained(const float *rows, int32_t row_len, int32_t rew
  * mbpo_icem_sample_batched: problem b draws with seed = seeds[b] (device uint64[n_problems]) at the shared `offset` — bit for bit
  *   mbpo_icem_sample(seed = seeds[b], offset, rng_dev = NULL) on problem b's slices.  n_problems <= 65535.
  * mbpo_icem_update_batched: one workgroup per problem, bit for bit mbpo_icem_update_constrained on problem b's slices
- *   (particle_cost [n_problems*NC*n_particles] or NULL).  workspace: n_problems*n_candidates int32. */
+ *   (particle_cost [n_problems*NC*n_particles] or NULL).  workspace: n_problems*n_candidates int32; need not be initialised. */
 int mbpo_icem_sample_batched(const float *mean, const float *std, const float *prev_elites, const float *u_min, const float *u_max,
                              int32_t n_samples, int32_t n_prev, int32_t horizon, int32_t u_dim, int32_t n_particles, float exponent,
                              int32_t n_problems, const uint64_t *seeds, uint64_t offset, float *actions, float *candidates, void *stream);
