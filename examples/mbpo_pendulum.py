@@ -6,7 +6,7 @@
                       ->  the policy acts on the TRUE PendulumSystem.
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
-                                     [--real-ratio R] [--normalize-inputs] [--resample-starts]
+                                     [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -23,6 +23,10 @@ mean / std; the rollouts run the members with the scaler folded into their first
 --resample-starts: MBPO's branched rollouts — SACOptimizer(resample_starts=True): every reset inside the fused model rollout is followed
 by a fresh draw from the true buffer, so an env's consecutive model episodes start at different real states instead of the one state
 its first reset chose.
+--optimistic BETA: hallucinated control (optimistic exploration in the style of H-UCRL) — the MODEL system becomes
+EnsembleSystem(mode="optimistic", beta=BETA): the policy emits [u | eta] and the model's next state is the members' mean moved by
+beta * (std over members) * eta, anywhere inside the ensemble's confidence set; on the TRUE system only the controls act
+(model.env_action).  Not with --real-ratio (real rows have no eta columns).  No learning curve is claimed for it.
 """
 from __future__ import annotations
 
@@ -47,12 +51,13 @@ def collect_uniform(system, n, gen, dev):
     return x, u, nxt.reward, nxt.x_next
 
 
-def true_return(system, optimizer, opt_state, steps=200):
+def true_return(system, optimizer, opt_state, steps=200, env_action=lambda a: a):
+    """env_action: the controls of a policy action (EnsembleSystem.env_action: an optimistic model's policy also emits eta)."""
     start = system.reset()
     x, total, true_params = start.x_next, 0.0, start.system_params      # the TRUE system's own parameters
     for _ in range(steps):
         u, opt_state = optimizer.act(x, opt_state, evaluate=True)
-        nxt = system.step(x, u, true_params)
+        nxt = system.step(x, env_action(u), true_params)
         x, total = nxt.x_next, total + float(nxt.reward)
     return total
 
@@ -68,7 +73,7 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
     env = BraxWrapper(system=optimizer.system, system_params=opt_state.system_params, sample_buffer_state=opt_state.true_buffer_state,
                       sample_buffer=optimizer.true_buffer)
     trainer = optimizer.agent_class(environment=env, **optimizer.agent_kwargs)
-    X, U = optimizer.system.x_dim, optimizer.system.u_dim
+    X, U = optimizer.system.x_dim, optimizer.system.action_dim      # (the model rows' action width)
     shares = []
 
     def progress(env_steps, metrics):
@@ -88,7 +93,7 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
 
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False):
+        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -103,8 +108,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
     tbs = true_buffer.init(seed)
     dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
     termination = None if terminate_speed is None else BoxTermination.from_intervals(3, {2: (-terminate_speed, terminate_speed)})
-    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), mode="mean", predict_delta=True,
-                           termination=termination)
+    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), predict_delta=True, termination=termination,
+                           **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic)))
     dyn_params = dyn.init_params(seed + 1)
     history = []
     for it in range(iters):
@@ -130,7 +135,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
             out, shares = optimizer.train(opt_state=state), None
         else:
             out, shares = train_reporting_terminations(optimizer, state, verbose)
-        ret = true_return(true_system, optimizer, out.optimizer_state)
+        ret = true_return(true_system, optimizer, out.optimizer_state, env_action=model.env_action)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
                             seconds=time.time() - t0))
         if elites:
@@ -160,7 +165,9 @@ if __name__ == "__main__":
     ap.add_argument("--resample-starts", action="store_true",
                     help="after every reset inside the model rollouts draw the env's next start state from the true buffer (MBPO's "
                          "branched rollouts) instead of returning to the same state every time")
+    ap.add_argument("--optimistic", type=float, default=None, metavar="BETA",
+                    help="hallucinated control: the policy also picks the model's next state inside mean +- BETA * (std over members)")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
         terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
-        resample_starts=a.resample_starts)
+        resample_starts=a.resample_starts, optimistic=a.optimistic)

@@ -149,11 +149,35 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
  * about the row — discount, truncation, next_observation = the post-reset obs, the termination rules, the reward — is unchanged.
  * Both system kinds, every ensemble mode and reward kind, with or without a termination box, with a policy or open-loop `actions`.
  * All four start_* fields zero (a zero-initialised descriptor): off, every kernel runs what it ran before.  MBPO_ERR_ARG, checked
- * before any device use: rows without state or state without rows, start_row_len < x_dim, start_max_size outside (0, 2^31 - 1). */
+ * before any device use: rows without state or state without rows, start_row_len < x_dim, start_max_size outside (0, 2^31 - 1).
+ *
+ * Hallucinated control (optimistic exploration in the style of H-UCRL: the policy also picks the next state inside the ensemble's
+ * epistemic confidence set.  Not in the reference tree; build-defined).  A rollout is hallucinated when halluc_beta ([x_dim], device)
+ * is non-NULL.  Then:
+ *   action width   u_dim stays the width the policy emits, the rows carry and SAC's critics see: A = u_env + x_dim.  An action is
+ *                  [u (u_env) | eta (x_dim)], both parts whatever the policy or the open-loop `actions` give; the kernel adds no clip
+ *                  of its own beyond action_clip.
+ *   dynamics input the dynamics read [x, u] only: dynamics.dims[0] == x_dim + u_env == u_dim.
+ *   next state     with mu_e,c member e's mean head at (x, u):
+ *                    m_c  = (sum_e mu_e,c) / E           e ascending: the MBPO_ENS_MEAN sum, unchanged
+ *                    q_c  = sum_e (mu_e,c - m_c)^2       e ascending
+ *                    sd_c = sqrtf(q_c / E)               population std (EnsembleDynamics.next_state's var(unbiased=False))
+ *                    x'_c = base_c + m_c + beta_c * sd_c * eta_c          base = x when ens_predict_delta
+ *   action_repeat  > 1: eta is held and sd is recomputed at every inner step.
+ *   elites         the members are the elites (the kernels see E = n_elites).
+ *   member outputs x_dim (mean only) is accepted, like 2x and 2x + 2.
+ *   reward         evaluated at the pre-step (x, u); eta never enters it.  Pendulum reward: x_dim == 3 && u_env == 1.  Quadratic
+ *                  reward: params stay [t[x], q[x], r[u_env]], the control cost runs over the u_env columns.  Learned reward: the
+ *                  mean over members of the reward head, as in MBPO_ENS_MEAN.
+ *   unchanged      termination (the box on x'), resets, fresh starts, ppo_extras (log_prob summed over all A dims), env_major, the
+ *                  normaliser, the Philox streams, the row layout (at action width A).
+ * MBPO_ERR_ARG, checked before any device use, when halluc_beta is set with system_kind != MBPO_SYS_ENSEMBLE, ens_mode !=
+ * MBPO_ENS_MEAN, u_dim <= x_dim, or a dynamics input width other than u_dim.  NULL (a zero-initialised descriptor): off, every kernel
+ * runs what it ran before. */
 typedef struct mbpo_rollout_desc {
   mbpo_mlp_desc policy;   /* [x_dim] -> [2*u_dim] */
   mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std) or [2*x_dim+2] (+ reward mean, raw std: MBPO_REWARD_LEARNED);
-                             ignored for MBPO_SYS_PENDULUM */
+                             ignored for MBPO_SYS_PENDULUM.  With halluc_beta: [u_dim] -> ... (u_dim = x_dim + the control width) */
   int32_t x_dim, u_dim;
   int64_t n_envs;          /* N */
   int32_t n_steps;         /* S = num_env_steps_between_updates (SAC) or unroll_length (PPO) */
@@ -190,6 +214,8 @@ typedef struct mbpo_rollout_desc {
    *   [obs(x), action(u), reward, discount, next_obs(x), {log_prob, raw_action(u)}, truncation] */
   float *transitions;     /* [S*N, row_len] */
   int32_t row_len;        /* 2x+u+3 (+1+u with ppo_extras) */
+  /* hallucinated control (see above): NULL = off */
+  const float *halluc_beta;    /* [x_dim] */
   /* fresh starts (see above): all four zero = off.  (They sit in front of the termination pair, which closes the descriptor.) */
   const float *start_rows;     /* [start_max_size, start_row_len] ring storage; the start state is columns 0 .. x_dim of a row */
   int64_t start_max_size;

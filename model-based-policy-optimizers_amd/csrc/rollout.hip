@@ -151,8 +151,25 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 // LR: MBPO_REWARD_LEARNED (a flag of its own, as in k_model_rollout64)
 // START: a start buffer is set (include/mbpo_hip.h "fresh starts").  A flag of its own: as a run-time test on start.rows it added 32 to
 // 40 bytes of scratch per lane to every instantiation and two spilled registers to <128, false> (profiles/r09_fresh_starts_registers.txt)
-template <int H, bool LR, bool START>
-__global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
+// the controls the dynamics and the rewards see (u_env).  An expression, not a variable, and `if constexpr (HAL)` throughout: an
+// instantiation with HAL = false is then emitted exactly as it was before the flag existed.  (With a local `UE` and run-time `if (HAL)`
+// tests, all constant and all folded, seven existing k_model_rollout64 instantiations still came out with one to four SGPR spills more
+// or fewer: profiles/r10_hallucinated_registers.txt.)
+#define RO_UE (HAL ? U - X : U)
+// HAL: hallucinated control (halluc_beta is set; include/mbpo_hip.h "hallucinated control").  A flag of its own, like the others: the
+// instantiations without it compile to what they were (profiles/r10_hallucinated_registers.txt).  The action is [u (UE) | eta (X)]:
+// the member chains read the x + UE leading columns of s_xu (every input-layer routine masks k >= dims[0] itself, none relies on zero
+// pad columns, so eta may sit where the padding was), the rewards read the UE control columns, the combine section reads eta.
+// Only the HAL instantiations take the argument block that carries beta (RolloutArgsHal): every other one keeps the kernel-argument
+// type it had, and RolloutArgs — which k_rollout_lean embeds — its layout.
+struct RolloutArgsHal : RolloutArgs {
+  const float *halluc_beta;     // [x_dim]
+};
+template <bool HAL>
+using RolloutArgsFor = typename std::conditional<HAL, RolloutArgsHal, RolloutArgs>::type;
+
+template <int H, bool LR, bool START, bool HAL>
+__global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
@@ -174,6 +191,10 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
   float *s_steps = s_row + 16 * ((D + 3) & ~3);  // [16]
   float *s_done = s_steps + 16;                  // [16]
   float *s_rew = s_done + 16;                    // [16]
+  // HAL: beta staged once per workgroup, [X] floats behind s_rew (the host sizes this region for k_model_rollout64's second row
+  // buffer; the tile load's barrier below orders it before its first use)
+  if constexpr (HAL)
+    for (int idx = tid; idx < X; idx += nthreads) s_rew[16 + idx] = A.halluc_beta[idx];
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -298,7 +319,7 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
             const float *tp = A.reward_params, *qp = tp + X, *rp = qp + X;
             float cx = 0.f, cu = 0.f;
             for (int c = 0; c < X; ++c) { float dd = xr[c] - tp[c]; cx += qp[c] * (dd * dd); }
-            for (int d = 0; d < U; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
+            for (int d = 0; d < RO_UE; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
             rew = -cx - cu;
           }
           s_rew[r] += rew;
@@ -321,7 +342,16 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgs A) {
             if (A.ens_mode == MBPO_ENS_MEAN) {
               float acc = 0.f;
               for (int e = 0; e < E; ++e) acc += s_y[(e * 16 + r) * A.ld_y + c];
-              v = base + acc / (float)E;
+              if constexpr (HAL) {
+                // x' = base + m + beta * sd * eta, sd the population std of the members' means (two passes over the E tiles in s_y)
+                const float m = acc / (float)E;
+                float q = 0.f;
+                for (int e = 0; e < E; ++e) { const float dm = s_y[(e * 16 + r) * A.ld_y + c] - m; q += dm * dm; }
+                const float sd = sqrtf(q / (float)E);
+                v = base + m + s_rew[16 + c] * sd * s_xu[r * A.ld_xu + U + c];      // eta: action columns UE .. UE + X, X + UE == U
+              } else {
+                v = base + acc / (float)E;
+              }
             } else {
               int mem = 0;
               long long eidx = ((long long)s * AR + ar) * N + env;
@@ -457,8 +487,16 @@ __device__ __forceinline__ int ro_tid_now(int wave) {
 // TERM: a termination box is set (a flag of its own for the same reason: the run-time test cost the plain instantiation two spilled
 // registers in the step loop; with it the step gains one barrier)
 // START: a start buffer is set (a flag of its own, likewise): section D replaces the first_obs element it has just consumed
-template <bool WIDE, bool LR, bool TERM, bool START>
-__global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64 AA) {
+// HAL: hallucinated control (a flag of its own, likewise; see k_model_rollout): section C's 'mean' branch adds beta * sd * eta
+// (the HAL instantiations' argument block, for the reason given at RolloutArgsHal)
+struct RolloutArgs64Hal : RolloutArgs64 {
+  const float *halluc_beta;     // [x_dim]
+};
+template <bool HAL>
+using RolloutArgs64For = typename std::conditional<HAL, RolloutArgs64Hal, RolloutArgs64>::type;
+
+template <bool WIDE, bool LR, bool TERM, bool START, bool HAL>
+__global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64For<HAL> AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
   constexpr int HT = 4;
@@ -491,9 +529,13 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
   // load per term: ~1.5 k of that section's 3.6 k cycles)
   float *s_rp = s_scr + ((16 * (X + U) + 16 + 3) & ~3);   // [2X+U] quadratic (target, q, r) or [3] pendulum
   if (!LR) {
-    const int n_rp = (A.reward_kind == MBPO_REWARD_PENDULUM) ? 3 : 2 * X + U;
+    const int n_rp = (A.reward_kind == MBPO_REWARD_PENDULUM) ? 3 : 2 * X + RO_UE;
     for (int idx = tid_; idx < n_rp; idx += nthreads) s_rp[idx] = A.reward_params[idx];
   }
+  // HAL: beta staged once per workgroup, in the X floats of s_rp that the reward's narrower control cost leaves free: s_rp[X + U + c]
+  // (2X + UE == X + U)
+  if constexpr (HAL)
+    for (int idx = tid_; idx < X; idx += nthreads) s_rp[X + U + idx] = AA.halluc_beta[idx];
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -628,7 +670,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
             const float *tp = s_rp, *qp = tp + X, *rp = qp + X;
             float cx = 0.f, cu = 0.f;
             for (int c = 0; c < X; ++c) { float dd = xr[c] - tp[c]; cx += qp[c] * (dd * dd); }
-            for (int d = 0; d < U; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
+            for (int d = 0; d < RO_UE; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
             rew = -cx - cu;
           }
           s_rew[r] += rew;
@@ -649,7 +691,16 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
             if (A.ens_mode == MBPO_ENS_MEAN) {
               float acc = 0.f;
               for (int e = 0; e < E; ++e) acc += s_y[(e * 16 + r) * ld_y + c];
-              v = base + acc / (float)E;
+              if constexpr (HAL) {
+                // x' = base + m + beta * sd * eta, sd the population std of the members' means (two passes over the E tiles in s_y)
+                const float m = acc / (float)E;
+                float q = 0.f;
+                for (int e = 0; e < E; ++e) { const float dm = s_y[(e * 16 + r) * ld_y + c] - m; q += dm * dm; }
+                const float sd = sqrtf(q / (float)E);
+                v = base + m + s_rp[X + U + c] * sd * s_xu[r * ld_xu + U + c];      // eta: action columns UE .. UE + X, X + UE == U
+              } else {
+                v = base + acc / (float)E;
+              }
             } else {
               int mem = 0;
               const long long eidx = ((long long)s * AR + ar) * N + env;
@@ -843,6 +894,12 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
                "model_rollout: term_low and term_high must both be set or both NULL");
   MBPO_REQUIRE(d->reward_params || d->reward_kind == MBPO_REWARD_LEARNED, MBPO_ERR_ARG, "model_rollout: reward_params is NULL");
   const int X = d->x_dim, U = d->u_dim;
+  // hallucinated control: the action is [u (UE) | eta (x_dim)], the dynamics and the rewards see the UE leading columns
+  const bool hal = d->halluc_beta != nullptr;
+  MBPO_REQUIRE(!hal || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG, "model_rollout: halluc_beta needs system_kind ENSEMBLE");
+  MBPO_REQUIRE(!hal || d->ens_mode == MBPO_ENS_MEAN, MBPO_ERR_ARG, "model_rollout: halluc_beta needs ens_mode MEAN");
+  MBPO_REQUIRE(!hal || U > X, MBPO_ERR_ARG, "model_rollout: halluc_beta needs u_dim > x_dim (the action is [u | eta], eta [x_dim]); got u_dim %d, x_dim %d", U, X);
+  const int UE = hal ? U - X : U;
   int rc = mbpo_check_start_buffer(d->start_rows, d->start_max_size, d->start_row_len, d->start_state, X, "model_rollout");
   if (rc != MBPO_OK) return rc;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
@@ -851,8 +908,8 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
                MBPO_ERR_ARG, "model_rollout: unknown reward_kind %d", d->reward_kind);
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_LEARNED || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG,
                "model_rollout: the learned reward needs system_kind ENSEMBLE");
-  MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && U == 1), MBPO_ERR_ARG,
-               "model_rollout: pendulum reward needs x_dim=3,u_dim=1");
+  MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && UE == 1), MBPO_ERR_ARG,
+               "model_rollout: pendulum reward needs x_dim=3,u_dim=1 (with halluc_beta: u_dim = 1 + x_dim)");
   RolloutArgs A;
   int H = 64;
   const bool has_policy = (d->actions == nullptr);
@@ -872,7 +929,10 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     if (rc != MBPO_OK) return rc;
     E = A.dyn.n_nets;
     dyn_out = A.dyn.dims[A.dyn.n_layers];
-    MBPO_REQUIRE(A.dyn.dims[0] == X + U, MBPO_ERR_ARG, "model_rollout: dynamics input must be x_dim+u_dim");
+    MBPO_REQUIRE(hal || A.dyn.dims[0] == X + U, MBPO_ERR_ARG, "model_rollout: dynamics input must be x_dim+u_dim");
+    MBPO_REQUIRE(!hal || A.dyn.dims[0] == U, MBPO_ERR_ARG,
+                 "model_rollout: with halluc_beta the dynamics input must be u_dim = x_dim + the control width (the dynamics read [x, u] only); got %d, u_dim %d",
+                 A.dyn.dims[0], U);
     MBPO_REQUIRE(dyn_out == 2 * X || dyn_out == 2 * X + 2 || (dyn_out == X && !(d->ens_sample_noise && d->ens_mode != MBPO_ENS_MEAN)),
                  MBPO_ERR_ARG, "model_rollout: dynamics output must be 2*x_dim (mean, raw std), 2*x_dim+2 (+ reward mean, raw std) or "
                  "x_dim (mean only, no sampling)");
@@ -940,6 +1000,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     // the kernel specialised for the benchmark networks (rollout_lean.hip): MBPO_ROLLOUT_LEAN=0 / mbpo_debug_set_rollout_lean(0) keep the
     // generic one
     const int lean_mode = (int)mbpo_knob(KNOB_ROLLOUT_LEAN);      // 0 generic, 1 lean, 2 lean + two tiles in flight forced, 3 lean without
+    // (k_rollout_lean never sees hallucinated control: rollout_lean_supports refuses u_dim != 1, and halluc_beta needs u_dim > x_dim)
     if (lean_mode && rollout_lean_supports(A, has_policy, E)) {
       RoLeanArgs L;
       L.a = A;
@@ -971,7 +1032,12 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
       return mbpo_with_bool(wide, [&](auto W) {
         return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
           return mbpo_with_bool(A.start.rows != nullptr, [&](auto SB) {
-            return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value, SB.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AA);
+            return mbpo_with_bool(hal, [&](auto HL) {
+              RolloutArgs64For<HL.value> AH;
+              static_cast<RolloutArgs64 &>(AH) = AA;
+              if constexpr (HL.value) AH.halluc_beta = d->halluc_beta;
+              return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value, SB.value, HL.value>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AH);
+            });
           });
         });
       });
@@ -979,13 +1045,23 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   } else if (H == 128) {
     rc = mbpo_with_bool(lr, [&](auto LR) {
       return mbpo_with_bool(fresh, [&](auto SB) {
-        return mbpo_launch<k_model_rollout<128, LR.value, SB.value>>(grid, n_waves * 64, lds, st, "model_rollout", A);
+        return mbpo_with_bool(hal, [&](auto HL) {
+          RolloutArgsFor<HL.value> AH;
+          static_cast<RolloutArgs &>(AH) = A;
+          if constexpr (HL.value) AH.halluc_beta = d->halluc_beta;
+          return mbpo_launch<k_model_rollout<128, LR.value, SB.value, HL.value>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
+        });
       });
     });
   } else {
     rc = mbpo_with_bool(lr, [&](auto LR) {
       return mbpo_with_bool(fresh, [&](auto SB) {
-        return mbpo_launch<k_model_rollout<256, LR.value, SB.value>>(grid, n_waves * 64, lds, st, "model_rollout", A);
+        return mbpo_with_bool(hal, [&](auto HL) {
+          RolloutArgsFor<HL.value> AH;
+          static_cast<RolloutArgs &>(AH) = A;
+          if constexpr (HL.value) AH.halluc_beta = d->halluc_beta;
+          return mbpo_launch<k_model_rollout<256, LR.value, SB.value, HL.value>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
+        });
       });
     });
   }

@@ -81,6 +81,7 @@ class RolloutDesc(C.Structure):
         ("done", C.c_void_p),
         ("transitions", C.c_void_p),
         ("row_len", C.c_int32),
+        ("halluc_beta", C.c_void_p),
         ("start_rows", C.c_void_p),
         ("start_max_size", C.c_int64),
         ("start_row_len", C.c_int32),

@@ -287,13 +287,18 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
                   rng_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                   system=None, system_params=None, system_params_out: Optional[list] = None,
                   term_low: Optional[torch.Tensor] = None, term_high: Optional[torch.Tensor] = None,
-                  start_rows: Optional[torch.Tensor] = None, start_state: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  start_rows: Optional[torch.Tensor] = None, start_state: Optional[torch.Tensor] = None,
+                  halluc_beta: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused S-step model rollout for N envs (R1-R8).  Updates obs/steps/done in place; returns rows [S*N, D].
     system_kind == SYS_GENERIC (a user-defined `system`): the same contract through generic_rollout below.
     term_low / term_high ([x_dim] each, both or neither): the box termination of include/mbpo_hip.h (BoxTermination.kernel_spec).
     start_rows / start_state (both or neither): a replay ring's storage [max_size, row_len] and int32 device state — the fresh starts
-    of include/mbpo_hip.h: every reset is followed by a new draw into first_obs, which is then updated in place too."""
+    of include/mbpo_hip.h: every reset is followed by a new draw into first_obs, which is then updated in place too.
+    halluc_beta ([x_dim], device): the hallucinated control of include/mbpo_hip.h — u_dim is then the action width u_env + x_dim, an
+    action is [u | eta] and x' = base + mean + beta * std_over_members * eta (SYS_ENSEMBLE in ENS_MEAN only)."""
     if system_kind == _hip.SYS_GENERIC:
+        if halluc_beta is not None:
+            raise ValueError("halluc_beta belongs to the fused ensemble; a user-defined System forms its own next state")
         if term_low is not None or term_high is not None:
             raise ValueError("term_low / term_high belong to the fused systems; a user-defined System reports SystemState.done itself")
         if model_noise is not None or member_idx is not None:
@@ -369,6 +374,9 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
             raise ValueError(f"{nm} must be [x_dim]")
     d.term_low, d.term_high = ptr(term_low), ptr(term_high)
     _set_start_buffer(d, x_dim, start_rows, start_state)
+    if halluc_beta is not None and _req(halluc_beta, "halluc_beta").numel() != x_dim:
+        raise ValueError("halluc_beta must be [x_dim]")
+    d.halluc_beta = ptr(halluc_beta)
     check(lib.mbpo_model_rollout(C.byref(d), current_stream_ptr()), "mbpo_model_rollout")
     return out
 

@@ -147,6 +147,13 @@ def lecun_normal_flat(dims: Sequence[int], gen: torch.Generator) -> torch.Tensor
     return torch.cat(parts)
 
 
+def _refuse_optimistic(system) -> None:
+    """BPTT, fused or wide, does not differentiate an optimistic EnsembleSystem: the gradient through the members' spread is not built."""
+    if getattr(system, "optimistic", False):
+        raise ValueError("BPTT does not take EnsembleSystem(mode='optimistic'): the gradient through the ensemble spread "
+                         "(x' = mean + beta * std * eta) is not built; use SAC, PPO or iCEM")
+
+
 class BPTTOptimizer(BaseOptimizer):
     def __init__(self,
                  obs_dim: int,
@@ -183,6 +190,7 @@ class BPTTOptimizer(BaseOptimizer):
                  use_graph: bool = True,
                  *args, **kwargs):
         super().__init__(*args, **kwargs)
+        _refuse_optimistic(self.system)
         _hip.load()                                   # fail loudly without the HIP library
         self.use_graph = bool(use_graph)              # replay the train step as a hipGraph (single rank; see train())
         # data-parallel ranks: every rank runs num_samples_per_gradient_update trajectories from its own sampling
@@ -289,9 +297,14 @@ class BPTTOptimizer(BaseOptimizer):
         self._stats_sums_x, self._stats_ws_x = f(1 + 2 * X), f(ops.stats_workspace_floats(X))
         self._stats_sums_r, self._stats_ws_r = f(3), f(ops.stats_workspace_floats(1))
 
+    def set_system(self, system):
+        _refuse_optimistic(system)
+        super().set_system(system)
+
     # -- reference API --------------------------------------------------------------------------------------------
     def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None) -> BPTTState:
         assert self.system is not None, "BPTT optimizer requires system to be defined."
+        _refuse_optimistic(self.system)
         assert self.system.x_dim == self.obs_dim and self.system.u_dim == self.action_dim, \
             "input and action dimensions do not match with the system"
         critic_key, actor_key, system_key, key = K.split(key, 4)
@@ -350,6 +363,7 @@ class BPTTOptimizer(BaseOptimizer):
     # -- one train step on the working buffers ----------------------------------------------------------------------
     def _system_kwargs(self, system_params):
         # (rollout_policy's scan ignores SystemState.done, utils/optimizer_utils.py:85-93: no termination in the gradient or the evaluation)
+        _refuse_optimistic(self.system)      # (the fused and the wide path both start here)
         spec = without_termination(self.system.rollout_spec(system_params, self.device))
         if spec["system_kind"] == _hip.SYS_GENERIC:
             # a user-defined System (the reference's plug-in seam, base_systems.py:40-52): rollout_policy's scan

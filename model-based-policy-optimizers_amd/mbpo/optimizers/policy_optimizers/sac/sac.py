@@ -151,6 +151,9 @@ class SAC:
             raise NotImplementedError("wandb is not available in this environment")
         if not 0.0 <= real_ratio <= 1.0:
             raise ValueError(f"real_ratio={real_ratio} must lie in [0, 1]")
+        if real_ratio > 0 and getattr(getattr(environment, "system", None), "optimistic", False):
+            raise ValueError(f"real_ratio={real_ratio} > 0 on EnsembleSystem(mode='optimistic'): real rows carry u_dim action columns, "
+                             "model rows action_dim = u_dim + x_dim (the hallucinated controls), so they cannot share a minibatch")
         self.real_ratio = float(real_ratio)
         self.resample_starts = bool(resample_starts)
         self.n_real = int(batch_size * real_ratio)
@@ -248,7 +251,9 @@ class SAC:
                                                   sample_batch_size=batch_size * grad_updates_per_step, device=self.device)
         self.row_len = self.replay_buffer.row_len
         # real rows (the true buffer's transitions) must be a column prefix of the model rows: checked even when n_real == 0
-        self.replay_buffer.check_mixable(self.env.sample_buffer)
+        # (not on an optimistic system: its model rows are action_dim wide, real_ratio > 0 is refused above and nothing is ever mixed)
+        if not getattr(self.env.system, "optimistic", False):
+            self.replay_buffer.check_mixable(self.env.sample_buffer)
         # fixed device buffers (graph-replayable)
         S, N = num_env_steps_between_updates, num_envs
         self._rollout_rows = torch.empty(S * N, self.row_len, device=self.device)

@@ -321,7 +321,7 @@ class iCEMOptimizer(BaseOptimizer):
 
     def init(self, key: int, true_buffer_state=None) -> iCemOptimizerState:
         assert self.system is not None, "iCEM optimizer requires system to be defined."
-        self.agent = self.agent_class(horizon=self.horizon, action_dim=self.system.u_dim, key=self.key, opt_params=self.opt_params,
+        self.agent = self.agent_class(horizon=self.horizon, action_dim=self.system.action_dim, key=self.key, opt_params=self.opt_params,
                                       **self.agent_kwargs)
         self.agent.set_system(self.system)
         if true_buffer_state is None:

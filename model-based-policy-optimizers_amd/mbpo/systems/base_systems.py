@@ -45,6 +45,12 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
         self.x_dim = dynamics.x_dim
         self.u_dim = dynamics.u_dim
 
+    @property
+    def action_dim(self) -> int:
+        """What the policy (or a planner) emits and the model's transition rows carry.  u_dim — what the dynamics and the true buffer
+        see — for every system but the optimistic EnsembleSystem, whose actions also hold the hallucinated controls."""
+        return self.u_dim
+
     @staticmethod
     def system_params_vmap_axes(axes: int = 0):
         return SystemParams(dynamics_params=None, reward_params=None, key=axes)
@@ -68,16 +74,17 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
         dev = _device_of(x)
         single = x.dim() == 1
         xb = x.reshape(-1, self.x_dim).to(dev, torch.float32).contiguous().clone()
-        ub = u.reshape(-1, self.u_dim).to(dev, torch.float32).contiguous()
+        A = self.action_dim
+        ub = u.reshape(-1, A).to(dev, torch.float32).contiguous()
         n = xb.shape[0]
         key, sub = K.split(system_params.key)
         spec = self.rollout_spec(system_params, dev)
         if not terminate:
             spec = without_termination(spec)
-        rows = ops.model_rollout(x_dim=self.x_dim, u_dim=self.u_dim, actions=ub.reshape(1, n, self.u_dim), obs=xb,
+        rows = ops.model_rollout(x_dim=self.x_dim, u_dim=A, actions=ub.reshape(1, n, A), obs=xb,
                                  first_obs=xb.clone(), steps=torch.zeros(n, device=dev), done=torch.zeros(n, device=dev),
                                  n_steps=1, episode_length=2 ** 30, seed=sub, **spec)
-        X, U = self.x_dim, self.u_dim
+        X, U = self.x_dim, A
         x_next, reward = rows[:, X + U + 2:2 * X + U + 2], rows[:, X + U]
         # the episode cannot run out here (episode_length 2**30): done = 1 - discount is the system's own
         done = 1.0 - rows[:, X + U + 1] if "term_low" in spec else 0.0      # (no termination: SystemState's default)

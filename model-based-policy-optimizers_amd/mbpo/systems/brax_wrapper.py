@@ -43,7 +43,7 @@ class BraxWrapper:
             # randint(minval=0, maxval=0) yields 0 -> row 0 of the (all-zero dummy) buffer (base_optimizer.py:43-57)
             rows = self.sample_buffer.logical_data(bs)[0:1].expand(n, -1).contiguous()
         obs = rows[:, :X].contiguous()
-        reward = rows[:, X + self.system.u_dim].contiguous()
+        reward = rows[:, X + self.system.u_dim].contiguous()      # (the TRUE buffer's layout: u_dim, not action_dim)
         dev = obs.device
         z = lambda: torch.zeros(n, device=dev)
         first_obs = obs.clone()
@@ -61,7 +61,7 @@ class BraxWrapper:
 
     @property
     def action_size(self) -> int:
-        return self.system.u_dim
+        return self.system.action_dim      # what the policy emits (u_dim for every system but the optimistic EnsembleSystem)
 
     @property
     def observation_size(self) -> int:

@@ -8,7 +8,9 @@ model plugs into.  Semantics (build-defined, parity-unpinned; restated in oracle
     'mean' : x' = base + mean_e(mu_e)               — what System.step's `.mean()` consumes
     'ts1'  : member drawn per (env, step);  x' = base + mu_m (+ sigma_m * eps when sample_noise)   — MBPO-style
     'tsinf': member = env % E
-BPTT differentiates every mode (include/mbpo_hip.h, mbpo_bptt_desc): in 'ts1' / 'tsinf' by reparameterisation through the selected
+    'optimistic': hallucinated control (include/mbpo_hip.h "hallucinated control"; H-UCRL-style optimistic exploration): the policy
+             emits [u | eta], eta in [-1, 1]^x, and x' = base + mean_e(mu_e) + beta * std_e(mu_e) * eta (population std over members)
+BPTT differentiates every mode but 'optimistic' (include/mbpo_hip.h, mbpo_bptt_desc): in 'ts1' / 'tsinf' by reparameterisation through the selected
 member — mu_m, and with sample_noise sigma_m * eps — with the member and eps drawn from Philox per train step (the reference threads
 SystemParams.key through rollout_policy, utils/optimizer_utils.py:81-97).  sample_noise has no effect in 'mean' mode.
 
@@ -46,7 +48,8 @@ from mbpo.systems.rewards.base_rewards import Reward
 from mbpo.systems.termination import BoxTermination, termination_spec
 from mbpo.utils import keys as K
 
-_MODES = {"mean": _hip.ENS_MEAN, "ts1": _hip.ENS_TS1, "tsinf": _hip.ENS_TSINF}
+# ('optimistic' is ENS_MEAN plus halluc_beta: the mean of the members, moved inside their spread by the policy's eta)
+_MODES = {"mean": _hip.ENS_MEAN, "ts1": _hip.ENS_TS1, "tsinf": _hip.ENS_TSINF, "optimistic": _hip.ENS_MEAN}
 
 
 FIT_SITE_HOLDOUT = 1            # high word of the Philox offset of fit's holdout permutation (the sampler draws at offsets 0, 1, ...)
@@ -395,10 +398,16 @@ class EnsembleSystem(System):
     """termination: a BoxTermination on the next state (mbpo/systems/termination.py) — the model episodes of the SAC / PPO trainers
     and of the evaluators then end where the box is left or the state stops being finite (discount 0, truncation 0, reset to the
     env's first obs), and `step` reports SystemState.done.  iCEM, BPTT and rollout_actions / rollout_policy IGNORE it, as the
-    reference's scans ignore SystemState.done (utils/optimizer_utils.py:31-47, 85-93): their trajectories run on through the box."""
+    reference's scans ignore SystemState.done (utils/optimizer_utils.py:31-47, 85-93): their trajectories run on through the box.
+
+    mode='optimistic' (hallucinated control): two widths exist.  u_dim stays what the dynamics and the true buffer see; action_dim =
+    u_dim + x_dim is what the policy emits, the model's rows carry and SAC's critics see: an action is [u | eta] and the next state is
+    mean + beta * std_over_members * eta.  beta: a float or a length-x_dim sequence / tensor.  env_action(a) cuts the controls out
+    for the true system.  The reward is unchanged (eta never enters it).  Out of scope and refused: BPTT (the gradient through the
+    spread is not built), SAC's real_ratio > 0 (real rows carry u_dim action columns, model rows action_dim), members wider than 256."""
 
     def __init__(self, dynamics: EnsembleDynamics, reward: Reward, mode: str = "mean", predict_delta: bool = True,
-                 sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None):
+                 sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None, beta=1.0):
         super().__init__(dynamics=dynamics, reward=reward)
         if termination is not None and termination.x_dim != dynamics.x_dim:
             raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {dynamics.x_dim}")
@@ -413,6 +422,33 @@ class EnsembleSystem(System):
             elif reward.min_std != min_std:
                 raise ValueError(f"LearnedReward.min_std {reward.min_std} differs from the system's min_std {min_std}")
         self.mode, self.predict_delta, self.sample_noise, self.min_std = mode, predict_delta, sample_noise, min_std
+        self.optimistic = mode == "optimistic"
+        self.beta = None
+        if self.optimistic:
+            if dynamics.kernel_width is None:
+                raise ValueError("mode='optimistic' runs inside the fused rollout kernels, which take members up to 256 wide")
+            b = torch.as_tensor(beta, dtype=torch.float32).detach().cpu().reshape(-1)
+            if b.numel() == 1:
+                b = b.expand(dynamics.x_dim)
+            if b.numel() != dynamics.x_dim:
+                raise ValueError(f"beta must be a float or hold x_dim = {dynamics.x_dim} values, got {b.numel()}")
+            self.beta = b.clone()
+            self._beta_dev = {}
+
+    @property
+    def action_dim(self) -> int:
+        return self.u_dim + self.x_dim if self.optimistic else self.u_dim
+
+    def env_action(self, a: torch.Tensor) -> torch.Tensor:
+        """The controls of a policy action, for acting on the true system: a[..., :u_dim] (the whole action unless optimistic)."""
+        return a[..., :self.u_dim]
+
+    def _halluc_beta(self, device) -> torch.Tensor:
+        """beta as a device tensor, cached per device: nothing is copied host to device inside a captured graph."""
+        k = str(device)
+        if k not in self._beta_dev:
+            self._beta_dev[k] = self.beta.to(device).contiguous()
+        return self._beta_dev[k]
 
     def init_params(self, key: int) -> SystemParams:
         if not isinstance(self.reward, LearnedReward):
@@ -437,4 +473,5 @@ class EnsembleSystem(System):
         return dict(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dyn_params, dyn_spec=dyn_spec,
                     ens_mode=_MODES[self.mode], ens_predict_delta=self.predict_delta, ens_sample_noise=self.sample_noise,
                     ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec,
+                    **({"halluc_beta": self._halluc_beta(device)} if self.optimistic else {}),
                     **termination_spec(self.termination, self.x_dim, device))

@@ -48,8 +48,11 @@ class DifferentiableBuiltin:
     fused = False
 
     def __init__(self, system, spec: dict):
+        if spec.get("halluc_beta") is not None or getattr(system, "optimistic", False):
+            raise ValueError("no differentiable torch form for EnsembleSystem(mode='optimistic'): the gradient through the ensemble "
+                             "spread is not built")
         self.system, self.spec = system, spec
-        self.x_dim, self.u_dim = system.x_dim, system.u_dim
+        self.x_dim, self.u_dim = system.x_dim, system.u_dim      # (what the dynamics see; no optimistic system gets here)
         self.ens_mode, self.sample_noise, self.n_members = _hip.ENS_MEAN, False, 0
         kind = spec["system_kind"]
         if kind == _hip.SYS_ENSEMBLE:

@@ -33,7 +33,7 @@ def rollout_actions(system: System, system_params: SystemParams, init_state: tor
     """optimizer_utils.py:12-59: open-loop actions through System.step, one fused launch for all steps (a user-defined
     System: one System.step per step).  observation = [init, x'_0 .. x'_{H-2}], discount = 1."""
     assert actions.shape[0] == horizon
-    X, U = system.x_dim, system.u_dim
+    X, U = system.x_dim, system.action_dim      # (the rows carry what the planner emits: [u | eta] on an optimistic system)
     dev = _device(init_state)
     single = init_state.dim() == 1
     obs = init_state.reshape(-1, X).to(dev, torch.float32).contiguous().clone()
@@ -81,7 +81,7 @@ def rollout_policy(system: System, system_params: SystemParams, init_state: torc
     """optimizer_utils.py:63-116: `policy(obs, policy_state) -> (action, new_policy_state)` is an arbitrary callable (e.g.
     `optimizer.act`), so the steps are walked on the host: the callable, then System.step (one launch).  The trainers never
     take this route — they hand the whole unroll to the fused kernel."""
-    X, U = system.x_dim, system.u_dim
+    X, U = system.x_dim, system.action_dim
     dev = _device(init_state)
     single = init_state.dim() == 1
     obs = init_state.reshape(-1, X).to(dev, torch.float32)

@@ -252,6 +252,42 @@ def main():
     if want("rollout_case"): attempt(rollout_case, 4096, 17, 6, 10, 5, (64, 64, 64), (64, 64, 64), 20)     # C5 shape through the rollout kernel
     if want("rollout_case"): attempt(rollout_case, 4096, 4, 1, 7, 5, (64, 64, 64), (200, 200, 200, 200), 20)   # MBPO's model, stored at 256
 
+    # hallucinated control (mbpo_rollout_desc.halluc_beta; EnsembleSystem(mode="optimistic")) next to the plain 'mean' rollout of the
+    # same shape on the same kernel: k_model_rollout64 (mbpo_debug_set_rollout_lean(0): the optimistic action width u + x keeps the
+    # rollout off k_rollout_lean, so the like-for-like baseline is the tile kernel, not the benchmark's default path)
+    def rollout_optimistic_case(N, X, UE, E, S, hid, reps):
+        lib = _hip.load()
+        dd = [X + UE, *hid, 2 * X]
+        dp = lecun_flat(dd, g, E).to(dev)
+        obs = torch.randn(N, X, generator=g).to(dev)
+        first = obs.clone()
+        steps, done = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+        rp = torch.cat([torch.zeros(X), torch.ones(X), torch.ones(UE) * 0.1]).to(dev)
+        beta = torch.ones(X, device=dev)
+        lib.mbpo_debug_set_rollout_lean(0)
+        try:
+            for mode, U, extra in (("mean", UE, {}), ("optimistic", UE + X, dict(halluc_beta=beta))):
+                pd = [X, *hid, 2 * U]
+                pp = lecun_flat(pd, g).to(dev)
+                rows = torch.empty(S * N, 2 * X + U + 3, device=dev)
+
+                def run():
+                    ops.model_rollout(policy_params=pp, policy_spec=ops.MlpSpec(pd), x_dim=X, u_dim=U, obs=obs, first_obs=first, steps=steps,
+                                      done=done, n_steps=S, episode_length=S, system_kind=_hip.SYS_ENSEMBLE, dyn_params=dp,
+                                      dyn_spec=ops.MlpSpec(dd, "swish", E), reward_kind=_hip.REWARD_QUADRATIC, reward_params=rp, seed=1,
+                                      offset=0, out=rows, **extra)
+                t, te = both(run, reps)
+                flop = N * S * (2 * E * mlp_macs(dd) + 2 * mlp_macs(pd))
+                out.append(mfma_entry("k_model_rollout64", "mbpo_model_rollout",
+                                      {"N": N, "x": X, "u_env": UE, "action_width": U, "E": E, "S": S, "policy": list(hid), "member": list(hid),
+                                       "reward": "quadratic", "mode": mode, "rollout_lean": 0}, t, flop,
+                                      "2*E*M + 2*P FLOP per transition", {"transitions_per_s": N * S / t}))
+                log(f"rollout ({mode}, k_model_rollout64) N={N} x={X} u_env={UE} E={E} {hid}: {t * 1e6:.1f} us  {N * S / t / 1e6:.1f} M transitions/s")
+        finally:
+            lib.mbpo_debug_set_rollout_lean(-1)
+
+    if want("rollout_optimistic_case"): rollout_optimistic_case(4096, 4, 1, 5, 5, (64, 64, 64), 50)      # C2's shape, 'mean' and 'optimistic'
+
     # ---------------------------------------------------------------- R2: vmapped ensemble forward (System.step outside the fused rollout)
     def ens_fwd_case(N, X, U, E, hid, reps):
         dd = [X + U, *hid, 2 * X]
