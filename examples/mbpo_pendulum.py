@@ -6,7 +6,7 @@
                       ->  the policy acts on the TRUE PendulumSystem.
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
-                                     [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA]
+                                     [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA] [--calibrate]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -27,6 +27,10 @@ its first reset chose.
 EnsembleSystem(mode="optimistic", beta=BETA): the policy emits [u | eta] and the model's next state is the members' mean moved by
 beta * (std over members) * eta, anywhere inside the ensemble's confidence set; on the TRUE system only the controls act
 (model.env_action).  Not with --real-ratio (real rows have no eta columns).  No learning curve is claimed for it.
+--calibrate: the spread of the members is calibrated on the fit's held-out rows (fit(holdout_ratio=0.2, calibrate=True): one factor per
+state dimension, EnsembleDynamics.calibrate); with --optimistic the model system is built with calibrated=True, so the policy moves
+the state inside mean +- BETA * calibration * std.  Every iteration prints the calibration vector and the coverage of the intervals at
+the 0.5 and 0.9 levels, before and after calibration, on the held-out rows and on 2000 fresh transitions.  No learning curve is claimed.
 """
 from __future__ import annotations
 
@@ -92,8 +96,31 @@ def train_reporting_terminations(optimizer, opt_state, verbose=True):
     return BraxOutput(optimizer_state=opt_state.replace(policy_params=policy_params, key=new_key), summary=metrics), shares
 
 
+def calibration_report(dyn, dyn_params, rows, n_rows, fit_key, true_system, dev, verbose=True, n_fresh=2000):
+    """The calibration vector and the coverage at the 0.5 and 0.9 levels (of 19), raw spread and calibrated, on the rows `fit` held
+    out (the same Philox permutation) and on n_fresh transitions the model has never seen."""
+    from mbpo import ops
+    from mbpo.systems.ensemble_system import FIT_SITE_HOLDOUT
+    from mbpo.utils import keys as K
+    n_hold = min(5000, int(math.floor(0.2 * n_rows)))
+    hold = ops.philox_permutation(n_rows, seed=K.PRNGKey(fit_key), offset=FIT_SITE_HOLDOUT << 32)[:n_hold].contiguous()
+    x, u, r, xn = collect_uniform(true_system, n_fresh, torch.Generator().manual_seed(fit_key + 12345), dev)
+    fresh = torch.cat([x, u, r[:, None], torch.ones(n_fresh, 1, device=dev), xn], 1).contiguous()
+    out = dict(calibration=[round(float(v), 4) for v in dyn_params.calibration])
+    levels = (9, 17)                                  # p = 10 / 20 and 18 / 20 of the 19 equispaced levels
+    for name, data, idx in (("holdout", rows, hold), ("fresh", fresh, None)):
+        for tag, flag in (("before", False), ("after", True)):
+            cov = dyn.coverage(dyn_params, data, idx=idx, calibrated=flag)[:, levels]
+            out[f"coverage_{name}_{tag}"] = [[round(float(v), 4) for v in row] for row in cov]
+    if verbose:
+        print(f"  calibration {out['calibration']}; coverage at levels (0.5, 0.9) per state dimension:", flush=True)
+        for name in ("holdout", "fresh"):
+            print(f"    {name:8s} before {out[f'coverage_{name}_before']}  after {out[f'coverage_{name}_after']}", flush=True)
+    return out
+
+
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None):
+        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None, calibrate=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
@@ -109,7 +136,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
     dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
     termination = None if terminate_speed is None else BoxTermination.from_intervals(3, {2: (-terminate_speed, terminate_speed)})
     model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), predict_delta=True, termination=termination,
-                           **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic)))
+                           **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic, calibrated=calibrate)))
     dyn_params = dyn.init_params(seed + 1)
     history = []
     for it in range(iters):
@@ -117,9 +144,13 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         x, u, r, xn = collect_uniform(true_system, n_true, gen, dev)
         tbs = true_buffer.insert(tbs, Transition(observation=x, action=u, reward=r, discount=torch.ones(n_true, device=dev), next_observation=xn))
         n_rows = true_buffer.size(tbs)
+        fit_kw = dict(holdout_ratio=0.2, n_elites=5) if elites else {}
+        if calibrate:
+            fit_kw.update(holdout_ratio=0.2, calibrate=True)
         dyn_params, losses = dyn.fit(dyn_params, true_buffer.logical_data(tbs), num_steps=model_steps, batch_size=256, learning_rate=3e-3,
-                                     key=seed + 10 * it, n_rows=n_rows, normalize_inputs=normalize_inputs,
-                                     **(dict(holdout_ratio=0.2, n_elites=5) if elites else {}))
+                                     key=seed + 10 * it, n_rows=n_rows, normalize_inputs=normalize_inputs, **fit_kw)
+        coverage = calibration_report(dyn, dyn_params, true_buffer.logical_data(tbs), n_rows, seed + 10 * it, true_system, dev,
+                                      verbose) if calibrate else None
         optimizer = SACOptimizer(system=model, true_buffer=true_buffer, num_timesteps=sac_steps, num_evals=2, reward_scaling=1,
                                  episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
                                  lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
@@ -143,6 +174,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                holdout_mse=[round(float(v), 6) for v in dyn_params.holdout[1]])
         if shares is not None:
             history[-1].update(terminated_share=[round(s, 4) for s in shares])
+        if coverage is not None:
+            history[-1].update(coverage)
         if verbose:
             print(history[-1], flush=True)
     return history
@@ -165,9 +198,12 @@ if __name__ == "__main__":
     ap.add_argument("--resample-starts", action="store_true",
                     help="after every reset inside the model rollouts draw the env's next start state from the true buffer (MBPO's "
                          "branched rollouts) instead of returning to the same state every time")
+    ap.add_argument("--calibrate", action="store_true",
+                    help="calibrate the members' spread on the fit's held-out rows and report the coverage before and after; with "
+                         "--optimistic the model system uses beta * calibration")
     ap.add_argument("--optimistic", type=float, default=None, metavar="BETA",
                     help="hallucinated control: the policy also picks the model's next state inside mean +- BETA * (std over members)")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
         terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
-        resample_starts=a.resample_starts, optimistic=a.optimistic)
+        resample_starts=a.resample_starts, optimistic=a.optimistic, calibrate=a.calibrate)

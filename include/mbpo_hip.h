@@ -743,6 +743,38 @@ int mbpo_ens_scaler_prepare(const float *rows, int64_t n_rows, int32_t row_len, 
 int mbpo_ens_fold_scaler(const float *params, int64_t n_params, int32_t n_members, int32_t dims0, int32_t dims1, const float *scaler,
                          float *out_params, void *stream);
 
+/* ---- N3d: calibration of the ensemble's spread on held-out rows (the statistical-model package the reference declares — `bsm`, in
+ * setup.py, never imported — recalibrates after every fit; restated from its procedure as remembered, unverified against its code,
+ * so the definition below is the authority; the reference has no model).  Per output dimension c one factor calibration[c] is picked
+ * from a grid so that the intervals built from calibration[c] * sd_c, sd the population std of the members' means (the sd the
+ * hallucinated rollouts form), cover the held-out targets as often as a Gaussian's would at P levels.  No kernel above changes: the
+ * result reaches the rollouts as halluc_beta = beta * calibration, formed by the caller.
+ * Inputs: y[e][k][c], e < n_members, k < n, c < x_dim: the members' mean heads, dense [n_members][n][y_stride], y_stride >= x_dim (the
+ * columns past x_dim are never read).  Row k is rows[idx[k]] of rows[n_rows][row_len], or rows[k] with idx == NULL (then n <= n_rows);
+ * an idx entry outside [0, n_rows) is clamped into it.  alphas[n_alphas]: the candidate factors; level_q[n_levels]: the thresholds
+ * of the levels, strictly increasing (the caller's contract: for the equispaced levels p_j = j / (P + 1), j = 1..P, level_q[j - 1] =
+ * 2 erfinv(p_j)^2, the chi-square(1) quantile; no kernel evaluates a quantile function); scale[x_dim] or NULL (all ones).
+ * Statistic of (k, c), every operation a single rounded fp32 operation (no fused multiply-add):
+ *   t  = row[next_obs_off + c] - (predict_delta ? row[c] : 0)
+ *   m  = (sum_e y[e][k][c]) / n_members, summed in member order from 0.0f
+ *   v  = (sum_e (y[e][k][c] - m)^2) / n_members     (two-pass; the square of the rollouts' sd, no square root taken)
+ *   d2 = (t - m)^2
+ * counts[c][a][j] = #{k : d2 <= (((alphas[a] * scale[c])^2) * level_q[j]) * v}, an IEEE comparison: a NaN on either side is "not
+ * covered", and v == 0 covers only d2 == 0 (and nothing where the factor in front of it overflowed to inf).  int32 [x_dim][A][P].
+ * Selection, exact in int64:  S[c][a] = sum_{j = 1..P} (counts[c][a][j - 1] * (P + 1) - j * n)^2;  best_idx[c] = argmin_a S[c][a],
+ * ties to the lower index;  calibration[c] = alphas[best_idx[c]] * scale[c].
+ * One memset and two launches on the stream, capturable into a hipGraph.  The entry point zeroes counts itself and accumulates in it
+ * with integer atomics, whose sum does not depend on their order: two calls give the same bits.  It takes no caller-owned scratch.
+ * counts, best_idx [x_dim] and calibration [x_dim] are overwritten in full.
+ * MBPO_ERR_ARG, before any device use: a null pointer (idx and scale may be NULL), n, n_rows, row_len, n_members, n_alphas, n_levels
+ * or x_dim <= 0, y_stride < x_dim, next_obs_off < 0 or next_obs_off + x_dim > row_len, n > n_rows without idx, and
+ * n * (n_levels + 1) > 2^28 (so that S cannot overflow).  MBPO_ERR_UNSUPPORTED: n_levels > 127, x_dim > 65535, n_alphas * n_levels >
+ * 2^24 or x_dim * n_alphas * n_levels > 2^29. */
+int mbpo_ens_calibrate(const float *y, int32_t n_members, int64_t n, int32_t y_stride, const float *rows, int64_t n_rows,
+                       int32_t row_len, const int32_t *idx, int32_t x_dim, int32_t next_obs_off, int32_t predict_delta,
+                       const float *alphas, int32_t n_alphas, const float *level_q, int32_t n_levels, const float *scale,
+                       int32_t *counts, int32_t *best_idx, float *calibration, void *stream);
+
 /* ---- N4: iCEM trajectory optimizer, device side (trajectory_optimizers/icem_optimizer.py:135-252) ---------------------
  * One iteration = mbpo_icem_sample -> mbpo_model_rollout(actions = the sampled sequences) -> mbpo_icem_update.
  * mbpo_icem_sample: coloured noise (utils/general_utils.py:81-208, powerlaw_psd_gaussian, as a direct inverse real DFT; Philox

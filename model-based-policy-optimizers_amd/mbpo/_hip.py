@@ -298,6 +298,8 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_ens_scaler_prepare.argtypes = [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.mbpo_ens_fold_scaler.restype = C.c_int
     lib.mbpo_ens_fold_scaler.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp]
+    lib.mbpo_ens_calibrate.restype = C.c_int
+    lib.mbpo_ens_calibrate.argtypes = [vp, i32, i64, i32, vp, i64, i32, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     u64 = C.c_uint64
     lib.mbpo_icem_sample.restype = C.c_int
     lib.mbpo_icem_sample.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, u64, u64, vp, vp, vp, vp]

@@ -1502,3 +1502,73 @@ def ens_fold_scaler(params: torch.Tensor, n_members: int, dims0: int, dims1: int
     check(lib.mbpo_ens_fold_scaler(params.data_ptr(), params.numel() // n_members, n_members, dims0, dims1, scaler.data_ptr(),
                                    out.data_ptr(), current_stream_ptr()), "mbpo_ens_fold_scaler")
     return out
+
+
+# ---- calibration of the ensemble's spread (N3d; csrc/ens_calibrate.hip) ------------------------------------------------------
+CAL_N_ALPHAS, CAL_ALPHA_ONE = 61, 20          # the default grid: alphas[a] = 10^((a - 20) / 20), 0.1 .. 100; alphas[20] is exactly 1
+_cal_const = {}                                # (kind, device, ...) -> device tensor: nothing is copied host to device on a later call
+
+
+def calibration_alphas() -> torch.Tensor:
+    """The default candidate factors (host, fp32): 61 values 10^((a - 20) / 20), computed in float64 and cast."""
+    a = torch.arange(CAL_N_ALPHAS, dtype=torch.float64)
+    return torch.pow(torch.tensor(10.0, dtype=torch.float64), (a - CAL_ALPHA_ONE) / 20.0).to(torch.float32)
+
+
+def calibration_levels(n_levels: int) -> torch.Tensor:
+    """level_q (host, fp32) of the equispaced levels p_j = j / (P + 1), j = 1..P: 2 erfinv(p_j)^2 in float64, cast."""
+    p = torch.arange(1, n_levels + 1, dtype=torch.float64) / (n_levels + 1)
+    return (2.0 * torch.erfinv(p) ** 2).to(torch.float32)
+
+
+def _cal_cached(key, make, device) -> torch.Tensor:
+    k = (*key, str(device))
+    if k not in _cal_const:
+        _cal_const[k] = make().to(device).contiguous()
+    return _cal_const[k]
+
+
+def ens_calibrate(y_members: torch.Tensor, rows: torch.Tensor, x_dim: int, u_dim: int, *, idx: Optional[torch.Tensor] = None,
+                  next_obs_off: Optional[int] = None, predict_delta: bool = True, alphas: Optional[torch.Tensor] = None,
+                  n_levels: int = 19, scale: Optional[torch.Tensor] = None, out=None):
+    """mbpo_ens_calibrate: (calibration [x] f32, best_idx [x] i32, counts [x, A, P] i32), all on the device, nothing read back.
+    y_members [E, n, >= x_dim]: the members' outputs on rows[idx] (idx int32 [n]; None: rows[:n]); the first x_dim columns are the
+    mean heads.  alphas: the candidate factors (None: calibration_alphas(); a sequence or host tensor is copied to the device, a
+    device tensor is used as it is); the levels are the n_levels equispaced ones.  scale [x] multiplies every alpha per dimension.
+    out: (calibration, best_idx, counts) to write into.  The default grid and the levels are cached per device, so a call with
+    device tensors only launches (capturable)."""
+    lib = load()
+    _req(y_members, "y_members"); _req(rows, "rows")
+    if y_members.dim() != 3 or rows.dim() != 2 or y_members.shape[2] < x_dim:
+        raise ValueError("y_members must be [E, n, >= x_dim] and rows [R, D]")
+    E, n, y_stride = (int(v) for v in y_members.shape)
+    dev = y_members.device
+    if idx is not None:
+        _req(idx, "idx", torch.int32)
+        if idx.dim() != 1 or idx.numel() != n:
+            raise ValueError("idx must be [n], one entry per row of y_members")
+    if n_levels <= 0:
+        raise ValueError("n_levels must be positive")
+    if alphas is None:
+        alphas = _cal_cached(("alphas",), calibration_alphas, dev)
+    elif not (isinstance(alphas, torch.Tensor) and alphas.is_cuda):
+        alphas = torch.as_tensor(alphas, dtype=torch.float32).reshape(-1).to(dev)
+    _req(alphas, "alphas")
+    level_q = _cal_cached(("levels", int(n_levels)), lambda: calibration_levels(int(n_levels)), dev)
+    if scale is not None:
+        _req(scale, "scale")
+        if scale.numel() != x_dim:
+            raise ValueError("scale must be [x_dim]")
+    A, P = int(alphas.numel()), int(n_levels)
+    if out is None:
+        out = (torch.empty(x_dim, device=dev, dtype=torch.float32), torch.empty(x_dim, device=dev, dtype=torch.int32),
+               torch.empty(x_dim, A, P, device=dev, dtype=torch.int32))
+    calibration, best_idx, counts = out
+    _req(calibration, "calibration"); _req(best_idx, "best_idx", torch.int32); _req(counts, "counts", torch.int32)
+    if calibration.numel() != x_dim or best_idx.numel() != x_dim or counts.numel() != x_dim * A * P:
+        raise ValueError("out must be (calibration [x], best_idx [x], counts [x, A, P])")
+    check(lib.mbpo_ens_calibrate(y_members.data_ptr(), E, n, y_stride, rows.data_ptr(), rows.shape[0], rows.shape[1], ptr(idx), x_dim,
+                                 x_dim + u_dim + 2 if next_obs_off is None else int(next_obs_off), int(bool(predict_delta)),
+                                 alphas.data_ptr(), A, level_q.data_ptr(), P, ptr(scale), counts.data_ptr(), best_idx.data_ptr(),
+                                 calibration.data_ptr(), current_stream_ptr()), "mbpo_ens_calibrate")
+    return calibration, best_idx, counts

@@ -31,6 +31,12 @@ of [x, u] on the training rows (mbpo_ens_scaler_fit), trains on a matrix prepare
 (mbpo_ens_scaler_prepare) — and leaves EnsembleDynamicsParams.params in NORMALISED coordinates.  Consumers never normalise: they run
 folded_params, the same members with the scaler folded into the first Dense layer (mbpo_ens_fold_scaler; W' = diag(1/std) W,
 b' = b - W'^T mean), on raw inputs — the same affine map, so no rollout, planning or BPTT kernel knows about the scaler.
+
+Calibration (what the reference's declared-but-unimported `bsm` does after a fit; restated as remembered, so include/mbpo_hip.h "N3d"
+is the definition): `calibrate` / `fit(calibrate=True)` pick one factor per state dimension on held-out rows (mbpo_ens_calibrate) so
+that mean +- z * calibration * std_e(mu_e) covers the true next state as often as a Gaussian's interval would, at 19 levels;
+`coverage` reads the covered fractions.  EnsembleSystem(mode="optimistic", calibrated=True) then hands the kernels
+halluc_beta = beta * calibration, and next_state reports std = sqrt(E[sigma^2] + calibration^2 Var[mu]).
 """
 from __future__ import annotations
 
@@ -64,13 +70,19 @@ class EnsembleDynamicsParams:
     scaler, when set, says that `params` live in normalised input coordinates (they are what `fit` trains and `evaluate` scores) and
     that every consumer runs folded_params instead: a COPY of params with the scaler folded into layer one, taken at the end of
     `fit(normalize_inputs=True)` and by `select_elites` / `EnsembleDynamics.fold`.  Changing params or scaler by hand leaves it stale
-    until `fold` is called; elite_params of a scaler-bearing object are picked from folded_params and go stale the same way."""
+    until `fold` is called; elite_params of a scaler-bearing object are picked from folded_params and go stale the same way.
+
+    calibration, when set, holds one factor per state dimension for the spread of the members the rollouts used WHEN IT WAS PICKED
+    (`calibrate`, `fit(calibrate=True)`): a later `fit`, `fold` or elite selection without a new `calibrate` leaves it stale, as
+    elite_params goes stale; `calibrate` rewrites the tensor in place, so consumers that hold it see the new factors.  Set it to None
+    to report and roll out the uncalibrated spread again."""
     params: torch.Tensor          # flat [E * P] device tensor (layout: include/mbpo_hip.h)
     elite_idx: Optional[torch.Tensor] = None       # int32 [n_elites]: the members the rollouts use, best first
     elite_params: Optional[torch.Tensor] = None    # [n_elites * P]
     holdout: Optional[torch.Tensor] = None         # [2, E]: held-out (NLL, squared error) of the members fit(holdout_ratio=) kept
     scaler: Optional[torch.Tensor] = None          # [2, x+u]: (mean; std) of the training inputs, fit(normalize_inputs=True)
     folded_params: Optional[torch.Tensor] = None   # [E * P]: params with the scaler folded into layer one (what consumers run)
+    calibration: Optional[torch.Tensor] = None     # [x_dim]: the factor on the members' spread picked on held-out rows (calibrate)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -139,7 +151,7 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             min_std: float = 1e-3, n_rows: Optional[int] = None, next_obs_off: Optional[int] = None,
             reward_off: Optional[int] = None, holdout_ratio: float = 0.0, max_holdout: int = 5000, eval_every: Optional[int] = None,
             max_evals_since_improvement: int = 5, rel_tol: float = 0.01, n_elites: Optional[int] = None,
-            normalize_inputs: bool = False, scaler_std_floor: float = ops.SCALER_STD_FLOOR):
+            normalize_inputs: bool = False, scaler_std_floor: float = ops.SCALER_STD_FLOOR, calibrate: bool = False):
         """Model learning (N3 — not in the reference, whose model would come from `bsm`): `num_steps` AdamW steps on the
         members' Gaussian negative log-likelihood, each member on its own bootstrapped minibatch (sampling with replacement
         from rows[:n_rows]; Philox randint on the device).  `rows` are true-buffer transition rows (obs, action, reward,
@@ -159,7 +171,11 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         target delta-encoded as `predict_delta` says, columns [x, u | reward | target] — so the steps above run unchanged on the
         prepared matrices and the scaler costs nothing per step.  dynamics_params.params are then in normalised coordinates;
         dynamics_params.scaler = the scaler and dynamics_params.folded_params = the members every consumer runs on raw inputs (`fold`);
-        the elites are picked from folded_params.  A refit refits the scaler on the new rows and continues from the same weights."""
+        the elites are picked from folded_params.  A refit refits the scaler on the new rows and continues from the same weights.
+
+        calibrate (needs a holdout: factors picked on training rows would be biased): after the snapshots are restored, and after the
+        fold and the elite selection if any, `self.calibrate` runs on the RAW held-out rows with this fit's predict_delta and
+        next_obs_off, through the members the rollouts use; dynamics_params.calibration = its factors.  False changes nothing."""
         dev = self.device
         if dynamics_params.scaler is not None and not normalize_inputs:
             raise ValueError("these parameters were fitted on normalised inputs (scaler is set): refit with normalize_inputs=True")
@@ -169,6 +185,8 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             reward_off = self.x_dim + self.u_dim
         if n_elites is not None and not holdout_ratio > 0:
             raise ValueError("n_elites needs a holdout (holdout_ratio > 0): the elites are picked by held-out error")
+        if calibrate and not holdout_ratio > 0:
+            raise ValueError("calibrate needs a holdout (holdout_ratio > 0): factors picked on the training rows are biased")
         rows = rows.to(dev, torch.float32).contiguous()
         R = int(rows.shape[0] if n_rows is None else n_rows)
         if R <= 0:
@@ -258,6 +276,8 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             members = self.fold(dynamics_params).folded_params
         if n_elites is not None:
             dynamics_params.elite_idx, dynamics_params.elite_params = ops.ens_pick_elites(members, E, holdout[1], n_elites)
+        if calibrate:
+            self.calibrate(dynamics_params, rows, idx=perm[:n_hold], next_obs_off=next_obs_off, predict_delta=predict_delta)
         return dynamics_params, losses[:steps_run]
 
     def fold(self, dynamics_params: EnsembleDynamicsParams) -> EnsembleDynamicsParams:
@@ -335,6 +355,50 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
             return self._consumer_params(dynamics_params), self.spec
         return dynamics_params.elite_params, self.elite_spec(int(dynamics_params.elite_idx.numel()))
 
+    def _calibration_call(self, dynamics_params, rows, idx, next_obs_off, predict_delta, alphas, n_levels, scale):
+        """The rollouts' members on the raw [x, u] of rows[idx], then mbpo_ens_calibrate: (calibration, best_idx, counts, n)."""
+        params, spec = self._rollout_members(dynamics_params)
+        if spec.n_nets < 2:
+            raise ValueError("calibration needs at least 2 rollout members: the spread of one member is identically zero")
+        rows = rows.to(self.device, torch.float32).contiguous()
+        if idx is not None:
+            idx = idx.to(self.device, torch.int32).contiguous()
+        xu = (rows if idx is None else rows[idx.long()])[:, :self.x_dim + self.u_dim].contiguous()
+        y = ops.ensemble_mlp_forward(params, spec, xu)
+        cal, best, counts = ops.ens_calibrate(y, rows, self.x_dim, self.u_dim, idx=idx, next_obs_off=next_obs_off,
+                                              predict_delta=predict_delta, alphas=alphas, n_levels=n_levels, scale=scale)
+        return cal, best, counts, int(xu.shape[0])
+
+    def calibrate(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                  next_obs_off: Optional[int] = None, predict_delta: bool = True, alphas=None, n_levels: int = 19,
+                  return_counts: bool = False):
+        """Pick dynamics_params.calibration ([x_dim], on the device) on rows[idx] (true-buffer transition rows the members were NOT
+        fitted on; idx None: all rows): the members the rollouts use — the elites when selected, the folded members with a scaler —
+        run on the raw [x, u] and mbpo_ens_calibrate picks, per state dimension, the factor of `alphas` (default: 61 values from 0.1 to
+        100) whose intervals' coverage at the n_levels equispaced levels is closest to nominal (include/mbpo_hip.h "N3d").  The
+        existing tensor is rewritten in place.  Nothing is read back.  Returns dynamics_params (return_counts: also best_idx and
+        counts [x, A, P])."""
+        cal, best, counts, _ = self._calibration_call(dynamics_params, rows, idx, next_obs_off, predict_delta, alphas, n_levels, None)
+        old = dynamics_params.calibration
+        if old is not None and old.shape == cal.shape and old.device == cal.device and old.dtype == cal.dtype:
+            old.copy_(cal)                       # in place: a system that caches beta * calibration sees the tensor's version change
+        else:
+            dynamics_params.calibration = cal
+        return (dynamics_params, best, counts) if return_counts else dynamics_params
+
+    def coverage(self, dynamics_params: EnsembleDynamicsParams, rows: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                 next_obs_off: Optional[int] = None, predict_delta: bool = True, n_levels: int = 19,
+                 calibrated: bool = True) -> torch.Tensor:
+        """[x_dim, n_levels] float: the fraction of rows[idx] whose true next state lies inside the interval of level p_j =
+        j / (n_levels + 1) around the members' mean, per state dimension — nominal coverage is p_j.  calibrated: the intervals are
+        scaled by dynamics_params.calibration when one is set (else, or with False, the raw spread).  The same kernel as `calibrate`,
+        at the single factor 1."""
+        scale = dynamics_params.calibration if calibrated else None
+        if scale is not None:
+            scale = scale.to(self.device, torch.float32).contiguous()
+        _, _, counts, n = self._calibration_call(dynamics_params, rows, idx, next_obs_off, predict_delta, [1.0], n_levels, scale)
+        return counts[:, 0, :].to(torch.float32) / n
+
     def member_outputs(self, x: torch.Tensor, u: torch.Tensor, dynamics_params: EnsembleDynamicsParams,
                        elites: bool = False) -> torch.Tensor:
         """[E, N, 2*x_dim] raw member outputs (+ [mu_r, raw_r] with learn_reward) — mbpo_ensemble_mlp_forward.  All members, also
@@ -345,13 +409,17 @@ class EnsembleDynamics(Dynamics[EnsembleDynamicsParams]):
         return ops.ensemble_mlp_forward(params, spec, xu)
 
     def next_state(self, x, u, dynamics_params, predict_delta: bool = True, min_std: float = 1e-3):
-        """Mixture moments over members (the elites when selected): mean = E_e[mu_e], std = sqrt(E_e[sigma_e^2] + Var_e[mu_e])."""
+        """Mixture moments over members (the elites when selected): mean = E_e[mu_e], std = sqrt(E_e[sigma_e^2] + Var_e[mu_e]); with a
+        calibration set, std = sqrt(E_e[sigma_e^2] + calibration^2 Var_e[mu_e])."""
         y = self.member_outputs(x, u, dynamics_params, elites=True)
         X = self.x_dim
         mu = y[..., :X] + (x.reshape(-1, X) if predict_delta else 0.0)
         sig = torch.nn.functional.softplus(y[..., X:2 * X]) + min_std
         mean = mu.mean(dim=0)
-        std = torch.sqrt((sig ** 2).mean(dim=0) + mu.var(dim=0, unbiased=False))
+        var_mu = mu.var(dim=0, unbiased=False)
+        if dynamics_params.calibration is not None:
+            var_mu = dynamics_params.calibration.to(var_mu.device, torch.float32) ** 2 * var_mu
+        std = torch.sqrt((sig ** 2).mean(dim=0) + var_mu)
         if x.dim() == 1:
             mean, std = mean[0], std[0]
         return Normal(mean, std), dynamics_params
@@ -404,10 +472,14 @@ class EnsembleSystem(System):
     u_dim + x_dim is what the policy emits, the model's rows carry and SAC's critics see: an action is [u | eta] and the next state is
     mean + beta * std_over_members * eta.  beta: a float or a length-x_dim sequence / tensor.  env_action(a) cuts the controls out
     for the true system.  The reward is unchanged (eta never enters it).  Out of scope and refused: BPTT (the gradient through the
-    spread is not built), SAC's real_ratio > 0 (real rows carry u_dim action columns, model rows action_dim), members wider than 256."""
+    spread is not built), SAC's real_ratio > 0 (real rows carry u_dim action columns, model rows action_dim), members wider than 256.
+    calibrated=True (optimistic only): the kernels get halluc_beta = beta * dynamics_params.calibration, one fp32 multiply on the
+    device into a buffer the system keeps, refreshed when the calibration tensor or its contents change; `beta` stays the user's
+    value.  rollout_spec refuses parameters without a calibration (run `calibrate` or `fit(calibrate=True)` first)."""
 
     def __init__(self, dynamics: EnsembleDynamics, reward: Reward, mode: str = "mean", predict_delta: bool = True,
-                 sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None, beta=1.0):
+                 sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None, beta=1.0,
+                 calibrated: bool = False):
         super().__init__(dynamics=dynamics, reward=reward)
         if termination is not None and termination.x_dim != dynamics.x_dim:
             raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {dynamics.x_dim}")
@@ -423,6 +495,9 @@ class EnsembleSystem(System):
                 raise ValueError(f"LearnedReward.min_std {reward.min_std} differs from the system's min_std {min_std}")
         self.mode, self.predict_delta, self.sample_noise, self.min_std = mode, predict_delta, sample_noise, min_std
         self.optimistic = mode == "optimistic"
+        self.calibrated = bool(calibrated)
+        if self.calibrated and not self.optimistic:
+            raise ValueError("calibrated=True scales the hallucinated control's beta: it needs mode='optimistic'")
         self.beta = None
         if self.optimistic:
             if dynamics.kernel_width is None:
@@ -434,6 +509,7 @@ class EnsembleSystem(System):
                 raise ValueError(f"beta must be a float or hold x_dim = {dynamics.x_dim} values, got {b.numel()}")
             self.beta = b.clone()
             self._beta_dev = {}
+            self._beta_cal = {}                  # device -> [buffer of beta * calibration, (calibration's data_ptr, version)]
 
     @property
     def action_dim(self) -> int:
@@ -450,6 +526,21 @@ class EnsembleSystem(System):
             self._beta_dev[k] = self.beta.to(device).contiguous()
         return self._beta_dev[k]
 
+    def _calibrated_beta(self, device, dynamics_params) -> torch.Tensor:
+        """beta * calibration in a buffer that lives as long as the system (one per device: the pointer a captured step holds stays
+        valid), multiplied again only when the calibration is another tensor or was written to since."""
+        cal = dynamics_params.calibration.to(device, torch.float32)
+        if cal.numel() != self.x_dim:
+            raise ValueError(f"the calibration must hold x_dim = {self.x_dim} values, got {cal.numel()}")
+        k, tag = str(device), (cal.data_ptr(), cal._version)
+        if k not in self._beta_cal:
+            self._beta_cal[k] = [torch.empty(self.x_dim, device=device, dtype=torch.float32), None]
+        slot = self._beta_cal[k]
+        if slot[1] != tag:
+            torch.mul(self._halluc_beta(device), cal.reshape(-1), out=slot[0])
+            slot[1] = tag
+        return slot[0]
+
     def init_params(self, key: int) -> SystemParams:
         if not isinstance(self.reward, LearnedReward):
             return super().init_params(key)
@@ -459,6 +550,9 @@ class EnsembleSystem(System):
 
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         rp = system_params.reward_params
+        if self.calibrated and system_params.dynamics_params.calibration is None:      # (refused before anything touches the device)
+            raise ValueError("calibrated=True but these dynamics parameters have no calibration: run EnsembleDynamics.calibrate "
+                             "(or fit(..., calibrate=True)) first")
         # (the learned reward has no parameter vector: its params hold a device tensor, whose repr would copy it to the host)
         # (the termination's device tensors are cached per device by BoxTermination.kernel_spec itself; its key here only makes the
         # spec's cache key change with the bounds)
@@ -473,5 +567,6 @@ class EnsembleSystem(System):
         return dict(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dyn_params, dyn_spec=dyn_spec,
                     ens_mode=_MODES[self.mode], ens_predict_delta=self.predict_delta, ens_sample_noise=self.sample_noise,
                     ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec,
-                    **({"halluc_beta": self._halluc_beta(device)} if self.optimistic else {}),
+                    **({"halluc_beta": self._calibrated_beta(device, system_params.dynamics_params) if self.calibrated
+                        else self._halluc_beta(device)} if self.optimistic else {}),
                     **termination_spec(self.termination, self.x_dim, device))

@@ -513,6 +513,62 @@ def main():
     if want("ens_scaler_case"): attempt(ens_fold_case, 7, (200, 200, 200, 200), 100)
     if want("ens_scaler_case"): attempt(ens_scaler_mse_case, 500)
 
+    # ---------------------------------------------------------------- N3d: calibration of the ensemble's spread (once per fit)
+    # mbpo_ens_calibrate (memset + count + pick) on n held-out rows at the default grid, next to the member forward that produces its
+    # input and to mbpo_ens_eval on the same rows and members.  Reported, not tuned.
+    def ens_calibrate_case(n, X, U, E, hid, reps):
+        from mbpo.systems import EnsembleDynamics
+        dyn = EnsembleDynamics(X, U, n_members=E, hidden_layer_sizes=hid, device=dev)
+        p = dyn.init_params(0)
+        rows = torch.randn(8192, 2 * X + U + 2, generator=g).to(dev)
+        idx = torch.randperm(8192, generator=g)[:n].to(torch.int32).to(dev)
+        xu = rows[idx.long(), :X + U].contiguous()
+        y = ops.ensemble_mlp_forward(p.params, dyn.spec, xu)
+        A, P = ops.CAL_N_ALPHAS, 19
+        outs = (torch.empty(X, device=dev), torch.empty(X, device=dev, dtype=torch.int32), torch.empty(X, A, P, device=dev, dtype=torch.int32))
+        ev = ops.EnsembleEval(x_dim=X, u_dim=U, spec=dyn.spec, device=dev)
+        t, te = both(lambda: ops.ens_calibrate(y, rows, X, U, idx=idx, out=outs), reps)
+        tf, _ = both(lambda: ops.ensemble_mlp_forward(p.params, dyn.spec, xu), reps)
+        tv, _ = both(lambda: ev(p.params, rows, idx), reps)
+        out.append({"kernel": "memset + k_ens_cal_count + k_ens_cal_pick", "entry": "mbpo_ens_calibrate",
+                    "config": {"n": n, "x": X, "u": U, "E": E, "A": A, "P": P, "member": list(hid), "group": "ens_calibrate"},
+                    "device_us": t * 1e6, "eager_us": te * 1e6, "forward_device_us": tf * 1e6, "ens_eval_device_us": tv * 1e6,
+                    "calibrate_over_forward_plus_eval": t / (tf + tv), "comparisons": n * X * A * P,
+                    "comparisons_per_s": n * X * A * P / t, "global_atomics_at_most": -(-n // 512) * X * A * P})
+        log(f"ens_calibrate n={n} x={X} E={E} A={A} P={P}: {t * 1e6:.1f} us (eager {te * 1e6:.1f} us); forward {tf * 1e6:.1f} us; "
+            f"ens_eval {tv * 1e6:.1f} us")
+
+    # Evidence, not a test: Pendulum, 7 members, 5 elites, 4000 true transitions with a 20 % holdout; coverage of the intervals at the
+    # 0.5 and 0.9 levels on 2000 FRESH transitions, raw spread and calibrated.
+    def ens_calibrate_coverage_case(steps, seed):
+        from mbpo.systems import EnsembleDynamics, PendulumSystem
+        system = PendulumSystem()
+        gg = torch.Generator().manual_seed(seed)
+
+        def draw(n):
+            th = (torch.rand(n, generator=gg) * 2 - 1) * math.pi
+            x = torch.stack([torch.cos(th), torch.sin(th), (torch.rand(n, generator=gg) * 2 - 1) * 8], 1).to(dev)
+            u = (torch.rand(n, 1, generator=gg) * 2 - 1).to(dev)
+            nxt = system.step(x, u, system.reset().system_params)
+            return torch.cat([x, u, nxt.reward[:, None], torch.ones(n, 1, device=dev), nxt.x_next], 1).contiguous()
+
+        train, fresh = draw(4000), draw(2000)
+        dyn = EnsembleDynamics(3, 1, n_members=7, device=dev)
+        p, losses = dyn.fit(dyn.init_params(seed + 1), train, num_steps=steps, batch_size=256, learning_rate=3e-3, key=seed, holdout_ratio=0.2,
+                            n_elites=5, calibrate=True)
+        lv = [9, 17]
+        res = {"calibration": [float(v) for v in p.calibration], "steps_run": int(losses.shape[0]), "levels": [0.5, 0.9],
+               "coverage_fresh_before": dyn.coverage(p, fresh, calibrated=False)[:, lv].tolist(),
+               "coverage_fresh_after": dyn.coverage(p, fresh, calibrated=True)[:, lv].tolist()}
+        log(f"calibration evidence (seed {seed}): {res}")
+        out.append({"kernel": "EnsembleDynamics.fit(calibrate=True) + coverage on fresh rows (evidence, unasserted)", "entry": "mbpo_ens_calibrate",
+                    "config": {"rows": 4000, "holdout_ratio": 0.2, "rows_fresh": 2000, "E": 7, "n_elites": 5, "steps": steps, "batch": 256,
+                               "lr": 3e-3, "seed": seed, "data": "Pendulum, uniform states and actions", "group": "ens_calibrate"}, **res})
+
+    if want("ens_calibrate_case"): attempt(ens_calibrate_case, 5000, 17, 6, 7, (64, 64, 64), 100)
+    if want("ens_calibrate_case"): attempt(ens_calibrate_case, 5000, 3, 1, 7, (64, 64, 64), 100)
+    if want("ens_calibrate_case"): attempt(ens_calibrate_coverage_case, 1500, 0)
+
     # ---------------------------------------------------------------- N4: iCEM planner at the reference's defaults (icem_optimizer.py:25-50)
     def icem_case(H, reps):
         from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
