@@ -7,6 +7,7 @@
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
                                      [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA] [--calibrate]
+                                     [--warm-start [--retain-buffer]]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -31,6 +32,12 @@ beta * (std over members) * eta, anywhere inside the ensemble's confidence set; 
 state dimension, EnsembleDynamics.calibrate); with --optimistic the model system is built with calibrated=True, so the policy moves
 the state inside mean +- BETA * calibration * std.  Every iteration prints the calibration vector and the coverage of the intervals at
 the 0.5 and 0.9 levels, before and after calibration, on the held-out rows and on 2000 fresh transitions.  No learning curve is claimed.
+--warm-start: MBPO's outer loop continues its learner — ONE SACOptimizer(warm_start=True) for all iterations, and the learner state
+(policy, critics, target critics, log_alpha, Adam moments and step count, observation normaliser) of one iteration's `train` is handed to
+the next in BraxState.learner_state, instead of SAC starting from a fresh initialisation after every model refit.  The optimizer keeps
+its trainer between the calls.  --retain-buffer: the model replay buffer is carried too (retain_replay_buffer=True), so an iteration
+starts on the previous iterations' model transitions and prefills nothing.  Every iteration prints its true_return.  Not with
+--terminate-speed (its reporting builds a trainer of its own).
 """
 from __future__ import annotations
 
@@ -120,11 +127,16 @@ def calibration_report(dyn, dyn_params, rows, n_rows, fit_key, true_system, dev,
 
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
-        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None, calibrate=False):
+        terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None, calibrate=False,
+        warm_start=False, retain_buffer=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
     from mbpo.types import Transition
+    if warm_start and terminate_speed is not None:
+        raise ValueError("--warm-start is not combined with --terminate-speed here: train_reporting_terminations builds its own trainer")
+    if retain_buffer and not warm_start:
+        raise ValueError("--retain-buffer needs --warm-start")
     dev = torch.device("cuda", torch.cuda.current_device())
     gen = torch.Generator().manual_seed(seed)
     true_system = PendulumSystem()
@@ -139,6 +151,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                            **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic, calibrated=calibrate)))
     dyn_params = dyn.init_params(seed + 1)
     history = []
+    optimizer, learner_state = None, None      # --warm-start: one optimizer, and the learner handed from iteration to iteration
     for it in range(iters):
         t0 = time.time()
         x, u, r, xn = collect_uniform(true_system, n_true, gen, dev)
@@ -151,21 +164,26 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                      key=seed + 10 * it, n_rows=n_rows, normalize_inputs=normalize_inputs, **fit_kw)
         coverage = calibration_report(dyn, dyn_params, true_buffer.logical_data(tbs), n_rows, seed + 10 * it, true_system, dev,
                                       verbose) if calibrate else None
-        optimizer = SACOptimizer(system=model, true_buffer=true_buffer, num_timesteps=sac_steps, num_evals=2, reward_scaling=1,
-                                 episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1, discounting=0.99,
-                                 lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=64,
-                                 max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16, deterministic_eval=True, tau=0.005,
-                                 num_env_steps_between_updates=5, real_ratio=real_ratio,
-                                 **(dict(resample_starts=True) if resample_starts else {}))
+        if optimizer is None or not warm_start:
+            optimizer = SACOptimizer(system=model, true_buffer=true_buffer, num_timesteps=sac_steps, num_evals=2, reward_scaling=1,
+                                     episode_length=10, episode_length_eval=10, normalize_observations=True, action_repeat=1,
+                                     discounting=0.99, lr_policy=3e-4, lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128,
+                                     grad_updates_per_step=64, max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16,
+                                     deterministic_eval=True, tau=0.005, num_env_steps_between_updates=5, real_ratio=real_ratio,
+                                     **(dict(resample_starts=True) if resample_starts else {}),
+                                     **(dict(warm_start=True, retain_replay_buffer=retain_buffer) if warm_start else {}))
         state = optimizer.init(key=seed + 3, true_buffer_state=tbs)
         sp = state.system_params.replace(dynamics_params=dyn_params)
         if learn_reward:
             sp = sp.replace(reward_params=dyn_params)      # the learned reward's parameters are the model's
         state = state.replace(system_params=sp)
+        if warm_start:
+            state = state.replace(learner_state=learner_state)      # None in the first iteration: a fresh initialisation
         if termination is None:
             out, shares = optimizer.train(opt_state=state), None
         else:
             out, shares = train_reporting_terminations(optimizer, state, verbose)
+        learner_state = out.optimizer_state.learner_state
         ret = true_return(true_system, optimizer, out.optimizer_state, env_action=model.env_action)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
                             seconds=time.time() - t0))
@@ -178,6 +196,10 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
             history[-1].update(coverage)
         if verbose:
             print(history[-1], flush=True)
+            if warm_start:
+                print(f"iteration {it}: true_return {ret:.1f} (SAC optimizer steps so far: {int(learner_state.step_count)})", flush=True)
+    if warm_start:
+        optimizer.close()
     return history
 
 
@@ -203,7 +225,12 @@ if __name__ == "__main__":
                          "--optimistic the model system uses beta * calibration")
     ap.add_argument("--optimistic", type=float, default=None, metavar="BETA",
                     help="hallucinated control: the policy also picks the model's next state inside mean +- BETA * (std over members)")
+    ap.add_argument("--warm-start", action="store_true",
+                    help="one SACOptimizer(warm_start=True) for all iterations: every iteration continues the previous one's learner")
+    ap.add_argument("--retain-buffer", action="store_true",
+                    help="with --warm-start: carry the model replay buffer from iteration to iteration too")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
         terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
-        resample_starts=a.resample_starts, optimistic=a.optimistic, calibrate=a.calibrate)
+        resample_starts=a.resample_starts, optimistic=a.optimistic, calibrate=a.calibrate, warm_start=a.warm_start,
+        retain_buffer=a.retain_buffer)

@@ -1,5 +1,9 @@
 """BraxOptimizer / SACOptimizer / PPOOptimizer — mirrors mbpo/optimizers/policy_optimizers/brax_optimizers.py:21-115
-(same constructor signatures, `init` / `act` / `train` semantics and key-split structure)."""
+(same constructor signatures, `init` / `act` / `train` semantics and key-split structure).
+
+Not in the reference (its SAC and PPO optimizers start every `train` from a fresh initialisation; its BPTT optimizer carries its
+state): warm_start=True carries the learner from one `train` to the next in BraxState.learner_state and keeps the trainer, with
+its captured training step, between the calls (DESIGN "warm start")."""
 from __future__ import annotations
 
 import dataclasses
@@ -19,6 +23,7 @@ from mbpo.utils.type_aliases import OptimizerState, OptimizerTrainingOutPut
 @dataclass
 class BraxState(OptimizerState):
     policy_params: Any = None          # (normalizer_params, policy_params)  (brax_optimizers.py:69-72)
+    learner_state: Any = None          # brax_utils.base.LearnerState with warm_start=True, else None (not in the reference)
 
 
 @dataclass
@@ -28,10 +33,19 @@ class BraxOutput(OptimizerTrainingOutPut):
 
 
 class BraxOptimizer(BaseOptimizer):
-    def __init__(self, agent_class, true_buffer: UniformSamplingQueue, system: Optional[System] = None, **agent_kwargs):
+    def __init__(self, agent_class, true_buffer: UniformSamplingQueue, system: Optional[System] = None, warm_start: bool = False,
+                 retain_replay_buffer: bool = False, **agent_kwargs):
+        """warm_start: `train` resumes the learner of opt_state.learner_state (None: the first call, a fresh initialisation) and
+        returns the new one in optimizer_state.learner_state; the trainer is kept between calls until close().
+        retain_replay_buffer (SAC, needs warm_start): the learner state also carries the model replay buffer, by reference."""
+        if retain_replay_buffer and not warm_start:
+            raise ValueError("retain_replay_buffer=True needs warm_start=True: the buffer travels in the learner state")
         super().__init__(system)
         self.agent_class = agent_class
         self.agent_kwargs = agent_kwargs
+        self.warm_start = bool(warm_start)
+        self.retain_replay_buffer = bool(retain_replay_buffer)
+        self._trainer = None               # warm_start: the trainer kept between train() calls
         self.true_buffer = true_buffer
         if system is None:
             self.dummy_trainer = None
@@ -40,6 +54,7 @@ class BraxOptimizer(BaseOptimizer):
             self.set_system(system)
 
     def set_system(self, system: System):
+        self.close()                       # a kept trainer was built on the previous system
         super().set_system(system)
         self.key, sys_key, buffer_key = K.split(self.key, 3)
         dummy_true_buffer_state = self.dummy_true_buffer_state(buffer_key)
@@ -73,6 +88,8 @@ class BraxOptimizer(BaseOptimizer):
         assert self.system is not None, "Brax optimizer requires system to be defined."
         env = BraxWrapper(system=self.system, system_params=opt_state.system_params,
                           sample_buffer_state=opt_state.true_buffer_state, sample_buffer=self.true_buffer)
+        if self.warm_start:
+            return self._train_warm(opt_state, env)
         trainer = self.agent_class(environment=env, **self.agent_kwargs)
         key, new_key = K.split(opt_state.key)
         try:
@@ -82,14 +99,55 @@ class BraxOptimizer(BaseOptimizer):
         new_opt_state = opt_state.replace(policy_params=policy_params, key=new_key)
         return BraxOutput(optimizer_state=new_opt_state, summary=metrics)
 
+    def _keeps_trainer(self) -> bool:
+        """The trainer is kept for the built-in (fused) Systems on a single rank.  A user-defined System (its own code runs between
+        the kernels and may hold state of the environment it was built with) and a process group (the peer-memory regions are
+        negotiated per trainer by all ranks together) get a new trainer per call; the learner state is carried all the same."""
+        return bool(self.system.fused) and self.agent_kwargs.get("process_group") is None
+
+    def _train_warm(self, opt_state: BraxState, env: BraxWrapper) -> BraxOutput:
+        """`train` with warm_start: the same key split; the learner ALWAYS comes from opt_state (a copy of a few hundred KB), so the
+        result never depends on which trainer is alive.  A kept trainer is rebound to the new environment; whether its captured
+        step replays or is captured again is decided by the trainer's own address check, nothing here forces either."""
+        trainer, self._trainer = self._trainer, None
+        if trainer is not None:
+            trainer.rebind(env)
+        else:
+            trainer = self.agent_class(environment=env, **self.agent_kwargs)
+        key, new_key = K.split(opt_state.key)
+        try:
+            policy_params, metrics = trainer.run_training(key=new_key, learner_state=opt_state.learner_state)
+        except BaseException:
+            trainer.close()
+            raise
+        learner_state = trainer.last_learner_state
+        if not self.retain_replay_buffer:
+            learner_state = learner_state.replace(replay=None)
+        if self._keeps_trainer():
+            self._trainer = trainer
+        else:
+            trainer.close()
+        new_opt_state = opt_state.replace(policy_params=policy_params, key=new_key, learner_state=learner_state)
+        return BraxOutput(optimizer_state=new_opt_state, summary=metrics)
+
+    def close(self) -> None:
+        """Release the kept trainer (its captured graph, and the buffers the graph keeps alive)."""
+        trainer, self._trainer = self._trainer, None
+        if trainer is not None:
+            trainer.close()
+
 
 class SACOptimizer(BraxOptimizer):
-    def __init__(self, true_buffer: UniformSamplingQueue, system: Optional[System] = None, **sac_kwargs):
+    def __init__(self, true_buffer: UniformSamplingQueue, system: Optional[System] = None, warm_start: bool = False,
+                 retain_replay_buffer: bool = False, **sac_kwargs):
         from mbpo.optimizers.policy_optimizers.sac.sac import SAC
-        super().__init__(agent_class=SAC, system=system, true_buffer=true_buffer, **sac_kwargs)
+        super().__init__(agent_class=SAC, system=system, true_buffer=true_buffer, warm_start=warm_start,
+                         retain_replay_buffer=retain_replay_buffer, **sac_kwargs)
 
 
 class PPOOptimizer(BraxOptimizer):
-    def __init__(self, true_buffer: UniformSamplingQueue, system: Optional[System] = None, **ppo_kwargs):
+    def __init__(self, true_buffer: UniformSamplingQueue, system: Optional[System] = None, warm_start: bool = False, **ppo_kwargs):
         from mbpo.optimizers.policy_optimizers.ppo.ppo import PPO
-        super().__init__(agent_class=PPO, system=system, true_buffer=true_buffer, **ppo_kwargs)
+        if ppo_kwargs.get("retain_replay_buffer"):
+            raise ValueError("retain_replay_buffer: PPO keeps no replay buffer")
+        super().__init__(agent_class=PPO, system=system, true_buffer=true_buffer, warm_start=warm_start, **ppo_kwargs)

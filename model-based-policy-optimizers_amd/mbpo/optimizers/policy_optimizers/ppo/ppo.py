@@ -22,7 +22,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 import torch
 
 from mbpo import _hip, ops
-from mbpo.optimizers.policy_optimizers.brax_utils.base import State
+from mbpo.optimizers.policy_optimizers.brax_utils.base import LearnerState, State, rehome_state
 from mbpo.optimizers.policy_optimizers.sac.sac import Evaluator, RunningStatisticsState, policy_act
 from mbpo.parallel import DataParallel
 from mbpo.systems.brax_wrapper import BraxWrapper
@@ -191,6 +191,8 @@ class PPO:
         self._graph = None
         self._graph_key = None
         self._graph_refs = None
+        self.last_learner_state: Optional[LearnerState] = None      # run_training: the state at the END of the call
+        self._env_home: Optional[State] = None     # the env State tensors of the last run_training (rehome_state)
 
     # ------------------------------------------------------------------------------------------------ policy / state
     def _norm(self, normalizer_params: RunningStatisticsState):
@@ -227,6 +229,48 @@ class PPO:
         self._stats_vec.zero_()
         self._stats_vec[1 + 2 * self.x_dim:] = 1.0
         return self._training_state(0)
+
+    # ------------------------------------------------------------------------------------------------ warm start
+    def learner_signature(self) -> Dict[str, Any]:
+        """What a LearnerState must agree with before it is loaded."""
+        return dict(trainer="PPO", x_dim=int(self.x_dim), action_dim=int(self.u_dim),
+                    policy_dims_logical=[int(v) for v in self.policy_dims_logical], policy_dims=[int(v) for v in self.policy_dims],
+                    value_dims_logical=[int(v) for v in self.value_dims_logical], value_dims=[int(v) for v in self.value_dims],
+                    normalize_observations=bool(self.normalize_observations))
+
+    def export_learner_state(self, buffer_state=None) -> LearnerState:
+        """The learner as a value: clones of the flat buffers and of the normaliser vector (PPO keeps no replay buffer)."""
+        if buffer_state is not None:
+            raise ValueError("PPO has no replay buffer to carry")
+        u = self.updater
+        return LearnerState(signature=self.learner_signature(), params=u.params.clone(), adam_m=u.adam_m.clone(),
+                            adam_v=u.adam_v.clone(), step_count=u.step_count.clone(), normalizer=self._stats_vec.clone())
+
+    def load_learner_state(self, ls: LearnerState) -> TrainingState:
+        """init_training_state's counterpart for a resumed call (SAC.load_learner_state): parameters, moments, step count and
+        normaliser are copied into the flat buffers; env_steps starts at 0.  A state of another architecture is a ValueError naming
+        the field; nothing has been copied then."""
+        ls.check(self.learner_signature())
+        u = self.updater
+        for name, t, n in (("params", ls.params, u.NPV), ("step_count", ls.step_count, 1),
+                           ("normalizer", ls.normalizer, self._stats_vec.numel())):
+            if t.numel() != n:
+                raise ValueError(f"learner state does not fit this trainer: {name} holds {t.numel()} values, the trainer's {n}")
+        u.load_state(ls.params, ls.adam_m, ls.adam_v, ls.step_count.reshape(()))
+        self._stats_vec.copy_(ls.normalizer)
+        if self.dp.group is not None:      # identical replicas: rank 0's learner everywhere, as the fresh initialisation is broadcast
+            for t in (u.params, u.adam_m, u.adam_v, u.step_count, self._stats_vec):
+                self.dp.broadcast(t, src=0)
+        return self._training_state(0)
+
+    def rebind(self, environment: BraxWrapper) -> None:
+        """Point a kept trainer at the environment of the next call (SAC.rebind): system parameters, true-buffer state; the
+        evaluations run on the training env.  The captured step is left alone: training_epoch's address check decides."""
+        if environment.system is not self.env.system:
+            raise ValueError("rebind: the environment wraps another System than the one this trainer was built on")
+        if environment.sample_buffer is not self.env.sample_buffer:
+            raise ValueError("rebind: the environment samples another true buffer than the one this trainer was built on")
+        self.env = environment
 
     def _training_state(self, env_steps: int) -> TrainingState:
         u = self.updater
@@ -368,18 +412,28 @@ class PPO:
         metrics = {'training/sps': sps, **{f'training/{name}': value for name, value in metrics.items()}}
         return training_state, env_state, metrics
 
-    def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
-        """ppo.py:279-339 (ppo_brax_env.py:315-367 with return_best_model)."""
+    def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None,
+                     learner_state: Optional[LearnerState] = None):
+        """ppo.py:279-339 (ppo_brax_env.py:315-367 with return_best_model).
+
+        learner_state (not in the reference): resume instead of initialising, as SAC.run_training — the key splits of a fresh call
+        (the init sub-key is split off and left unused), load_learner_state in init_training_state's place, env_steps from 0, the
+        Adam step count continued, the envs reset as in a fresh call.  Afterwards `last_learner_state` holds the state at the end of
+        the call (the LAST one, also with return_best_model)."""
         if self.resample_starts and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
             raise ValueError("resample_starts=True draws every reset's start state from the true buffer, but it is empty")
         key, subkey = K.split(key)
-        training_state = self.init_training_state(subkey)
+        if learner_state is None:
+            training_state = self.init_training_state(subkey)
+        else:
+            training_state = self.load_learner_state(learner_state)
         key, rb_key, env_key, eval_key = K.split(key, 4)
         rk = self.dp.rank_key      # data-generating keys differ per rank; the init key above is shared (parameters are broadcast)
         if self.resample_starts:
             env_state = self.env.reset(K.split(rk(env_key), self.num_envs), resample_first_obs=True)
         else:
             env_state = self.env.reset(K.split(rk(env_key), self.num_envs))
+        env_state = rehome_state(self._env_home, env_state)
         evaluator = Evaluator(self, self.env, num_eval_envs=self.num_eval_envs, episode_length=self.episode_length,
                               action_repeat=self.action_repeat, key=eval_key)
         all_metrics: List[Metrics] = []
@@ -404,10 +458,13 @@ class PPO:
             all_metrics.append(metrics)
             progress_fn(current_step, metrics)
         last_params = self._snapshot(training_state)
+        self.last_learner_state = self.export_learner_state()
+        self._env_home = env_state
         return (best_params if self.return_best_model else last_params), all_metrics
 
     def close(self) -> None:
         self._graph = self._graph_key = self._graph_refs = None
+        self._env_home = None
         if self.p2p is not None:
             self.p2p.close()
             self.p2p = None

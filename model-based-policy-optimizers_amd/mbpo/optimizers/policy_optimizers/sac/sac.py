@@ -8,6 +8,8 @@ Where the reference has                      this file issues
   (MBPO's real_ratio, not in the reference) -> mbpo_replay_sample_mixed in the sample's place when real_ratio > 0
   lax.scan of sgd_step (:324)            ->  G x (mbpo_sac_grads [+ all-reduce] + mbpo_sac_apply)
   jit(training_epoch) (:347-361)         ->  one captured hipGraph of a training_step, replayed per step
+  init_training_state per run (:376-402) ->  the same, or with run_training(learner_state=) load_learner_state: the learner of an
+                                             earlier call continued (warm start; not in the reference's SAC)
 
 Randomness: the reference splits a threefry key per call (sac.py:289,309-311,354-356).  Here every draw of a training_step
 is Philox(seed word, (call-site id << 32) + step index, stream, element) with the seed word (the epoch / prefill key) and
@@ -26,7 +28,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from mbpo import _hip, ops
-from mbpo.optimizers.policy_optimizers.brax_utils.base import State
+from mbpo.optimizers.policy_optimizers.brax_utils.base import LearnerState, State, rehome_state
 from mbpo.parallel import DataParallel
 from mbpo.replay import ReplayBufferState, UniformSamplingQueue
 from mbpo.systems.brax_wrapper import BraxWrapper
@@ -268,6 +270,8 @@ class SAC:
         self._graph_refs = None
         self._rng = ops.make_rng(self.device)      # device uint64[2]: {key of the running epoch / prefill, step index}
         self._eval_calls = 0
+        self.last_learner_state: Optional[LearnerState] = None      # run_training: the state at the END of the call
+        self._env_home: Optional[State] = None     # the env State tensors of the last run_training (rehome_state)
 
     # ------------------------------------------------------------------------------------------------ policy
     def make_policy(self, params, deterministic: bool = False):
@@ -303,6 +307,68 @@ class SAC:
         self._stats_vec.zero_()
         self._stats_vec[1 + 2 * self.x_dim:] = 1.0      # running_statistics.init_state: std = 1
         return self._training_state(env_steps=0)
+
+    # ------------------------------------------------------------------------------------------------ warm start
+    def learner_signature(self) -> Dict[str, Any]:
+        """What a LearnerState must agree with before it is loaded."""
+        return dict(trainer="SAC", x_dim=int(self.x_dim), action_dim=int(self.u_dim),
+                    policy_dims_logical=[int(v) for v in self.policy_dims_logical], policy_dims=[int(v) for v in self.policy_dims],
+                    q_dims_logical=[int(v) for v in self.q_dims_logical], q_dims=[int(v) for v in self.q_dims],
+                    normalize_observations=bool(self.normalize_observations))
+
+    def export_learner_state(self, buffer_state: Optional[ReplayBufferState] = None) -> LearnerState:
+        """The learner as a value: clones of the flat buffers and of the normaliser vector.  `buffer_state`, when given, is carried BY
+        REFERENCE (LearnerState.replay): the next call that loads the state inserts into that buffer in place."""
+        u = self.updater
+        u.finalize()             # a pending clip check belongs to the state that is being read
+        return LearnerState(signature=self.learner_signature(), params=u.params.clone(), target_q=u.target_q.clone(),
+                            adam_m=u.adam_m.clone(), adam_v=u.adam_v.clone(), step_count=u.step_count.clone(),
+                            normalizer=self._stats_vec.clone(), replay=buffer_state)
+
+    def _check_learner_state(self, ls: LearnerState) -> None:
+        """Every refusal, before anything is copied."""
+        ls.check(self.learner_signature())
+        u = self.updater
+        for name, t, n in (("params", ls.params, u.NP), ("target_q", ls.target_q, 2 * u.Q), ("step_count", ls.step_count, 1),
+                           ("normalizer", ls.normalizer, self._stats_vec.numel())):
+            if t is None or t.numel() != n:
+                raise ValueError(f"learner state does not fit this trainer: {name} holds {None if t is None else t.numel()} values, "
+                                 f"the trainer's {n}")
+        if ls.replay is not None:
+            rows, row_len = tuple(ls.replay.data.shape)
+            if rows != self.max_replay_size:
+                raise ValueError(f"learner state does not fit this trainer: max_replay_size is {rows} in the retained buffer, "
+                                 f"{self.max_replay_size} in the trainer")
+            if row_len != self.row_len:
+                raise ValueError(f"learner state does not fit this trainer: row_len is {row_len} in the retained buffer, "
+                                 f"{self.row_len} in the trainer")
+
+    def load_learner_state(self, ls: LearnerState) -> TrainingState:
+        """init_training_state's counterpart for a resumed call: the carried parameters, target critics, moments, step count and
+        normaliser are copied into the flat buffers (env_steps starts at 0: num_timesteps is per call).  A state of another
+        architecture, or a retained buffer of another size, is a ValueError naming the field; nothing has been copied then."""
+        self._check_learner_state(ls)
+        u = self.updater
+        u.finalize()
+        u.load_state(ls.params, ls.target_q, ls.adam_m, ls.adam_v, ls.step_count.reshape(()))
+        self._stats_vec.copy_(ls.normalizer)
+        if self.dp.group is not None:      # identical replicas: rank 0's learner everywhere, as the fresh initialisation is broadcast
+            for t in (u.params, u.target_q, u.adam_m, u.adam_v, u.step_count, self._stats_vec):
+                self.dp.broadcast(t, src=0)
+        return self._training_state(env_steps=0)
+
+    def rebind(self, environment: BraxWrapper) -> None:
+        """Point a kept trainer at the environment of the next call: its system parameters (they enter through `reset`), its
+        true-buffer state, and the eval env when that is the training env.  The System and the true-buffer queue must be the objects
+        this trainer was built on — every shape here was derived from them.  The captured step is left alone: training_epoch's
+        address check decides whether it replays."""
+        if environment.system is not self.env.system:
+            raise ValueError("rebind: the environment wraps another System than the one this trainer was built on")
+        if environment.sample_buffer is not self.env.sample_buffer:
+            raise ValueError("rebind: the environment samples another true buffer than the one this trainer was built on")
+        if self.eval_env is self.env:
+            self.eval_env = environment
+        self.env = environment
 
     def _training_state(self, env_steps: int) -> TrainingState:
         u = self.updater
@@ -382,11 +448,12 @@ class SAC:
         self.updater.finalize(rng_dev=self._rng)          # + the device RNG's step counter moves on (one launch)
         return training_state, env_state, buffer_state
 
-    def prefill_replay_buffer(self, training_state: TrainingState, env_state: State, buffer_state: ReplayBufferState, key: int):
-        """sac.py:329-345."""
+    def prefill_replay_buffer(self, training_state: TrainingState, env_state: State, buffer_state: ReplayBufferState, key: int,
+                              num_steps: Optional[int] = None):
+        """sac.py:329-345.  num_steps (a resumed call on a retained buffer): that many steps instead of num_prefill_actor_steps."""
         key, new_key = K.split(key)
         self.rekey(key)
-        for _ in range(self.num_prefill_actor_steps):
+        for _ in range(self.num_prefill_actor_steps if num_steps is None else num_steps):
             _, env_state, buffer_state = self.get_experience(training_state.normalizer_params, training_state.policy_params,
                                                              env_state, buffer_state)
             ops.rng_advance(self._rng)
@@ -489,6 +556,7 @@ class SAC:
         """Release the graph and the peer-memory regions (one P2PExchange per trainer: BraxOptimizer.train builds a trainer
         per call, brax_optimizers.py:95)."""
         self._graph = self._graph_key = self._graph_refs = None
+        self._env_home = None
         if self.p2p is not None:
             self.updater.p2p = None
             self.p2p.close()
@@ -511,20 +579,39 @@ class SAC:
             return env.reset(K.split(key, n), resample_first_obs=True)
         return env.reset(K.split(key, n))
 
-    def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None):
-        """sac.py:404-494 — same order of key splits and phases."""
+    def run_training(self, key: int, progress_fn: Callable[[int, Metrics], None] = lambda *args: None,
+                     learner_state: Optional[LearnerState] = None):
+        """sac.py:404-494 — same order of key splits and phases.
+
+        learner_state (not in the reference): resume instead of initialising.  The key splits are the ones of a fresh call (the
+        sub-key of init_training_state is split off and left unused), so the env reset, the buffer key, prefill, epochs and
+        evaluations see the keys they would see in a fresh call; load_learner_state takes init_training_state's place; env_steps
+        starts at 0 and the Adam step count continues; the envs are reset as in a fresh call.  With learner_state.replay the model
+        replay buffer is that one — replay_buffer.init is skipped, and prefill runs only the steps a fresh call's arithmetic
+        (ceil(rows / num_envs)) asks for to reach min_replay_size from the carried size.
+        Afterwards `last_learner_state` holds the state at the end of the call (the LAST one, also with return_best_model), with this
+        call's replay buffer by reference."""
         if self.n_real > 0 and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
             raise ValueError(f"real_ratio={self.real_ratio} draws {self.n_real} real rows per minibatch, but the true buffer is empty")
         if self.resample_starts and self.env.sample_buffer.size(self.env.sample_buffer_state) <= 0:
             raise ValueError("resample_starts=True draws every reset's start state from the true buffer, but it is empty")
         key, subkey = K.split(key)
-        training_state = self.init_training_state(subkey)
+        if learner_state is None:
+            training_state = self.init_training_state(subkey)
+        else:
+            training_state = self.load_learner_state(learner_state)
         key, rb_key, env_key, eval_key = K.split(key, 4)
         # the init key above is shared (rank 0's parameters are broadcast); everything that generates DATA is per rank, or
         # N ranks would roll out the same envs with the same noise and all-reduce N copies of one gradient
         rk = self.dp.rank_key
-        env_state = self.reset_envs(self.env, rk(env_key), self.num_envs)
-        buffer_state = self.replay_buffer.init(rk(rb_key))
+        env_state = rehome_state(self._env_home, self.reset_envs(self.env, rk(env_key), self.num_envs))
+        num_prefill = None
+        if learner_state is not None and learner_state.replay is not None:
+            buffer_state = learner_state.replay
+            missing = self.min_replay_size - self.replay_buffer.size(buffer_state)
+            num_prefill = max(0, math.ceil(missing / self.num_envs))
+        else:
+            buffer_state = self.replay_buffer.init(rk(rb_key))
         evaluator = Evaluator(self, self.eval_env, num_eval_envs=self.num_eval_envs, episode_length=self.episode_length_eval,
                               action_repeat=self.action_repeat, key=eval_key)
         all_metrics: List[Metrics] = []
@@ -539,7 +626,7 @@ class SAC:
             progress_fn(0, metrics)
         key, prefill_key = K.split(key)
         training_state, env_state, buffer_state, _ = self.prefill_replay_buffer(training_state, env_state, buffer_state,
-                                                                                 rk(prefill_key))
+                                                                                 rk(prefill_key), num_steps=num_prefill)
         if self.eval_key_fixed:
             key, eval_key = K.split(key)
         for _ in range(self.num_evals_after_init):
@@ -556,6 +643,8 @@ class SAC:
             progress_fn(training_state.env_steps, metrics)
         last_params = self._snapshot(training_state)
         params_to_return = best_params if self.return_best_model else last_params
+        self.last_learner_state = self.export_learner_state(buffer_state)
+        self._env_home = env_state
         return params_to_return, all_metrics
 
     def _snapshot(self, training_state: TrainingState):
