@@ -7,7 +7,7 @@
 
     python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
                                      [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA] [--calibrate]
-                                     [--warm-start [--retain-buffer]]
+                                     [--warm-start [--retain-buffer]] [--time-adaptive TMIN TMAX [--switch-cost C]]
 
 --learn-reward: the ensemble also learns the reward from the true transitions (EnsembleDynamics(learn_reward=True) + LearnedReward),
 so the model rollouts never see the Pendulum's reward formula.
@@ -38,6 +38,12 @@ the next in BraxState.learner_state, instead of SAC starting from a fresh initia
 its trainer between the calls.  --retain-buffer: the model replay buffer is carried too (retain_replay_buffer=True), so an iteration
 starts on the previous iterations' model transitions and prefills nothing.  Every iteration prints its true_return.  Not with
 --terminate-speed (its reporting builds a trainer of its own).
+--time-adaptive TMIN TMAX: the policy also chooses how long its torque is held — the MODEL system is built with
+TimeAdaptive(TMIN, TMAX, env_dt = the Pendulum's dt, switch_cost=C): the policy emits [u | tau], the fused rollouts hold u for k(tau)
+steps of the learned model, sum the rewards of the hold discounted by 0.99 per step and charge C per decision; SAC gets the matching
+non_equidistant_time options, so its target discounts every row by the time the row was held.  On the TRUE system an action is applied
+for model.hold_steps(a) steps (the kernels' own k); every iteration also reports the mean hold of that evaluation.  Not with
+--optimistic or --real-ratio.  No learning curve is claimed for it.
 """
 from __future__ import annotations
 
@@ -62,14 +68,22 @@ def collect_uniform(system, n, gen, dev):
     return x, u, nxt.reward, nxt.x_next
 
 
-def true_return(system, optimizer, opt_state, steps=200, env_action=lambda a: a):
-    """env_action: the controls of a policy action (EnsembleSystem.env_action: an optimistic model's policy also emits eta)."""
+def true_return(system, optimizer, opt_state, steps=200, env_action=lambda a: a, hold_steps=None, holds=None):
+    """env_action: the controls of a policy action (System.env_action: an optimistic model's policy also emits eta, a time-adaptive
+    one tau).  hold_steps (a time-adaptive model's System.hold_steps): every action is applied for hold_steps(a) true steps, `steps`
+    true steps in all; the holds taken are appended to `holds`."""
     start = system.reset()
     x, total, true_params = start.x_next, 0.0, start.system_params      # the TRUE system's own parameters
-    for _ in range(steps):
+    t = 0
+    while t < steps:
         u, opt_state = optimizer.act(x, opt_state, evaluate=True)
-        nxt = system.step(x, env_action(u), true_params)
-        x, total = nxt.x_next, total + float(nxt.reward)
+        k = 1 if hold_steps is None else min(int(hold_steps(u.reshape(1, -1))[0]), steps - t)
+        if holds is not None:
+            holds.append(k)
+        for _ in range(k):
+            nxt = system.step(x, env_action(u), true_params)
+            x, total = nxt.x_next, total + float(nxt.reward)
+        t += k
     return total
 
 
@@ -128,11 +142,19 @@ def calibration_report(dyn, dyn_params, rows, n_rows, fit_key, true_system, dev,
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
         terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None, calibrate=False,
-        warm_start=False, retain_buffer=False):
+        warm_start=False, retain_buffer=False, time_adaptive=None, switch_cost=0.0):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
-    from mbpo.systems import BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem
+    from mbpo.systems import (BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem,
+                              TimeAdaptive)
+    from mbpo.systems.dynamics.pendulum_dynamics import PendulumDynamicsParams
     from mbpo.types import Transition
+    if time_adaptive is not None and (optimistic is not None or real_ratio > 0):
+        raise ValueError("--time-adaptive is not combined with --optimistic or --real-ratio")
+    ta = None
+    if time_adaptive is not None:      # one model step is one step of the true Pendulum; 0.99 per step, as SAC's discounting below
+        dt = PendulumDynamicsParams().dt
+        ta = TimeAdaptive(time_adaptive[0], time_adaptive[1], dt, switch_cost=switch_cost, continuous_discounting=-math.log(0.99) / dt)
     if warm_start and terminate_speed is not None:
         raise ValueError("--warm-start is not combined with --terminate-speed here: train_reporting_terminations builds its own trainer")
     if retain_buffer and not warm_start:
@@ -148,6 +170,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
     dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
     termination = None if terminate_speed is None else BoxTermination.from_intervals(3, {2: (-terminate_speed, terminate_speed)})
     model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), predict_delta=True, termination=termination,
+                           time_adaptive=ta,
                            **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic, calibrated=calibrate)))
     dyn_params = dyn.init_params(seed + 1)
     history = []
@@ -171,6 +194,7 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
                                      grad_updates_per_step=64, max_replay_size=2 ** 15, min_replay_size=2 ** 9, num_eval_envs=16,
                                      deterministic_eval=True, tau=0.005, num_env_steps_between_updates=5, real_ratio=real_ratio,
                                      **(dict(resample_starts=True) if resample_starts else {}),
+                                     **({} if ta is None else ta.trainer_kwargs()),
                                      **(dict(warm_start=True, retain_replay_buffer=retain_buffer) if warm_start else {}))
         state = optimizer.init(key=seed + 3, true_buffer_state=tbs)
         sp = state.system_params.replace(dynamics_params=dyn_params)
@@ -184,7 +208,9 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
         else:
             out, shares = train_reporting_terminations(optimizer, state, verbose)
         learner_state = out.optimizer_state.learner_state
-        ret = true_return(true_system, optimizer, out.optimizer_state, env_action=model.env_action)
+        holds = []
+        ret = true_return(true_system, optimizer, out.optimizer_state, env_action=model.env_action,
+                          hold_steps=None if ta is None else model.hold_steps, holds=holds)
         history.append(dict(iteration=it, true_transitions=n_rows, model_nll=float(losses[-20:].mean()), true_return=ret,
                             seconds=time.time() - t0))
         if elites:
@@ -194,6 +220,8 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
             history[-1].update(terminated_share=[round(s, 4) for s in shares])
         if coverage is not None:
             history[-1].update(coverage)
+        if ta is not None:
+            history[-1].update(mean_hold=sum(holds) / len(holds), max_hold=ta.max_steps)
         if verbose:
             print(history[-1], flush=True)
             if warm_start:
@@ -229,8 +257,11 @@ if __name__ == "__main__":
                     help="one SACOptimizer(warm_start=True) for all iterations: every iteration continues the previous one's learner")
     ap.add_argument("--retain-buffer", action="store_true",
                     help="with --warm-start: carry the model replay buffer from iteration to iteration too")
+    ap.add_argument("--time-adaptive", type=float, nargs=2, default=None, metavar=("TMIN", "TMAX"),
+                    help="the policy also chooses how long its torque is held, between TMIN and TMAX seconds (multiples of the Pendulum's dt)")
+    ap.add_argument("--switch-cost", type=float, default=0.0, metavar="C", help="with --time-adaptive: charged once per decision")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
         terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
         resample_starts=a.resample_starts, optimistic=a.optimistic, calibrate=a.calibrate, warm_start=a.warm_start,
-        retain_buffer=a.retain_buffer)
+        retain_buffer=a.retain_buffer, time_adaptive=a.time_adaptive, switch_cost=a.switch_cost)

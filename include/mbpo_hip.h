@@ -173,7 +173,46 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
  *                  normaliser, the Philox streams, the row layout (at action width A).
  * MBPO_ERR_ARG, checked before any device use, when halluc_beta is set with system_kind != MBPO_SYS_ENSEMBLE, ens_mode !=
  * MBPO_ENS_MEAN, u_dim <= x_dim, or a dynamics input width other than u_dim.  NULL (a zero-initialised descriptor): off, every kernel
- * runs what it ran before. */
+ * runs what it ran before.
+ *
+ * Time-adaptive rollouts (the environment side of non_equidistant_time, lasgroup's "when to sense and control" setting: the policy
+ * also chooses how long its control is held.  The reference tree carries the loss side only — sac/losses.py:90-96,
+ * ppo/losses_new.py:105-112 — its wrapper lives elsewhere and is restated here as remembered, unverified: THIS TEXT IS THE
+ * DEFINITION, as for hallucinated control).  A rollout is time-adaptive when hold_max_steps = K > 0.  Then:
+ *   action width   u_dim stays the width the policy emits, the rows carry and the critics see: A = u_env + 1.  An action is
+ *                  [u (u_env) | tau], both parts whatever the policy or the open-loop `actions` give after action_clip.
+ *   dynamics input the dynamics and every reward read [x, u] only: dynamics.dims[0] == x_dim + u_env == x_dim + u_dim - 1.  Pendulum
+ *                  dynamics and reward: x_dim == 3 && u_env == 1.  Quadratic reward: params stay [t[x], q[x], r[u_env]].
+ *   hold           t = (hold_max_time - hold_min_time) / 2 * tau + (hold_max_time + hold_min_time) / 2      (one fused multiply-add)
+ *                  k = clamp((int) floor_divide(t, hold_dt), 1, K)
+ *                  with floor_divide jnp.floor_divide on floats (mod = fmodf(t, dt); div = (t - mod) / dt; div -= 1 where mod != 0
+ *                  and its sign differs from dt's; roundf(div)).  These are the operations, in their order, of the losses' per-sample
+ *                  discount exp(-continuous_discounting * floor_divide(t, env_dt) * env_dt): the time a row is discounted by is the
+ *                  time its control was held.  The clamp to 1 is the rollout's alone: where the floor gives 0 (tau = -1 to rounding,
+ *                  with hold_min_time == hold_dt) the loss discounts by exp(0) while the control is held for one hold_dt; a floor above
+ *                  K (hold_max_time beyond K * hold_dt) is cut to K likewise.
+ *   inner steps    j = 0 .. k - 1 with u held: r_j is the reward at the pre-step (x_j, u), x_{j+1} the system's step — every ensemble
+ *                  mode, ens_sample_noise, the learned reward, the Pendulum — exactly as an action_repeat inner step.  The model stays
+ *                  a model of one hold_dt.
+ *   reward         R = (sum_j w_j r_j) - hold_switch_cost, w_0 = 1, w_{j+1} = w_j * hold_gamma, every product rounded to fp32 before
+ *                  it is added, j ascending from 0.  The caller passes hold_gamma = exp(-continuous_discounting * env_dt) (formed in
+ *                  float64, rounded once); at 1 the sum is the plain sum action_repeat forms, bit for bit.
+ *   termination    with a box set it is checked after EVERY inner step: a row whose x_{j+1} is violated stops there — its state
+ *                  freezes, it takes no further reward, sys_done = 1 (so done = 1 and, unless the episode also ran out, truncation =
+ *                  0).  Without a box nothing is checked.
+ *   bookkeeping    steps += k_eff, the inner steps the row took (k, or fewer where it terminated); done / truncation / discount /
+ *                  the reset / fresh starts (one draw per decision, element s * n_envs + env) keep their formulas; next_observation is
+ *                  the post-reset obs.  episode_length counts model steps (an episode is episode_length * hold_dt of time) and may be
+ *                  overshot by less than one hold, as action_repeat overshoots it.
+ *   randomness     the member / model-noise / learned-reward element index is ((s * K + j) * n_envs + env): action_repeat's with K
+ *                  in its place, whatever k the row has.  Explicit model_noise is [S, K, N, x_dim], member_idx [S, K, N].
+ *   unchanged      the policy's sampling, action_clip, ppo_extras (log_prob summed over all A dims), env_major, the normaliser, the
+ *                  row layout (at action width A).
+ * MBPO_ERR_ARG, checked before any device use, when hold_max_steps is set and: it lies outside [1, 64]; action_repeat != 1; halluc_beta
+ * is set; u_dim < 2; the dynamics input width is not x_dim + u_dim - 1; hold_dt <= 0; hold_min_time > hold_max_time; hold_gamma outside
+ * (0, 1]; hold_switch_cost < 0.  MBPO_ERR_UNSUPPORTED for 64-wide networks with more than 16 inputs or outputs (no such instantiation).
+ * All six fields zero (a zero-initialised descriptor): off, every kernel runs what it ran before.  The kernel specialised for the
+ * benchmark networks and mbpo_episode_step never see the option. */
 typedef struct mbpo_rollout_desc {
   mbpo_mlp_desc policy;   /* [x_dim] -> [2*u_dim] */
   mbpo_mlp_desc dynamics; /* [x_dim+u_dim] -> [2*x_dim] (mean, raw std) or [2*x_dim+2] (+ reward mean, raw std: MBPO_REWARD_LEARNED);
@@ -221,11 +260,23 @@ typedef struct mbpo_rollout_desc {
   int64_t start_max_size;
   int32_t start_row_len;       /* >= x_dim */
   const int32_t *start_state;  /* device int32[>= 3] {insert_position, sample_position, head, ...} */
+  /* time-adaptive rollouts (see above): hold_max_steps 0 = off.  (They too sit in front of the termination pair.) */
+  int32_t hold_max_steps;      /* K in [1, 64] */
+  float hold_min_time, hold_max_time, hold_dt;   /* tau in [-1, 1] -> [hold_min_time, hold_max_time]; hold_dt = env_dt > 0 */
+  float hold_gamma;            /* exp(-continuous_discounting * env_dt) in (0, 1] */
+  float hold_switch_cost;      /* >= 0, charged once per decision */
   /* termination (see above): each [x_dim], both NULL = none (a zero-initialised descriptor), exactly one NULL = MBPO_ERR_ARG */
   const float *term_low, *term_high;
 } mbpo_rollout_desc;
 
 int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream);
+
+/* steps_out[i] = the k a time-adaptive rollout holds the control of actions[i] for ("time-adaptive rollouts" above, from the last of
+ * its action_dim columns; the same device function, one thread per row): for host code that applies an action to the true system
+ * for as long as the model held it.  actions [n, action_dim], steps_out int32 [n], both on the device.  MBPO_ERR_ARG before any device
+ * use: n < 0, action_dim < 1, env_dt <= 0, min_time > max_time, max_steps outside [1, 64], a NULL pointer with n > 0. */
+int mbpo_hold_steps(const float *actions, int64_t n, int32_t action_dim, float min_time, float max_time, float env_dt,
+                    int32_t max_steps, int32_t *steps_out, void *stream);
 
 /* ---- R1/R4-R7 for a USER-DEFINED System: the non-fused env step ------------------------------------
  * replaces: the same reference lines as mbpo_model_rollout, split at the reference's own plug-in seam — System.step

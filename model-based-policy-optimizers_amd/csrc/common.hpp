@@ -345,11 +345,26 @@ __device__ __forceinline__ float floor_divide_f(float x1, float x2) {
   return roundf(div);
 }
 
+// The switch time of non_equidistant_time in env steps, before any clamp: the last action component `a`, mapped affinely from [-1, 1]
+// to [tl, tu], floor-divided by env_dt.  Shared by the losses' discount (n1_discount) and the time-adaptive rollouts (hold_steps), so
+// that the time a row is discounted by and the time its control was held come from the same operations in the same order.
+__device__ __forceinline__ float switch_time_steps(float a, float tl, float tu, float dt) {
+  const float t = (tu - tl) / 2.0f * a + (tu + tl) / 2.0f;
+  return floor_divide_f(t, dt);
+}
+
 // N1 per-sample discount of non_equidistant_time (sac/losses.py:90-96, ppo/losses_new.py:105-112): the switch time encoded in the
 // last action component `a`, mapped affinely from [-1, 1] to [tl, tu], floored to a multiple of env_dt; exp(-cd * t).  The
 // operation order of sac.hip's in-kernel form.
 __device__ __forceinline__ float n1_discount(float a, float cd, float tl, float tu, float dt) {
-  float t = (tu - tl) / 2.0f * a + (tu + tl) / 2.0f;
-  t = floor_divide_f(t, dt) * dt;
+  const float t = switch_time_steps(a, tl, tu, dt) * dt;
   return expf(-cd * t);
+}
+
+// Time-adaptive rollouts (include/mbpo_hip.h "time-adaptive rollouts"): the model steps the control of action [u | a] is held for,
+// clamp((int) switch_time_steps, 1, K).  The clamp to 1 is the rollout's alone: where the loss's floor gives 0 (a = -1 to rounding)
+// the row is discounted by exp(0) and held for one env_dt.
+__device__ __forceinline__ int hold_steps(float a, float tl, float tu, float dt, int K) {
+  const int k = (int)switch_time_steps(a, tl, tu, dt);
+  return k < 1 ? 1 : (k > K ? K : k);
 }

@@ -155,7 +155,7 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 // instantiation with HAL = false is then emitted exactly as it was before the flag existed.  (With a local `UE` and run-time `if (HAL)`
 // tests, all constant and all folded, seven existing k_model_rollout64 instantiations still came out with one to four SGPR spills more
 // or fewer: profiles/r10_hallucinated_registers.txt.)
-#define RO_UE (HAL ? U - X : U)
+#define RO_UE (HAL ? U - X : (TA ? U - 1 : U))
 // HAL: hallucinated control (halluc_beta is set; include/mbpo_hip.h "hallucinated control").  A flag of its own, like the others: the
 // instantiations without it compile to what they were (profiles/r10_hallucinated_registers.txt).  The action is [u (UE) | eta (X)]:
 // the member chains read the x + UE leading columns of s_xu (every input-layer routine masks k >= dims[0] itself, none relies on zero
@@ -165,11 +165,56 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 struct RolloutArgsHal : RolloutArgs {
   const float *halluc_beta;     // [x_dim]
 };
-template <bool HAL>
-using RolloutArgsFor = typename std::conditional<HAL, RolloutArgsHal, RolloutArgs>::type;
+// TA: a time-adaptive rollout (hold_max_steps > 0; include/mbpo_hip.h "time-adaptive rollouts").  A flag of its own, like HAL, with an
+// argument block of its own.  The action is [u (U - 1) | tau]: the member chains and the rewards read the x + U - 1 leading columns
+// of s_xu, tau sits where the padding was.  The hold is the action_repeat loop with a per-row count: the host hands these
+// instantiations K in action_repeat (the descriptor's own must be 1), so every element index ((s * AR + ar) * N + env) is the
+// documented one ((s * K + j) * N + env) without another formula; the rows' k, the steps they took and whether they terminated live
+// in LDS (s_hold: [0, 16) k, [16, 32) inner steps taken, [32, 48) terminated, [48] the tile's largest k, which bounds the loop).  The
+// member chains run on the whole tile; reward and next state are committed for the rows with j < k that have not terminated.
+struct HoldArgs {
+  int max_steps;                // K
+  float min_time, max_time, dt, gamma, switch_cost;
+};
+struct RolloutArgsTA : RolloutArgs {
+  HoldArgs hold;
+};
+template <bool HAL, bool TA = false>
+using RolloutArgsFor = typename std::conditional<TA, RolloutArgsTA, typename std::conditional<HAL, RolloutArgsHal, RolloutArgs>::type>::type;
 
-template <int H, bool LR, bool START, bool HAL>
-__global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
+// TA: the rows' hold counts, once per decision by the first wave (the action is in s_xu, a barrier behind its writers): k = 0 for the
+// rows past the batch, which are then never committed.  The caller's barrier publishes s_hold.
+template <class Args>
+__device__ __forceinline__ void hold_setup(const Args &H, float *s_hold, const float *s_xu, int ld_xu, int tau_col, long long env0,
+                                           long long N, int wave, int lane) {
+  if (wave == 0) {
+    int kk = 0;
+    if (lane < 16 && env0 + lane < N) kk = hold_steps(s_xu[lane * ld_xu + tau_col], H.min_time, H.max_time, H.dt, H.max_steps);
+    if (lane < 16) {
+      s_hold[lane] = (float)kk;
+      s_hold[16 + lane] = 0.f;
+      s_hold[32 + lane] = 0.f;
+    }
+    for (int off = 8; off; off >>= 1) {
+      const int o = __shfl_xor(kk, off);
+      kk = o > kk ? o : kk;
+    }
+    if (lane == 0) s_hold[48] = (float)kk;
+  }
+}
+// row r is still being stepped at inner step j
+__device__ __forceinline__ bool hold_live(const float *s_hold, int r, int j) { return (float)j < s_hold[r] && s_hold[32 + r] == 0.f; }
+// the tile's largest k: the inner loop's bound, uniform over the workgroup
+__device__ __forceinline__ int hold_bound(const float *s_hold) { return __builtin_amdgcn_readfirstlane((int)s_hold[48]); }
+// w_j = gamma^j as the running product forms it (w_0 = 1, w_{j+1} = w_j * gamma)
+__device__ __forceinline__ float hold_weight(float gamma, int j) {
+  float w = 1.f;
+  for (int i = 0; i < j; ++i) w *= gamma;
+  return w;
+}
+
+template <int H, bool LR, bool START, bool HAL, bool TA = false>
+__global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL, TA> A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
@@ -195,6 +240,8 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
   // buffer; the tile load's barrier below orders it before its first use)
   if constexpr (HAL)
     for (int idx = tid; idx < X; idx += nthreads) s_rew[16 + idx] = A.halluc_beta[idx];
+  float *const s_hold = s_rew + 16;              // TA: [49] floats of the same region (never together with HAL)
+  (void)s_hold;
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -293,9 +340,15 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
         s_row[tid * D + 2 * X + U + 2] = lp;  // log_prob (summed over action dims)
       }
       if (A.ppo_extras) __syncthreads();
+      float hold_w = 1.f;                        // TA: w_j
+      if constexpr (TA) {
+        hold_setup(A.hold, s_hold, s_xu, A.ld_xu, X + U - 1, env0, N, wave, lane);
+        __syncthreads();
+      }
+      const int ARN = TA ? (int)s_hold[48] : AR; // TA: the tile's largest k (workgroup-uniform)
 
       // ---- EpisodeWrapper inner scan over action_repeat (training.py:91-97) ----
-      for (int ar = 0; ar < AR; ++ar) {
+      for (int ar = 0; ar < ARN; ++ar) {
         if (A.system_kind == MBPO_SYS_ENSEMBLE) {
           // one wave per ensemble member chain (no barrier inside a chain), n_chains members side by side
           for (int e0 = 0; e0 < E; e0 += A.n_chains) {
@@ -322,11 +375,16 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
             for (int d = 0; d < RO_UE; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
             rew = -cx - cu;
           }
-          s_rew[r] += rew;
+          if constexpr (TA) {
+            const float wr = hold_w * rew;       // the product rounded on its own, then added (no fused multiply-add)
+            if (hold_live(s_hold, r, ar)) s_rew[r] += wr;
+          } else {
+            s_rew[r] += rew;
+          }
         }
         __syncthreads();
         if (A.system_kind == MBPO_SYS_PENDULUM) {
-          if (tid < 16) {
+          if (tid < 16 && (!TA || hold_live(s_hold, tid, ar))) {
             float xn[3];
             pendulum_step(s_xu + tid * A.ld_xu, s_xu[tid * A.ld_xu + X], A.sys_params, xn);
             s_xu[tid * A.ld_xu + 0] = xn[0];
@@ -375,21 +433,33 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL> A) {
           __syncthreads();
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             int r = idx / X, c = idx - r * X;
-            s_xu[r * A.ld_xu + c] = s_hA[r * X + c];
+            if (!TA || hold_live(s_hold, r, ar)) s_xu[r * A.ld_xu + c] = s_hA[r * X + c];
           }
         }
         __syncthreads();
+        if constexpr (TA) {
+          // the rows that took this step: count it, and stop a row whose new state leaves the box
+          if (tid < 16 && hold_live(s_hold, tid, ar)) {
+            s_hold[16 + tid] += 1.f;
+            if (term_row_done(A, s_xu + tid * A.ld_xu, X) != 0.f) s_hold[32 + tid] = 1.f;
+          }
+          hold_w *= A.hold.gamma;
+          __syncthreads();
+        }
       }
 
       // ---- EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137) + Transition (acting.py:46-55) ----
       if (tid < 16) {
         const int r = tid;
-        float st = s_steps[r] + (float)AR;
-        float sys_done = term_row_done(A, s_xu + r * A.ld_xu, X);  // SystemState.done: 0 (base_systems.py:25) or the termination box
+        float st = s_steps[r] + (TA ? s_hold[16 + r] : (float)AR);   // TA: the inner steps the row took
+        // SystemState.done: 0 (base_systems.py:25) or the termination box (TA: on any inner step the row took)
+        float sys_done = TA ? s_hold[32 + r] : term_row_done(A, s_xu + r * A.ld_xu, X);
         float dn = (st >= (float)A.episode_length) ? 1.f : sys_done;
         float trunc = (st >= (float)A.episode_length) ? (1.f - sys_done) : 0.f;
         s_steps[r] = st;
         s_done[r] = dn;
+        if constexpr (TA) s_row[r * D + X + U] = s_rew[r] - A.hold.switch_cost;
+        else
         s_row[r * D + X + U] = s_rew[r];
         s_row[r * D + X + U + 1] = 1.f - dn;
         s_row[r * D + D - 1] = trunc;
@@ -492,11 +562,21 @@ __device__ __forceinline__ int ro_tid_now(int wave) {
 struct RolloutArgs64Hal : RolloutArgs64 {
   const float *halluc_beta;     // [x_dim]
 };
-template <bool HAL>
-using RolloutArgs64For = typename std::conditional<HAL, RolloutArgs64Hal, RolloutArgs64>::type;
+// TA: a time-adaptive rollout (a flag of its own, likewise; see k_model_rollout): section C commits the reward and the next state of
+// the rows still held and re-emits the state of the others, so the scratch always holds every row's current state and section D reads
+// it as before; a row's termination is decided after each of its inner steps, into s_hold, and copied to where section D reads it.
+// Nothing here is a new local variable of the TA = false path (s_hold is the expression RO64_HOLD, the loop bound and the weight are
+// re-derived where they are used): with locals, all dead and all folded, fourteen LR instantiations came out with one to ten SGPR
+// spills more or fewer, as the note at RO_UE reports for HAL.  One barrier
+// more per decision (the rows' k) and none per inner step.
+struct RolloutArgs64TA : RolloutArgs64 {
+  HoldArgs hold;
+};
+template <bool HAL, bool TA = false>
+using RolloutArgs64For = typename std::conditional<TA, RolloutArgs64TA, typename std::conditional<HAL, RolloutArgs64Hal, RolloutArgs64>::type>::type;
 
-template <bool WIDE, bool LR, bool TERM, bool START, bool HAL>
-__global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64For<HAL> AA) {
+template <bool WIDE, bool LR, bool TERM, bool START, bool HAL, bool TA = false>
+__global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64For<HAL, TA> AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
   constexpr int HT = 4;
@@ -536,6 +616,8 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
   // (2X + UE == X + U)
   if constexpr (HAL)
     for (int idx = tid_; idx < X; idx += nthreads) s_rp[X + U + idx] = AA.halluc_beta[idx];
+  // TA: the rows' k, inner steps taken and terminated flags, the tile's largest k (the host adds these 64 floats)
+#define RO64_HOLD (s_rp + ((2 * X + U + 4 + 3) & ~3))
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -638,10 +720,14 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
       }
       __syncthreads();
       RO_STAMP(3);
+      if constexpr (TA) {
+        hold_setup(AA.hold, RO64_HOLD, s_xu, ld_xu, X + U - 1, env0, N, wave, lane);
+        __syncthreads();
+      }
 
-      // ---- EpisodeWrapper inner scan over action_repeat (training.py:91-97) ----
+      // ---- EpisodeWrapper inner scan over action_repeat (training.py:91-97); TA: up to the tile's largest k ----
 #pragma nounroll
-      for (int ar = 0; ar < AR; ++ar) {
+      for (int ar = 0; ar < (TA ? hold_bound(RO64_HOLD) : AR); ++ar) {
         if (E > 0) {
 #pragma nounroll
           for (int e0 = 0; e0 < E; e0 += A.n_chains) {
@@ -673,10 +759,18 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
             for (int d = 0; d < RO_UE; ++d) { float uu = xr[X + d]; cu += rp[d] * (uu * uu); }
             rew = -cx - cu;
           }
-          s_rew[r] += rew;
+          if constexpr (TA) {
+            const float wr = hold_weight(AA.hold.gamma, ar) * rew;       // the product rounded on its own, then added (no fused multiply-add)
+            if (hold_live(RO64_HOLD, r, ar)) s_rew[r] += wr;
+          } else {
+            s_rew[r] += rew;
+          }
           if (A.system_kind == MBPO_SYS_PENDULUM) {
             float xn[3];
             pendulum_step(xr, xr[X], A.sys_params, xn);
+            if constexpr (TA) {
+              if (!hold_live(RO64_HOLD, r, ar)) { xn[0] = xr[0]; xn[1] = xr[1]; xn[2] = xr[2]; }
+            }
             s_scr[r * X + 0] = xn[0];
             s_scr[r * X + 1] = xn[1];
             s_scr[r * X + 2] = xn[2];
@@ -719,11 +813,22 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
                 v += sg * eps;
               }
             }
+            if constexpr (TA) {
+              if (!hold_live(RO64_HOLD, r, ar)) v = s_xu[r * ld_xu + c];      // a row that is not held any more keeps its state
+            }
             s_scr[r * X + c] = v;
           }
         }
         __syncthreads();
-        if (ar + 1 < AR) {   // the next inner step starts from the new state
+        if constexpr (TA) {
+          // the rows that took this step: count it, and stop a row whose new state leaves the box (the next reader of either is behind
+          // a barrier: the one below, or the one in front of section D)
+          if (tid < 16 && hold_live(RO64_HOLD, tid, ar)) {
+            RO64_HOLD[16 + tid] += 1.f;
+            if (TERM && term_row_done(A, s_scr + tid * X, X) != 0.f) RO64_HOLD[32 + tid] = 1.f;
+          }
+        }
+        if (ar + 1 < (TA ? hold_bound(RO64_HOLD) : AR)) {   // the next inner step starts from the new state
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             const int r = idx & 15, c = idx >> 4;
             s_xu[r * ld_xu + c] = s_scr[r * X + c];
@@ -734,6 +839,10 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
 
       // TERM: the rows' SystemState.done, once per row by 16 threads (the 16 floats behind the log-prob scratch), read by section D
       float *s_sd = s_scr + 16 * (X + U);
+      if constexpr (TA) {
+        if (TERM && tid < 16) s_sd[tid] = RO64_HOLD[32 + tid];      // the rows that left the box inside their hold
+        __syncthreads();      // ... and the rows' step counts are complete
+      } else
       if (TERM) {
         if (tid < 16) s_sd[tid] = term_row_done(A, s_scr + tid * X, X);
         __syncthreads();
@@ -742,7 +851,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
       // ---- section D: EpisodeWrapper / AutoReset post-step (training.py:98-107, 126-137) + Transition (acting.py:46-55) ----
       for (int idx = tid; idx < 16 * X; idx += nthreads) {
         const int r = idx & 15, c = idx >> 4;
-        const float st = steps_cur[r] + (float)AR;
+        const float st = steps_cur[r] + (TA ? RO64_HOLD[16 + r] : (float)AR);
         const bool dn = st >= (float)A.episode_length || (TERM && s_sd[r] != 0.f);
         const float v = dn ? s_first[r * ld_x + c] : s_scr[r * X + c];
         s_obs[r * ld_x + c] = v;
@@ -752,12 +861,14 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
       }
       if (tid < 16) {
         const int r = tid;
-        const float st = steps_cur[r] + (float)AR;
+        const float st = steps_cur[r] + (TA ? RO64_HOLD[16 + r] : (float)AR);   // TA: the inner steps the row took
         const float sys_done = TERM ? s_sd[r] : 0.f;  // SystemState.done: 0 (base_systems.py:25) or the termination box
         const float dn = (st >= (float)A.episode_length) ? 1.f : sys_done;
         const float trunc = (st >= (float)A.episode_length) ? (1.f - sys_done) : 0.f;
         steps_nxt[r] = st;
         s_done[r] = dn;
+        if constexpr (TA) s_row[r * D + X + U] = s_rew[r] - AA.hold.switch_cost;
+        else
         s_row[r * D + X + U] = s_rew[r];
         s_row[r * D + X + U + 1] = 1.f - dn;
         s_row[r * D + D - 1] = trunc;
@@ -899,7 +1010,19 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   MBPO_REQUIRE(!hal || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG, "model_rollout: halluc_beta needs system_kind ENSEMBLE");
   MBPO_REQUIRE(!hal || d->ens_mode == MBPO_ENS_MEAN, MBPO_ERR_ARG, "model_rollout: halluc_beta needs ens_mode MEAN");
   MBPO_REQUIRE(!hal || U > X, MBPO_ERR_ARG, "model_rollout: halluc_beta needs u_dim > x_dim (the action is [u | eta], eta [x_dim]); got u_dim %d, x_dim %d", U, X);
-  const int UE = hal ? U - X : U;
+  // time-adaptive: the action is [u (UE) | tau], the dynamics and the rewards see the UE leading columns
+  const bool ta = d->hold_max_steps != 0;
+  if (ta) {
+    MBPO_REQUIRE(d->hold_max_steps >= 1 && d->hold_max_steps <= 64, MBPO_ERR_ARG, "model_rollout: hold_max_steps %d outside [1, 64]", d->hold_max_steps);
+    MBPO_REQUIRE(d->action_repeat == 1, MBPO_ERR_ARG, "model_rollout: hold_max_steps needs action_repeat 1 (the hold is the repeat); got %d", d->action_repeat);
+    MBPO_REQUIRE(!hal, MBPO_ERR_ARG, "model_rollout: hold_max_steps and halluc_beta cannot both be set");
+    MBPO_REQUIRE(U >= 2, MBPO_ERR_ARG, "model_rollout: hold_max_steps needs u_dim >= 2 (the action is [u | tau]); got u_dim %d", U);
+    MBPO_REQUIRE(d->hold_dt > 0.f, MBPO_ERR_ARG, "model_rollout: hold_dt must be positive");
+    MBPO_REQUIRE(d->hold_min_time <= d->hold_max_time, MBPO_ERR_ARG, "model_rollout: hold_min_time > hold_max_time");
+    MBPO_REQUIRE(d->hold_gamma > 0.f && d->hold_gamma <= 1.f, MBPO_ERR_ARG, "model_rollout: hold_gamma outside (0, 1]");
+    MBPO_REQUIRE(d->hold_switch_cost >= 0.f, MBPO_ERR_ARG, "model_rollout: hold_switch_cost is negative");
+  }
+  const int UE = hal ? U - X : (ta ? U - 1 : U);
   int rc = mbpo_check_start_buffer(d->start_rows, d->start_max_size, d->start_row_len, d->start_state, X, "model_rollout");
   if (rc != MBPO_OK) return rc;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
@@ -909,7 +1032,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_LEARNED || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG,
                "model_rollout: the learned reward needs system_kind ENSEMBLE");
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && UE == 1), MBPO_ERR_ARG,
-               "model_rollout: pendulum reward needs x_dim=3,u_dim=1 (with halluc_beta: u_dim = 1 + x_dim)");
+               "model_rollout: pendulum reward needs x_dim=3,u_dim=1 (with halluc_beta: u_dim = 1 + x_dim; with hold_max_steps: u_dim = 2)");
   RolloutArgs A;
   int H = 64;
   const bool has_policy = (d->actions == nullptr);
@@ -929,7 +1052,10 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     if (rc != MBPO_OK) return rc;
     E = A.dyn.n_nets;
     dyn_out = A.dyn.dims[A.dyn.n_layers];
-    MBPO_REQUIRE(hal || A.dyn.dims[0] == X + U, MBPO_ERR_ARG, "model_rollout: dynamics input must be x_dim+u_dim");
+    MBPO_REQUIRE(hal || ta || A.dyn.dims[0] == X + U, MBPO_ERR_ARG, "model_rollout: dynamics input must be x_dim+u_dim");
+    MBPO_REQUIRE(!ta || A.dyn.dims[0] == X + U - 1, MBPO_ERR_ARG,
+                 "model_rollout: with hold_max_steps the dynamics input must be x_dim + u_dim - 1 (the dynamics read [x, u] only); got %d, x_dim %d, u_dim %d",
+                 A.dyn.dims[0], X, U);
     MBPO_REQUIRE(!hal || A.dyn.dims[0] == U, MBPO_ERR_ARG,
                  "model_rollout: with halluc_beta the dynamics input must be u_dim = x_dim + the control width (the dynamics read [x, u] only); got %d, u_dim %d",
                  A.dyn.dims[0], U);
@@ -944,7 +1070,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     MBPO_REQUIRE(Hd == H || A.dyn.n_layers == 1, MBPO_ERR_UNSUPPORTED,
                  "model_rollout: policy and dynamics hidden widths must match (got %d vs %d)", H, Hd);
   } else if (d->system_kind == MBPO_SYS_PENDULUM) {
-    MBPO_REQUIRE(X == 3 && U == 1, MBPO_ERR_ARG, "model_rollout: pendulum system needs x_dim=3,u_dim=1");
+    MBPO_REQUIRE(X == 3 && UE == 1, MBPO_ERR_ARG, "model_rollout: pendulum system needs x_dim=3,u_dim=1 (with hold_max_steps: u_dim = 2)");
     MBPO_REQUIRE(d->sys_params, MBPO_ERR_ARG, "model_rollout: sys_params is NULL");
     memset(&A.dyn, 0, sizeof(A.dyn));  // unused
   } else {
@@ -955,7 +1081,9 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   if (d->n_envs == 0 || d->n_steps == 0) return MBPO_OK;
 
   A.x_dim = X; A.u_dim = U; A.n_envs = d->n_envs; A.n_steps = d->n_steps;
-  A.episode_length = d->episode_length; A.action_repeat = d->action_repeat;
+  A.episode_length = d->episode_length;
+  A.action_repeat = ta ? d->hold_max_steps : d->action_repeat;      // TA: K, the stride of the inner-step element indices
+  const HoldArgs hold{d->hold_max_steps, d->hold_min_time, d->hold_max_time, d->hold_dt, d->hold_gamma, d->hold_switch_cost};
   A.system_kind = d->system_kind; A.ens_mode = d->ens_mode; A.ens_predict_delta = d->ens_predict_delta;
   A.ens_sample_noise = d->ens_sample_noise; A.ens_min_std = d->ens_min_std;
   A.reward_kind = d->reward_kind; A.reward_params = d->reward_params; A.sys_params = d->sys_params;
@@ -978,7 +1106,8 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   A.ld_y = up4(ymax) + 4;
   const int scr = 16 * (X + U) + 16;
   const size_t fixed_f = 3ull * 16 * A.ld_x + 16ull * A.ld_xu + (size_t)A.n_out * 16 * A.ld_y + 2ull * 16 * up4(d->row_len) + 80 +
-                         (size_t)up4(scr) + (size_t)up4(2 * X + U + 4);   // + staged reward parameters (k_model_rollout64)
+                         (size_t)up4(scr) + (size_t)up4(2 * X + U + 4) +  // + staged reward parameters (k_model_rollout64)
+                         (ta ? 64 : 0);                                   // + the rows' hold state (k_model_rollout64)
   A.n_chains = pick_chains(E, fixed_f, A.ld_h);
   MBPO_REQUIRE(A.n_chains >= 1, MBPO_ERR_UNSUPPORTED, "model_rollout: shapes do not fit 160 KiB of LDS");
   size_t lds = (fixed_f + 2ull * A.n_chains * 16 * A.ld_h) * sizeof(float);
@@ -986,7 +1115,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   long long n_tiles = (d->n_envs + 15) >> 4;
   int grid = (int)(n_tiles < 4LL * mbpo_num_cus() ? n_tiles : 4LL * mbpo_num_cus());
   hipStream_t st = (hipStream_t)stream;
-  if (!has_policy && d->system_kind == MBPO_SYS_PENDULUM && d->reward_kind == MBPO_REWARD_PENDULUM && !d->ppo_extras &&
+  if (!ta && !has_policy && d->system_kind == MBPO_SYS_PENDULUM && d->reward_kind == MBPO_REWARD_PENDULUM && !d->ppo_extras &&
       mbpo_knob_override(KNOB_ROLLOUT_LEAN) != 0) {      // (mbpo_debug_set_rollout_lean(0), not the environment: the tile kernel, for the A/B test)
     const dim3 ogrid((unsigned)((d->n_envs + 255) / 256));
     if (A.start.rows) hipLaunchKernelGGL(k_openloop_pendulum<true>, ogrid, dim3(256), 0, st, A);
@@ -1001,7 +1130,8 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     // generic one
     const int lean_mode = (int)mbpo_knob(KNOB_ROLLOUT_LEAN);      // 0 generic, 1 lean, 2 lean + two tiles in flight forced, 3 lean without
     // (k_rollout_lean never sees hallucinated control: rollout_lean_supports refuses u_dim != 1, and halluc_beta needs u_dim > x_dim)
-    if (lean_mode && rollout_lean_supports(A, has_policy, E)) {
+    // (nor a time-adaptive one: hold_max_steps needs u_dim >= 2)
+    if (lean_mode && !ta && rollout_lean_supports(A, has_policy, E)) {
       RoLeanArgs L;
       L.a = A;
       L.E = E;
@@ -1028,6 +1158,21 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     if (AA.a.n_chains < 1) AA.a.n_chains = 1;
     lds = (fixed_f + 2ull * (AA.a.n_chains > 1 ? AA.a.n_chains : 1) * 16 * A.ld_h) * sizeof(float);
     const bool wide = net_is_wide(AA.sh_pi) || net_is_wide(AA.sh_dyn);
+    if (ta) {
+      // the TA instantiations: every LR / TERM / START combination of the narrow kernel
+      MBPO_REQUIRE(!wide, MBPO_ERR_UNSUPPORTED,
+                   "model_rollout: hold_max_steps has no k_model_rollout64<WIDE> instantiation (64-wide networks with more than 16 inputs or outputs)");
+      RolloutArgs64TA AH;
+      static_cast<RolloutArgs64 &>(AH) = AA;
+      AH.hold = hold;
+      rc = mbpo_with_bool(lr, [&](auto LR) {
+        return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
+          return mbpo_with_bool(fresh, [&](auto SB) {
+            return mbpo_launch<k_model_rollout64<false, LR.value, TM.value, SB.value, false, true>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AH);
+          });
+        });
+      });
+    } else
     rc = mbpo_with_bool(lr, [&](auto LR) {
       return mbpo_with_bool(wide, [&](auto W) {
         return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
@@ -1040,6 +1185,16 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
             });
           });
         });
+      });
+    });
+  } else if (ta) {
+    RolloutArgsTA AH;
+    static_cast<RolloutArgs &>(AH) = A;
+    AH.hold = hold;
+    rc = mbpo_with_bool(lr, [&](auto LR) {
+      return mbpo_with_bool(fresh, [&](auto SB) {
+        if (H == 128) return mbpo_launch<k_model_rollout<128, LR.value, SB.value, false, true>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
+        return mbpo_launch<k_model_rollout<256, LR.value, SB.value, false, true>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
       });
     });
   } else if (H == 128) {
@@ -1067,5 +1222,30 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   }
   if (rc != MBPO_OK) return rc;
   MBPO_CHECK_LAUNCH("model_rollout");
+  return MBPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mbpo_hold_steps: the k of a time-adaptive rollout (hold_steps, common.hpp) for n actions, one thread per row — for host code that
+// applies an action to the true system for as long as the model held it.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_hold_steps(const float *actions, long long n, int A, float tl, float tu, float dt, int K, int *out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = hold_steps(actions[i * A + A - 1], tl, tu, dt, K);
+}
+
+extern "C" int mbpo_hold_steps(const float *actions, int64_t n, int32_t action_dim, float min_time, float max_time, float env_dt,
+                               int32_t max_steps, int32_t *steps_out, void *stream) {
+  MBPO_REQUIRE(n >= 0, MBPO_ERR_ARG, "hold_steps: n < 0");
+  MBPO_REQUIRE(action_dim >= 1, MBPO_ERR_ARG, "hold_steps: action_dim must be positive");
+  MBPO_REQUIRE(env_dt > 0.f, MBPO_ERR_ARG, "hold_steps: env_dt must be positive");
+  MBPO_REQUIRE(min_time <= max_time, MBPO_ERR_ARG, "hold_steps: min_time > max_time");
+  MBPO_REQUIRE(max_steps >= 1 && max_steps <= 64, MBPO_ERR_ARG, "hold_steps: max_steps %d outside [1, 64]", max_steps);
+  if (n == 0) return MBPO_OK;
+  MBPO_REQUIRE(actions && steps_out, MBPO_ERR_ARG, "hold_steps: null pointer");
+  MBPO_REQUIRE(n <= 256LL * 2147483647LL, MBPO_ERR_ARG, "hold_steps: n too large");
+  hipLaunchKernelGGL(k_hold_steps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, actions, (long long)n, action_dim, min_time,
+                     max_time, env_dt, max_steps, steps_out);
+  MBPO_CHECK_LAUNCH("hold_steps");
   return MBPO_OK;
 }

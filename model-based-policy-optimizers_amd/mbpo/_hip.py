@@ -86,6 +86,12 @@ class RolloutDesc(C.Structure):
         ("start_max_size", C.c_int64),
         ("start_row_len", C.c_int32),
         ("start_state", C.c_void_p),
+        ("hold_max_steps", C.c_int32),
+        ("hold_min_time", C.c_float),
+        ("hold_max_time", C.c_float),
+        ("hold_dt", C.c_float),
+        ("hold_gamma", C.c_float),
+        ("hold_switch_cost", C.c_float),
         ("term_low", C.c_void_p),
         ("term_high", C.c_void_p),
     ]
@@ -274,6 +280,8 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_mlp_layered_workspace_floats.argtypes = [C.POINTER(MlpDesc), i64]
     lib.mbpo_mlp_layered_vjp.restype = C.c_int
     lib.mbpo_mlp_layered_vjp.argtypes = [C.POINTER(MlpDesc), vp, i64, vp, vp, vp, vp, vp, vp]
+    lib.mbpo_hold_steps.restype = C.c_int
+    lib.mbpo_hold_steps.argtypes = [vp, i64, i32, f32, f32, f32, i32, vp, vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

@@ -288,15 +288,22 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
                   system=None, system_params=None, system_params_out: Optional[list] = None,
                   term_low: Optional[torch.Tensor] = None, term_high: Optional[torch.Tensor] = None,
                   start_rows: Optional[torch.Tensor] = None, start_state: Optional[torch.Tensor] = None,
-                  halluc_beta: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  halluc_beta: Optional[torch.Tensor] = None,
+                  hold_max_steps: int = 0, hold_min_time: float = 0.0, hold_max_time: float = 0.0, hold_dt: float = 0.0,
+                  hold_gamma: float = 1.0, hold_switch_cost: float = 0.0) -> torch.Tensor:
     """Fused S-step model rollout for N envs (R1-R8).  Updates obs/steps/done in place; returns rows [S*N, D].
     system_kind == SYS_GENERIC (a user-defined `system`): the same contract through generic_rollout below.
     term_low / term_high ([x_dim] each, both or neither): the box termination of include/mbpo_hip.h (BoxTermination.kernel_spec).
     start_rows / start_state (both or neither): a replay ring's storage [max_size, row_len] and int32 device state — the fresh starts
     of include/mbpo_hip.h: every reset is followed by a new draw into first_obs, which is then updated in place too.
     halluc_beta ([x_dim], device): the hallucinated control of include/mbpo_hip.h — u_dim is then the action width u_env + x_dim, an
-    action is [u | eta] and x' = base + mean + beta * std_over_members * eta (SYS_ENSEMBLE in ENS_MEAN only)."""
+    action is [u | eta] and x' = base + mean + beta * std_over_members * eta (SYS_ENSEMBLE in ENS_MEAN only).
+    hold_max_steps = K > 0 with the other hold_* (TimeAdaptive.kernel_spec): the time-adaptive rollouts of include/mbpo_hip.h — u_dim is
+    then the action width u_env + 1, an action is [u | tau] and u is held for k(tau) <= K model steps; action_repeat must be 1,
+    model_noise is [S,K,N,x] and member_idx [S,K,N]."""
     if system_kind == _hip.SYS_GENERIC:
+        if hold_max_steps:
+            raise ValueError("hold_max_steps belongs to the fused systems; a user-defined System steps once per call")
         if halluc_beta is not None:
             raise ValueError("halluc_beta belongs to the fused ensemble; a user-defined System forms its own next state")
         if term_low is not None or term_high is not None:
@@ -356,14 +363,15 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
         _req(policy_noise, "policy_noise")
         if policy_noise.numel() != n_steps * n_envs * u_dim:
             raise ValueError("policy_noise must be [S,N,u]")
+    inner = int(hold_max_steps) if hold_max_steps else action_repeat      # inner steps the explicit random tensors are laid out for
     if model_noise is not None:
         _req(model_noise, "model_noise")
-        if model_noise.numel() != n_steps * action_repeat * n_envs * x_dim:
-            raise ValueError("model_noise must be [S,AR,N,x]")
+        if model_noise.numel() != n_steps * inner * n_envs * x_dim:
+            raise ValueError("model_noise must be [S,AR,N,x] ([S,K,N,x] with hold_max_steps = K)")
     if member_idx is not None:
         _req(member_idx, "member_idx", torch.int32)
-        if member_idx.numel() != n_steps * action_repeat * n_envs:
-            raise ValueError("member_idx must be [S,AR,N]")
+        if member_idx.numel() != n_steps * inner * n_envs:
+            raise ValueError("member_idx must be [S,AR,N] ([S,K,N] with hold_max_steps = K)")
     d.policy_noise, d.model_noise, d.member_idx = ptr(policy_noise), ptr(model_noise), ptr(member_idx)
     d.seed, d.offset = seed, offset
     d.rng_dev = rng_ptr(rng_dev)
@@ -377,7 +385,27 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
     if halluc_beta is not None and _req(halluc_beta, "halluc_beta").numel() != x_dim:
         raise ValueError("halluc_beta must be [x_dim]")
     d.halluc_beta = ptr(halluc_beta)
+    if hold_max_steps:
+        d.hold_max_steps, d.hold_min_time, d.hold_max_time, d.hold_dt = int(hold_max_steps), hold_min_time, hold_max_time, hold_dt
+        d.hold_gamma, d.hold_switch_cost = hold_gamma, hold_switch_cost
     check(lib.mbpo_model_rollout(C.byref(d), current_stream_ptr()), "mbpo_model_rollout")
+    return out
+
+
+def hold_steps(actions: torch.Tensor, min_time: float, max_time: float, env_dt: float, max_steps: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_hold_steps: int32 [n], the model steps a time-adaptive rollout holds each of `actions` [n, A] for (from the last column)."""
+    lib = load()
+    _req(actions, "actions")
+    if actions.dim() != 2 or actions.shape[1] < 1:
+        raise ValueError(f"actions must be [n, A], got {tuple(actions.shape)}")
+    n, A = actions.shape
+    if out is None:
+        out = torch.empty(n, device=actions.device, dtype=torch.int32)
+    elif _req(out, "out", torch.int32).shape != (n,):
+        raise ValueError(f"out must be int32 [{n}]")
+    check(lib.mbpo_hold_steps(actions.data_ptr(), n, A, float(min_time), float(max_time), float(env_dt), int(max_steps),
+                              out.data_ptr(), current_stream_ptr()), "mbpo_hold_steps")
     return out
 
 

@@ -29,6 +29,7 @@ from mbpo.replay import ReplayBufferState, UniformSamplingQueue
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
 from mbpo.systems.rewards.base_rewards import RewardParams
 from mbpo.systems.termination import without_termination
+from mbpo.systems.time_adaptive import refuse_time_adaptive
 from mbpo.types import Transition
 from mbpo.utils import keys as K
 from mbpo.utils.type_aliases import OptimizerState, OptimizerTrainingOutPut
@@ -152,6 +153,7 @@ def _refuse_optimistic(system) -> None:
     if getattr(system, "optimistic", False):
         raise ValueError("BPTT does not take EnsembleSystem(mode='optimistic'): the gradient through the ensemble spread "
                          "(x' = mean + beta * std * eta) is not built; use SAC, PPO or iCEM")
+    refuse_time_adaptive(system, "BPTT")      # (nor a time-adaptive one: its objective sums per-step rewards)
 
 
 class BPTTOptimizer(BaseOptimizer):

@@ -27,6 +27,7 @@ from mbpo.optimizers.policy_optimizers.sac.sac import Evaluator, RunningStatisti
 from mbpo.parallel import DataParallel
 from mbpo.systems.brax_wrapper import BraxWrapper
 from mbpo.systems.ensemble_system import lecun_uniform_flat
+from mbpo.systems.time_adaptive import check_trainer
 from mbpo.utils import keys as K
 
 Metrics = Dict[str, Any]
@@ -114,6 +115,11 @@ class PPO:
             raise ValueError(f"max_grad_norm must be > 0 (or None: no clipping), got {max_grad_norm}")
         if non_equidistant_time and not env_dt > 0:
             raise ValueError("non_equidistant_time needs env_dt > 0 (losses_new.py:110 floors the switch time to multiples of it)")
+        # a time-adaptive system (mbpo/systems/time_adaptive.py): the hold is the repeat, and the loss must discount by the time the
+        # rollout held
+        check_trainer(getattr(environment, "system", None), "PPO", action_repeat=action_repeat, non_equidistant_time=non_equidistant_time,
+                      continuous_discounting=continuous_discounting, min_time_between_switches=min_time_between_switches,
+                      max_time_between_switches=max_time_between_switches, env_dt=env_dt)
         self.return_best_model = return_best_model
         self.resample_starts = bool(resample_starts)
         self.episode_length = episode_length

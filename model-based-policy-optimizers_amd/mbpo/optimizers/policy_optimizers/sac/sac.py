@@ -33,6 +33,7 @@ from mbpo.parallel import DataParallel
 from mbpo.replay import ReplayBufferState, UniformSamplingQueue
 from mbpo.systems.brax_wrapper import BraxWrapper
 from mbpo.systems.ensemble_system import lecun_uniform_flat
+from mbpo.systems.time_adaptive import check_trainer
 from mbpo.types import Transition
 from mbpo.utils import keys as K
 
@@ -156,6 +157,11 @@ class SAC:
         if real_ratio > 0 and getattr(getattr(environment, "system", None), "optimistic", False):
             raise ValueError(f"real_ratio={real_ratio} > 0 on EnsembleSystem(mode='optimistic'): real rows carry u_dim action columns, "
                              "model rows action_dim = u_dim + x_dim (the hallucinated controls), so they cannot share a minibatch")
+        # a time-adaptive system (mbpo/systems/time_adaptive.py): the hold is the repeat, real rows have no tau column, and the loss
+        # must discount by the time the rollout held
+        check_trainer(getattr(environment, "system", None), "SAC", action_repeat=action_repeat, non_equidistant_time=non_equidistant_time,
+                      continuous_discounting=continuous_discounting, min_time_between_switches=min_time_between_switches,
+                      max_time_between_switches=max_time_between_switches, env_dt=env_dt, real_ratio=real_ratio)
         self.real_ratio = float(real_ratio)
         self.resample_starts = bool(resample_starts)
         self.n_real = int(batch_size * real_ratio)
@@ -253,8 +259,9 @@ class SAC:
                                                   sample_batch_size=batch_size * grad_updates_per_step, device=self.device)
         self.row_len = self.replay_buffer.row_len
         # real rows (the true buffer's transitions) must be a column prefix of the model rows: checked even when n_real == 0
-        # (not on an optimistic system: its model rows are action_dim wide, real_ratio > 0 is refused above and nothing is ever mixed)
-        if not getattr(self.env.system, "optimistic", False):
+        # (not where action_dim != u_dim — an optimistic or a time-adaptive system: the model rows are action_dim wide, real_ratio > 0
+        # is refused above and nothing is ever mixed)
+        if self.env.system.action_dim == self.env.system.u_dim:
             self.replay_buffer.check_mixable(self.env.sample_buffer)
         # fixed device buffers (graph-replayable)
         S, N = num_env_steps_between_updates, num_envs

@@ -36,6 +36,7 @@ from mbpo.systems.base_systems import System
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
 from mbpo.systems.rewards.base_rewards import RewardParams
 from mbpo.systems.termination import without_termination
+from mbpo.systems.time_adaptive import refuse_time_adaptive
 from mbpo.utils import keys as K
 from mbpo.utils.type_aliases import OptimizerState, OptimizerTrainingOutPut
 
@@ -80,6 +81,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
     def __init__(self, horizon: int, action_dim: int, key: int = K.PRNGKey(0), opt_params: iCemParams = iCemParams(), cost_fn=None,
                  use_optimism: bool = False, use_pessimism: bool = False, *args, **kwargs):
         super().__init__(*args, **kwargs)
+        refuse_time_adaptive(self.system, "iCEM")
         self.cost_fn = cost_fn       # evaluated on the host side of the seam, between two launches (see the module docstring)
         self.lib = _hip.load()
         self.horizon, self.action_dim = int(horizon), int(action_dim)
@@ -92,6 +94,10 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             raise ValueError("num_elites must be in (0, num_samples + carried elites]")
         self._bufs = None
         self._bbufs = None
+
+    def set_system(self, system):
+        refuse_time_adaptive(system, "iCEM")      # (single and batched: the candidates' objective sums per-step rewards)
+        super().set_system(system)
 
     # -- reference API ------------------------------------------------------------------------------------------------
     def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None, batch_size: Optional[int] = None) -> iCemOptimizerState:
@@ -306,6 +312,7 @@ class iCEMOptimizer(BaseOptimizer):
 
     def __init__(self, horizon: int, opt_params: iCemParams = iCemParams(), system: Optional[System] = None, key: int = K.PRNGKey(0),
                  batch_size: Optional[int] = None, **agent_kwargs):
+        refuse_time_adaptive(system, "iCEM")
         super().__init__(system, key)
         self.horizon, self.key, self.opt_params = horizon, key, opt_params
         self.batch_size = None if batch_size is None else int(batch_size)
@@ -314,6 +321,10 @@ class iCEMOptimizer(BaseOptimizer):
         self.agent_class, self.agent_kwargs = iCemTO, agent_kwargs
         if system is not None:
             self.set_system(system)
+
+    def set_system(self, system):
+        refuse_time_adaptive(system, "iCEM")
+        super().set_system(system)
 
     @property
     def can_act_in_batches(self):

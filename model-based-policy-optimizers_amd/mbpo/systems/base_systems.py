@@ -39,17 +39,41 @@ class SystemState(Generic[DynamicsParams, RewardParams]):
 
 
 class System(ABC, Generic[DynamicsParams, RewardParams]):
-    def __init__(self, dynamics: Dynamics, reward: Reward):
+    time_adaptive = None      # (a subclass that never calls __init__ is not time-adaptive)
+
+    def __init__(self, dynamics: Dynamics, reward: Reward, time_adaptive=None):
+        """time_adaptive: a mbpo.systems.TimeAdaptive — the policy emits [u | tau] and the fused rollout holds u for k(tau) model
+        steps (include/mbpo_hip.h "time-adaptive rollouts").  Fused systems only: a user-defined System steps once per call."""
         self.dynamics = dynamics
         self.reward = reward
         self.x_dim = dynamics.x_dim
         self.u_dim = dynamics.u_dim
+        if time_adaptive is not None and not self.fused:
+            raise ValueError(f"time_adaptive needs a fused system (PendulumSystem, EnsembleSystem): the hold runs inside the rollout "
+                             f"kernel, and {type(self).__name__}.step is user code that steps once per call")
+        self.time_adaptive = time_adaptive
 
     @property
     def action_dim(self) -> int:
         """What the policy (or a planner) emits and the model's transition rows carry.  u_dim — what the dynamics and the true buffer
-        see — for every system but the optimistic EnsembleSystem, whose actions also hold the hallucinated controls."""
-        return self.u_dim
+        see — unless the actions hold more than controls: the optimistic EnsembleSystem's hallucinated controls (u_dim + x_dim), a
+        time-adaptive system's hold time (u_dim + 1)."""
+        return self.u_dim + (1 if self.time_adaptive is not None else 0)
+
+    def env_action(self, a: torch.Tensor) -> torch.Tensor:
+        """The controls of a policy action, for acting on the true system: a[..., :u_dim] (the whole action where action_dim == u_dim)."""
+        return a[..., :self.u_dim]
+
+    def hold_steps(self, a: torch.Tensor) -> torch.Tensor:
+        """int32 [n]: the model steps the fused rollouts hold each of the actions a [n, action_dim] (or one, [action_dim]) for —
+        mbpo_hold_steps, the kernels' own function — so that host code acts on the true system for exactly as long."""
+        from mbpo import ops
+        if self.time_adaptive is None:
+            raise ValueError("hold_steps needs a time-adaptive system (time_adaptive=TimeAdaptive(...))")
+        ta = self.time_adaptive
+        ab = a.reshape(-1, self.action_dim).to(_device_of(a), torch.float32).contiguous()
+        k = ops.hold_steps(ab, ta.min_time_between_switches, ta.max_time_between_switches, ta.env_dt, ta.max_steps)
+        return k[0] if a.dim() == 1 else k
 
     @staticmethod
     def system_params_vmap_axes(axes: int = 0):
@@ -57,7 +81,8 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
 
     def step(self, x: torch.Tensor, u: torch.Tensor, system_params: SystemParams) -> SystemState:
         """Systems that exist as device code (PendulumSystem, EnsembleSystem): one fused launch of the rollout kernel with
-        open-loop actions and S=1 (csrc/rollout.hip).  A user-defined System overrides this with its own BATCHED torch code
+        open-loop actions and S=1 (csrc/rollout.hip).  On a time-adaptive system u is an action [u | tau] and the step is one
+        decision: x_next after k(tau) model steps (fewer where the box was left), reward the hold's discounted sum less switch_cost.  A user-defined System overrides this with its own BATCHED torch code
         (x [N, x_dim], u [N, u_dim] on the device -> SystemState with x_next [N, x_dim], reward [N]); the trainers then step it
         between the HIP policy and bookkeeping kernels (ops.generic_rollout).
         With a termination set (PendulumSystem / EnsembleSystem(termination=)) SystemState.done is the box's verdict on the next state;

@@ -475,12 +475,21 @@ class EnsembleSystem(System):
     spread is not built), SAC's real_ratio > 0 (real rows carry u_dim action columns, model rows action_dim), members wider than 256.
     calibrated=True (optimistic only): the kernels get halluc_beta = beta * dynamics_params.calibration, one fp32 multiply on the
     device into a buffer the system keeps, refreshed when the calibration tensor or its contents change; `beta` stays the user's
-    value.  rollout_spec refuses parameters without a calibration (run `calibrate` or `fit(calibrate=True)` first)."""
+    value.  rollout_spec refuses parameters without a calibration (run `calibrate` or `fit(calibrate=True)` first).
+
+    time_adaptive (a TimeAdaptive; every mode but 'optimistic'): action_dim = u_dim + 1, an action is [u | tau] and the fused rollouts
+    hold u for k(tau) steps of the members (mbpo/systems/time_adaptive.py).  The members stay a model of one env_dt, fitted on
+    base-rate transitions with u_dim action columns as before."""
 
     def __init__(self, dynamics: EnsembleDynamics, reward: Reward, mode: str = "mean", predict_delta: bool = True,
                  sample_noise: bool = False, min_std: float = 1e-3, termination: Optional[BoxTermination] = None, beta=1.0,
-                 calibrated: bool = False):
-        super().__init__(dynamics=dynamics, reward=reward)
+                 calibrated: bool = False, time_adaptive=None):
+        if time_adaptive is not None and mode == "optimistic":
+            raise ValueError("time_adaptive together with mode='optimistic' is not built: the action would be [u | eta | tau] and no "
+                             "rollout kernel holds a hallucinated control")
+        if time_adaptive is not None and dynamics.kernel_width is None:
+            raise ValueError("time_adaptive runs inside the fused rollout kernels, which take members up to 256 wide")
+        super().__init__(dynamics=dynamics, reward=reward, time_adaptive=time_adaptive)
         if termination is not None and termination.x_dim != dynamics.x_dim:
             raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {dynamics.x_dim}")
         self.termination = termination
@@ -513,11 +522,7 @@ class EnsembleSystem(System):
 
     @property
     def action_dim(self) -> int:
-        return self.u_dim + self.x_dim if self.optimistic else self.u_dim
-
-    def env_action(self, a: torch.Tensor) -> torch.Tensor:
-        """The controls of a policy action, for acting on the true system: a[..., :u_dim] (the whole action unless optimistic)."""
-        return a[..., :self.u_dim]
+        return self.u_dim + self.x_dim if self.optimistic else super().action_dim
 
     def _halluc_beta(self, device) -> torch.Tensor:
         """beta as a device tensor, cached per device: nothing is copied host to device inside a captured graph."""
@@ -569,4 +574,5 @@ class EnsembleSystem(System):
                     ens_min_std=self.min_std, reward_kind=kind, reward_params=rvec,
                     **({"halluc_beta": self._calibrated_beta(device, system_params.dynamics_params) if self.calibrated
                         else self._halluc_beta(device)} if self.optimistic else {}),
+                    **({} if self.time_adaptive is None else self.time_adaptive.kernel_spec()),
                     **termination_spec(self.termination, self.x_dim, device))

@@ -14,9 +14,10 @@ from mbpo.systems.termination import BoxTermination, termination_spec
 
 
 class PendulumSystem(System[PendulumDynamicsParams, PendulumRewardParams]):
-    def __init__(self, termination: Optional[BoxTermination] = None):
-        """termination (not in the reference): a BoxTermination on the next state [cos, sin, thetadot]; see EnsembleSystem."""
-        super().__init__(dynamics=PendulumDynamics(), reward=PendulumReward())
+    def __init__(self, termination: Optional[BoxTermination] = None, time_adaptive=None):
+        """termination (not in the reference): a BoxTermination on the next state [cos, sin, thetadot]; see EnsembleSystem.
+        time_adaptive (not in the reference): a TimeAdaptive — actions are [u | tau]; see EnsembleSystem."""
+        super().__init__(dynamics=PendulumDynamics(), reward=PendulumReward(), time_adaptive=time_adaptive)
         if termination is not None and termination.x_dim != self.x_dim:
             raise ValueError(f"the termination has {termination.x_dim} dimensions, the system {self.x_dim}")
         self.termination = termination
@@ -26,10 +27,12 @@ class PendulumSystem(System[PendulumDynamicsParams, PendulumRewardParams]):
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         dp = system_params.dynamics_params or PendulumDynamicsParams()
         rp = system_params.reward_params or PendulumRewardParams()
-        ck = (dataclasses.astuple(dp), dataclasses.astuple(rp), str(device), None if self.termination is None else self.termination.key)
+        ck = (dataclasses.astuple(dp), dataclasses.astuple(rp), str(device), None if self.termination is None else self.termination.key,
+              self.time_adaptive)
         if getattr(self, "_spec_key", None) != ck:     # device vectors are cached: no H2D copy inside a captured graph
             kind, rvec = self.reward.kernel_spec(rp, device)
             self._spec = dict(system_kind=_hip.SYS_PENDULUM, sys_params=dp.vector(device), reward_kind=kind, reward_params=rvec,
+                              **({} if self.time_adaptive is None else self.time_adaptive.kernel_spec()),
                               **termination_spec(self.termination, self.x_dim, device))
             self._spec_key = ck
         return dict(self._spec)

@@ -288,6 +288,48 @@ def main():
 
     if want("rollout_optimistic_case"): rollout_optimistic_case(4096, 4, 1, 5, 5, (64, 64, 64), 50)      # C2's shape, 'mean' and 'optimistic'
 
+    # time-adaptive rollouts (mbpo_rollout_desc.hold_*; TimeAdaptive) at C2's shape with action width A = 2, next to the plain C2 row of
+    # the same session: the plain rollout at u_dim = 2 (its dynamics read both columns), the hold at t_lo = t_hi = env_dt (every k = 1:
+    # the cost of the flag alone) and at t_hi = 4 env_dt (tau is sampled: k in 1 .. 4, a tile runs to its largest k).  All three on
+    # k_model_rollout64 (u_dim = 2 keeps the rollout off k_rollout_lean).  A record, no target.
+    def rollout_time_adaptive_case(N, X, UE, E, S, hid, reps):
+        from mbpo.systems import TimeAdaptive
+        A, dt = UE + 1, 0.05
+        obs = torch.randn(N, X, generator=g).to(dev)
+        first = obs.clone()
+        steps, done = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+        pd = [X, *hid, 2 * A]
+        pp = lecun_flat(pd, g).to(dev)
+        rows = torch.empty(S * N, 2 * X + A + 3, device=dev)
+        for label, ue, hold in (("off", A, None), ("k=1", UE, TimeAdaptive(dt, dt, dt)), ("k<=4", UE, TimeAdaptive(dt, 4 * dt, dt))):
+            dd = [X + ue, *hid, 2 * X]
+            dp = lecun_flat(dd, g, E).to(dev)
+            rp = torch.cat([torch.zeros(X), torch.ones(X), torch.ones(ue) * 0.1]).to(dev)
+            extra = {} if hold is None else hold.kernel_spec()
+
+            def run():
+                ops.model_rollout(policy_params=pp, policy_spec=ops.MlpSpec(pd), x_dim=X, u_dim=A, obs=obs, first_obs=first, steps=steps,
+                                  done=done, n_steps=S, episode_length=S, system_kind=_hip.SYS_ENSEMBLE, dyn_params=dp,
+                                  dyn_spec=ops.MlpSpec(dd, "swish", E), reward_kind=_hip.REWARD_QUADRATIC, reward_params=rp, seed=1,
+                                  offset=0, out=rows, **extra)
+            t, te = both(run, reps)
+            torch.cuda.synchronize()
+            mean_k = 1.0
+            if hold is not None:
+                mean_k = float(ops.hold_steps(rows[:, X:X + A].contiguous(), dt, hold.max_time_between_switches, dt, hold.max_steps).float().mean())
+            flop = N * S * (2 * E * mlp_macs(dd) * mean_k + 2 * mlp_macs(pd))
+            out.append(mfma_entry("k_model_rollout64", "mbpo_model_rollout",
+                                  {"N": N, "x": X, "u_env": ue, "action_width": A, "E": E, "S": S, "policy": list(hid), "member": list(hid),
+                                   "reward": "quadratic", "time_adaptive": label, "hold_max_steps": 0 if hold is None else hold.max_steps,
+                                   "mean_hold": mean_k}, t, flop, "2*E*M*mean_hold + 2*P FLOP per decision",
+                                  {"decisions_per_s": N * S / t, "model_steps_per_s": N * S * mean_k / t}))
+            log(f"rollout (time-adaptive {label}, k_model_rollout64) N={N} x={X} A={A} E={E} {hid}: {t * 1e6:.1f} us  mean hold {mean_k:.2f}  "
+                f"{N * S * mean_k / t / 1e6:.1f} M model steps/s")
+
+    if args.only is not None and want("rollout_time_adaptive_case"):      # the plain C2 row in the same session (a full run has it above)
+        rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50)
+    if want("rollout_time_adaptive_case"): rollout_time_adaptive_case(4096, 4, 1, 5, 5, (64, 64, 64), 50)
+
     # ---------------------------------------------------------------- R2: vmapped ensemble forward (System.step outside the fused rollout)
     def ens_fwd_case(N, X, U, E, hid, reps):
         dd = [X + U, *hid, 2 * X]
