@@ -5,7 +5,7 @@
                       ->  SACOptimizer on EnsembleSystem (short model rollouts branched from true states + SAC updates)
                       ->  the policy acts on the TRUE PendulumSystem.
 
-    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V]
+    python examples/mbpo_pendulum.py [--iters 2 --model-steps 1500 --sac-steps 40000] [--learn-reward] [--elites] [--terminate-speed V] [--term-reward]
                                      [--real-ratio R] [--normalize-inputs] [--resample-starts] [--optimistic BETA] [--calibrate]
                                      [--warm-start [--retain-buffer]] [--time-adaptive TMIN TMAX [--switch-cost C]]
 
@@ -44,6 +44,10 @@ steps of the learned model, sum the rewards of the hold discounted by 0.99 per s
 non_equidistant_time options, so its target discounts every row by the time the row was held.  On the TRUE system an action is applied
 for model.hold_steps(a) steps (the kernels' own k); every iteration also reports the mean hold of that evaluation.  Not with
 --optimistic or --real-ratio.  No learning curve is claimed for it.
+--term-reward: the MODEL's reward is a TermReward written as data instead of the Pendulum's formula — on the observation
+(cos th, sin th, thdot): -(cos th - 1)^2 - sin^2 th - 0.1 thdot^2 - 0.02 u^2 plus the tolerance bonus
+exp(-4 ((cos th - 1)^2 + sin^2 th)) around upright, evaluated inside the fused rollouts.  The true system keeps the Pendulum's own
+reward, which is what the evaluation reports.  Not with --learn-reward.  No learning curve is claimed for it.
 """
 from __future__ import annotations
 
@@ -142,11 +146,11 @@ def calibration_report(dyn, dyn_params, rows, n_rows, fit_key, true_system, dev,
 
 def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbose=True, learn_reward=False, elites=False,
         terminate_speed=None, real_ratio=0.0, normalize_inputs=False, resample_starts=False, optimistic=None, calibrate=False,
-        warm_start=False, retain_buffer=False, time_adaptive=None, switch_cost=0.0):
+        warm_start=False, retain_buffer=False, time_adaptive=None, switch_cost=0.0, term_reward=False):
     from mbpo.optimizers import SACOptimizer
     from mbpo.replay import UniformSamplingQueue
     from mbpo.systems import (BoxTermination, EnsembleDynamics, EnsembleSystem, LearnedReward, PendulumReward, PendulumSystem,
-                              TimeAdaptive)
+                              TimeAdaptive, Group, Term, TermReward)
     from mbpo.systems.dynamics.pendulum_dynamics import PendulumDynamicsParams
     from mbpo.types import Transition
     if time_adaptive is not None and (optimistic is not None or real_ratio > 0):
@@ -169,7 +173,13 @@ def run(iters=2, n_true=4000, model_steps=1500, sac_steps=40_000, seed=0, verbos
     tbs = true_buffer.init(seed)
     dyn = EnsembleDynamics(3, 1, n_members=7 if elites else 5, learn_reward=learn_reward)
     termination = None if terminate_speed is None else BoxTermination.from_intervals(3, {2: (-terminate_speed, terminate_speed)})
-    model = EnsembleSystem(dyn, LearnedReward(dyn) if learn_reward else PendulumReward(), predict_delta=True, termination=termination,
+    if term_reward and learn_reward:
+        raise ValueError("--term-reward is not combined with --learn-reward")
+    upright = [Term("x", 0, "square", 1.0, 1.0), Term("x", 1, "square", 1.0)]          # (cos th - 1)^2 + sin^2 th
+    known = TermReward(3, 1, groups=[Group(upright + [Term("x", 2, "square", 0.1), Term("u", 0, "square", 0.02)], weight=-1.0),
+                                     Group([Term("x", 0, "square", -4.0, 1.0), Term("x", 1, "square", -4.0)], link="exp")])
+    reward = known if term_reward else (LearnedReward(dyn) if learn_reward else PendulumReward())
+    model = EnsembleSystem(dyn, reward, predict_delta=True, termination=termination,
                            time_adaptive=ta,
                            **(dict(mode="mean") if optimistic is None else dict(mode="optimistic", beta=optimistic, calibrated=calibrate)))
     dyn_params = dyn.init_params(seed + 1)
@@ -260,8 +270,10 @@ if __name__ == "__main__":
     ap.add_argument("--time-adaptive", type=float, nargs=2, default=None, metavar=("TMIN", "TMAX"),
                     help="the policy also chooses how long its torque is held, between TMIN and TMAX seconds (multiples of the Pendulum's dt)")
     ap.add_argument("--switch-cost", type=float, default=0.0, metavar="C", help="with --time-adaptive: charged once per decision")
+    ap.add_argument("--term-reward", action="store_true",
+                    help="the model's reward is a TermReward (a quadratic cost on (cos th, sin th, thdot, u) plus an exp tolerance bonus)")
     a = ap.parse_args()
     run(a.iters, model_steps=a.model_steps, sac_steps=a.sac_steps, seed=a.seed, learn_reward=a.learn_reward, elites=a.elites,
         terminate_speed=a.terminate_speed, real_ratio=a.real_ratio, normalize_inputs=a.normalize_inputs,
         resample_starts=a.resample_starts, optimistic=a.optimistic, calibrate=a.calibrate, warm_start=a.warm_start,
-        retain_buffer=a.retain_buffer, time_adaptive=a.time_adaptive, switch_cost=a.switch_cost)
+        retain_buffer=a.retain_buffer, time_adaptive=a.time_adaptive, switch_cost=a.switch_cost, term_reward=a.term_reward)

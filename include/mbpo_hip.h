@@ -121,6 +121,44 @@ int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *x, int32_t 
  * mbpo_ens_nll_grads and reported as the reward's std by the host API, never read by a rollout).  reward_params may be NULL.
  * The analytic rewards accept a 2x + 2 ensemble too and ignore its reward head. */
 #define MBPO_REWARD_LEARNED 2
+/* Term rewards (a known closed-form reward written as data.  Not in the reference tree; build-defined: THIS TEXT IS THE DEFINITION).
+ * Needs MBPO_SYS_ENSEMBLE.  With UE the control width the dynamics see (u_dim, less x_dim with halluc_beta, less 1 with hold_max_steps:
+ * eta and tau never enter a reward) and x' the next state the step produced (the members' mean, the drawn member plus its noise, or
+ * the hallucinated state; before termination and auto-reset):
+ *   z   = [x (x_dim) | u (UE) | x_next (x_dim)],   x_next = x' if every component of x' is finite, else x (the pre-step state)
+ *   s_g = sum_{k in group g} c_k * f_k(z[i_k] - t_k)         k ascending from the group's first term, one accumulator from 0
+ *   r   = bias + sum_g w_g * L_g(s_g)                        g ascending, one accumulator from bias
+ * every product and every sum rounded to fp32 on its own (no fused multiply-add), with the accurate cosf / sinf / expf / tanhf / sqrtf.
+ *   f: 0 identity v, 1 square v * v, 2 abs |v|, 3 relu max(v, 0), 4 cos, 5 sin             (MBPO_TERM_FN_*)
+ *   L: 0 identity s, 1 sqrt(max(s, 0)), 2 exp, 3 tanh                                      (MBPO_TERM_LINK_*)
+ * No product of two different columns exists.  reward_params is a table of MBPO_REWARD_TERMS_FLOATS fp32 values, always of its full
+ * length, small integers stored as exact floats:
+ *   [0, 4)                          header  [n_groups, n_terms, bias, 0]
+ *   [4, 4 + 4 * MAX_GROUPS)         group g [w, link, first_term, n_terms]
+ *   [4 + 4 * MAX_GROUPS, FLOATS)    term k  [z_index, fn, c, t]
+ * The kernels clamp n_groups to [0, MAX_GROUPS], the header's n_terms to [0, MAX_TERMS], a group's first_term to [0, n_terms] and its
+ * count to [0, n_terms - first_term]; a term whose z_index lies outside [0, 2 * x_dim + UE) or whose fn is unknown contributes 0, and so
+ * does a group whose link is unknown: whatever the vector holds, no read leaves it or the row.  The reward of an inner step
+ * (action_repeat, or a time-adaptive hold) is formed from that inner step's (x_j, u, x_{j+1}) and accumulated as the other kinds are.
+ * The non-finite rule keeps the reward of a diverged (then terminal) row finite.  The tile kernels (64 / 128 / 256 wide) run it; the
+ * kernel specialised for the benchmark networks never takes it.  mbpo_bptt_actor_grads (MBPO_SYS_ENSEMBLE) takes tables whose terms
+ * all read x or u (z_index < x_dim + u_dim): d r / d z_c = sum_g w_g L_g'(s_g) sum_{k in g: i_k = c} c_k f_k'(z_c - t_k), abs and relu
+ * with gradient 0 at 0 (torch's), the sqrt link with gradient 0 at s <= 0.  The gradient through next-state terms is not built: there
+ * a next-state column reads x and takes no gradient, and the host API (BPTTOptimizer) refuses such a table before any launch. */
+#define MBPO_REWARD_TERMS 3
+#define MBPO_REWARD_TERMS_MAX_GROUPS 16
+#define MBPO_REWARD_TERMS_MAX_TERMS 128
+#define MBPO_REWARD_TERMS_FLOATS (4 + 4 * MBPO_REWARD_TERMS_MAX_GROUPS + 4 * MBPO_REWARD_TERMS_MAX_TERMS)
+#define MBPO_TERM_FN_IDENTITY 0
+#define MBPO_TERM_FN_SQUARE 1
+#define MBPO_TERM_FN_ABS 2
+#define MBPO_TERM_FN_RELU 3
+#define MBPO_TERM_FN_COS 4
+#define MBPO_TERM_FN_SIN 5
+#define MBPO_TERM_LINK_IDENTITY 0
+#define MBPO_TERM_LINK_SQRT 1
+#define MBPO_TERM_LINK_EXP 2
+#define MBPO_TERM_LINK_TANH 3
 
 /* Termination (SystemState.done of the fused systems, base_systems.py:25; MBPO's termination functions): a box on the step's
  * pre-auto-reset next state x', term_low / term_high [x_dim] (unbounded dimensions carry -inf / +inf; the bounds are closed):
@@ -277,6 +315,15 @@ int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream);
  * use: n < 0, action_dim < 1, env_dt <= 0, min_time > max_time, max_steps outside [1, 64], a NULL pointer with n > 0. */
 int mbpo_hold_steps(const float *actions, int64_t n, int32_t action_dim, float min_time, float max_time, float env_dt,
                     int32_t max_steps, int32_t *steps_out, void *stream);
+
+/* out[i] = the reward of row i as the rollout kernels form it, one thread per row, by the same device function: for
+ * Reward.__call__ on the host side and for tests.  MBPO_REWARD_TERMS ("term rewards" above; u_dim is the control width UE) and
+ * MBPO_REWARD_QUADRATIC; every other kind is MBPO_ERR_UNSUPPORTED.  x [n, x_dim], u [n, u_dim], x_next [n, x_dim] or NULL, out [n], all
+ * on the device.  x_next == NULL makes the x_next columns of z read x — for a table the caller knows to be free of next-state terms;
+ * a row of x_next with a non-finite component reads x likewise.  The quadratic reward ignores x_next.  No workspace; capturable.
+ * MBPO_ERR_ARG before any device use: n < 0, x_dim < 1, u_dim < 1, or with n > 0 a NULL reward_params, x, u or out. */
+int mbpo_reward_eval(int32_t reward_kind, const float *reward_params, const float *x, const float *u, const float *x_next, int64_t n,
+                     int32_t x_dim, int32_t u_dim, float *out, void *stream);
 
 /* ---- R1/R4-R7 for a USER-DEFINED System: the non-fused env step ------------------------------------
  * replaces: the same reference lines as mbpo_model_rollout, split at the reference's own plug-in seam — System.step

@@ -15,6 +15,7 @@
 // Algorithmic FLOP per (trajectory, step): 3*(2P) + 2*(2*E*M) + 2*(2*2V)  (SURVEY §8d).
 #include "common.hpp"
 #include "chain_run.hpp"
+#include "reward_terms.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -108,8 +109,10 @@ __device__ __forceinline__ void pend_vjp(const float *x, float u, const float *s
   *du = uin ? g_raw * dt * c * mt : 0.f;
 }
 
+template <bool TERMS>
 __device__ __forceinline__ float reward_fwd(const BpttArgs &A, const float *xu) {
   const int X = A.X, U = A.U;
+  if constexpr (TERMS) return reward_terms_eval(A.reward_params, xu, xu + X, xu, X, U);      // (a next-state column would read x: refused by the host API)
   if (A.reward_kind == MBPO_REWARD_PENDULUM) {
     const float *rp = A.reward_params;
     const float PI_F = 3.14159265358979323846f, TWO_PI_F = 6.28318530717958647692f;
@@ -126,8 +129,10 @@ __device__ __forceinline__ float reward_fwd(const BpttArgs &A, const float *xu) 
   return -cx - cu;
 }
 // one component (c < X: state, c >= X: action) of g * d reward / d(x,u): lets the (row, column) threads of a section each take one
+template <bool TERMS>
 __device__ __forceinline__ float reward_grad_comp(const BpttArgs &A, const float *xu, float g, int c) {
   const int X = A.X;
+  if constexpr (TERMS) return g * reward_terms_grad_comp(A.reward_params, xu, xu + X, X, A.U, c);
   if (A.reward_kind == MBPO_REWARD_PENDULUM) {
     const float *rp = A.reward_params;
     if (c == 2) return g * (-0.2f * xu[2]);
@@ -152,10 +157,20 @@ __device__ __forceinline__ float reward_grad_comp(const BpttArgs &A, const float
 // TS: the trajectory-sampling instantiation ('ts1' / 'tsinf').  A uniform branch on A.ts alone kept the mean path's results but not its
 // register allocation (+3 VGPRs, +30 SGPR spills, +1 % per BASELINE config-5 train step); with TS = false every TS branch is compiled
 // out and the mean kernel is the one it was.
+// (LR has three values: FORMULA the Pendulum / quadratic reward, LEARNED as described next, TERMS the term table of
+// csrc/reward_terms.hpp through reward_fwd / reward_grad_comp's TERMS forms; compile-time for the reason given here)
+#define BP_LR_FORMULA 0
+#define BP_LR_LEARNED 1
+#define BP_LR_TERMS 2
+template <class F>
+static int bptt_with_lr(int lr, F &&f) {
+  if (lr == BP_LR_TERMS) return f(std::integral_constant<int, BP_LR_TERMS>{});
+  return lr == BP_LR_LEARNED ? f(std::integral_constant<int, BP_LR_LEARNED>{}) : f(std::integral_constant<int, BP_LR_FORMULA>{});
+}
 // LR: MBPO_REWARD_LEARNED — the reward is read from the members' reward head (column 2X) in the forward sweep and its gradient enters the
 // member output gradient (E_DYE); reward_grad_comp is skipped.  A template flag for the same reason as TS: the other instantiations keep
 // their register allocation.
-template <int H, bool WIDE, bool TS, bool LR>
+template <int H, bool WIDE, bool TS, int LR>
 __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -223,7 +238,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
   bool first_tile = true;
   const long long n_tiles = (A.n + 15) >> 4;
   const bool ens = A.system_kind == MBPO_SYS_ENSEMBLE;
-  constexpr bool lrw = LR;                    // (ensemble only: the reward is the members' head, column 2X)
+  constexpr bool lrw = LR == BP_LR_LEARNED;                    // (ensemble only: the reward is the members' head, column 2X)
   const int NR = ens ? (E + EC - 1) / EC : 0;   // ensemble rounds of EC member chains
   const int Rm = ens ? NR : 1;                  // model ops of a forward step (pendulum: one elementwise op)
   const int nF = Rm + 3, nB = 5 + (ens ? 2 * NR : 1);
@@ -460,7 +475,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
         } else if (elem == E_NN) {
           if (tid < 16) {
             const long long i = row0 + tid;
-            const float rew = lrw ? s_rl[tid] : reward_fwd(A, s_xu + tid * ld_xu);
+            const float rew = lrw ? s_rl[tid] : reward_fwd<LR == BP_LR_TERMS>(A, s_xu + tid * ld_xu);
             if (i < A.n) A.w_rs[i * HZ + t] = rew;
             s_scal[tid] = rew;
           }
@@ -628,7 +643,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             const int r = idx / X, c = idx - r * X;
             const bool ok = row0 + r < A.n;
-            if (!LR) s_dxu[r * ld_xu + c] += reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, c);   // dL/dr_t = dL/dR_t / r_std
+            if (LR != BP_LR_LEARNED) s_dxu[r * ld_xu + c] += reward_grad_comp<LR == BP_LR_TERMS>(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, c);   // dL/dr_t = dL/dR_t / r_std
           }
           for (int idx = tid; idx < 16 * U; idx += nthreads) {
             const int r = idx / U, d = idx - r * U;
@@ -646,7 +661,7 @@ __global__ void __launch_bounds__(512) k_bptt_actor(BpttArgs A) {
             const float q = (u - mu) / sg;
             const float lp = -0.5f * q * q - fm_log(sg) - LOG_SQRT_2PI_B - fm_log(om);
             const float dlp_da = (-q / sg) / om + 2.f * a / om;
-            const float Ga = s_dxu[r * ld_xu + X + d] + (LR ? 0.f : reward_grad_comp(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, X + d)) +
+            const float Ga = s_dxu[r * ld_xu + X + d] + (LR == BP_LR_LEARNED ? 0.f : reward_grad_comp<LR == BP_LR_TERMS>(A, s_xu + r * ld_xu, ok ? s_gR[t] / r_std : 0.f, X + d)) +
                              w_lp * dlp_da;
             const float l_mu = w_lp * (q / sg), l_sr = w_lp * ((q * q - 1.f) / sg) * dsig;
             const float a_mu = Ga * dadw, a_sr = Ga * dadw * eps * dsig;
@@ -763,8 +778,8 @@ static int bptt_plan(const mbpo_bptt_desc *d, BpttPlan *pl, bool need_ptrs) {
     MBPO_REQUIRE(false, MBPO_ERR_ARG, "bptt: unknown system_kind");
   }
   MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_QUADRATIC || (d->reward_kind == MBPO_REWARD_PENDULUM && d->x_dim == 3 && d->u_dim == 1) ||
-                   (d->reward_kind == MBPO_REWARD_LEARNED && E > 0 && dyn_out == 2 * d->x_dim + 2),
-               MBPO_ERR_ARG, "bptt: bad reward_kind (the learned reward needs an ensemble with outputs 2x + 2)");
+                   (d->reward_kind == MBPO_REWARD_LEARNED && E > 0 && dyn_out == 2 * d->x_dim + 2) || (d->reward_kind == MBPO_REWARD_TERMS && E > 0),
+               MBPO_ERR_ARG, "bptt: bad reward_kind (the learned reward needs an ensemble with outputs 2x + 2, the term reward an ensemble)");
   pl->H = 64;
   pl->LH = lh;
   pl->ld_x = up4(d->x_dim) + 4;
@@ -869,8 +884,8 @@ extern "C" int mbpo_bptt_actor_grads(const mbpo_bptt_desc *d, void *stream) {
   if (A.system_kind == MBPO_SYS_ENSEMBLE) A.sh_dyn = net_shape(A.dyn);
   else A.sh_dyn = NetShape{A.X + A.U, 0, A.X, 0};
   const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_cr) || net_is_wide(A.sh_dyn);
-  const bool lr = A.reward_kind == MBPO_REWARD_LEARNED;
-  rc = mbpo_with_bool(lr, [&](auto LR) {
+  const int lr = A.reward_kind == MBPO_REWARD_TERMS ? BP_LR_TERMS : (A.reward_kind == MBPO_REWARD_LEARNED ? BP_LR_LEARNED : BP_LR_FORMULA);
+  rc = bptt_with_lr(lr, [&](auto LR) {
     return mbpo_with_bool(A.ts != 0, [&](auto TS) {
       return mbpo_with_bool(wide, [&](auto W) {
         return mbpo_launch<k_bptt_actor<64, W.value, TS.value, LR.value>>(pl.n_slabs, 512, pl.lds, st, "bptt_actor_grads", A);

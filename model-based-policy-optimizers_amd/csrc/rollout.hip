@@ -12,6 +12,7 @@
 #include "ens_lean.hpp"
 #include "rollout_shared.hpp"
 #include "rollout_lean.hpp"
+#include "reward_terms.hpp"
 #include <stdlib.h>
 #include <string.h>
 
@@ -148,7 +149,20 @@ extern "C" int mbpo_ensemble_mlp_forward(const mbpo_mlp_desc *mlp, const float *
 // ------------------------------------------------------------------------------------------------
 // R1-R8 fused rollout.
 // ------------------------------------------------------------------------------------------------
-// LR: MBPO_REWARD_LEARNED (a flag of its own, as in k_model_rollout64)
+// LR: how the reward is formed, three values (the learned reward and the term table exclude each other, so the third value adds half
+// the instantiations, not double): FORMULA the Pendulum / quadratic reward picked by a run-time test of reward_kind, LEARNED
+// MBPO_REWARD_LEARNED, TERMS MBPO_REWARD_TERMS (csrc/reward_terms.hpp).  Compile-time, so that the instantiations that existed before a
+// value was added are emitted as they were (profiles/r14_term_reward_registers.txt).
+#define RO_LR_FORMULA 0
+#define RO_LR_LEARNED 1
+#define RO_LR_TERMS 2
+template <class F>
+static int mbpo_with_lr(int lr, F &&f) {
+  if (lr == RO_LR_TERMS) return f(std::integral_constant<int, RO_LR_TERMS>{});
+  return lr == RO_LR_LEARNED ? f(std::integral_constant<int, RO_LR_LEARNED>{}) : f(std::integral_constant<int, RO_LR_FORMULA>{});
+}
+// TERMS: the reward reads the next state, so it is formed behind the barrier that follows the next-state write instead of in front of
+// it, from the table staged in LDS (MBPO_REWARD_TERMS_FLOATS floats behind everything else: the host grows the block for this kind only)
 // START: a start buffer is set (include/mbpo_hip.h "fresh starts").  A flag of its own: as a run-time test on start.rows it added 32 to
 // 40 bytes of scratch per lane to every instantiation and two spilled registers to <128, false> (profiles/r09_fresh_starts_registers.txt)
 // the controls the dynamics and the rewards see (u_env).  An expression, not a variable, and `if constexpr (HAL)` throughout: an
@@ -213,7 +227,7 @@ __device__ __forceinline__ float hold_weight(float gamma, int j) {
   return w;
 }
 
-template <int H, bool LR, bool START, bool HAL, bool TA = false>
+template <int H, int LR, bool START, bool HAL, bool TA = false>
 __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL, TA> A) {
   extern __shared__ __align__(16) float smem[];
   constexpr int HT = H / 16;
@@ -242,6 +256,9 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL, TA> A
     for (int idx = tid; idx < X; idx += nthreads) s_rew[16 + idx] = A.halluc_beta[idx];
   float *const s_hold = s_rew + 16;              // TA: [49] floats of the same region (never together with HAL)
   (void)s_hold;
+  // TERMS: the table staged once per workgroup behind beta / the hold state (the tile load's barrier below orders it before its first use)
+  if constexpr (LR == RO_LR_TERMS)
+    for (int idx = tid; idx < MBPO_REWARD_TERMS_FLOATS; idx += nthreads) s_rew[16 + ((X + 3) & ~3) + 64 + idx] = A.reward_params[idx];
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -360,11 +377,11 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL, TA> A
           __syncthreads();
         }
         // reward uses the pre-step x and the action; next state from the system
-        if (tid < 16) {
+        if (LR != RO_LR_TERMS && tid < 16) {
           const int r = tid;
           const float *xr = s_xu + r * A.ld_xu;
           float rew;
-          if (LR) {
+          if (LR == RO_LR_LEARNED) {
             rew = learned_reward(A, s_y, A.ld_y, E, r, env0 + r, ((long long)s * AR + ar) * N + env0 + r, rng_seed, rng_off);
           } else if (A.reward_kind == MBPO_REWARD_PENDULUM) {
             rew = pendulum_reward(xr, xr[X], A.reward_params);
@@ -431,6 +448,21 @@ __global__ void __launch_bounds__(512) k_model_rollout(RolloutArgsFor<HAL, TA> A
             s_hA[r * X + c] = v;  // scratch (s_y must stay intact until every thread has read it)
           }
           __syncthreads();
+          if constexpr (LR == RO_LR_TERMS) {
+            // the reward on this inner step's (x, u, x'): x and u still in s_xu, x' in the scratch; the copy below waits for it
+            if (tid < 16) {
+              const int r = tid;
+              const float *xr = s_xu + r * A.ld_xu;
+              const float rew = reward_terms_eval(s_rew + 16 + ((X + 3) & ~3) + 64, xr, xr + X, reward_terms_next(s_hA + r * X, xr, X), X, RO_UE);
+              if constexpr (TA) {
+                const float wr = hold_w * rew;   // the product rounded on its own, then added (no fused multiply-add)
+                if (hold_live(s_hold, r, ar)) s_rew[r] += wr;
+              } else {
+                s_rew[r] += rew;
+              }
+            }
+            __syncthreads();
+          }
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             int r = idx / X, c = idx - r * X;
             if (!TA || hold_live(s_hold, r, ar)) s_xu[r * A.ld_xu + c] = s_hA[r * X + c];
@@ -575,7 +607,7 @@ struct RolloutArgs64TA : RolloutArgs64 {
 template <bool HAL, bool TA = false>
 using RolloutArgs64For = typename std::conditional<TA, RolloutArgs64TA, typename std::conditional<HAL, RolloutArgs64Hal, RolloutArgs64>::type>::type;
 
-template <bool WIDE, bool LR, bool TERM, bool START, bool HAL, bool TA = false>
+template <bool WIDE, int LR, bool TERM, bool START, bool HAL, bool TA = false>
 __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs64For<HAL, TA> AA) {
   extern __shared__ __align__(16) float smem[];
   const RolloutArgs &A = AA.a;
@@ -608,7 +640,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
   // reward parameters staged once: section C read them from global memory inside a runtime-trip loop (one exposed scalar
   // load per term: ~1.5 k of that section's 3.6 k cycles)
   float *s_rp = s_scr + ((16 * (X + U) + 16 + 3) & ~3);   // [2X+U] quadratic (target, q, r) or [3] pendulum
-  if (!LR) {
+  if (LR == RO_LR_FORMULA) {
     const int n_rp = (A.reward_kind == MBPO_REWARD_PENDULUM) ? 3 : 2 * X + RO_UE;
     for (int idx = tid_; idx < n_rp; idx += nthreads) s_rp[idx] = A.reward_params[idx];
   }
@@ -618,6 +650,11 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
     for (int idx = tid_; idx < X; idx += nthreads) s_rp[X + U + idx] = AA.halluc_beta[idx];
   // TA: the rows' k, inner steps taken and terminated flags, the tile's largest k (the host adds these 64 floats)
 #define RO64_HOLD (s_rp + ((2 * X + U + 4 + 3) & ~3))
+  // TERMS: the table staged once per workgroup, behind the hold state where there is one (the host adds MBPO_REWARD_TERMS_FLOATS floats
+  // for this kind only; the tile load's barrier below orders it before its first use)
+#define RO64_TAB (RO64_HOLD + (TA ? 64 : 0))
+  if constexpr (LR == RO_LR_TERMS)
+    for (int idx = tid_; idx < MBPO_REWARD_TERMS_FLOATS; idx += nthreads) RO64_TAB[idx] = A.reward_params[idx];
 
   const RngKey rk_ = rng_resolve(A.seed, A.offset, A.rng_dev);
   const unsigned long long rng_off = rk_.offset, rng_seed = rk_.seed;
@@ -747,8 +784,9 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
         if (tid < 16) {
           const int r = tid;
           const float *xr = s_xu + r * ld_xu;
+          if constexpr (LR != RO_LR_TERMS) {      // (TERMS: behind the barrier below, once the next state exists)
           float rew;
-          if (LR) {
+          if (LR == RO_LR_LEARNED) {
             rew = learned_reward(A, s_y, ld_y, E, r, env0 + r, ((long long)s * AR + ar) * N + env0 + r, rng_seed, rng_off);
           } else if (A.reward_kind == MBPO_REWARD_PENDULUM) {
             rew = pendulum_reward(xr, xr[X], s_rp);
@@ -764,6 +802,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
             if (hold_live(RO64_HOLD, r, ar)) s_rew[r] += wr;
           } else {
             s_rew[r] += rew;
+          }
           }
           if (A.system_kind == MBPO_SYS_PENDULUM) {
             float xn[3];
@@ -820,6 +859,21 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
           }
         }
         __syncthreads();
+        if constexpr (LR == RO_LR_TERMS) {
+          // the reward on this inner step's (x, u, x'): x and u still in s_xu, x' in the scratch.  In front of the hold's bookkeeping
+          // (the same 16 threads, in program order): whether a row was live is asked before this step can stop it.
+          if (tid < 16) {
+            const int r = tid;
+            const float *xr = s_xu + r * ld_xu;
+            const float rew = reward_terms_eval(RO64_TAB, xr, xr + X, reward_terms_next(s_scr + r * X, xr, X), X, RO_UE);
+            if constexpr (TA) {
+              const float wr = hold_weight(AA.hold.gamma, ar) * rew;       // the product rounded on its own, then added (no fused multiply-add)
+              if (hold_live(RO64_HOLD, r, ar)) s_rew[r] += wr;
+            } else {
+              s_rew[r] += rew;
+            }
+          }
+        }
         if constexpr (TA) {
           // the rows that took this step: count it, and stop a row whose new state leaves the box (the next reader of either is behind
           // a barrier: the one below, or the one in front of section D)
@@ -829,6 +883,7 @@ __global__ void __launch_bounds__(64 * RO64_WAVES) k_model_rollout64(RolloutArgs
           }
         }
         if (ar + 1 < (TA ? hold_bound(RO64_HOLD) : AR)) {   // the next inner step starts from the new state
+          if constexpr (LR == RO_LR_TERMS) __syncthreads();      // (the term reward above still reads the pre-step x in s_xu)
           for (int idx = tid; idx < 16 * X; idx += nthreads) {
             const int r = idx & 15, c = idx >> 4;
             s_xu[r * ld_xu + c] = s_scr[r * X + c];
@@ -1027,8 +1082,11 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   if (rc != MBPO_OK) return rc;
   const int want_row = 2 * X + U + 3 + (d->ppo_extras ? 1 + U : 0);
   MBPO_REQUIRE(d->row_len == want_row, MBPO_ERR_ARG, "model_rollout: row_len %d != expected %d", d->row_len, want_row);
-  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_PENDULUM || d->reward_kind == MBPO_REWARD_QUADRATIC || d->reward_kind == MBPO_REWARD_LEARNED,
+  MBPO_REQUIRE(d->reward_kind == MBPO_REWARD_PENDULUM || d->reward_kind == MBPO_REWARD_QUADRATIC || d->reward_kind == MBPO_REWARD_LEARNED ||
+                   d->reward_kind == MBPO_REWARD_TERMS,
                MBPO_ERR_ARG, "model_rollout: unknown reward_kind %d", d->reward_kind);
+  MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_TERMS || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG,
+               "model_rollout: the term reward needs system_kind ENSEMBLE");
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_LEARNED || d->system_kind == MBPO_SYS_ENSEMBLE, MBPO_ERR_ARG,
                "model_rollout: the learned reward needs system_kind ENSEMBLE");
   MBPO_REQUIRE(d->reward_kind != MBPO_REWARD_PENDULUM || (X == 3 && UE == 1), MBPO_ERR_ARG,
@@ -1105,9 +1163,11 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
   int ymax = 2 * U > dyn_out ? 2 * U : dyn_out;
   A.ld_y = up4(ymax) + 4;
   const int scr = 16 * (X + U) + 16;
+  const bool terms = d->reward_kind == MBPO_REWARD_TERMS;
   const size_t fixed_f = 3ull * 16 * A.ld_x + 16ull * A.ld_xu + (size_t)A.n_out * 16 * A.ld_y + 2ull * 16 * up4(d->row_len) + 80 +
                          (size_t)up4(scr) + (size_t)up4(2 * X + U + 4) +  // + staged reward parameters (k_model_rollout64)
-                         (ta ? 64 : 0);                                   // + the rows' hold state (k_model_rollout64)
+                         (ta ? 64 : 0) +                                  // + the rows' hold state (k_model_rollout64)
+                         (terms ? MBPO_REWARD_TERMS_FLOATS : 0);          // + the staged term table (this kind only)
   A.n_chains = pick_chains(E, fixed_f, A.ld_h);
   MBPO_REQUIRE(A.n_chains >= 1, MBPO_ERR_UNSUPPORTED, "model_rollout: shapes do not fit 160 KiB of LDS");
   size_t lds = (fixed_f + 2ull * A.n_chains * 16 * A.ld_h) * sizeof(float);
@@ -1123,7 +1183,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     MBPO_CHECK_LAUNCH("model_rollout");
     return MBPO_OK;
   }
-  const bool lr = d->reward_kind == MBPO_REWARD_LEARNED;
+  const int lr = terms ? RO_LR_TERMS : (d->reward_kind == MBPO_REWARD_LEARNED ? RO_LR_LEARNED : RO_LR_FORMULA);
   const bool fresh = A.start.rows != nullptr;
   if (H == 64) {
     // the kernel specialised for the benchmark networks (rollout_lean.hip): MBPO_ROLLOUT_LEAN=0 / mbpo_debug_set_rollout_lean(0) keep the
@@ -1165,7 +1225,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
       RolloutArgs64TA AH;
       static_cast<RolloutArgs64 &>(AH) = AA;
       AH.hold = hold;
-      rc = mbpo_with_bool(lr, [&](auto LR) {
+      rc = mbpo_with_lr(lr, [&](auto LR) {
         return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
           return mbpo_with_bool(fresh, [&](auto SB) {
             return mbpo_launch<k_model_rollout64<false, LR.value, TM.value, SB.value, false, true>>(grid, 64 * RO64_WAVES, lds, st, "model_rollout", AH);
@@ -1173,7 +1233,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
         });
       });
     } else
-    rc = mbpo_with_bool(lr, [&](auto LR) {
+    rc = mbpo_with_lr(lr, [&](auto LR) {
       return mbpo_with_bool(wide, [&](auto W) {
         return mbpo_with_bool(A.term_low != nullptr, [&](auto TM) {
           return mbpo_with_bool(A.start.rows != nullptr, [&](auto SB) {
@@ -1191,14 +1251,14 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
     RolloutArgsTA AH;
     static_cast<RolloutArgs &>(AH) = A;
     AH.hold = hold;
-    rc = mbpo_with_bool(lr, [&](auto LR) {
+    rc = mbpo_with_lr(lr, [&](auto LR) {
       return mbpo_with_bool(fresh, [&](auto SB) {
         if (H == 128) return mbpo_launch<k_model_rollout<128, LR.value, SB.value, false, true>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
         return mbpo_launch<k_model_rollout<256, LR.value, SB.value, false, true>>(grid, n_waves * 64, lds, st, "model_rollout", AH);
       });
     });
   } else if (H == 128) {
-    rc = mbpo_with_bool(lr, [&](auto LR) {
+    rc = mbpo_with_lr(lr, [&](auto LR) {
       return mbpo_with_bool(fresh, [&](auto SB) {
         return mbpo_with_bool(hal, [&](auto HL) {
           RolloutArgsFor<HL.value> AH;
@@ -1209,7 +1269,7 @@ extern "C" int mbpo_model_rollout(const mbpo_rollout_desc *d, void *stream) {
       });
     });
   } else {
-    rc = mbpo_with_bool(lr, [&](auto LR) {
+    rc = mbpo_with_lr(lr, [&](auto LR) {
       return mbpo_with_bool(fresh, [&](auto SB) {
         return mbpo_with_bool(hal, [&](auto HL) {
           RolloutArgsFor<HL.value> AH;
@@ -1247,5 +1307,41 @@ extern "C" int mbpo_hold_steps(const float *actions, int64_t n, int32_t action_d
   hipLaunchKernelGGL(k_hold_steps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, actions, (long long)n, action_dim, min_time,
                      max_time, env_dt, max_steps, steps_out);
   MBPO_CHECK_LAUNCH("hold_steps");
+  return MBPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mbpo_reward_eval: the reward of n rows as the rollout kernels form it, one thread per row — the term table through the kernels' own
+// reward_terms_eval (read from global memory: every lane of a wave walks the same records), the quadratic reward in section C's
+// expressions.  For Reward.__call__ on the host side and for the tests that pin the rollouts' reward column bit for bit.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_reward_eval(int kind, const float *rp, const float *x, const float *u, const float *x_next, long long n,
+                                                     int X, int U, float *out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float *xr = x + i * X, *ur = u + i * U;
+  if (kind == MBPO_REWARD_TERMS) {
+    out[i] = reward_terms_eval(rp, xr, ur, reward_terms_next(x_next ? x_next + i * X : nullptr, xr, X), X, U);
+  } else {
+    const float *tp = rp, *qp = tp + X, *rr = qp + X;
+    float cx = 0.f, cu = 0.f;
+    for (int c = 0; c < X; ++c) { float dd = xr[c] - tp[c]; cx += qp[c] * (dd * dd); }
+    for (int d = 0; d < U; ++d) { float uu = ur[d]; cu += rr[d] * (uu * uu); }
+    out[i] = -cx - cu;
+  }
+}
+
+extern "C" int mbpo_reward_eval(int32_t reward_kind, const float *reward_params, const float *x, const float *u, const float *x_next, int64_t n,
+                                int32_t x_dim, int32_t u_dim, float *out, void *stream) {
+  MBPO_REQUIRE(reward_kind == MBPO_REWARD_TERMS || reward_kind == MBPO_REWARD_QUADRATIC, MBPO_ERR_UNSUPPORTED,
+               "reward_eval: reward_kind %d is not evaluated here (MBPO_REWARD_TERMS and MBPO_REWARD_QUADRATIC are)", reward_kind);
+  MBPO_REQUIRE(n >= 0, MBPO_ERR_ARG, "reward_eval: n < 0");
+  MBPO_REQUIRE(x_dim >= 1 && u_dim >= 1, MBPO_ERR_ARG, "reward_eval: x_dim and u_dim must be positive");
+  if (n == 0) return MBPO_OK;
+  MBPO_REQUIRE(reward_params && x && u && out, MBPO_ERR_ARG, "reward_eval: null pointer");
+  MBPO_REQUIRE(n <= 256LL * 2147483647LL, MBPO_ERR_ARG, "reward_eval: n too large");
+  hipLaunchKernelGGL(k_reward_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)reward_kind, reward_params, x, u,
+                     x_next, (long long)n, (int)x_dim, (int)u_dim, out);
+  MBPO_CHECK_LAUNCH("reward_eval");
   return MBPO_OK;
 }

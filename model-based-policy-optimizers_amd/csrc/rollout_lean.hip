@@ -515,6 +515,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_rollout_lean(const RoLeanArgs AA
 
 bool rollout_lean_supports(const RolloutArgs &A, bool has_policy, int E) {
   if (!has_policy || A.actions) return false;
+  if (A.reward_kind == MBPO_REWARD_TERMS) return false;      // (the kernel reads every non-Pendulum reward as quadratic parameters)
   const int X = A.x_dim;
   if (A.u_dim != 1 || X < 2 || X > 4 || A.action_repeat != 1) return false;      // (the state wave holds 16 envs x <= 4 obs elements)
   auto net_ok = [](const MlpDev &m, int k_in) {

@@ -20,6 +20,11 @@ SYS_GENERIC = 100      # host-side only: a user-defined System, stepped outside 
 ENS_MEAN, ENS_TS1, ENS_TSINF = 0, 1, 2
 STREAM_POLICY_NOISE, STREAM_MODEL_NOISE, STREAM_MEMBER = 1, 2, 3     # Philox stream ids (csrc/common.hpp)
 REWARD_PENDULUM, REWARD_QUADRATIC, REWARD_LEARNED = 0, 1, 2
+REWARD_TERMS = 3           # a term table (include/mbpo_hip.h "term rewards"; mbpo.systems.TermReward)
+REWARD_TERMS_MAX_GROUPS, REWARD_TERMS_MAX_TERMS = 16, 128
+REWARD_TERMS_FLOATS = 4 + 4 * REWARD_TERMS_MAX_GROUPS + 4 * REWARD_TERMS_MAX_TERMS
+TERM_FN_IDS = {"identity": 0, "square": 1, "abs": 2, "relu": 3, "cos": 4, "sin": 5}
+TERM_LINK_IDS = {"identity": 0, "sqrt": 1, "exp": 2, "tanh": 3}
 
 _LIB_PATH = Path(__file__).resolve().parent / "_lib" / "libmbpo_hip.so"
 
@@ -282,6 +287,10 @@ def _bind_optional(lib: C.CDLL) -> None:
     lib.mbpo_mlp_layered_vjp.argtypes = [C.POINTER(MlpDesc), vp, i64, vp, vp, vp, vp, vp, vp]
     lib.mbpo_hold_steps.restype = C.c_int
     lib.mbpo_hold_steps.argtypes = [vp, i64, i32, f32, f32, f32, i32, vp, vp]
+    fn = getattr(lib, "mbpo_reward_eval", None)      # (bound when present: an A/B run against an older library still loads)
+    if fn is not None:
+        fn.restype = C.c_int
+        fn.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, vp, vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

@@ -324,6 +324,8 @@ def model_rollout(*, policy_params: Optional[torch.Tensor] = None, policy_spec: 
         _req(t, nm)
     if reward_params is not None or reward_kind != _hip.REWARD_LEARNED:      # (the learned reward has no parameter vector)
         _req(reward_params, "reward_params")
+    if reward_kind == _hip.REWARD_TERMS and reward_params.numel() < _hip.REWARD_TERMS_FLOATS:
+        raise ValueError(f"a term table holds {_hip.REWARD_TERMS_FLOATS} floats, reward_params {reward_params.numel()}")
     if obs.shape != (n_envs, x_dim) or first_obs.shape != (n_envs, x_dim):
         raise ValueError("obs/first_obs must be [N, x_dim]")
     if steps.shape != (n_envs,) or done.shape != (n_envs,):
@@ -406,6 +408,33 @@ def hold_steps(actions: torch.Tensor, min_time: float, max_time: float, env_dt: 
         raise ValueError(f"out must be int32 [{n}]")
     check(lib.mbpo_hold_steps(actions.data_ptr(), n, A, float(min_time), float(max_time), float(env_dt), int(max_steps),
                               out.data_ptr(), current_stream_ptr()), "mbpo_hold_steps")
+    return out
+
+
+def reward_eval(reward_kind: int, reward_params: torch.Tensor, x: torch.Tensor, u: torch.Tensor,
+                x_next: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_reward_eval: [n], the reward of the rows x [n, x_dim], u [n, u_dim] (the controls the dynamics see), x_next [n, x_dim] or
+    None, as the rollout kernels form it — REWARD_TERMS (reward_params: the packed table) and REWARD_QUADRATIC.  x_next None makes
+    the next-state columns read x: only for a table without next-state terms."""
+    lib = load()
+    _req(reward_params, "reward_params")
+    _req(x, "x")
+    _req(u, "u")
+    if x.dim() != 2 or u.dim() != 2 or u.shape[0] != x.shape[0]:
+        raise ValueError(f"x must be [n, x_dim] and u [n, u_dim], got {tuple(x.shape)} and {tuple(u.shape)}")
+    n, X = x.shape
+    U = u.shape[1]
+    need = _hip.REWARD_TERMS_FLOATS if reward_kind == _hip.REWARD_TERMS else 2 * X + U
+    if reward_params.numel() < need:
+        raise ValueError(f"reward_params holds {reward_params.numel()} floats, this kind reads {need}")
+    if x_next is not None and _req(x_next, "x_next").shape != x.shape:
+        raise ValueError(f"x_next must be {tuple(x.shape)}, got {tuple(x_next.shape)}")
+    if out is None:
+        out = torch.empty(n, device=x.device, dtype=torch.float32)
+    elif _req(out, "out").shape != (n,):
+        raise ValueError(f"out must be [{n}]")
+    check(lib.mbpo_reward_eval(int(reward_kind), reward_params.data_ptr(), x.data_ptr(), u.data_ptr(), ptr(x_next), n, X, U,
+                               out.data_ptr(), current_stream_ptr()), "mbpo_reward_eval")
     return out
 
 

@@ -154,6 +154,14 @@ def _refuse_optimistic(system) -> None:
         raise ValueError("BPTT does not take EnsembleSystem(mode='optimistic'): the gradient through the ensemble spread "
                          "(x' = mean + beta * std * eta) is not built; use SAC, PPO or iCEM")
     refuse_time_adaptive(system, "BPTT")      # (nor a time-adaptive one: its objective sums per-step rewards)
+    _refuse_next_state_terms(getattr(system, "reward", None))
+
+
+def _refuse_next_state_terms(reward_or_params) -> None:
+    """BPTT, fused or wide, takes a TermReward whose terms all read x or u (the reward itself, or its parameters after a `replace`)."""
+    if getattr(reward_or_params, "has_next_state_terms", False):
+        raise ValueError("BPTT does not take a TermReward with x_next terms: the gradient through next-state terms is not built; "
+                         "use SAC, PPO or iCEM, or write the reward on (x, u)")
 
 
 class BPTTOptimizer(BaseOptimizer):
@@ -366,6 +374,7 @@ class BPTTOptimizer(BaseOptimizer):
     def _system_kwargs(self, system_params):
         # (rollout_policy's scan ignores SystemState.done, utils/optimizer_utils.py:85-93: no termination in the gradient or the evaluation)
         _refuse_optimistic(self.system)      # (the fused and the wide path both start here)
+        _refuse_next_state_terms(system_params.reward_params)
         spec = without_termination(self.system.rollout_spec(system_params, self.device))
         if spec["system_kind"] == _hip.SYS_GENERIC:
             # a user-defined System (the reference's plug-in seam, base_systems.py:40-52): rollout_policy's scan

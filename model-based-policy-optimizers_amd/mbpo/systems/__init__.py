@@ -6,5 +6,6 @@ from mbpo.systems.rewards.base_rewards import RewardParams, Reward
 # not in the reference (its learned model would come from the external `bsm` package, setup.py:22)
 from mbpo.systems.ensemble_system import EnsembleDynamics, EnsembleDynamicsParams, EnsembleSystem, LearnedReward
 from mbpo.systems.rewards.pendulum_reward import QuadraticReward
+from mbpo.systems.rewards.term_reward import TermReward, TermRewardParams, Term, Group
 from mbpo.systems.termination import BoxTermination
 from mbpo.systems.time_adaptive import TimeAdaptive

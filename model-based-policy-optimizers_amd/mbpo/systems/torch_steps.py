@@ -4,7 +4,7 @@ takes (bptt_optimizer.py:183-186 accepts any `actor_features` / `critic_features
 
     PendulumSystem   dynamics/pendulum_dynamics.py:29-63, rewards/pendulum_reward.py:27-42 (restated; the fused kernels hold the
                      same arithmetic in csrc/rollout.hip)
-    EnsembleSystem   every mode, with the member MLPs as HIP autograd nodes (ops.HipMlp), quadratic or Pendulum reward in torch:
+    EnsembleSystem   every mode, with the member MLPs as HIP autograd nodes (ops.HipMlp), quadratic, Pendulum or term reward in torch:
                      'mean': x' = [x +] mean_e mu_e([x, u]);  'ts1' / 'tsinf': x' = [x +] mu_m (+ (softplus(raw_m) + min_std) * eps),
                      the member m and eps of the step handed in by ops.BpttActorGradGeneric (the fused kernel's Philox draws), the
                      gradient pathwise through the selected member (the draw itself is not differentiated); a learned reward
@@ -87,6 +87,8 @@ class DifferentiableBuiltin:
                     nxt = nxt + (torch.nn.functional.softplus(ym[:, X:2 * X]) + spec["ens_min_std"]) * noise
         if rew is None and spec["reward_kind"] == _hip.REWARD_PENDULUM:
             rew = pendulum_reward(x, u, system_params.reward_params)
+        elif rew is None and spec["reward_kind"] == _hip.REWARD_TERMS:
+            rew = self.system.reward.torch_reward(x, u, system_params.reward_params)      # (TermReward's own torch form; x / u terms only)
         elif rew is None:
             rew = quadratic_reward(x, u, spec["reward_params"], X, U)
         return SystemState(x_next=nxt, reward=rew, system_params=system_params)

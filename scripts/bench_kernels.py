@@ -330,6 +330,50 @@ def main():
         rollout_case(4096, 4, 1, 5, 5, (64, 64, 64), (64, 64, 64), 50)
     if want("rollout_time_adaptive_case"): rollout_time_adaptive_case(4096, 4, 1, 5, 5, (64, 64, 64), 50)
 
+    # term rewards (MBPO_REWARD_TERMS; mbpo.systems.TermReward) at C2's shape on k_model_rollout64 (mbpo_debug_set_rollout_lean(0):
+    # k_rollout_lean never takes the kind, so the like-for-like baseline is the tile kernel): the quadratic kind, the same function as a
+    # table (TermReward.from_quadratic: 5 square terms in 2 groups), and a 12-term table holding cos, exp and sqrt, two of its terms on
+    # the next state.  One session.  A record, no target.
+    def rollout_term_reward_case(N, X, U, E, S, hid, reps):
+        from mbpo.systems import Group, Term, TermReward
+        lib = _hip.load()
+        pd, dd = [X, *hid, 2 * U], [X + U, *hid, 2 * X]
+        pp, dp = lecun_flat(pd, g).to(dev), lecun_flat(dd, g, E).to(dev)
+        obs = torch.randn(N, X, generator=g).to(dev)
+        first = obs.clone()
+        steps, done = torch.zeros(N, device=dev), torch.zeros(N, device=dev)
+        rows = torch.empty(S * N, 2 * X + U + 3, device=dev)
+        tgt, q, r = [0.0] * X, [1.0] * X, [0.1] * U
+        twelve = TermReward(X, U, bias=0.5, groups=[
+            Group([Term("x", c, "square", 1.0) for c in range(X)], weight=-1.0),
+            Group([Term("u", 0, "square", 0.1)], weight=-1.0),
+            Group([Term("x", 0, "square", 1.0, 0.5), Term("x", 1, "square", 1.0, -0.5)], weight=-0.5, link="sqrt"),
+            Group([Term("x_next", 0, "square", -4.0), Term("x_next", 1, "square", -4.0)], weight=1.0, link="exp"),
+            Group([Term("x", 2, "cos", 1.0), Term("x", 3, "sin", 0.5), Term("u", 0, "abs", -0.1)], weight=0.3),
+        ])
+        assert sum(len(gr.terms) for gr in twelve.init_params(0).groups) == 12
+        quad_tab = TermReward.from_quadratic(tgt, q, r)
+        cases = (("quadratic", _hip.REWARD_QUADRATIC, torch.tensor(tgt + q + r).to(dev)),
+                 ("terms: from_quadratic", _hip.REWARD_TERMS, quad_tab.kernel_spec(quad_tab.init_params(0), dev)[1]),
+                 ("terms: 12 terms (cos, exp, sqrt)", _hip.REWARD_TERMS, twelve.kernel_spec(twelve.init_params(0), dev)[1]))
+        lib.mbpo_debug_set_rollout_lean(0)
+        try:
+            for label, rk, rp in cases:
+                def run():
+                    ops.model_rollout(policy_params=pp, policy_spec=ops.MlpSpec(pd), x_dim=X, u_dim=U, obs=obs, first_obs=first, steps=steps,
+                                      done=done, n_steps=S, episode_length=S, system_kind=_hip.SYS_ENSEMBLE, dyn_params=dp,
+                                      dyn_spec=ops.MlpSpec(dd, "swish", E), reward_kind=rk, reward_params=rp, seed=1, offset=0, out=rows)
+                t, te = both(run, reps)
+                flop = N * S * (2 * E * mlp_macs(dd) + 2 * mlp_macs(pd))
+                out.append(mfma_entry("k_model_rollout64", "mbpo_model_rollout",
+                                      {"N": N, "x": X, "u": U, "E": E, "S": S, "policy": list(hid), "member": list(hid), "reward": label,
+                                       "rollout_lean": 0}, t, flop, "2*E*M + 2*P FLOP per transition", {"transitions_per_s": N * S / t}))
+                log(f"rollout ({label}, k_model_rollout64) N={N} x={X} E={E} {hid}: {t * 1e6:.1f} us  {N * S / t / 1e6:.1f} M transitions/s")
+        finally:
+            lib.mbpo_debug_set_rollout_lean(-1)
+
+    if want("rollout_term_reward_case"): rollout_term_reward_case(4096, 4, 1, 5, 5, (64, 64, 64), 50)      # C2's shape, three rewards
+
     # ---------------------------------------------------------------- R2: vmapped ensemble forward (System.step outside the fused rollout)
     def ens_fwd_case(N, X, U, E, hid, reps):
         dd = [X + U, *hid, 2 * X]
