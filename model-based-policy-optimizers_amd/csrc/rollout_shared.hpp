@@ -1,5 +1,6 @@
-// rollout_shared.hpp — what the rollout kernels share (csrc/rollout.hip: the generic kernels; csrc/rollout_lean.hip: the kernel specialised
-// for the benchmark networks): the argument block, the analytic Pendulum step / reward, the hardware-transcendental helpers.
+// rollout_shared.hpp — what the rollout kernels share (csrc/rollout64_kernel.hpp, csrc/rollout_wide_kernel.hpp and csrc/rollout.hip: the
+// generic kernels; csrc/rollout_lean.hip: the kernel specialised for the benchmark networks): the argument block, the analytic Pendulum
+// step / reward, the hardware-transcendental helpers, the host's plan helpers.
 #pragma once
 #include "common.hpp"
 
@@ -18,6 +19,25 @@ static inline int mbpo_check_start_buffer(const float *rows, long long max_size,
   MBPO_REQUIRE(row_len >= x_dim, MBPO_ERR_ARG, "%s: start_row_len %d < x_dim %d", who, row_len, x_dim);
   MBPO_REQUIRE(max_size > 0 && max_size < 2147483647LL, MBPO_ERR_ARG, "%s: start_max_size outside (0, 2^31 - 1)", who);
   return MBPO_OK;
+}
+
+// host: plan helpers of the generic tile kernels (the rollouts and the ensemble forward, ens_forward.hip)
+static inline int hidden_width(const MlpDev &m) {
+  // all hidden layers must share one width H in {64,128,256}; a 1-layer MLP (no hidden) uses the 64 build.
+  if (m.n_layers == 1) return 64;
+  int H = m.dims[1];
+  for (int l = 2; l < m.n_layers; ++l)
+    if (m.dims[l] != H) return -1;
+  return H;
+}
+
+// how many chains (waves) a workgroup runs side by side: one per member, capped at 8 waves (512 threads: two waves per
+// SIMD keep 256 VGPRs each) and by the LDS that the per-chain ping-pong tiles need next to `fixed_floats` of other
+// buffers; larger ensembles run in rounds of n_chains members
+static inline int pick_chains(int n_members, size_t fixed_floats, int ld_h) {
+  int c = n_members < 1 ? 1 : (n_members > 8 ? 8 : n_members);
+  while (c >= 1 && (fixed_floats + 2ull * c * 16 * ld_h) * sizeof(float) > 160 * 1024) --c;
+  return c;
 }
 
 struct RolloutArgs {
