@@ -17,8 +17,10 @@
 //    instead of one column of four rows — every activation / delta store is one ds_write_b128 (was 4 x b32), every pre-activation
 //    read of the backward one ds_read_b128, every weight-gradient store one global_store_dwordx4 (was 4 dwords: 16 + 1 store
 //    instructions per wave and layer became 4 + 1).  a*b = b*a and the k order is unchanged, so the sums are the same bits.
-//  * The weights of a whole PHASE (thin layer, two hidden layers, output layer) are requested at once, one phase ahead, into
-//    registers that are simply named per layer: no register-set swapping, no loop unrolled by two, no descriptor fetch.
+//  * The weights of a whole PHASE (thin layer, two hidden layers, output layer) are requested ahead of their use, into registers
+//    that are simply named per layer: no register-set swapping, no loop unrolled by two, no descriptor fetch.  Every request is a
+//    global_load (the pointers are pinned in the global address space), so each first use waits with a counted s_waitcnt vmcnt(N)
+//    and leaves what was requested behind it in flight; see "Waits" below for what the compiled kernel does and does not do.
 //  * The wave that forms a network's output layer keeps it in registers and runs the elementwise section itself (NormalTanh
 //    sample / value hand-off) — the output image maps matrix row i to column i & 3, so all four lane groups hold (loc, raw) of
 //    their row and the actor role's two samples run side by side in one pass.  One barrier and one LDS round trip less per section.
@@ -45,6 +47,23 @@
 // 64 separate 64-byte segments where the strided dword request touches four.  Image-major copies were timed the same way: 16 fully
 // contiguous dword requests per image 10.8 us (no change), four contiguous 1-KB requests per image 11.2 us (worse).  The request
 // pattern is not the lever; a reordered copy of the weights is not worth keeping.
+//
+// Waits (round 16, profiles/r16_sac_lean_waits.json).  Until then the pinned pointers were generic ones: 658 flat_load, and hipcc
+// must take flat results as returning out of order — 66 of the 67 vector-memory waits of k_sac_lean<4> were s_waitcnt vmcnt(0),
+// the tile reached LDS only when every weight request issued behind it had landed, and each first use of an image drained the
+// riding requests of the next phase as well.  Now: no flat instruction, 170 of 205 waits counted.  What is left at vmcnt(0), and why:
+//  * if (c == 0) X else Y compiles to "Y; then X unless Y ran", and the wait pass takes the edge Y -> X for real.  Requests in Y
+//    then cost X a wait as soon as X writes a register Y loaded into (its temporaries do).  Where both chains request, the code is
+//    therefore ONE sequence addressed by data (critic role: first requests, F0 hidden steps), or two ifs in a row with the arm
+//    that computes first (actor role: chain 1's images, which also get registers of their own, K1 / K2, chosen by v_cndmask at
+//    their use).  The arms that only compute (thin layers, epilogues) stay if / else: nothing is requested in them.
+//  * a wait behind a join counts the arm with the fewest requests; single-arm requests (output images, backward images) make the
+//    first use of what was requested before them wait for them too.  They were requested two or more steps earlier.
+// Measured with it (same box, five alternating rounds, graph of 64 chained updates): the update pair 15.26-15.33 -> 14.86-14.94 us.
+// The address space alone gave 15.17-15.24; the rest came from the actor role's chain 1 spreading its 57 requests over the three
+// steps chain 0 walks first (they sat in one step, whose barrier they held for 2.5 k cycles).  Measured and NOT kept: the thin
+// step's requests ahead of the thin layer instead of behind it (14.87-14.91, no change); F1's two output images requested at one
+// place in the output step, which removes a register copy that waits for everything in flight (15.02-15.07: worse).
 #include "common.hpp"
 #include "chain_run.hpp"
 #include "lean_blocks.hpp"
@@ -81,7 +100,54 @@ constexpr int O_STAGE = O_TILES + N_TILES * LT;      // [2][GST] weight gradient
 constexpr int GST = LH * LH + LH;                    // one hidden layer's block: dW [64][64] (16-byte chunks rotated per row) then db [64]
 constexpr size_t LEAN_LDS_BYTES = (size_t)(O_STAGE + 2 * GST) * sizeof(float);
 
-#define LEAN_STAMP(i)                                                                   \
+// img_out_request (lean_blocks.hpp) with the output width as data: the same addresses, so the same image
+__device__ __forceinline__ void img_out_request_n(float (&w)[16], const float *__restrict__ W, int n, int lane) {
+  const int i = lane & 15, g = lane >> 4;
+  const int col = ((i & 3) < n) ? (i & 3) : 0;
+  const float *p = W + (16 * g) * n + col;
+#pragma unroll
+  for (int s = 0; s < 16; ++s) w[s] = p[s * n];
+}
+
+// one of two register images, by a uniform condition (v_cndmask on an SGPR pair: 20 VALU instructions)
+__device__ __forceinline__ ImgF img_select(bool first, const ImgF &A, const ImgF &B) {
+  ImgF R;
+#pragma unroll
+  for (int s = 0; s < 16; ++s) R.w[s] = first ? A.w[s] : B.w[s];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) R.b[i] = first ? A.b[i] : B.b[i];
+  return R;
+}
+
+// hid_fwd (lean_blocks.hpp) with the tiles and STORE_Z as data, for a step that two chains walk with riding requests: one MFMA /
+// request sequence for both (see the note on the critic role's first requests); only the epilogue, which requests nothing, branches
+template <class PF>
+__device__ __forceinline__ void hid_fwd_sel(const ImgF &I, const float *xin, float *h_out, float *z_out, bool store_z, int c0, int lane, PF pf) {
+  const int j = lane & 15, g = lane >> 4;
+  float av[16];
+  read_row16(av, xin, lane);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    acc = MFMA(I.w[s], av[s], acc);
+    pf(s);
+    PIN_ORDER();
+  }
+  float zv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) zv[i] = acc[i] + I.b[i];
+  const int o = j * LDH + c0 + 4 * g;
+  if (store_z) {
+    float dv[4];
+    swish_and_grad4(zv, dv);
+    store_vec_lds<4>(z_out + o, dv);
+  } else {
+    act_apply_vec<4>(zv, MBPO_ACT_SWISH);
+  }
+  store_vec_lds<4>(h_out + o, zv);
+}
+
+#define LEAN_STAMP(i)                                                                \
   if (STAMPS) {                                                                         \
     if (A.stamps && tile == 0 && tid == 0) {                                            \
       unsigned long long t_;                                                            \
@@ -115,10 +181,18 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
   // The chain waves' arguments: ONE scalar load of the first 16 dwords, pinned in SGPRs here.  (Left to itself hipcc fetched the
   // argument block piecemeal next to each use, every piece with a full wait, and the clip words behind a pointer in between: six
   // dependent scalar round trips — 5.4 k cycles — before the tile load was issued.)
-  const float *a_params = A.params, *a_target_q = A.target_q, *a_batch = A.batch, *a_norm_mean = A.norm_mean, *a_norm_std = A.norm_std;
-  float *a_slab_pi = A.slab_pi, *a_slab_q = A.slab_q;
+  // Pinned as GLOBAL-address-space pointers (as k_sac_reduce_apply does, sac.hip): a generic pointer out of an asm statement makes
+  // every access behind it a flat one, and flat results may return out of order — hipcc then drains the whole vector-memory queue
+  // (s_waitcnt vmcnt(0), with lgkmcnt(0) beside it) at every first use, so nothing requested ahead survived a wait.  Global
+  // results return in order: each first use waits with a counted vmcnt(N) for its own request and leaves the N behind it in flight.
+  typedef __attribute__((address_space(1))) float GF;
+  GF *g_params = (GF *)A.params, *g_target_q = (GF *)A.target_q, *g_batch = (GF *)A.batch, *g_norm_mean = (GF *)A.norm_mean,
+     *g_norm_std = (GF *)A.norm_std, *g_slab_pi = (GF *)A.slab_pi, *g_slab_q = (GF *)A.slab_q;
   int B = A.B;
-  asm volatile("" : "+s"(a_params), "+s"(a_target_q), "+s"(a_batch), "+s"(a_norm_mean), "+s"(a_norm_std), "+s"(a_slab_pi), "+s"(a_slab_q), "+s"(B));
+  asm volatile("" : "+s"(g_params), "+s"(g_target_q), "+s"(g_batch), "+s"(g_norm_mean), "+s"(g_norm_std), "+s"(g_slab_pi), "+s"(g_slab_q), "+s"(B));
+  const float *a_params = (const float *)g_params, *a_target_q = (const float *)g_target_q, *a_batch = (const float *)g_batch,
+              *a_norm_mean = (const float *)g_norm_mean, *a_norm_std = (const float *)g_norm_std;
+  float *a_slab_pi = (float *)g_slab_pi, *a_slab_q = (float *)g_slab_q;
   const int row0 = tile * 16;
   {
     const int tid = tid_;
@@ -159,9 +233,12 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
   auto run = [&](const bool second_pass) __attribute__((always_inline)) {
     const int tid = opaque(tid_), lane = tid & 63;
     const float *const pi_p = a_params;
-    // ---- the tile's transitions: ONE coalesced dword per thread (the 16 rows are contiguous), requested before anything else —
-    // vector-memory results return in order, so whatever is requested in front of it is waited for with it.  Column cc of row r goes
-    // to: obs -> s_qin, action -> s_qin[X] (critic role), reward / discount / truncation -> s_aux, next obs -> s_qin2 (critic role).
+    // ---- the tile's transitions: ONE coalesced dword per thread (the 16 rows are contiguous), requested before anything else
+    // (with the normaliser's two words).  Global results return in order, so tile_to_lds() waits with s_waitcnt vmcnt(N), N = the
+    // weight requests the wave has issued behind the tile (X = 4, critic role: 23, the output waves 41; actor role: 22 / 39 / 0),
+    // and those stay in flight across the first barrier.  For that the call sits in EVERY arm of the request code below: one call
+    // behind the join waits with the smallest N of the arms.  Column cc of row r goes to: obs -> s_qin, action -> s_qin[X]
+    // (critic role), reward / discount / truncation -> s_aux, next obs -> s_qin2 (critic role).
     const bool has_elem = tid < 16 * D;
     const int r_t = tid / D, cc_t = tid - r_t * D;
     const bool is_obs = cc_t < X, is_obs2 = cc_t >= X + 3 && cc_t < 2 * X + 3;
@@ -308,23 +385,25 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
       ImgF I1, I2;
       float wo[16];
       float bo0 = 0.f, bo1 = 0.f;
-      if (c == 0) {
-        thin_col_request<KP>(*reinterpret_cast<float(*)[KP + 1]>(&tw[0]), pi_p, lane);
-        img_fwd_request(I1, pi_p + N::P_W1, c0, lane);
-        if (sub == 0) {
-          img_out_request<2>(wo, pi_p + N::P_OUT, lane);
-          bo0 = pi_p[N::P_OUT + LH * 2];
-          bo1 = pi_p[N::P_OUT + LH * 2 + 1];
-        }
+      // ONE request sequence for both chains, addressed by data: an if / else over the chain with requests in both arms compiles
+      // to "arm 1, then arm 0 unless arm 1 ran", and the wait pass takes that edge for real — arm 0 then waits for arm 1's
+      // requests (here: for the tile, before it issued a single weight request).  Chain 0 requests one row more than its thin
+      // layer has (the first row of its W1: in bounds, unused).
+      const float *const f0_p = c == 0 ? pi_p : qk_p;
+      const int f0_w1 = c == 0 ? N::P_W1 : N::Q_W1, n_out = 2 - c;
+      thin_col_request<KQ>(tw, f0_p, lane);
+      PIN_ORDER();      // (request order is wait order now: left alone, hipcc issues half of the thin column behind the image)
+      img_fwd_request(I1, f0_p + f0_w1, c0, lane);
+      // the wave that forms the chain's output layer has 19 requests more behind the tile: the tile's wait sits in each arm, so
+      // that each counts its own (a wait behind the join would count the shorter arm's for both)
+      if (sub == c) {
+        img_out_request_n(wo, f0_p + f0_w1 + 2 * HID, n_out, lane);
+        bo0 = f0_p[f0_w1 + 2 * HID + LH * n_out];
+        bo1 = f0_p[f0_w1 + 2 * HID + LH * n_out + n_out - 1];      // (chain 1: bo0 again, unused)
+        tile_to_lds();
       } else {
-        thin_col_request<KQ>(tw, qk_p, lane);
-        img_fwd_request(I1, qk_p + N::Q_W1, c0, lane);
-        if (sub == 1) {
-          img_out_request<1>(wo, qk_p + N::Q_OUT, lane);
-          bo0 = qk_p[N::Q_OUT + LH];
-        }
+        tile_to_lds();
       }
-      tile_to_lds();
       __syncthreads();
       LEAN_STAMP(1);
       // ---- F0 thin layer; the target critics' thin columns are requested here (6 requests) ----
@@ -340,15 +419,13 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
       // ---- F0 hidden layers; F1's two images are requested in their MFMA shadows ----
       {
         auto pf = make_pf([&](int s) __attribute__((always_inline)) { img_fwd_request_piece(J1, qt_p + N::Q_W1, c0, lane, s); });
-        if (c == 0) hid_fwd<false>(I1, TILE(0), TILE(1), nullptr, c0, lane, pf);
-        else hid_fwd<true>(I1, TILE(7), TILE(8), TILE(5), c0, lane, pf);
+        hid_fwd_sel(I1, TILE(c == 0 ? 0 : 7), TILE(c == 0 ? 1 : 8), TILE(5), c != 0, c0, lane, pf);
       }
       __syncthreads();
       LEAN_STAMP(3);
       {
         auto pf = make_pf([&](int s) __attribute__((always_inline)) { img_fwd_request_piece(J2, qt_p + N::Q_W1 + HID, c0, lane, s); });
-        if (c == 0) hid_fwd<false>(I2, TILE(1), TILE(0), nullptr, c0, lane, pf);
-        else hid_fwd<true>(I2, TILE(8), TILE(9), TILE(6), c0, lane, pf);
+        hid_fwd_sel(I2, TILE(c == 0 ? 1 : 8), TILE(c == 0 ? 0 : 9), TILE(6), c != 0, c0, lane, pf);
       }
       __syncthreads();
       LEAN_STAMP(4);
@@ -443,7 +520,8 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
       float wo[16];
       float bo0 = 0.f, bo1 = 0.f;
       float tw1[KQ + 1];
-      ImgF J1, J2;
+      ImgF J1, J2;      // chain 0's F1 images (riding requests)
+      ImgF K1, K2;      // chain 1's: names of their own, see below
       float wo1[16];
       float bq = 0.f;
       if (c == 0) {
@@ -453,36 +531,47 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
           img_out_request<2>(wo, pi_p + N::P_OUT, lane);
           bo0 = pi_p[N::P_OUT + LH * 2];
           bo1 = pi_p[N::P_OUT + LH * 2 + 1];
+          tile_to_lds();
+        } else {
+          tile_to_lds();
         }
-      }      // (chain 1 walks nothing before F1: its requests wait behind the first barrier, out of the launch's first burst)
-      tile_to_lds();
+      } else {      // (chain 1 walks nothing before F1: its requests wait behind the first barrier, out of the launch's first burst)
+        tile_to_lds();
+      }      // (the tile's wait in every arm: each counts the requests IT has behind the tile)
       __syncthreads();
       LEAN_STAMP(1);
       // (the second hidden layer's images are requested here, not at the top: eight waves x 17 requests less in the prologue's burst)
+      // Chain 1 is idle until F1 and spreads its requests over the three steps chain 0 walks first, one image a step: the CU's
+      // address path takes a wave-instruction every ~7 cycles, and 4 waves x 57 requests in this one step held its barrier for
+      // 2.5 k cycles while the next two steps left the path idle.  (In order of use, so that each first use waits for its own.)
+      // (Two ifs in a row, the second on a copy of c that hipcc cannot see through, not if / else: an if / else compiles to "the
+      // else arm, then the if arm unless the else arm ran", the wait pass takes that edge for real, and chain 0 would wait for
+      // chain 1's requests before its first MFMA — in fact for its own of the step before.)
+      int c_again = c;
+      asm volatile("" : "+s"(c_again));
+      thin_col_request<KQ>(tw1, q_p, lane);
+      PIN_ORDER();
       if (c == 0) {
         thin_first<KP, true, false>(tw, s_qin, TILE(7), TILE(4), nullptr, sub, lane);
-        thin_col_request<KQ>(tw1, q_p, lane);
         img_fwd_request(I2, pi_p + N::P_W1 + HID, c0, lane);
-      } else {
-        thin_col_request<KQ>(tw1, q_p, lane);
-        img_fwd_request(J1, q_p + N::Q_W1, c0, lane);
-        img_fwd_request(J2, q_p + N::Q_W1 + HID, c0, lane);
-        if (sub == 2) {
-          img_out_request<1>(wo1, q_p + N::Q_OUT, lane);
-          bq = q_p[N::Q_OUT + LH];
-        }
       }
+      if (c_again != 0) img_fwd_request(K1, q_p + N::Q_W1, c0, lane);
       __syncthreads();
       LEAN_STAMP(2);
       if (c == 0) {
         auto pf = make_pf([&](int s) __attribute__((always_inline)) { img_fwd_request_piece(J1, q_p + N::Q_W1, c0, lane, s); });
         hid_fwd<true>(I1, TILE(7), TILE(8), TILE(5), c0, lane, pf);
       }
+      if (c_again != 0) img_fwd_request(K2, q_p + N::Q_W1 + HID, c0, lane);
       __syncthreads();
       LEAN_STAMP(3);
       if (c == 0) {
         auto pf = make_pf([&](int s) __attribute__((always_inline)) { img_fwd_request_piece(J2, q_p + N::Q_W1 + HID, c0, lane, s); });
         hid_fwd<true>(I2, TILE(8), TILE(9), TILE(6), c0, lane, pf);
+      }
+      if (c_again != 0 && sub == 2) {
+        img_out_request<1>(wo1, q_p + N::Q_OUT, lane);
+        bq = q_p[N::Q_OUT + LH];
       }
       __syncthreads();
       LEAN_STAMP(4);
@@ -521,10 +610,10 @@ __global__ void __launch_bounds__(LEAN_THREADS) k_sac_lean(const SacLeanArgs A) 
       thin_first<KQ, false, true>(tw1, s_qin, TILE(tv0), nullptr, TILE(tt0), sub, lane);
       __syncthreads();
       LEAN_STAMP(6);
-      hid_fwd_jvp(J1, TILE(tv0), TILE(tt0), TILE(tv0 + 1), TILE(tt0 + 1), c0, lane);
+      hid_fwd_jvp(img_select(c == 0, J1, K1), TILE(tv0), TILE(tt0), TILE(tv0 + 1), TILE(tt0 + 1), c0, lane);
       __syncthreads();
       LEAN_STAMP(7);
-      hid_fwd_jvp(J2, TILE(tv0 + 1), TILE(tt0 + 1), TILE(tv0), TILE(tt0), c0, lane);
+      hid_fwd_jvp(img_select(c == 0, J2, K2), TILE(tv0 + 1), TILE(tt0 + 1), TILE(tv0), TILE(tt0), c0, lane);
       __syncthreads();
       LEAN_STAMP(8);
       float zq[4], hc[16];
