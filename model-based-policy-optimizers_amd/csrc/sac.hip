@@ -1,4 +1,4 @@
-// sac.hip — S3-S8: SAC sgd_step as three kernels (see include/mbpo_hip.h for the flat state layout).
+// sac.hip — S3-S8: SAC sgd_step as three kernels (see include/mbpo_hip.h for the flat state layout), and its host half.
 //
 //   k_sac_fwd_bwd   2 workgroups per 16-sample tile: a CRITIC role (pi(s') fwd, target-Q fwd, Q fwd+bwd) and an
 //                   ACTOR role (pi(s) fwd+bwd, alpha loss, Q fwd + input-gradient bwd).  All three losses are taken
@@ -15,6 +15,12 @@
 //                   sac/sac.py:96) practically never triggers; when it does, the consumer recomputes the clipped step from the
 //                   undo log (same formulas, same order: bit-identical to the three-launch path).  A device-wide meeting point
 //                   inside one launch was measured SLOWER than the kernel boundary it removes (round 1: 48 vs 40 us).
+//
+// Host half (behind the kernels): every update takes ONE path:  sac_plan (validate, sizes, workspace offsets)  ->  sac_variant (which
+// forward/backward kernel)  ->  sac_fill_* (the kernels' argument blocks)  ->  sac_update (the launches).  The entry points differ in
+// whether the forward/backward half runs and in the SacReduceKind that follows it.
+// The kernels stay in this one unit, in this order: the device code object is then byte for byte the one it was before the host half
+// was rewritten, so what a captured graph replays is unchanged by construction (DESIGN.md "Where dispatch lives").
 //
 // Algorithmic work per sample per sgd_step: 2*(5P + 12Q) FLOP — latency-bound at B=256, hence the
 // few fat launches and the slab scheme instead of a tree of small kernels.
@@ -70,6 +76,44 @@ struct SacArgs {
                                 // steps instead of 16 on the role that bounds the kernel
 };
 
+// The dynamic LDS of k_sac_fwd_bwd: float offsets of its regions in carve order, `end` = the launch's LDS size in floats.  The host's
+// one statement of the layout (sac_plan's byte count, sac_chain_table's operands); the carve at the top of the kernel keeps its own
+// expressions and must agree with this.
+struct SacLds {
+  long long row, sn, sn2, qin, qin2, pp, store, y, dy, dx, eps, a, sig, raw, lp, lpa, scal, gn, end;
+};
+static inline SacLds sac_lds(int row_len, int ld_x, int ld_xu, int ld_h, int ld_y, int LH, int U) {
+  const long long T = 16LL * ld_h, U4 = (16LL * U + 3) & ~3LL;      // one hidden tile; one [16][U] sample array
+  SacLds L;
+  L.row = 0;                                      // [16][D] (flat copy of the tile's transitions)
+  L.sn = L.row + 16LL * ((row_len + 3) & ~3);     // [16][ld_x]   normalised obs
+  L.sn2 = L.sn + 16LL * ld_x;                     // [16][ld_x]   normalised next obs
+  L.qin = L.sn2 + 16LL * ld_x;                    // [16][ld_xu]  [sn, a]
+  L.qin2 = L.qin + 16LL * ld_xu;                  // [16][ld_xu]  [s'n, a']
+  L.pp = L.qin2 + 16LL * ld_xu;                   // 4 tiles: ping-pong hidden / delta tiles
+  L.store = L.pp + 4 * T;                         // 4*LH tiles: stored z / h
+  L.y = L.store + 4LL * LH * T;                   // [3][16][ld_y]  network outputs
+  L.dy = L.y + 3 * 16LL * ld_y;                   // [2][16][ld_y]  output gradients
+  L.dx = L.dy + 2 * 16LL * ld_y;                  // [2][16][ld_xu] critic input gradients (actor role)
+  L.eps = L.dx + 2 * 16LL * ld_xu;                // six [16][U] sample arrays
+  L.a = L.eps + U4;
+  L.sig = L.a + U4;
+  L.raw = L.sig + U4;
+  L.lp = L.raw + U4;
+  L.lpa = L.lp + U4;
+  L.scal = L.lpa + U4;                            // [4][16]
+  L.gn = L.scal + 64;                             // [4]: group norms of the previous speculative optimizer step
+  L.end = L.gn + 4;
+  return L;
+}
+
+// Which forward/backward kernel one update launches and how (sac.hip, sac_variant): the layered path (sac_layered.hip), the
+// specialised k_sac_lean (sac_lean.hip), or the instantiation of k_sac_fwd_bwd that sac_fwd_bwd_launch picks.
+struct SacVariant {
+  bool layered, lean, split, jvp, thin, wide_any;
+  int H, wg_per_tile;
+};
+
 // Timeline stamps for DESIGN.md's phase breakdown: one s_memtime per phase boundary, written by thread 0 of tile 0.
 #define SAC_STAMP(i)                                                                   \
   if (A.stamps && tile == 0 && tid == 0) {                                             \
@@ -77,18 +121,6 @@ struct SacArgs {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");         \
     A.stamps[role * 16 + (i)] = t_;                                                    \
   }
-
-static unsigned long long *g_sac_stamps = nullptr;
-// Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_sac_fwd_bwd, 1 = the specialised k_sac_lean
-// where it applies, -1 = the MBPO_SAC_LEAN environment default (on).  tests/test_gpu_sac_lean.py flips it inside one process.
-extern "C" int mbpo_debug_set_sac_lean(int mode) { return mbpo_knob_set_override(KNOB_SAC_LEAN, mode); }
-// Measurement hook (not part of include/mbpo_hip.h): device buffer of >= 32 uint64 that k_sac_fwd_bwd fills with
-// s_memtime stamps at its phase boundaries (tile 0, both roles); NULL switches the stamps off.
-extern "C" int mbpo_debug_set_stamps(void *buf) {
-  g_sac_stamps = (unsigned long long *)buf;
-  return MBPO_OK;
-}
-
 
 // Workgroup = 8 waves = one 16-sample tile in one ROLE.  Wave w = (chain c = w/2, sub = w%2): each network chain is
 // shared by 2 waves (column slices of H/2), chains advance side by side in lockstep, one workgroup barrier per layer
@@ -135,6 +167,8 @@ __global__ void __launch_bounds__(64 * SP * NCH) k_sac_fwd_bwd(SacArgs A) {
   const int T = 16 * ld_h;  // one hidden tile
 
   // ---- LDS carve (every region a multiple of 4 floats: rows stay 16-byte aligned) ----
+  // The layout is SacLds (above), which the host sizes the launch and fills the chain table from: the two must agree.  The
+  // carve keeps its own expressions (a folded local has moved scalar-register spills in this kernel before).
   float *s_row = smem;                      // [16][D] (flat copy of the tile's transitions)
   const int D4 = D;
   float *s_sn = s_row + 16 * ((D + 3) & ~3);  // [16][ld_x]   normalised obs
@@ -534,6 +568,18 @@ struct SacReduceArgs {
   unsigned int *seq;
 };
 
+// What follows the forward/backward launch of one update:
+//   PLAIN           k_sac_reduce: grads[i] = sum over tiles of slab[t][i]; loss metrics; per-group sum-of-squares partials
+//   PUSH            k_sac_reduce_push: the local sums go to every rank's exchange region (k_sac_gather completes them)
+//   EXCHANGE        k_sac_reduce_exchange: push, wait for the peers and sum the world slots in one launch
+//   APPLY           k_sac_reduce_apply<false>: the reduction and the unclipped optimizer step in one launch (the default path)
+//   APPLY_EXCHANGE  k_sac_reduce_apply<true>: the same with the peer exchange in between
+enum class SacReduceKind { NONE, PLAIN, PUSH, EXCHANGE, APPLY, APPLY_EXCHANGE };
+// the kinds whose workgroups wait inside the kernel for the peers' same kernel: the whole grid must be co-resident
+static inline bool sac_reduce_waits(SacReduceKind k) { return k == SacReduceKind::EXCHANGE || k == SacReduceKind::APPLY_EXCHANGE; }
+// the kinds that use the peer exchange regions at all
+static inline bool sac_reduce_p2p(SacReduceKind k) { return k == SacReduceKind::PUSH || sac_reduce_waits(k); }
+
 // sum-of-squares partials per workgroup and optimizer group (0 policy, 1 critics, 2 alpha), fixed order
 __device__ __forceinline__ void group_sumsq(float g, int i, int P, int Q2, int NP, float *ss_part, float *quick = nullptr,
                                             float blk_lim = 0.f) {
@@ -568,9 +614,10 @@ __device__ __forceinline__ void group_sumsq(float g, int i, int P, int Q2, int N
   }
 }
 
-__global__ void __launch_bounds__(256) k_sac_reduce(SacReduceArgs A) {
-  const int NP = A.P + A.Q2 + 1;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// One element of the multi-launch reductions (k_sac_reduce, k_sac_reduce_push, k_sac_reduce_exchange): element i's slab sum over the
+// tiles, returned; the thread that owns log_alpha (i == NP - 1) also forms the loss metrics, adds them to metrics_accum and records in
+// seq[1] that nothing is pending any more.
+__device__ __forceinline__ float sac_reduce_element(const SacReduceArgs &A, int i, int NP) {
   const unsigned int seq_issued = (i == NP - 1) ? A.seq[0] : 0u;      // requested beside the slab sums
   float g = 0.f;
   if (i < A.P) {
@@ -597,6 +644,13 @@ __global__ void __launch_bounds__(256) k_sac_reduce(SacReduceArgs A) {
       A.metrics_accum[4] = a4 + 1.0f;
     }
   }
+  return g;
+}
+
+__global__ void __launch_bounds__(256) k_sac_reduce(SacReduceArgs A) {
+  const int NP = A.P + A.Q2 + 1;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const float g = sac_reduce_element(A, i, NP);
   if (i < NP) A.grads[i] = g;
   group_sumsq(g, i, A.P, A.Q2, NP, A.ss_part);
 }
@@ -606,32 +660,7 @@ __global__ void __launch_bounds__(256) k_sac_reduce_push(SacReduceArgs A, P2pDev
   const int NP = A.P + A.Q2 + 1;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const unsigned epoch = X.epoch[0];
-  const unsigned int seq_issued = (i == NP - 1) ? A.seq[0] : 0u;      // requested beside the slab sums
-  float g = 0.f;
-  if (i < A.P) {
-    g = slab_sum<16>(A.slab_pi, A.P, A.n_tiles, i);
-  } else if (i < A.P + A.Q2) {
-    const int j = i - A.P;
-    g = slab_sum<16>(A.slab_q, A.Q2, A.n_tiles, j);
-  } else if (i == NP - 1) {
-    // (all loads of the three sums in flight together: this one thread is the kernel's critical path)
-    const float ce = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 0) + slab_sum<16>(A.slab_ex, 4, A.n_tiles, 3), ac = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 1),
-                al = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 2);
-    const float invB = 1.0f / (float)A.B;
-    g = al * invB;
-    const float m0 = 0.5f * ce * (0.5f * invB), m1 = ac * invB, m2 = al * invB;
-    A.metrics[0] = m0;
-    A.metrics[1] = m1;
-    A.seq[1] = seq_issued;       // nothing is pending any more: this step is not speculative
-    A.metrics[2] = m2;
-    if (A.metrics_accum) {       // (no load of what was just stored: each such round trip is part of the launch's tail)
-      const float a0 = A.metrics_accum[0], a1 = A.metrics_accum[1], a2 = A.metrics_accum[2], a4 = A.metrics_accum[4];
-      A.metrics_accum[0] = a0 + m0;
-      A.metrics_accum[1] = a1 + m1;
-      A.metrics_accum[2] = a2 + m2;
-      A.metrics_accum[4] = a4 + 1.0f;
-    }
-  }
+  const float g = sac_reduce_element(A, i, NP);
   p2p_push(X, epoch, i, NP, g);
 }
 
@@ -657,31 +686,7 @@ __global__ void __launch_bounds__(256) k_sac_reduce_exchange(SacReduceArgs A, P2
   const int NP = A.P + A.Q2 + 1;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const unsigned epoch = X.epoch[0], want = X.epoch[1];
-  const unsigned int seq_issued = (i == NP - 1) ? A.seq[0] : 0u;      // requested beside the slab sums
-  float g = 0.f;
-  if (i < A.P) {
-    g = slab_sum<16>(A.slab_pi, A.P, A.n_tiles, i);
-  } else if (i < A.P + A.Q2) {
-    const int j = i - A.P;
-    g = slab_sum<16>(A.slab_q, A.Q2, A.n_tiles, j);
-  } else if (i == NP - 1) {
-    const float ce = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 0) + slab_sum<16>(A.slab_ex, 4, A.n_tiles, 3), ac = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 1),
-                al = slab_sum<16>(A.slab_ex, 4, A.n_tiles, 2);
-    const float invB = 1.0f / (float)A.B;
-    g = al * invB;
-    const float m0 = 0.5f * ce * (0.5f * invB), m1 = ac * invB, m2 = al * invB;
-    A.metrics[0] = m0;
-    A.metrics[1] = m1;
-    A.seq[1] = seq_issued;       // nothing is pending any more: this step is not speculative
-    A.metrics[2] = m2;
-    if (A.metrics_accum) {       // (no load of what was just stored: each such round trip is part of the launch's tail)
-      const float a0 = A.metrics_accum[0], a1 = A.metrics_accum[1], a2 = A.metrics_accum[2], a4 = A.metrics_accum[4];
-      A.metrics_accum[0] = a0 + m0;
-      A.metrics_accum[1] = a1 + m1;
-      A.metrics_accum[2] = a2 + m2;
-      A.metrics_accum[4] = a4 + 1.0f;
-    }
-  }
+  const float g = sac_reduce_element(A, i, NP);
   p2p_push(X, epoch, i, NP, g);
   const bool ok = p2p_wait(X, want);
   float gs = 0.f;
@@ -738,8 +743,6 @@ __global__ void __launch_bounds__(256) k_sac_apply(SacOptArgs A) {
     if (!(s_scale[0] < A.max_norm) || !(s_scale[1] < A.max_norm) || !(s_scale[2] < A.max_norm)) A.seq[SAC_CTL_CLIP_EVENTS] += 1u;
   }
 }
-
-// ------------------------------------------------------------------------------------------------ host side
 
 // ------------------------------------------------------------------------------------------------
 // One batch of up to NB slab terms of one column, t0 <= t < min(t0 + NB, n_tiles).  Every load of the batch is issued without a
@@ -954,8 +957,69 @@ __global__ void __launch_bounds__(1024) k_sac_finalize(SacOptArgs O, unsigned lo
   if (tid == 0) O.seq[1] = O.seq[0];
 }
 
+// ------------------------------------------------------------------------------------------------ launches
+constexpr int SP64 = 4;   // waves per chain at hidden width 64
+
+static int sac_fwd_bwd_launch(const SacVariant &v, int grid_, size_t lds, hipStream_t st, const SacArgs &A) {
+  const dim3 grid(grid_);
+  const bool wide_any = v.wide_any, split = v.split;
+  if (v.H == 64) {
+    if (wide_any) return mbpo_launch<k_sac_fwd_bwd<64, SP64, true>>(grid, 256 * SP64, lds, st, "sac_grads", A);
+    else if (split && v.thin) return mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2, true>>(grid, 128 * SP64, lds, st, "sac_grads", A);
+    else if (split) return mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2>>(grid, 128 * SP64, lds, st, "sac_grads", A);
+    else return mbpo_launch<k_sac_fwd_bwd<64, SP64, false>>(grid, 256 * SP64, lds, st, "sac_grads", A);
+  } else if (split && !wide_any) {
+    return mbpo_launch<k_sac_fwd_bwd<128, 4, false, 2>>(grid, 512, lds, st, "sac_grads", A);
+  } else {
+    return mbpo_launch<k_sac_fwd_bwd<128, 2, false>>(grid, 512, lds, st, "sac_grads", A);
+  }
+}
+
+static void sac_reduce_launch(SacReduceKind kind, int n_red, hipStream_t st, const SacReduceArgs &R, const SacOptArgs &O, const P2pDev &X) {
+  const dim3 grid(n_red), block(256);
+  switch (kind) {
+    case SacReduceKind::NONE: break;
+    case SacReduceKind::PLAIN: hipLaunchKernelGGL(k_sac_reduce, grid, block, 0, st, R); break;
+    case SacReduceKind::PUSH: hipLaunchKernelGGL(k_sac_reduce_push, grid, block, 0, st, R, X); break;
+    case SacReduceKind::EXCHANGE: hipLaunchKernelGGL(k_sac_reduce_exchange, grid, block, 0, st, R, X); break;
+    // (<true> is named before <false>, and the ladder above before both: templates are emitted in the order the host first names
+    // them, and the unit's device code object is kept byte for byte)
+    case SacReduceKind::APPLY_EXCHANGE: hipLaunchKernelGGL(k_sac_reduce_apply<true>, grid, block, 0, st, R, O, X); break;
+    case SacReduceKind::APPLY: hipLaunchKernelGGL(k_sac_reduce_apply<false>, grid, block, 0, st, R, O, X); break;
+  }
+}
+
+static void sac_sumsq_launch(int n_red, hipStream_t st, const float *grads, int P, int Q2, float *ss_part) {
+  hipLaunchKernelGGL(k_sac_sumsq, dim3(n_red), dim3(256), 0, st, grads, P, Q2, ss_part);
+}
+
+static void sac_gather_launch(int n_red, hipStream_t st, const P2pDev &X, float *grads, int P, int Q2, float *ss_part) {
+  hipLaunchKernelGGL(k_sac_gather, dim3(n_red), dim3(256), 0, st, X, grads, P, Q2, ss_part);
+}
+
+static void sac_apply_launch(int n_red, hipStream_t st, const SacOptArgs &O) {
+  hipLaunchKernelGGL(k_sac_apply, dim3(n_red), dim3(256), 0, st, O);
+}
+
+static void sac_finalize_launch(hipStream_t st, const SacOptArgs &O, unsigned long long *rng_dev, unsigned long long rng_inc) {
+  hipLaunchKernelGGL(k_sac_finalize, dim3(1), dim3(1024), 0, st, O, rng_dev, rng_inc);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+static unsigned long long *g_sac_stamps = nullptr;
+// Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_sac_fwd_bwd, 1 = the specialised k_sac_lean
+// where it applies, -1 = the MBPO_SAC_LEAN environment default (on).  tests/test_gpu_sac_lean.py flips it inside one process.
+extern "C" int mbpo_debug_set_sac_lean(int mode) { return mbpo_knob_set_override(KNOB_SAC_LEAN, mode); }
+// Measurement hook (not part of include/mbpo_hip.h): device buffer of >= 32 uint64 that k_sac_fwd_bwd fills with
+// s_memtime stamps at its phase boundaries (tile 0, both roles); NULL switches the stamps off.
+extern "C" int mbpo_debug_set_stamps(void *buf) {
+  g_sac_stamps = (unsigned long long *)buf;
+  return MBPO_OK;
+}
+
 struct SacPlan {
   MlpDev pi, q, qt;
+  NetShape sh_pi, sh_q;
   int P, Q, NP, n_tiles, H, LH, n_red;
   size_t lds;
   int ld_x, ld_xu, ld_h, ld_y;
@@ -990,6 +1054,8 @@ static int sac_plan(const mbpo_sac_desc *d, SacPlan *pl, bool need_ptrs) {
   pl->qt = pl->q;
   pl->qt.params = d->target_q;
   pl->NP = pl->P + 2 * pl->Q + 1;
+  pl->sh_pi = net_shape(pl->pi);
+  pl->sh_q = net_shape(pl->q);
   pl->H = Hp;
   const int lhp = d->policy_layers - 1, lhq = d->q_layers - 1;
   pl->LH = lhp > lhq ? lhp : lhq;
@@ -1000,10 +1066,7 @@ static int sac_plan(const mbpo_sac_desc *d, SacPlan *pl, bool need_ptrs) {
   pl->ld_xu = up4(d->x_dim + d->u_dim) + 4;
   pl->ld_h = Hp + 4;
   pl->ld_y = up4(2 * d->u_dim) + 4;
-  const int U = d->u_dim;
-  size_t f = 16ull * up4(d->row_len) + 2ull * 16 * pl->ld_x + 2ull * 16 * pl->ld_xu + 4ull * 16 * pl->ld_h +
-             (size_t)pl->LH * 4 * 16 * pl->ld_h + 5ull * 16 * pl->ld_y + 2ull * 16 * pl->ld_xu + 6ull * up4(16 * U) + 64 + 4;
-  pl->lds = f * sizeof(float);
+  pl->lds = (size_t)sac_lds(d->row_len, pl->ld_x, pl->ld_xu, pl->ld_h, pl->ld_y, pl->LH, d->u_dim).end * sizeof(float);
   if (!pl->layered && pl->lds > 160 * 1024) pl->layered = true;      // more stored activations than a tile's LDS holds
   if (pl->layered) pl->n_tiles = 1;
   pl->off_slab_pi = 0;
@@ -1039,15 +1102,13 @@ extern "C" int64_t mbpo_sac_control_offset(const mbpo_sac_desc *d) {
   return pl.off_seq;
 }
 
-constexpr int SP64 = 4;   // waves per chain at hidden width 64
-
-// LDS offsets (floats) of the tiles the chains use; must mirror the carve at the top of k_sac_fwd_bwd
-static void sac_chain_table(const SacPlan &pl, int D, SacArgs *A, bool split, bool jvp) {
-  const int ld_x = pl.ld_x, ld_xu = pl.ld_xu, ld_h = pl.ld_h, ld_y = pl.ld_y, LH = pl.LH;
-  const int T = 16 * ld_h;
-  const int o_row = 0;
-  const int o_sn = o_row + 16 * ((D + 3) & ~3), o_sn2 = o_sn + 16 * ld_x, o_qin = o_sn2 + 16 * ld_x, o_qin2 = o_qin + 16 * ld_xu;
-  const int o_pp = o_qin2 + 16 * ld_xu, o_st0 = o_pp + 4 * T, o_y = o_st0 + 4 * LH * T, o_dy = o_y + 3 * 16 * ld_y, o_dx = o_dy + 2 * 16 * ld_y;
+// the chain descriptors of every (table role, phase, chain); LDS operands as SacLds offsets
+static void sac_chain_table(const SacPlan &pl, int D, int U, SacArgs *A, bool split, bool jvp) {
+  const int ld_x = pl.ld_x, ld_xu = pl.ld_xu, ld_y = pl.ld_y, LH = pl.LH;
+  const int T = 16 * pl.ld_h;
+  const SacLds L = sac_lds(D, ld_x, ld_xu, pl.ld_h, ld_y, LH, U);
+  const int o_sn = (int)L.sn, o_sn2 = (int)L.sn2, o_qin = (int)L.qin, o_qin2 = (int)L.qin2;
+  const int o_pp = (int)L.pp, o_st0 = (int)L.store, o_y = (int)L.y, o_dy = (int)L.dy, o_dx = (int)L.dx;
   const int o_st1 = o_st0 + LH * T, o_st2 = o_st0 + 2 * LH * T, o_st3 = o_st0 + 3 * LH * T;
   const int P = pl.P, Q = pl.Q;   // params = [policy | critic0 | critic1 | log_alpha]; target_q = [critic0 | critic1]
   for (int role = 0; role < 3; ++role)
@@ -1146,217 +1207,222 @@ static void sac_fill_opt(const mbpo_sac_desc *d, const SacPlan &pl, SacOptArgs *
   A->wd[0] = d->wd_policy; A->wd[1] = d->wd_q; A->wd[2] = d->wd_alpha;
   A->max_norm = d->max_grad_norm; A->tau = d->tau; A->one_minus_tau = (float)(1.0 - (double)d->tau); A->grad_scale = d->grad_scale;
 }
+static SacOptArgs sac_opt(const mbpo_sac_desc *d, const SacPlan &pl) {
+  SacOptArgs O;
+  sac_fill_opt(d, pl, &O);
+  return O;
+}
 
-// phase_mask: bit0 = k_sac_fwd_bwd, bit1 = the slab reduction.  apply_in_reduce: the reduction launch is k_sac_reduce_apply.
-static int sac_grads_impl(const mbpo_sac_desc *d, int phase_mask, void *stream, const mbpo_p2p_desc *xd = nullptr,
-                          bool exchange_in_reduce = false, bool apply_in_reduce = false) {
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  MBPO_REQUIRE(d->batch, MBPO_ERR_ARG, "sac_grads: null batch");
-  MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG, "sac_grads: norm_mean/norm_std mismatch");
-  SacArgs A;
-  A.pi = pl.pi; A.q = pl.q; A.qt = pl.qt;
-  A.sh_pi = net_shape(pl.pi);
-  A.sh_q = net_shape(pl.q);
+// Which forward/backward kernel one update launches.  The knobs in this order: split, jvp (asked only where it can apply), thin, lean.
+static SacVariant sac_variant(const mbpo_sac_desc *d, const SacPlan &pl) {
+  const NetShape &sh_pi = pl.sh_pi, &sh_q = pl.sh_q;
+  SacVariant v;
+  v.layered = pl.layered;
+  v.H = pl.H;
   // three workgroups per tile (one critic each): at hidden width 128 a phase is MFMA-bound on its CU, at 64 the two critic
   // workgroups finish before the actor role does and 8-wave workgroups have cheaper barriers (26.9 -> 24.0 us with the forward-mode
   // actor role).  The WIDE kernels keep two workgroups per tile.  MBPO_SAC_SPLIT=0/1 overrides (measurement).
   const long long split_env = mbpo_knob(KNOB_SAC_SPLIT);
-  const bool wide_any = net_is_wide(A.sh_pi) || net_is_wide(A.sh_q);
-  const bool split = split_env >= 0 ? split_env != 0 : !wide_any;
-  A.split = split ? 1 : 0;
-  const int wg_per_tile = split ? 3 : 2;
+  v.wide_any = net_is_wide(sh_pi) || net_is_wide(sh_q);
+  v.split = split_env >= 0 ? split_env != 0 : !v.wide_any;
+  v.wg_per_tile = v.split ? 3 : 2;
   // forward-mode dQ/da in the actor role: one action dimension (one tangent), register-image kernels with one-tile network ends
-  const bool reg_path = (pl.H == 64 || split) && !wide_any && pl.LH >= 2;
-  const bool jvp = d->u_dim == 1 && reg_path && mbpo_knob(KNOB_SAC_JVP) != 0;
-  A.jvp = jvp ? 1 : 0;
+  const bool reg_path = (pl.H == 64 || v.split) && !v.wide_any && pl.LH >= 2;
+  v.jvp = d->u_dim == 1 && reg_path && mbpo_knob(KNOB_SAC_JVP) != 0;
   // thin layers: the three-workgroup launch at H = 64 with forward-mode actor (no input-gradient chains), small input / output
   // layers and at least one H x H layer in each network
-  A.thin = (mbpo_knob(KNOB_SAC_THIN) != 0 && split && jvp && pl.H == 64 && A.sh_pi.K_in <= THIN_KMAX && A.sh_q.K_in <= THIN_KMAX &&
-            A.sh_pi.N_out <= THIN_NMAX && A.sh_q.N_out <= THIN_NMAX && A.sh_pi.L >= 3 && A.sh_q.L >= 3) ? 1 : 0;
-  if (!pl.layered) sac_chain_table(pl, d->row_len, &A, split, jvp);
-  A.X = d->x_dim; A.U = d->u_dim; A.B = d->batch_size; A.D = d->row_len;
-  A.batch = d->batch; A.norm_mean = d->norm_mean; A.norm_std = d->norm_std;
-  A.log_alpha = d->params + pl.NP - 1;
-  A.noise_alpha = d->noise_alpha; A.noise_critic = d->noise_critic; A.noise_actor = d->noise_actor;
-  A.seed = d->seed; A.offset = d->offset; A.rng_dev = (const unsigned long long *)d->rng_dev;
-  sac_fill_opt(d, pl, &A.opt);
-  A.step_count_rw = d->step_count;
-  A.stamps = g_sac_stamps;
+  v.thin = mbpo_knob(KNOB_SAC_THIN) != 0 && v.split && v.jvp && pl.H == 64 && sh_pi.K_in <= THIN_KMAX && sh_q.K_in <= THIN_KMAX &&
+           sh_pi.N_out <= THIN_NMAX && sh_q.N_out <= THIN_NMAX && sh_pi.L >= 3 && sh_q.L >= 3;
+  // MBPO_SAC_LEAN=0 keeps the generic kernel on the benchmark networks too (A/B runs, the bit-identity test)
+  v.lean = mbpo_knob(KNOB_SAC_LEAN) != 0 && !pl.layered && v.thin &&
+           sac_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->q_dims, d->q_layers,
+                             d->q_activation);
+  return v;
+}
+
+// p2p_epoch: the peer exchange's epoch words where this update's reduction uses the exchange regions, else null
+static void sac_fill_args(const mbpo_sac_desc *d, const SacPlan &pl, const SacVariant &v, const SacOptArgs &O, unsigned int *p2p_epoch,
+                          SacArgs *A) {
+  A->pi = pl.pi; A->q = pl.q; A->qt = pl.qt;
+  A->sh_pi = pl.sh_pi; A->sh_q = pl.sh_q;
+  A->split = v.split ? 1 : 0; A->jvp = v.jvp ? 1 : 0; A->thin = v.thin ? 1 : 0;
+  sac_chain_table(pl, d->row_len, d->u_dim, A, v.split, v.jvp);
+  A->X = d->x_dim; A->U = d->u_dim; A->B = d->batch_size; A->D = d->row_len;
+  A->batch = d->batch; A->norm_mean = d->norm_mean; A->norm_std = d->norm_std;
+  A->log_alpha = d->params + pl.NP - 1;
+  A->noise_alpha = d->noise_alpha; A->noise_critic = d->noise_critic; A->noise_actor = d->noise_actor;
+  A->seed = d->seed; A->offset = d->offset; A->rng_dev = (const unsigned long long *)d->rng_dev;
+  A->opt = O;
+  A->step_count_rw = d->step_count;
+  A->stamps = g_sac_stamps;
+  A->p2p_epoch = p2p_epoch;
+  A->p2p_blocks = (unsigned)pl.n_red;
+  A->discounting = d->discounting; A->reward_scaling = d->reward_scaling; A->target_entropy = d->target_entropy;
+  A->neq = d->non_equidistant_time; A->neq_cd = d->continuous_discounting; A->neq_tl = d->min_time_between_switches;
+  A->neq_tu = d->max_time_between_switches; A->neq_dt = d->env_dt;
+  A->slab_pi = d->workspace + pl.off_slab_pi; A->slab_q = d->workspace + pl.off_slab_q; A->slab_ex = d->workspace + pl.off_slab_ex;
+  A->ld_x = pl.ld_x; A->ld_xu = pl.ld_xu; A->ld_h = pl.ld_h; A->ld_y = pl.ld_y; A->LH = pl.LH;
+}
+
+// the benchmark networks: every shape a compile-time constant (sac_lean.hip), same slabs bit for bit
+static void sac_fill_lean(const mbpo_sac_desc *d, const SacPlan &pl, const SacOptArgs &O, unsigned int *p2p_epoch, SacLeanArgs *L) {
+  L->params = d->params; L->target_q = d->target_q; L->batch = d->batch; L->norm_mean = d->norm_mean; L->norm_std = d->norm_std;
+  L->noise_alpha = d->noise_alpha; L->noise_critic = d->noise_critic; L->noise_actor = d->noise_actor;
+  L->rng_dev = (const unsigned long long *)d->rng_dev; L->seed = d->seed; L->offset = d->offset;
+  L->slab_pi = d->workspace + pl.off_slab_pi; L->slab_q = d->workspace + pl.off_slab_q; L->slab_ex = d->workspace + pl.off_slab_ex;
+  L->step_count_rw = d->step_count; L->p2p_epoch = p2p_epoch; L->p2p_blocks = (unsigned)pl.n_red; L->B = d->batch_size;
+  L->discounting = d->discounting; L->reward_scaling = d->reward_scaling; L->target_entropy = d->target_entropy;
+  L->neq = d->non_equidistant_time; L->neq_cd = d->continuous_discounting; L->neq_tl = d->min_time_between_switches;
+  L->neq_tu = d->max_time_between_switches; L->neq_dt = d->env_dt;
+  L->stamps = g_sac_stamps;
+  L->pad0 = 0;
+  L->opt = O;
+}
+
+static void sac_fill_reduce(const mbpo_sac_desc *d, const SacPlan &pl, const SacOptArgs &O, SacReduceArgs *R) {
+  R->slab_pi = d->workspace + pl.off_slab_pi; R->slab_q = d->workspace + pl.off_slab_q; R->slab_ex = d->workspace + pl.off_slab_ex;
+  R->n_tiles = pl.n_tiles; R->P = pl.P; R->Q2 = 2 * pl.Q; R->B = d->batch_size;
+  R->grads = d->grads; R->metrics = d->metrics; R->metrics_accum = d->metrics_accum; R->ss_part = d->workspace + pl.off_ss; R->step_count = d->step_count;
+  R->seq = O.seq;
+}
+
+// One update: the forward/backward half (fwd) in the variant's kernel, then the reduction `kind` (NONE: nothing).  xd: the peer exchange
+// of the p2p kinds.
+static int sac_update(const mbpo_sac_desc *d, bool fwd, SacReduceKind kind, void *stream, const mbpo_p2p_desc *xd = nullptr) {
+  SacPlan pl;
+  int rc = sac_plan(d, &pl, true);
+  if (rc != MBPO_OK) return rc;
+  if (sac_reduce_waits(kind)) {
+    // every workgroup of the reduction waits inside the kernel for the peers' same kernel: they must all be resident at once
+    const bool step = kind == SacReduceKind::APPLY_EXCHANGE;
+    MBPO_REQUIRE(pl.n_red <= 1024, MBPO_ERR_UNSUPPORTED, "%s: %d workgroups cannot be assumed co-resident; use "
+                 "mbpo_sac_grads_p2p + mbpo_sac_gather_p2p%s", step ? "sac_step_p2p" : "sac_grads_exchange_p2p", pl.n_red,
+                 step ? " + mbpo_sac_apply" : "");
+  }
+  MBPO_REQUIRE(d->batch, MBPO_ERR_ARG, "sac_grads: null batch");
+  MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG, "sac_grads: norm_mean/norm_std mismatch");
   P2pDev X;
   memset(&X, 0, sizeof(X));
-  A.p2p_epoch = nullptr;
-  A.p2p_blocks = (unsigned)pl.n_red;
-  if (xd) {
+  if (sac_reduce_p2p(kind)) {
     rc = mbpo_p2p_make_dev(xd, &X);
     if (rc != MBPO_OK) return rc;
     MBPO_REQUIRE(xd->n_max >= pl.NP, MBPO_ERR_ARG, "sac_grads_p2p: exchange regions hold %lld floats, the gradient has %d",
                  (long long)xd->n_max, pl.NP);
-    A.p2p_epoch = X.epoch;
   }
-  A.discounting = d->discounting; A.reward_scaling = d->reward_scaling; A.target_entropy = d->target_entropy;
-  A.neq = d->non_equidistant_time; A.neq_cd = d->continuous_discounting; A.neq_tl = d->min_time_between_switches;
-  A.neq_tu = d->max_time_between_switches; A.neq_dt = d->env_dt;
-  MBPO_REQUIRE(!A.neq || A.neq_dt > 0.f, MBPO_ERR_ARG, "sac: non_equidistant_time needs env_dt > 0");
-  A.slab_pi = d->workspace + pl.off_slab_pi; A.slab_q = d->workspace + pl.off_slab_q; A.slab_ex = d->workspace + pl.off_slab_ex;
-  A.ld_x = pl.ld_x; A.ld_xu = pl.ld_xu; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
+  MBPO_REQUIRE(!d->non_equidistant_time || d->env_dt > 0.f, MBPO_ERR_ARG, "sac: non_equidistant_time needs env_dt > 0");
+  const SacVariant v = sac_variant(d, pl);
+  const SacOptArgs O = sac_opt(d, pl);
+  unsigned int *p2p_epoch = sac_reduce_p2p(kind) ? X.epoch : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  // MBPO_SAC_LEAN=0 keeps the generic kernel on the benchmark networks too (A/B runs, the bit-identity test)
-  const bool lean = mbpo_knob(KNOB_SAC_LEAN) != 0 && !pl.layered && A.thin &&
-                    sac_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->q_dims, d->q_layers,
-                                      d->q_activation);
-  if (pl.layered) {
-    if (phase_mask & 1) {
-      const SacLayeredBegin bg = {d->step_count, A.opt.seq, A.opt.slot_word, A.p2p_epoch, A.p2p_blocks};
-      rc = sac_layered_fwd_bwd(d, pl.pi, pl.q, pl.qt, d->workspace + pl.off_layered, A.slab_pi, A.slab_q, A.slab_ex, bg, st);
-      if (rc != MBPO_OK) return rc;
-    }
-  } else if ((phase_mask & 1) && lean) {
-    // the benchmark networks: every shape a compile-time constant (sac_lean.hip), same slabs bit for bit
-    SacLeanArgs L;
-    L.params = d->params; L.target_q = d->target_q; L.batch = d->batch; L.norm_mean = d->norm_mean; L.norm_std = d->norm_std;
-    L.noise_alpha = d->noise_alpha; L.noise_critic = d->noise_critic; L.noise_actor = d->noise_actor;
-    L.rng_dev = A.rng_dev; L.seed = A.seed; L.offset = A.offset;
-    L.slab_pi = A.slab_pi; L.slab_q = A.slab_q; L.slab_ex = A.slab_ex;
-    L.step_count_rw = d->step_count; L.p2p_epoch = A.p2p_epoch; L.p2p_blocks = A.p2p_blocks; L.B = d->batch_size;
-    L.discounting = A.discounting; L.reward_scaling = A.reward_scaling; L.target_entropy = A.target_entropy;
-    L.neq = A.neq; L.neq_cd = A.neq_cd; L.neq_tl = A.neq_tl; L.neq_tu = A.neq_tu; L.neq_dt = A.neq_dt;
-    L.stamps = g_sac_stamps;
-    L.pad0 = 0;
-    L.opt = A.opt;
-    rc = sac_lean_launch(L, d->x_dim, pl.n_tiles, stream);
-    if (rc != MBPO_OK) return rc;
-  } else if (phase_mask & 1) {
-    const dim3 grid(wg_per_tile * pl.n_tiles);
-    if (pl.H == 64) {
-      if (wide_any) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, true>>(grid, 256 * SP64, pl.lds, st, "sac_grads", A);
-      else if (split && A.thin) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2, true>>(grid, 128 * SP64, pl.lds, st, "sac_grads", A);
-      else if (split) rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false, 2>>(grid, 128 * SP64, pl.lds, st, "sac_grads", A);
-      else rc = mbpo_launch<k_sac_fwd_bwd<64, SP64, false>>(grid, 256 * SP64, pl.lds, st, "sac_grads", A);
-    } else if (split && !wide_any) {
-      rc = mbpo_launch<k_sac_fwd_bwd<128, 4, false, 2>>(grid, 512, pl.lds, st, "sac_grads", A);
+  if (fwd) {
+    if (v.layered) {
+      const SacLayeredBegin bg = {d->step_count, O.seq, O.slot_word, p2p_epoch, (unsigned)pl.n_red};
+      rc = sac_layered_fwd_bwd(d, pl.pi, pl.q, pl.qt, d->workspace + pl.off_layered, d->workspace + pl.off_slab_pi,
+                               d->workspace + pl.off_slab_q, d->workspace + pl.off_slab_ex, bg, st);
+    } else if (v.lean) {
+      SacLeanArgs L;
+      sac_fill_lean(d, pl, O, p2p_epoch, &L);
+      rc = sac_lean_launch(L, d->x_dim, pl.n_tiles, stream);
     } else {
-      rc = mbpo_launch<k_sac_fwd_bwd<128, 2, false>>(grid, 512, pl.lds, st, "sac_grads", A);
+      SacArgs A;
+      sac_fill_args(d, pl, v, O, p2p_epoch, &A);
+      rc = sac_fwd_bwd_launch(v, v.wg_per_tile * pl.n_tiles, pl.lds, st, A);
     }
     if (rc != MBPO_OK) return rc;
   }
-  if (!(phase_mask & 2)) {
+  if (kind == SacReduceKind::NONE) {
     MBPO_CHECK_LAUNCH("sac_grads");
     return MBPO_OK;
   }
   SacReduceArgs R;
-  R.slab_pi = A.slab_pi; R.slab_q = A.slab_q; R.slab_ex = A.slab_ex;
-  R.n_tiles = pl.n_tiles; R.P = pl.P; R.Q2 = 2 * pl.Q; R.B = d->batch_size;
-  R.grads = d->grads; R.metrics = d->metrics; R.metrics_accum = d->metrics_accum; R.ss_part = d->workspace + pl.off_ss; R.step_count = d->step_count;
-  R.seq = A.opt.seq;
-  if (apply_in_reduce && pl.layered) {
+  sac_fill_reduce(d, pl, O, &R);
+  if (v.layered && (kind == SacReduceKind::APPLY || kind == SacReduceKind::APPLY_EXCHANGE)) {
     // no speculative step on the layered path (two launches out of ~50 is nothing to win): the reduction, then the clipped
     // optimizer step — what mbpo_sac_step is defined to equal bit for bit
-    if (xd) hipLaunchKernelGGL(k_sac_reduce_exchange, dim3(pl.n_red), dim3(256), 0, st, R, X);
-    else hipLaunchKernelGGL(k_sac_reduce, dim3(pl.n_red), dim3(256), 0, st, R);
-    hipLaunchKernelGGL(k_sac_apply, dim3(pl.n_red), dim3(256), 0, st, A.opt);
-  } else if (apply_in_reduce) {
-    if (xd) hipLaunchKernelGGL(k_sac_reduce_apply<true>, dim3(pl.n_red), dim3(256), 0, st, R, A.opt, X);
-    else hipLaunchKernelGGL(k_sac_reduce_apply<false>, dim3(pl.n_red), dim3(256), 0, st, R, A.opt, X);
-  } else if (xd && exchange_in_reduce) hipLaunchKernelGGL(k_sac_reduce_exchange, dim3(pl.n_red), dim3(256), 0, st, R, X);
-  else if (xd) hipLaunchKernelGGL(k_sac_reduce_push, dim3(pl.n_red), dim3(256), 0, st, R, X);
-  else hipLaunchKernelGGL(k_sac_reduce, dim3(pl.n_red), dim3(256), 0, st, R);
+    sac_reduce_launch(kind == SacReduceKind::APPLY ? SacReduceKind::PLAIN : SacReduceKind::EXCHANGE, pl.n_red, st, R, O, X);
+    sac_apply_launch(pl.n_red, st, O);
+  } else {
+    sac_reduce_launch(kind, pl.n_red, st, R, O, X);
+  }
   MBPO_CHECK_LAUNCH("sac_grads");
   return MBPO_OK;
 }
 
+// The entry points that only plan and launch one optimizer-side kernel (on sac_opt(d, pl) where the kernel takes SacOptArgs).
+template <class Launch>
+static int sac_opt_entry(const mbpo_sac_desc *d, const char *what, Launch &&launch) {
+  SacPlan pl;
+  int rc = sac_plan(d, &pl, true);
+  if (rc != MBPO_OK) return rc;
+  rc = launch(pl);
+  if (rc != MBPO_OK) return rc;
+  MBPO_CHECK_LAUNCH(what);
+  return MBPO_OK;
+}
+
+extern "C" int mbpo_sac_grads(const mbpo_sac_desc *d, void *stream) { return sac_update(d, true, SacReduceKind::PLAIN, stream); }
+
+extern "C" int mbpo_sac_grads_phase(const mbpo_sac_desc *d, int32_t phase_mask, void *stream) {
+  MBPO_REQUIRE(phase_mask >= 1 && phase_mask <= 3, MBPO_ERR_ARG, "sac_grads_phase: phase_mask must be 1, 2 or 3");
+  // bit0 = the forward/backward launch, bit1 = the slab reduction
+  return sac_update(d, (phase_mask & 1) != 0, (phase_mask & 2) ? SacReduceKind::PLAIN : SacReduceKind::NONE, stream);
+}
+
 extern "C" int mbpo_sac_grads_p2p(const mbpo_sac_desc *d, const mbpo_p2p_desc *x, void *stream) {
   MBPO_REQUIRE(x, MBPO_ERR_ARG, "sac_grads_p2p: null exchange descriptor");
-  return sac_grads_impl(d, 3, stream, x);
+  return sac_update(d, true, SacReduceKind::PUSH, stream, x);
 }
 
 extern "C" int mbpo_sac_grads_exchange_p2p(const mbpo_sac_desc *d, const mbpo_p2p_desc *x, void *stream) {
   MBPO_REQUIRE(x, MBPO_ERR_ARG, "sac_grads_exchange_p2p: null exchange descriptor");
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  // every workgroup of the reduction waits inside the kernel: they must all be resident at once
-  MBPO_REQUIRE(pl.n_red <= 1024, MBPO_ERR_UNSUPPORTED, "sac_grads_exchange_p2p: %d workgroups cannot be assumed co-resident; use "
-               "mbpo_sac_grads_p2p + mbpo_sac_gather_p2p", pl.n_red);
-  return sac_grads_impl(d, 3, stream, x, true);
-}
-
-extern "C" int mbpo_sac_gather_p2p(const mbpo_sac_desc *d, const mbpo_p2p_desc *x, void *stream) {
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  P2pDev X;
-  rc = mbpo_p2p_make_dev(x, &X);
-  if (rc != MBPO_OK) return rc;
-  MBPO_REQUIRE(x->n_max >= pl.NP, MBPO_ERR_ARG, "sac_gather_p2p: exchange regions too small");
-  hipLaunchKernelGGL(k_sac_gather, dim3(pl.n_red), dim3(256), 0, (hipStream_t)stream, X, d->grads, pl.P, 2 * pl.Q, d->workspace + pl.off_ss);
-  MBPO_CHECK_LAUNCH("sac_gather_p2p");
-  return MBPO_OK;
-}
-
-extern "C" int mbpo_sac_grads(const mbpo_sac_desc *d, void *stream) { return sac_grads_impl(d, 3, stream); }
-
-extern "C" int mbpo_sac_grads_phase(const mbpo_sac_desc *d, int32_t phase_mask, void *stream) {
-  MBPO_REQUIRE(phase_mask >= 1 && phase_mask <= 3, MBPO_ERR_ARG, "sac_grads_phase: phase_mask must be 1, 2 or 3");
-  return sac_grads_impl(d, phase_mask, stream);
-}
-
-extern "C" int mbpo_sac_grad_norms(const mbpo_sac_desc *d, void *stream) {
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  hipLaunchKernelGGL(k_sac_sumsq, dim3(pl.n_red), dim3(256), 0, (hipStream_t)stream, (const float *)d->grads, pl.P, 2 * pl.Q,
-                     d->workspace + pl.off_ss);
-  MBPO_CHECK_LAUNCH("sac_grad_norms");
-  return MBPO_OK;
-}
-
-extern "C" int mbpo_sac_apply(const mbpo_sac_desc *d, void *stream) {
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  SacOptArgs A;
-  sac_fill_opt(d, pl, &A);
-  hipLaunchKernelGGL(k_sac_apply, dim3(pl.n_red), dim3(256), 0, (hipStream_t)stream, A);
-  MBPO_CHECK_LAUNCH("sac_apply");
-  return MBPO_OK;
+  return sac_update(d, true, SacReduceKind::EXCHANGE, stream, x);
 }
 
 // One sgd_step in TWO launches: k_sac_fwd_bwd, then k_sac_reduce_apply (slab reduction + [peer exchange +] unclipped optimizer
 // step + undo log).  The clip check is resolved by the next mbpo_sac_step / mbpo_sac_grads launch or by mbpo_sac_finalize.
-extern "C" int mbpo_sac_step(const mbpo_sac_desc *d, void *stream) { return sac_grads_impl(d, 3, stream, nullptr, false, true); }
+extern "C" int mbpo_sac_step(const mbpo_sac_desc *d, void *stream) { return sac_update(d, true, SacReduceKind::APPLY, stream); }
 
 extern "C" int mbpo_sac_step_p2p(const mbpo_sac_desc *d, const mbpo_p2p_desc *x, void *stream) {
   MBPO_REQUIRE(x, MBPO_ERR_ARG, "sac_step_p2p: null exchange descriptor");
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  // every workgroup of the reduction waits inside the kernel for the peers' same kernel: they must all be resident at once
-  MBPO_REQUIRE(pl.n_red <= 1024, MBPO_ERR_UNSUPPORTED, "sac_step_p2p: %d workgroups cannot be assumed co-resident; use "
-               "mbpo_sac_grads_p2p + mbpo_sac_gather_p2p + mbpo_sac_apply", pl.n_red);
-  return sac_grads_impl(d, 3, stream, x, true, true);
+  return sac_update(d, true, SacReduceKind::APPLY_EXCHANGE, stream, x);
+}
+
+extern "C" int mbpo_sac_gather_p2p(const mbpo_sac_desc *d, const mbpo_p2p_desc *x, void *stream) {
+  return sac_opt_entry(d, "sac_gather_p2p", [&](const SacPlan &pl) -> int {
+    P2pDev X;
+    const int rc = mbpo_p2p_make_dev(x, &X);
+    if (rc != MBPO_OK) return rc;
+    MBPO_REQUIRE(x->n_max >= pl.NP, MBPO_ERR_ARG, "sac_gather_p2p: exchange regions too small");
+    sac_gather_launch(pl.n_red, (hipStream_t)stream, X, d->grads, pl.P, 2 * pl.Q, d->workspace + pl.off_ss);
+    return MBPO_OK;
+  });
+}
+
+extern "C" int mbpo_sac_grad_norms(const mbpo_sac_desc *d, void *stream) {
+  return sac_opt_entry(d, "sac_grad_norms", [&](const SacPlan &pl) -> int {
+    sac_sumsq_launch(pl.n_red, (hipStream_t)stream, d->grads, pl.P, 2 * pl.Q, d->workspace + pl.off_ss);
+    return MBPO_OK;
+  });
+}
+
+extern "C" int mbpo_sac_apply(const mbpo_sac_desc *d, void *stream) {
+  return sac_opt_entry(d, "sac_apply", [&](const SacPlan &pl) -> int {
+    sac_apply_launch(pl.n_red, (hipStream_t)stream, sac_opt(d, pl));
+    return MBPO_OK;
+  });
 }
 
 extern "C" int mbpo_sac_finalize(const mbpo_sac_desc *d, void *stream) {
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  SacOptArgs A;
-  sac_fill_opt(d, pl, &A);
-  hipLaunchKernelGGL(k_sac_finalize, dim3(1), dim3(1024), 0, (hipStream_t)stream, A, (unsigned long long *)nullptr, 0ull);
-  MBPO_CHECK_LAUNCH("sac_finalize");
-  return MBPO_OK;
+  return sac_opt_entry(d, "sac_finalize", [&](const SacPlan &pl) -> int {
+    sac_finalize_launch((hipStream_t)stream, sac_opt(d, pl), nullptr, 0ull);
+    return MBPO_OK;
+  });
 }
 
 extern "C" int mbpo_sac_finalize_advance(const mbpo_sac_desc *d, uint64_t *rng_dev, uint64_t inc, void *stream) {
   MBPO_REQUIRE(rng_dev, MBPO_ERR_ARG, "sac_finalize_advance: null rng_dev");
-  SacPlan pl;
-  int rc = sac_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  SacOptArgs A;
-  sac_fill_opt(d, pl, &A);
-  hipLaunchKernelGGL(k_sac_finalize, dim3(1), dim3(1024), 0, (hipStream_t)stream, A, (unsigned long long *)rng_dev, (unsigned long long)inc);
-  MBPO_CHECK_LAUNCH("sac_finalize_advance");
-  return MBPO_OK;
+  return sac_opt_entry(d, "sac_finalize_advance", [&](const SacPlan &pl) -> int {
+    sac_finalize_launch((hipStream_t)stream, sac_opt(d, pl), (unsigned long long *)rng_dev, (unsigned long long)inc);
+    return MBPO_OK;
+  });
 }

@@ -22,12 +22,6 @@ __device__ __forceinline__ LSample l_sample(float loc, float raw, float eps) {
   o.lp = -0.5f * eps * eps - fm_log(o.sigma) - L_LOG_SQRT_2PI - ldj;
   return o;
 }
-__device__ __forceinline__ float l_floor_divide(float x1, float x2) {
-  const float mod = fmodf(x1, x2);
-  float div = (x1 - mod) / x2;
-  if (mod != 0.0f && ((x2 < 0.0f) != (mod < 0.0f))) div -= 1.0f;
-  return roundf(div);
-}
 
 struct PrepArgs {
   const float *batch, *mean, *std;
@@ -124,7 +118,7 @@ __global__ void __launch_bounds__(1024) k_sacl_losses(LossArgs A) {
     if (A.neq) {                                                                          // :90-96
       const float pseudo = row[X + U - 1];
       float tfa = (A.neq_tu - A.neq_tl) / 2.0f * pseudo + (A.neq_tu + A.neq_tl) / 2.0f;
-      tfa = l_floor_divide(tfa, A.neq_dt) * A.neq_dt;
+      tfa = floor_divide_f(tfa, A.neq_dt) * A.neq_dt;
       gamma = expf(-A.neq_cd * tfa);
     }
     const float target = row[X + U] * A.reward_scaling + row[X + U + 1] * gamma * next_v;   // :101-103
