@@ -3,7 +3,10 @@
 //   k_ppo_values    V(obs) on all B*T samples + the bootstrap V(next_obs[:, T-1]); also splits the row columns the
 //                   GAE scan needs (truncation, termination, scaled reward) into [B,T] arrays.            [fp32 MFMA]
 //   mbpo_gae_scan   vs, advantages (scan.hip; batch-major, wavefront-shuffle scan)                         [HBM]
-//   k_moments_*     mean / population std of the advantages over the whole minibatch (two passes)         [HBM]
+//   k_ppo_values_gae  both of the above and the moments' first stage in one launch, where a workgroup's LDS holds whole trajectories:
+//                   values, GAE and {n, mean, M2} partials of the advantages, which k_ppo_moments_combine merges.  [fp32 MFMA]
+//   k_moments_*     mean / population std of the advantages over the whole minibatch after the separate launches: k_moments_fused
+//                   (one workgroup, up to PPO_MOM_FUSED_MAX elements), else k_moments_partial / k_moments_final, two passes.  [HBM]
 //   k_ppo_fwd_bwd   policy and value forward + hand-written backward of the clipped-surrogate / value / entropy losses;
 //                   a workgroup walks many 16-sample tiles and ACCUMULATES its weight gradients into its own slab
 //                   (8 waves: policy and value chains, 2 waves each; backward: dgrad + wgrad chains side by side).  [fp32 MFMA]
@@ -100,7 +103,7 @@ __global__ void __launch_bounds__(256) k_ppo_values(PpoArgs A) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ moments (two passes)
+// ------------------------------------------------------------------------------------------------ wave sum (moments, norms)
 __device__ __forceinline__ float ppo_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -658,41 +661,130 @@ __global__ void __launch_bounds__(256) k_ppo_clip_apply(PpoClipArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
+// validate + geometry (ppo_plan) -> kernels for the shape (ppo_variant) -> one fill function per argument block -> one launch function
+// per stage -> ppo_update.
+
+// The dynamic LDS of the tile kernels: float offsets of their regions in carve order, `end` = the layout's size in floats.  The host's
+// one statement of the layouts (ppo_plan's byte counts, the LDS sizes of both values + GAE launches); the carves at the top of
+// k_ppo_values, k_ppo_values_gae (ppo_lean.hip: k_ppo_vg_lean) and k_ppo_fwd_bwd keep their own expressions and must agree with this.
+struct PpoLds {
+  struct { long long x, pp, y, end; } values;                                    // k_ppo_values
+  // k_ppo_values_gae: NC per-chain blocks of `chain` floats (the values layout), then the [G][.] arrays: val .. end count from there
+  struct { long long chain, val, tr, te, rw, adv, dc, end; } vg;
+  struct { long long row, x, store, pp, y, dy, scal, eps, lpt, ent, end; } fb;   // k_ppo_fwd_bwd
+};
+static inline PpoLds ppo_lds(int row_len, int U, int ld_x, int ld_h, int ld_y, int LH, long long G, int T, bool neq) {
+  const long long TT = 16LL * ld_h, U4 = (16LL * U + 3) & ~3LL;      // one hidden tile; one [16][U] array
+  const long long GR4 = (G * (T + 1) + 3) & ~3LL, GT4 = (G * T + 3) & ~3LL;
+  PpoLds L;
+  auto &v = L.values;      // [16][ld_x] normalised obs | 2 hidden tiles | [16][ld_y]
+  v.x = 0; v.pp = v.x + 16LL * ld_x; v.y = v.pp + 2 * TT; v.end = v.y + 16LL * ld_y;
+  auto &g = L.vg;          // [G][T + 1] values (the last of each row: the bootstrap) | [G][T] truncation | termination | scaled reward |
+                           // advantages | per-sample discount (neq only)
+  g.chain = v.end; g.val = 0; g.tr = g.val + GR4; g.te = g.tr + GT4; g.rw = g.te + GT4; g.adv = g.rw + GT4; g.dc = g.adv + GT4;
+  g.end = g.dc + (neq ? GT4 : 0);
+  auto &f = L.fb;          // [16][D] flat copy of the tile's rows | [16][ld_x] normalised obs | 4*LH tiles: policy z,h, value z,h | 4 tiles:
+                           // delta ping-pong | [2][16][ld_y] logits, value | [2][16][ld_y] their gradients | [4][16] | three [16][U] arrays
+  f.row = 0; f.x = f.row + 16LL * up4(row_len); f.store = f.x + 16LL * ld_x; f.pp = f.store + 4LL * LH * TT; f.y = f.pp + 4 * TT;
+  f.dy = f.y + 2 * 16LL * ld_y; f.scal = f.dy + 2 * 16LL * ld_y; f.eps = f.scal + 64; f.lpt = f.eps + U4; f.ent = f.lpt + U4; f.end = f.ent + U4;
+  return L;
+}
+
+// Which kernels one update launches (ppo_variant): everything that is a choice rather than geometry.
+enum PpoLayeredBy { PPO_FUSED = 0, PPO_LAYERED_KNOB, PPO_LAYERED_WIDTHS, PPO_LAYERED_LDS };
+enum class PpoValues { LAYERED, VG_LEAN, VG, SEPARATE };
+enum class PpoMoments { NONE, COMBINE, FUSED, TWO_PASS };
+struct PpoVariant {
+  // hidden layers outside the fused kernels' range (one width in {64,128} for both networks), MBPO_PPO_LAYERED=1, or more stored
+  // activations than a tile's LDS holds: values pre-pass and loss forward/backward run layer by layer (ppo_layered.hip) and leave ONE
+  // slab; GAE scan, moments, reduction, metrics and AdamW are shared
+  PpoLayeredBy layered;
+  bool lean;                 // the benchmark networks (64 x 3 or 64 x 2, swish, u = 1): k_ppo_lean (ppo_lean.hip), one workgroup and ONE slab per CU
+  bool vg_lean;              // k_ppo_vg_lean instead of k_ppo_values_gae: the value network alone decides (64 x 2 or 64 x 3)
+  bool sp2;                  // H == 64, one-tile network ends, more tiles than CUs: the two-workgroups-per-CU launch (k_ppo_fwd_bwd<64, 2>)
+  bool wide;                 // k_ppo_fwd_bwd<64, 4, true>: a network end wider than one tile (chain_run.hpp fast_shape)
+  int H;                     // the tile kernels' hidden width (64 or 128 unless layered)
+  PpoValues values;          // stages 1-3: layered | values + GAE + moment partials in one launch (lean or generic) | three separate stages
+  PpoMoments moments;        // COMBINE after a values + GAE launch; else one workgroup up to PPO_MOM_FUSED_MAX elements, two passes above
+  bool reduce_two_stage;     // 64 slabs or more: k_ppo_reduce_groups first
+  int n_slabs;               // one gradient slab per resident workgroup of the forward/backward launch
+  int vg_G, n_vg, NC;        // values + GAE: trajectories per workgroup, workgroups (0 = not that launch), value chains (<= 4 tiles at a time)
+  int vgrid;                 // k_ppo_values' grid
+};
+
 struct PpoPlan {
   MlpDev pi, v;
-  int P, V, NPV, H, LH, n_slabs;
-  int sp2;            // H == 64, one-tile network ends, more tiles than CUs: the two-workgroups-per-CU launch (k_ppo_fwd_bwd<64, 2>)
-  long long M;
+  NetShape sh_pi, sh_v;
+  int P, V, NPV, LH;
+  int Hp, Hv;                // the common hidden width of each network (-1: none)
+  long long M, tiles;
   int ld_x, ld_h, ld_y;
-  size_t lds_values, lds_fb;
-  long long off_baseline, off_boot, off_trunc, off_term, off_rew, off_vs, off_adv, off_mom, off_part, off_slabs, off_extras, off_layered, total;
-  // values + GAE + moment partials in one launch (k_ppo_values_gae): vg_G trajectories per workgroup, n_vg workgroups; 0 = the three
-  // separate launches (layered shapes; trajectories too long for a workgroup's LDS arrays; MBPO_PPO_VALUES_GAE=0)
-  int vg_G, n_vg;
-  bool vg_lean;              // k_ppo_vg_lean instead of k_ppo_values_gae
-  size_t lds_vg;
-  long long off_mompart;
-  // hidden layers outside the fused kernels' range (one width in {64,128}): values pre-pass and loss forward/backward run layer by
-  // layer (ppo_layered.hip) and leave ONE slab; GAE scan, moments, reduction, metrics and AdamW are shared
-  bool layered;
-  // the benchmark networks (64 x 3, swish, u = 1): k_ppo_lean (ppo_lean.hip) — one workgroup and ONE slab per CU
-  bool lean;
   // ppo_brax_env.py's options: neq -> per-sample discount (off_disc: [M], the separate-scan and layered paths); clip -> n_ss sum-of-
   // squares partials at off_sspart (one per 64 gradient elements, k_ppo_reduce<true>'s grid).  Neither takes workspace when off.
   bool neq, clip;
   int n_ss;
-  long long off_disc, off_sspart;
+  int vg_fit;                // trajectories per workgroup of a values + GAE launch; 0 = too long for a workgroup's LDS arrays
+  PpoLds lds;
+  size_t lds_values, lds_fb;
+  PpoVariant var;            // (the workspace holds n_slabs slabs and n_vg moment partials: the carve follows the choice)
+  long long off_baseline, off_boot, off_trunc, off_term, off_rew, off_vs, off_adv, off_mom, off_part, off_slabs, off_extras, off_mompart,
+      off_disc, off_sspart, off_layered, total;
 };
 
-// Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_ppo_fwd_bwd, 1 = k_ppo_lean where it applies,
-// -1 = the MBPO_PPO_LEAN environment default (on).
-static unsigned long long *g_ppo_stamps = nullptr;
 // measurement hook: device buffer of >= 64 uint64 that k_ppo_lean fills with s_memtime stamps (workgroup 0, 12 per tile); NULL = off
+static unsigned long long *g_ppo_stamps = nullptr;
 extern "C" int mbpo_debug_set_ppo_stamps(void *buf) {
   g_ppo_stamps = (unsigned long long *)buf;
   return MBPO_OK;
 }
+// Measurement / test hook (not part of include/mbpo_hip.h): 0 = always the generic k_ppo_fwd_bwd, 1 = k_ppo_lean where it applies,
+// -1 = the MBPO_PPO_LEAN environment default (on).
 extern "C" int mbpo_debug_set_ppo_lean(int mode) { return mbpo_knob_set_override(KNOB_PPO_LEAN, mode); }
+
+// The one place where a shape is mapped to kernels.  The knobs in this order: layered, sp2, lean, values + GAE.
+//   values    LAYERED   ppo_layered_values                       fwd/bwd  layered      ppo_layered_fwd_bwd
+//             VG_LEAN   k_ppo_vg_lean                                     lean         k_ppo_lean
+//             VG        k_ppo_values_gae<H, NC, neq>                      H = 64       k_ppo_fwd_bwd<64, 4, wide> | <64, 2, false> (sp2)
+//             SEPARATE  k_ppo_values<H, neq>, then the GAE scan           H = 128      k_ppo_fwd_bwd<128, 2, false>
+//   moments   COMBINE   k_ppo_moments_combine                    reduce   [k_ppo_reduce_groups,] k_ppo_reduce<false>, or with a
+//             FUSED     k_moments_fused                                   clipped fused step k_ppo_reduce<true> + k_ppo_clip_apply
+//             TWO_PASS  k_moments_partial / k_moments_final x 2
+static PpoVariant ppo_variant(const mbpo_ppo_desc *d, const PpoPlan &pl) {
+  const int cus = mbpo_num_cus();
+  PpoVariant v;
+  v.H = pl.Hp;
+  // decided once, before anything depends on it
+  v.layered = mbpo_knob(KNOB_PPO_LAYERED) != 0 ? PPO_LAYERED_KNOB
+              : !(pl.Hp == pl.Hv && (pl.Hp == 64 || pl.Hp == 128)) ? PPO_LAYERED_WIDTHS
+              : (pl.lds_fb > 160 * 1024 || pl.lds_values > 160 * 1024) ? PPO_LAYERED_LDS : PPO_FUSED;
+  const bool fused = !v.layered;
+  const bool wide_ends = net_is_wide(pl.sh_pi) || net_is_wide(pl.sh_v);
+  const bool want_sp2 = fused && pl.Hp == 64 && !wide_ends && pl.tiles > cus && mbpo_knob(KNOB_PPO_SP2) != 0;
+  const bool want_lean = mbpo_knob(KNOB_PPO_LEAN) != 0;
+  v.lean = want_lean && fused &&
+           ppo_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->value_dims, d->value_layers,
+                             d->value_activation);
+  v.vg_lean = want_lean && fused && d->u_dim == 1 &&      // (the kernel's row offsets assume u = 1)
+              ppo_vg_lean_supports(d->x_dim, d->value_dims, d->value_layers, d->value_activation);
+  v.sp2 = want_sp2 && !v.lean;
+  v.wide = fused && !v.lean && pl.Hp == 64 && wide_ends;
+  // one gradient slab per RESIDENT workgroup: a 1024-thread (or 512 x 256-VGPR) workgroup fills a CU's registers, so more of them
+  // per CU only waited their turn while k_ppo_reduce summed twice the slabs (512 x 17 k floats = 35 MB per minibatch at C3's
+  // T = 40: 22 us of a 158 us minibatch_step, rocprofv3 round 3).  The 512-thread / 128-VGPR launch (sp2) holds two per CU.
+  const long long cap = (v.sp2 ? 2LL : 1LL) * cus;
+  v.n_slabs = fused ? (int)(pl.tiles < cap ? pl.tiles : cap) : 1;
+  v.reduce_two_stage = v.n_slabs >= 64;
+  v.vg_G = (fused && mbpo_knob(KNOB_PPO_VALUES_GAE) != 0) ? pl.vg_fit : 0;
+  v.n_vg = v.vg_G ? (d->batch_size + v.vg_G - 1) / v.vg_G : 0;
+  const long long tiles_wg = ((long long)v.vg_G * (d->unroll_length + 1) + 15) / 16;
+  v.NC = (int)(tiles_wg >= 4 ? 4 : tiles_wg);
+  v.values = v.layered ? PpoValues::LAYERED : !v.vg_G ? PpoValues::SEPARATE : v.vg_lean ? PpoValues::VG_LEAN : PpoValues::VG;
+  const long long vt = (pl.M + d->batch_size + 15) / 16;
+  v.vgrid = (int)(vt < 4LL * cus ? vt : 4LL * cus);
+  v.moments = !d->normalize_advantage ? PpoMoments::NONE : v.vg_G ? PpoMoments::COMBINE
+              : pl.M <= PPO_MOM_FUSED_MAX ? PpoMoments::FUSED : PpoMoments::TWO_PASS;
+  return v;
+}
 
 static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(d, MBPO_ERR_ARG, "ppo: null descriptor");
@@ -706,8 +798,6 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   MBPO_REQUIRE(!d->non_equidistant_time || d->env_dt > 0.f, MBPO_ERR_ARG, "ppo: non_equidistant_time needs env_dt > 0");
   pl->neq = d->non_equidistant_time != 0;
   pl->clip = d->max_grad_norm > 0.f;
-  const int Hp = same_hidden(d->policy_dims, d->policy_layers), Hv = same_hidden(d->value_dims, d->value_layers);
-  pl->layered = mbpo_knob(KNOB_PPO_LAYERED) != 0 || !(Hp == Hv && (Hp == 64 || Hp == 128));
   int rc = mbpo_make_mlp_dev_from(d->policy_dims, d->policy_layers, d->policy_activation, d->params, 1, "ppo.policy", &pl->pi);
   if (rc != MBPO_OK) return rc;
   pl->P = pl->pi.n_params;
@@ -716,47 +806,17 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
   pl->V = pl->v.n_params;
   pl->v.params = d->params ? d->params + pl->P : nullptr;
   pl->NPV = pl->P + pl->V;
-  pl->H = Hp;
+  pl->sh_pi = net_shape(pl->pi);
+  pl->sh_v = net_shape(pl->v);
+  pl->Hp = same_hidden(d->policy_dims, d->policy_layers);
+  pl->Hv = same_hidden(d->value_dims, d->value_layers);
   const int lhp = d->policy_layers - 1, lhv = d->value_layers - 1;
   pl->LH = lhp > lhv ? lhp : lhv;
   pl->M = (long long)d->batch_size * d->unroll_length;
+  pl->tiles = (pl->M + 15) / 16;
   pl->ld_x = up4(d->x_dim) + 4;
-  pl->ld_h = Hp + 4;
+  pl->ld_h = pl->Hp + 4;
   pl->ld_y = up4(2 * d->u_dim) + 4;
-  pl->lds_values = sizeof(float) * (16ull * pl->ld_x + 2ull * 16 * pl->ld_h + 16ull * pl->ld_y);
-  pl->lds_fb = sizeof(float) * (16ull * up4(d->row_len) + 16ull * pl->ld_x + (size_t)pl->LH * 4 * 16 * pl->ld_h + 4ull * 16 * pl->ld_h +
-                                4ull * 16 * pl->ld_y + 64 + 3ull * ((16 * d->u_dim + 3) & ~3));
-  long long tiles = (pl->M + 15) / 16;
-  // one gradient slab per RESIDENT workgroup: a 1024-thread (or 512 x 256-VGPR) workgroup fills a CU's registers, so more of them
-  // per CU only waited their turn while k_ppo_reduce summed twice the slabs (512 x 17 k floats = 35 MB per minibatch at C3's
-  // T = 40: 22 us of a 158 us minibatch_step, rocprofv3 round 3).  The 512-thread / 128-VGPR launch (sp2) holds two per CU.
-  {
-    const NetShape sp_ = NetShape{d->x_dim, d->policy_layers, 2 * d->u_dim, 0}, sv_ = NetShape{d->x_dim, d->value_layers, 1, 0};
-    pl->sp2 = (Hp == 64 && !net_is_wide(sp_) && !net_is_wide(sv_) && tiles > mbpo_num_cus() && mbpo_knob(KNOB_PPO_SP2) != 0) ? 1 : 0;
-  }
-  long long cap = (pl->sp2 ? 2LL : 1LL) * mbpo_num_cus();
-  {
-    const bool want_lean = mbpo_knob(KNOB_PPO_LEAN) != 0;
-    pl->lean = want_lean && !pl->layered &&
-               ppo_lean_supports(d->x_dim, d->u_dim, d->policy_dims, d->policy_layers, d->policy_activation, d->value_dims, d->value_layers,
-                                 d->value_activation);
-    if (pl->lean) cap = mbpo_num_cus();
-    // the values + GAE launch has its own specialised form: the value network alone decides (64 x 2 or 64 x 3)
-    pl->vg_lean = want_lean && !pl->layered && d->u_dim == 1 &&      // (the kernel's row offsets assume u = 1)
-                  ppo_vg_lean_supports(d->x_dim, d->value_dims, d->value_layers, d->value_activation);
-  }
-  pl->n_slabs = (int)(tiles < cap ? tiles : cap);
-  if (!pl->layered && (pl->lds_fb > 160 * 1024 || pl->lds_values > 160 * 1024)) pl->layered = true;     // more stored activations than a tile's LDS holds
-  if (pl->layered) {
-    pl->sp2 = 0;
-    pl->n_slabs = 1;
-    pl->lean = false;
-    pl->vg_lean = false;
-  }
-  Carve c;
-  pl->off_baseline = c.take(pl->M); pl->off_boot = c.take(d->batch_size); pl->off_trunc = c.take(pl->M); pl->off_term = c.take(pl->M);
-  pl->off_rew = c.take(pl->M); pl->off_vs = c.take(pl->M); pl->off_adv = c.take(pl->M); pl->off_mom = c.take(4); pl->off_part = c.take(PPO_MOM_WGS);
-  pl->off_slabs = c.take((long long)pl->n_slabs * pl->NPV); pl->off_extras = c.take((long long)pl->n_slabs * 4);
   {
     // G = 1 while that does not oversubscribe the chip (a tile with a few rows of one trajectory wastes MFMA lanes nobody else wants:
     // the launch is a latency chain per workgroup); beyond 4 workgroups per CU, more trajectories per workgroup
@@ -765,21 +825,25 @@ static int ppo_plan(const mbpo_ppo_desc *d, PpoPlan *pl, bool need_ptrs) {
     const long long cap_wg = 4LL * mbpo_num_cus() < 1024 ? 4LL * mbpo_num_cus() : 1024;
     long long G = (d->batch_size + cap_wg - 1) / cap_wg;
     if (G < 1) G = 1;
-    const long long R = (long long)d->unroll_length + 1;
-    // the [G][R] / [G][T] LDS arrays: values, truncation, termination, reward, advantages (+ the per-sample discount with neq), each
+    // the [G][T + 1] / [G][T] LDS arrays: values, truncation, termination, reward, advantages (+ the per-sample discount with neq), each
     // at most 1024 floats' worth of the constant-discount launch's five
-    const int n_arr = pl->neq ? 6 : 5;
-    pl->vg_G = (!pl->layered && mbpo_knob(KNOB_PPO_VALUES_GAE) != 0 && n_arr * G * R <= 5 * 1024) ? (int)G : 0;
-    pl->n_vg = pl->vg_G ? (int)((d->batch_size + pl->vg_G - 1) / pl->vg_G) : 0;
-    const long long GT = (long long)pl->vg_G * d->unroll_length;
-    pl->lds_vg = pl->lds_values + sizeof(float) * (size_t)(((pl->vg_G * R + 3) & ~3LL) + (n_arr - 1) * ((GT + 3) & ~3LL));
-    pl->off_mompart = c.take(4LL * (pl->n_vg > 0 ? pl->n_vg : 1));
+    pl->vg_fit = (pl->neq ? 6 : 5) * G * (d->unroll_length + 1LL) <= 5 * 1024 ? (int)G : 0;
   }
+  pl->lds = ppo_lds(d->row_len, d->u_dim, pl->ld_x, pl->ld_h, pl->ld_y, pl->LH, pl->vg_fit, d->unroll_length, pl->neq);
+  pl->lds_values = sizeof(float) * (size_t)pl->lds.values.end;
+  pl->lds_fb = sizeof(float) * (size_t)pl->lds.fb.end;
+  pl->var = ppo_variant(d, *pl);
+  const PpoVariant &v = pl->var;
+  Carve c;
+  pl->off_baseline = c.take(pl->M); pl->off_boot = c.take(d->batch_size); pl->off_trunc = c.take(pl->M); pl->off_term = c.take(pl->M);
+  pl->off_rew = c.take(pl->M); pl->off_vs = c.take(pl->M); pl->off_adv = c.take(pl->M); pl->off_mom = c.take(4); pl->off_part = c.take(PPO_MOM_WGS);
+  pl->off_slabs = c.take((long long)v.n_slabs * pl->NPV); pl->off_extras = c.take((long long)v.n_slabs * 4);
+  pl->off_mompart = c.take(4LL * (v.n_vg > 0 ? v.n_vg : 1));
   pl->off_disc = c.take(pl->neq ? pl->M : 0);
   pl->n_ss = (pl->NPV + 63) / 64;
   pl->off_sspart = c.take(pl->clip ? pl->n_ss : 0);
   pl->off_layered = c.off;
-  if (pl->layered) c.off += ppo_layered_floats(d, pl->pi, pl->v);
+  if (v.layered) c.off += ppo_layered_floats(d, pl->pi, pl->v);
   pl->total = c.off;
   if (need_ptrs)
     MBPO_REQUIRE(d->params && d->adam_m && d->adam_v && d->step_count && d->grads && d->workspace && d->metrics, MBPO_ERR_ARG,
@@ -794,162 +858,179 @@ extern "C" int64_t mbpo_ppo_workspace_floats(const mbpo_ppo_desc *d) {
   return pl.total;
 }
 
+// ---- one fill function per argument block
+static void ppo_fill_args(const mbpo_ppo_desc *d, const PpoPlan &pl, PpoArgs *A) {
+  float *ws = d->workspace;
+  A->pi = pl.pi; A->v = pl.v;
+  A->sh_pi = pl.sh_pi; A->sh_v = pl.sh_v;
+  A->X = d->x_dim; A->U = d->u_dim; A->B = d->batch_size; A->T = d->unroll_length; A->D = d->row_len;
+  A->data = d->data; A->norm_mean = d->norm_mean; A->norm_std = d->norm_std; A->ent_noise = d->entropy_noise;
+  A->step_count_rw = d->step_count;
+  A->mom_inline = 0;
+  A->mom_part = ws + pl.off_mompart; A->mom_parts = pl.var.n_vg; A->vg_G = pl.var.vg_G;
+  A->seed = d->seed; A->offset = d->offset; A->rng_dev = (const unsigned long long *)d->rng_dev;
+  A->entropy_cost = d->entropy_cost; A->discounting = d->discounting; A->reward_scaling = d->reward_scaling;
+  A->gae_lambda = d->gae_lambda; A->clip_eps = d->clipping_epsilon; A->normalize_advantage = d->normalize_advantage;
+  A->baseline = ws + pl.off_baseline; A->boot = ws + pl.off_boot; A->trunc = ws + pl.off_trunc; A->term = ws + pl.off_term;
+  A->rew = ws + pl.off_rew; A->vs = ws + pl.off_vs; A->adv = ws + pl.off_adv; A->mom = ws + pl.off_mom;
+  A->slabs = ws + pl.off_slabs; A->extras = ws + pl.off_extras; A->n_slabs = pl.var.n_slabs;
+  A->ld_x = pl.ld_x; A->ld_h = pl.ld_h; A->ld_y = pl.ld_y; A->LH = pl.LH;
+  A->disc = pl.neq ? ws + pl.off_disc : nullptr;
+  A->neq_cd = d->continuous_discounting; A->neq_tl = d->min_time_between_switches; A->neq_tu = d->max_time_between_switches;
+  A->neq_dt = d->env_dt;
+}
+
+// k_ppo_vg_lean on the value network's resident images (ppo_lean.hip): the same bits as k_ppo_values_gae
+static void ppo_fill_vg_lean(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, PpoVgLeanArgs *V) {
+  V->v_params = d->params + pl.pi.n_params; V->data = d->data; V->norm_mean = d->norm_mean; V->norm_std = d->norm_std;
+  V->B = d->batch_size; V->T = d->unroll_length; V->D = A.D; V->G = pl.var.vg_G; V->n_hid = d->value_layers - 2;
+  V->reward_scaling = d->reward_scaling; V->discounting = d->discounting; V->gae_lambda = d->gae_lambda;
+  V->vs = A.vs; V->adv = A.adv; V->mom_part = A.mom_part; V->step_count_rw = A.step_count_rw;
+  V->neq = pl.neq ? 1 : 0; V->neq_cd = A.neq_cd; V->neq_tl = A.neq_tl; V->neq_tu = A.neq_tu; V->neq_dt = A.neq_dt;
+}
+
+static void ppo_fill_lean(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, PpoLeanArgs *L) {
+  L->params = d->params; L->data = d->data; L->norm_mean = d->norm_mean; L->norm_std = d->norm_std;
+  L->adv = A.adv; L->vs = A.vs; L->mom = A.mom; L->ent_noise = d->entropy_noise;
+  L->rng_dev = A.rng_dev; L->seed = A.seed; L->offset = A.offset;
+  L->slabs = A.slabs; L->extras = A.extras; L->M = pl.M;
+  L->entropy_cost = d->entropy_cost; L->clip_eps = d->clipping_epsilon; L->normalize_advantage = d->normalize_advantage;
+  L->stamps = g_ppo_stamps;
+}
+
+// the optimizer's operands, the same fields in PpoReduceArgs, PpoApplyArgs and PpoClipArgs
+template <class OptArgs>
+static void ppo_fill_opt(const mbpo_ppo_desc *d, OptArgs *O) {
+  O->params = d->params; O->adam_m = d->adam_m; O->adam_v = d->adam_v; O->grads = d->grads; O->step_count = d->step_count;
+  O->lr = d->lr; O->wd = d->wd; O->grad_scale = d->grad_scale;
+}
+
+// fuse_apply: the reduce launch also applies AdamW (params != nullptr); the loss partials are one set per slab (the layered path
+// names its own in ppo_fwd_bwd_launch)
+static void ppo_fill_reduce(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, bool fuse_apply, PpoReduceArgs *R) {
+  ppo_fill_opt(d, R);
+  if (!fuse_apply) R->params = nullptr;
+  R->slabs = A.slabs; R->extras = A.extras; R->n_slabs = pl.var.n_slabs; R->n_extras = pl.var.n_slabs;
+  R->slab_step = pl.var.reduce_two_stage ? 16 : 1;
+  R->NPV = pl.NPV; R->M = pl.M; R->entropy_cost = d->entropy_cost;
+  R->metrics = d->metrics; R->metrics_accum = d->metrics_accum;
+  R->ss_part = d->workspace + pl.off_sspart;
+}
+
+// ---- one launch function per stage, each a switch over the variant
+// A runtime int selects a template int among V, Vs... (the last one where none matches): f is called with std::integral_constant<int, .>{}.
+template <int V, int... Vs, class F>
+static int ppo_with_int(int v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+  else return v == V ? f(std::integral_constant<int, V>{}) : ppo_with_int<Vs...>(v, f);
+}
+
+// 1. values pre-pass; with a values + GAE launch also 2 and the first half of 3
+static int ppo_values_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, PpoArgs *A, hipStream_t st) {
+  const PpoVariant &v = pl.var;
+  switch (v.values) {
+    case PpoValues::LAYERED: {
+      float *values = nullptr;
+      const int rc = ppo_layered_values(d, pl.pi, pl.v, d->workspace + pl.off_layered, A->trunc, A->term, A->rew, A->disc, &values, st);
+      if (rc != MBPO_OK) return rc;
+      A->baseline = values;
+      A->boot = values + pl.M;
+      return MBPO_OK;
+    }
+    case PpoValues::VG_LEAN: {
+      PpoVgLeanArgs V;
+      ppo_fill_vg_lean(d, pl, *A, &V);
+      return ppo_vg_lean_launch(V, d->x_dim, v.n_vg, (size_t)pl.lds.vg.end, st);
+    }
+    case PpoValues::VG: {
+      // NC = the workgroup's value chains (1..4), each with its own block of LDS
+      const size_t lds = sizeof(float) * (size_t)(v.NC * pl.lds.vg.chain + pl.lds.vg.end);
+      return ppo_with_int<64, 128>(v.H, [&](auto H) {
+        return ppo_with_int<1, 2, 3, 4>(v.NC, [&](auto NC) {
+          return mbpo_with_bool(pl.neq, [&](auto Q) {
+            constexpr int h = decltype(H)::value, nc = decltype(NC)::value;
+            return mbpo_launch<k_ppo_values_gae<h, nc, Q.value>>(v.n_vg, 256 * nc, lds, st, "ppo_grads", *A);
+          }); }); });
+    }
+    case PpoValues::SEPARATE:
+      return ppo_with_int<64, 128>(v.H, [&](auto H) {
+        return mbpo_with_bool(pl.neq, [&](auto Q) {
+          return mbpo_launch<k_ppo_values<decltype(H)::value, Q.value>>(v.vgrid, 256, pl.lds_values, st, "ppo_grads", *A);
+        }); });
+  }
+  return MBPO_OK;
+}
+
+// 2. GAE on [B,T] (batch-major: the data's native layout, no transpose)   losses.py:94-99,128-184 (losses_new.py:181-226 with neq)
+static int ppo_gae_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, hipStream_t st) {
+  if (pl.var.vg_G) return MBPO_OK;      // (done by the values + GAE launch)
+  if (pl.neq)
+    return mbpo_gae_scan_discounts(A.trunc, A.term, A.rew, A.baseline, A.boot, A.disc, A.vs, A.adv, d->batch_size, d->unroll_length,
+                                   d->gae_lambda, 0, st);
+  return mbpo_gae_scan(A.trunc, A.term, A.rew, A.baseline, A.boot, A.vs, A.adv, d->batch_size, d->unroll_length, d->discounting,
+                       d->gae_lambda, 0, st);
+}
+
+// 3. advantage moments over the whole minibatch
+static void ppo_moments_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, hipStream_t st) {
+  const float *adv = A.adv, *mom = A.mom;
+  switch (pl.var.moments) {
+    case PpoMoments::NONE: return;
+    case PpoMoments::COMBINE:
+      hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.var.n_vg, (float)pl.M, A.mom);
+      return;
+    case PpoMoments::FUSED: hipLaunchKernelGGL(k_moments_fused, dim3(1), dim3(1024), 0, st, adv, pl.M, A.mom); return;
+    case PpoMoments::TWO_PASS: {
+      float *part = d->workspace + pl.off_part;
+      const long long blocks = (pl.M + 255) / 256;
+      const int g = (int)(blocks < PPO_MOM_WGS ? blocks : PPO_MOM_WGS);
+      hipLaunchKernelGGL(k_moments_partial<0>, dim3(g), dim3(256), 0, st, adv, pl.M, mom, part);
+      hipLaunchKernelGGL(k_moments_final<0>, dim3(1), dim3(64), 0, st, (const float *)part, g, pl.M, A.mom);
+      hipLaunchKernelGGL(k_moments_partial<1>, dim3(g), dim3(256), 0, st, adv, pl.M, mom, part);
+      hipLaunchKernelGGL(k_moments_final<1>, dim3(1), dim3(64), 0, st, (const float *)part, g, pl.M, A.mom);
+      return;
+    }
+  }
+}
+
+// 4. loss forward/backward into the slabs (the layered path: ONE slab, and loss partials of its own for the reduce launch)
+static int ppo_fwd_bwd_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoArgs &A, PpoReduceArgs *R, hipStream_t st) {
+  const PpoVariant &v = pl.var;
+  if (v.layered) {
+    float *extras = nullptr;
+    const int rc = ppo_layered_fwd_bwd(d, pl.pi, pl.v, d->workspace + pl.off_layered, A.vs, A.adv, A.mom, A.slabs, &extras, &R->n_extras, st);
+    R->extras = extras;
+    return rc;
+  }
+  if (v.lean) {
+    PpoLeanArgs L;
+    ppo_fill_lean(d, pl, A, &L);
+    return ppo_lean_launch(L, d->x_dim, d->policy_layers - 2, v.n_slabs, st);
+  }
+  // (the instantiations are named in this order: it is their order in the device code object)
+  if (v.wide) return mbpo_launch<k_ppo_fwd_bwd<64, 4, true>>(v.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
+  if (v.H == 64 && !v.sp2) return mbpo_launch<k_ppo_fwd_bwd<64, 4, false>>(v.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
+  if (v.sp2) return mbpo_launch<k_ppo_fwd_bwd<64, 2, false>>(v.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);      // (never wide)
+  return mbpo_launch<k_ppo_fwd_bwd<128, 2, false>>(v.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);
+}
+
+// [3P optax.chain(clip_by_global_norm, adamw)] on the n_ss partials at off_sspart
 static void ppo_clip_apply_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, hipStream_t st) {
   PpoClipArgs C;
-  C.params = d->params; C.adam_m = d->adam_m; C.adam_v = d->adam_v; C.grads = d->grads; C.step_count = d->step_count;
-  C.ss_part = d->workspace + pl.off_sspart; C.NPV = pl.NPV; C.n_parts = pl.n_ss;
-  C.lr = d->lr; C.wd = d->wd; C.grad_scale = d->grad_scale; C.max_norm = d->max_grad_norm;
+  ppo_fill_opt(d, &C);
+  C.ss_part = d->workspace + pl.off_sspart; C.NPV = pl.NPV; C.n_parts = pl.n_ss; C.max_norm = d->max_grad_norm;
   // a few elements per thread: every workgroup re-adds all n_ss partials, so the grid is kept to at most 4 per CU
   const int want = (pl.NPV + 255) / 256, cap = 4 * mbpo_num_cus();
   hipLaunchKernelGGL(k_ppo_clip_apply, dim3(want < cap ? want : cap), dim3(256), 0, st, C);
 }
 
-// k_ppo_values_gae<H, NC, NEQ>: NC = the workgroup's value chains (1..4), NEQ = per-sample discounts
-template <int H, int NC>
-static int values_gae_launch(const PpoPlan &pl, size_t lds, hipStream_t st, const PpoArgs &A) {
-  return mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values_gae<H, NC, Q.value>>(pl.n_vg, 256 * NC, lds, st, "ppo_grads", A); });
-}
-template <int H>
-static int values_gae_launch(int NC, const PpoPlan &pl, size_t lds, hipStream_t st, const PpoArgs &A) {
-  if (NC == 1) return values_gae_launch<H, 1>(pl, lds, st, A);
-  if (NC == 2) return values_gae_launch<H, 2>(pl, lds, st, A);
-  if (NC == 3) return values_gae_launch<H, 3>(pl, lds, st, A);
-  return values_gae_launch<H, 4>(pl, lds, st, A);
-}
-
-static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply) {
-  PpoPlan pl;
-  int rc = ppo_plan(d, &pl, true);
-  if (rc != MBPO_OK) return rc;
-  MBPO_REQUIRE(d->data, MBPO_ERR_ARG, "ppo_grads: null data");
-  MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG, "ppo_grads: norm_mean/norm_std mismatch");
-  float *ws = d->workspace;
-  PpoArgs A;
-  A.pi = pl.pi; A.v = pl.v;
-  A.sh_pi = net_shape(pl.pi);
-  A.sh_v = net_shape(pl.v);
-  A.X = d->x_dim; A.U = d->u_dim; A.B = d->batch_size; A.T = d->unroll_length; A.D = d->row_len;
-  A.data = d->data; A.norm_mean = d->norm_mean; A.norm_std = d->norm_std; A.ent_noise = d->entropy_noise;
-  A.step_count_rw = d->step_count;
-  A.mom_inline = 0;
-  A.mom_part = ws + pl.off_mompart; A.mom_parts = pl.n_vg; A.vg_G = pl.vg_G;
-  A.seed = d->seed; A.offset = d->offset; A.rng_dev = (const unsigned long long *)d->rng_dev;
-  A.entropy_cost = d->entropy_cost; A.discounting = d->discounting; A.reward_scaling = d->reward_scaling;
-  A.gae_lambda = d->gae_lambda; A.clip_eps = d->clipping_epsilon; A.normalize_advantage = d->normalize_advantage;
-  A.baseline = ws + pl.off_baseline; A.boot = ws + pl.off_boot; A.trunc = ws + pl.off_trunc; A.term = ws + pl.off_term;
-  A.rew = ws + pl.off_rew; A.vs = ws + pl.off_vs; A.adv = ws + pl.off_adv; A.mom = ws + pl.off_mom;
-  A.slabs = ws + pl.off_slabs; A.extras = ws + pl.off_extras; A.n_slabs = pl.n_slabs;
-  A.ld_x = pl.ld_x; A.ld_h = pl.ld_h; A.ld_y = pl.ld_y; A.LH = pl.LH;
-  A.disc = pl.neq ? ws + pl.off_disc : nullptr;
-  A.neq_cd = d->continuous_discounting; A.neq_tl = d->min_time_between_switches; A.neq_tu = d->max_time_between_switches;
-  A.neq_dt = d->env_dt;
-  hipStream_t st = (hipStream_t)stream;
-  // 1. values pre-pass
-  long long vt = (pl.M + d->batch_size + 15) / 16;
-  int vgrid = (int)(vt < 4LL * mbpo_num_cus() ? vt : 4LL * mbpo_num_cus());
-  if (pl.layered) {
-    float *values = nullptr;
-    rc = ppo_layered_values(d, pl.pi, pl.v, ws + pl.off_layered, A.trunc, A.term, A.rew, A.disc, &values, st);
-    if (rc != MBPO_OK) return rc;
-    A.baseline = values;
-    A.boot = values + pl.M;
-  } else if (pl.vg_G && pl.vg_lean) {
-    // 1-3 in one launch on the value network's resident images (ppo_lean.hip k_ppo_vg_lean: the same bits as k_ppo_values_gae)
-    PpoVgLeanArgs V;
-    V.v_params = d->params + pl.pi.n_params; V.data = d->data; V.norm_mean = d->norm_mean; V.norm_std = d->norm_std;
-    V.B = d->batch_size; V.T = d->unroll_length; V.D = A.D; V.G = pl.vg_G; V.n_hid = d->value_layers - 2;
-    V.reward_scaling = d->reward_scaling; V.discounting = d->discounting; V.gae_lambda = d->gae_lambda;
-    V.vs = A.vs; V.adv = A.adv; V.mom_part = A.mom_part; V.step_count_rw = A.step_count_rw;
-    V.neq = pl.neq ? 1 : 0; V.neq_cd = A.neq_cd; V.neq_tl = A.neq_tl; V.neq_tu = A.neq_tu; V.neq_dt = A.neq_dt;
-    const long long GR = (long long)pl.vg_G * (d->unroll_length + 1), GT = (long long)pl.vg_G * d->unroll_length;
-    rc = ppo_vg_lean_launch(V, d->x_dim, pl.n_vg, (size_t)(((GR + 3) & ~3LL) + (pl.neq ? 5 : 4) * ((GT + 3) & ~3LL)), stream);
-    if (rc != MBPO_OK) return rc;
-    if (d->normalize_advantage)
-      hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.n_vg, (float)pl.M, A.mom);
-  } else if (pl.vg_G) {
-    // 1-3 in one launch: values, GAE, the moments' per-workgroup partials
-    const int tiles_wg = (int)(((long long)pl.vg_G * (d->unroll_length + 1) + 15) / 16);
-    const int NCv = tiles_wg >= 4 ? 4 : tiles_wg;
-    const size_t lds = pl.lds_vg + (size_t)(NCv - 1) * pl.lds_values;
-    rc = pl.H == 64 ? values_gae_launch<64>(NCv, pl, lds, st, A) : values_gae_launch<128>(NCv, pl, lds, st, A);
-    if (rc != MBPO_OK) return rc;
-    if (d->normalize_advantage)
-      hipLaunchKernelGGL(k_ppo_moments_combine, dim3(1), dim3(256), 0, st, (const float *)A.mom_part, pl.n_vg, (float)pl.M, A.mom);
-  } else {
-    if (pl.H == 64) {
-      rc = mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values<64, Q.value>>(vgrid, 256, pl.lds_values, st, "ppo_grads", A); });
-    } else {
-      rc = mbpo_with_bool(pl.neq, [&](auto Q) { return mbpo_launch<k_ppo_values<128, Q.value>>(vgrid, 256, pl.lds_values, st, "ppo_grads", A); });
-    }
-    if (rc != MBPO_OK) return rc;
-  }
-  // 2. GAE on [B,T] (batch-major: the data's native layout, no transpose)   losses.py:94-99,128-184 (losses_new.py:181-226 with neq)
-  if (!pl.vg_G) {
-    if (pl.neq)
-      rc = mbpo_gae_scan_discounts(A.trunc, A.term, A.rew, A.baseline, A.boot, A.disc, A.vs, A.adv, d->batch_size, d->unroll_length,
-                                   d->gae_lambda, 0, stream);
-    else
-      rc = mbpo_gae_scan(A.trunc, A.term, A.rew, A.baseline, A.boot, A.vs, A.adv, d->batch_size, d->unroll_length, d->discounting,
-                         d->gae_lambda, 0, stream);
-    if (rc != MBPO_OK) return rc;
-  }
-  // 3. advantage moments over the whole minibatch
-  if (d->normalize_advantage && !pl.vg_G) {
-    float *part = ws + pl.off_part;
-    long long blocks = (pl.M + 255) / 256;
-    int g = (int)(blocks < PPO_MOM_WGS ? blocks : PPO_MOM_WGS);
-    if (pl.M <= PPO_MOM_FUSED_MAX) hipLaunchKernelGGL(k_moments_fused, dim3(1), dim3(1024), 0, st, (const float *)A.adv, pl.M, A.mom);
-    else {
-    hipLaunchKernelGGL(k_moments_partial<0>, dim3(g), dim3(256), 0, st, (const float *)A.adv, pl.M, (const float *)A.mom, part);
-    hipLaunchKernelGGL(k_moments_final<0>, dim3(1), dim3(64), 0, st, (const float *)part, g, pl.M, A.mom);
-    hipLaunchKernelGGL(k_moments_partial<1>, dim3(g), dim3(256), 0, st, (const float *)A.adv, pl.M, (const float *)A.mom, part);
-    hipLaunchKernelGGL(k_moments_final<1>, dim3(1), dim3(64), 0, st, (const float *)part, g, pl.M, A.mom);
-    }
-  }
-  // 4. loss forward/backward
-  float *layered_extras = nullptr;
-  int layered_n_extras = 0;
-  if (pl.layered) {
-    rc = ppo_layered_fwd_bwd(d, pl.pi, pl.v, ws + pl.off_layered, A.vs, A.adv, A.mom, A.slabs, &layered_extras, &layered_n_extras, st);
-    if (rc != MBPO_OK) return rc;
-  } else if (pl.lean) {
-    PpoLeanArgs L;
-    L.params = d->params; L.data = d->data; L.norm_mean = d->norm_mean; L.norm_std = d->norm_std;
-    L.adv = A.adv; L.vs = A.vs; L.mom = A.mom; L.ent_noise = d->entropy_noise;
-    L.rng_dev = A.rng_dev; L.seed = A.seed; L.offset = A.offset;
-    L.slabs = A.slabs; L.extras = A.extras; L.M = pl.M;
-    L.entropy_cost = d->entropy_cost; L.clip_eps = d->clipping_epsilon; L.normalize_advantage = d->normalize_advantage;
-    L.stamps = g_ppo_stamps;
-    rc = ppo_lean_launch(L, d->x_dim, d->policy_layers - 2, pl.n_slabs, stream);
-    if (rc != MBPO_OK) return rc;
-  } else if (pl.H == 64) {
-    const bool wide = net_is_wide(A.sh_pi) || net_is_wide(A.sh_v);
-    // (sp2 is only ever planned for networks that are not wide)
-    if (wide && !pl.sp2) rc = mbpo_launch<k_ppo_fwd_bwd<64, 4, true>>(pl.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
-    else if (!pl.sp2) rc = mbpo_launch<k_ppo_fwd_bwd<64, 4, false>>(pl.n_slabs, 1024, pl.lds_fb, st, "ppo_grads", A);
-    else rc = mbpo_launch<k_ppo_fwd_bwd<64, 2, false>>(pl.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);
-    if (rc != MBPO_OK) return rc;
-  } else {
-    rc = mbpo_launch<k_ppo_fwd_bwd<128, 2, false>>(pl.n_slabs, 512, pl.lds_fb, st, "ppo_grads", A);
-    if (rc != MBPO_OK) return rc;
-  }
-  // 5. reduce
-  PpoReduceArgs R;
-  R.slabs = A.slabs; R.extras = A.extras; R.n_slabs = pl.n_slabs; R.NPV = pl.NPV; R.M = pl.M; R.entropy_cost = d->entropy_cost;
-  R.n_extras = pl.n_slabs;
-  if (pl.layered) { R.extras = layered_extras; R.n_extras = layered_n_extras; }
-  R.grads = d->grads; R.metrics = d->metrics; R.metrics_accum = d->metrics_accum; R.step_count = d->step_count;
-  R.params = fuse_apply ? d->params : nullptr; R.adam_m = d->adam_m; R.adam_v = d->adam_v;
-  R.lr = d->lr; R.wd = d->wd; R.grad_scale = d->grad_scale;
-  R.ss_part = ws + pl.off_sspart;
+// 5. grads = the sum of the slabs, loss metrics; fuse_apply: and the optimizer step
+static void ppo_reduce_launch(const mbpo_ppo_desc *d, const PpoPlan &pl, const PpoReduceArgs &R, bool fuse_apply, hipStream_t st) {
   // The one-stage sum reads 256-byte pieces 68 KB apart: 22.7 us for the 35 MB of 512 slabs (C3, T = 40), unchanged by 4x the loads
   // in flight or by 1-KB pieces.  With many slabs: first groups of 16 over 4-KB contiguous runs, in place, then the 32 group sums.
-  R.slab_step = 1;
-  if (pl.n_slabs >= 64) {
-    hipLaunchKernelGGL(k_ppo_reduce_groups, dim3((pl.NPV + 1023) / 1024, (pl.n_slabs + 15) / 16), dim3(256), 0, st, A.slabs, pl.NPV,
-                       pl.n_slabs);
-    R.slab_step = 16;
-  }
+  if (pl.var.reduce_two_stage)
+    hipLaunchKernelGGL(k_ppo_reduce_groups, dim3((pl.NPV + 1023) / 1024, (R.n_slabs + 15) / 16), dim3(256), 0, st,
+                       d->workspace + pl.off_slabs, pl.NPV, R.n_slabs);
   if (fuse_apply && pl.clip) {
     // clip_by_global_norm needs every workgroup's part of the norm before any element may move: the reduce launch leaves the
     // partials, one more launch clips and applies (the same partials and arithmetic as mbpo_ppo_apply: the same bits)
@@ -958,32 +1039,54 @@ static int ppo_grads_impl(const mbpo_ppo_desc *d, void *stream, bool fuse_apply)
   } else {
     hipLaunchKernelGGL(k_ppo_reduce<false>, dim3((pl.NPV + 63) / 64), dim3(256), 0, st, R);
   }
+}
+
+// One minibatch update: the five stages in order.  fuse_apply: mbpo_ppo_step, no seam for a collective.
+static int ppo_update(const mbpo_ppo_desc *d, void *stream, bool fuse_apply) {
+  PpoPlan pl;
+  int rc = ppo_plan(d, &pl, true);
+  if (rc != MBPO_OK) return rc;
+  MBPO_REQUIRE(d->data, MBPO_ERR_ARG, "ppo_grads: null data");
+  MBPO_REQUIRE((d->norm_mean == nullptr) == (d->norm_std == nullptr), MBPO_ERR_ARG, "ppo_grads: norm_mean/norm_std mismatch");
+  hipStream_t st = (hipStream_t)stream;
+  PpoArgs A;
+  ppo_fill_args(d, pl, &A);
+  rc = ppo_values_launch(d, pl, &A, st);
+  if (rc != MBPO_OK) return rc;
+  rc = ppo_gae_launch(d, pl, A, st);
+  if (rc != MBPO_OK) return rc;
+  ppo_moments_launch(d, pl, A, st);
+  PpoReduceArgs R;
+  ppo_fill_reduce(d, pl, A, fuse_apply, &R);
+  rc = ppo_fwd_bwd_launch(d, pl, A, &R, st);
+  if (rc != MBPO_OK) return rc;
+  ppo_reduce_launch(d, pl, R, fuse_apply, st);
   MBPO_CHECK_LAUNCH("ppo_grads");
   return MBPO_OK;
 }
 
-extern "C" int mbpo_ppo_grads(const mbpo_ppo_desc *d, void *stream) { return ppo_grads_impl(d, stream, false); }
+extern "C" int mbpo_ppo_grads(const mbpo_ppo_desc *d, void *stream) { return ppo_update(d, stream, false); }
 
 // One minibatch_step without a seam for a collective: the reduce launch applies AdamW to the elements it has just summed
 // (k_ppo_apply's arithmetic, bit for bit) — one launch less per minibatch_step.
-extern "C" int mbpo_ppo_step(const mbpo_ppo_desc *d, void *stream) { return ppo_grads_impl(d, stream, true); }
+extern "C" int mbpo_ppo_step(const mbpo_ppo_desc *d, void *stream) { return ppo_update(d, stream, true); }
 
 extern "C" int mbpo_ppo_apply(const mbpo_ppo_desc *d, void *stream) {
   PpoPlan pl;
   int rc = ppo_plan(d, &pl, true);
   if (rc != MBPO_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
   if (pl.clip) {
     // the norm of the (all-reduced) scaled gradient as it stands in `grads` now, then the clipped step
-    hipLaunchKernelGGL(k_ppo_sumsq, dim3(pl.n_ss), dim3(64), 0, (hipStream_t)stream, (const float *)d->grads, pl.NPV, d->grad_scale,
+    hipLaunchKernelGGL(k_ppo_sumsq, dim3(pl.n_ss), dim3(64), 0, st, (const float *)d->grads, pl.NPV, d->grad_scale,
                        d->workspace + pl.off_sspart);
-    ppo_clip_apply_launch(d, pl, (hipStream_t)stream);
-    MBPO_CHECK_LAUNCH("ppo_apply");
-    return MBPO_OK;
+    ppo_clip_apply_launch(d, pl, st);
+  } else {
+    PpoApplyArgs A;
+    ppo_fill_opt(d, &A);
+    A.NPV = pl.NPV;
+    hipLaunchKernelGGL(k_ppo_apply, dim3((pl.NPV + 255) / 256), dim3(256), 0, st, A);
   }
-  PpoApplyArgs A;
-  A.params = d->params; A.adam_m = d->adam_m; A.adam_v = d->adam_v; A.grads = d->grads; A.step_count = d->step_count;
-  A.NPV = pl.NPV; A.lr = d->lr; A.wd = d->wd; A.grad_scale = d->grad_scale;
-  hipLaunchKernelGGL(k_ppo_apply, dim3((pl.NPV + 255) / 256), dim3(256), 0, (hipStream_t)stream, A);
   MBPO_CHECK_LAUNCH("ppo_apply");
   return MBPO_OK;
 }

@@ -1,11 +1,17 @@
-"""PPO minibatch_step launched repeatedly (for rocprofv3 --kernel-trace --stats): BASELINE config 3 shape B=512, T=5 / 40."""
-import math, os, sys, torch
+"""PPO minibatch_step launched repeatedly (for rocprofv3 --kernel-trace --stats): BASELINE config 3 shape B=512, T=5 / 40.
+
+    python scripts/ppo_step_time.py [T] [--time]
+
+--time  also print microseconds per eager minibatch_step (the host plans every call): wall clock around a synchronised loop, and the
+        part of it the host spent issuing the calls."""
+import math, os, sys, time, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'model-based-policy-optimizers_amd'))
 from mbpo import ops
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
 X, U, hid = 4, 1, (64, 64, 64)
-T = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+argv = [a for a in sys.argv[1:] if a != "--time"]
+T = int(argv[0]) if argv else 5
 
 
 def lecun(dims):
@@ -26,3 +32,13 @@ data = data.to(dev)
 for _ in range(100):
     up.minibatch_step(data)
 torch.cuda.synchronize()
+if "--time" in sys.argv:
+    N = 2000
+    for rep in range(3):
+        t0 = time.perf_counter()
+        for _ in range(N):
+            up.minibatch_step(data)
+        t1 = time.perf_counter()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        print(f"ppo_step_time T={T}: {(t2 - t0) / N * 1e6:.2f} us per minibatch_step ({(t1 - t0) / N * 1e6:.2f} us issuing)", flush=True)

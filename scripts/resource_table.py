@@ -13,7 +13,7 @@ import sys
 from pathlib import Path
 
 DEFAULT = Path(__file__).resolve().parent.parent / "model-based-policy-optimizers_amd" / "build"
-KEYS = ["k_sac_fwd_bwd", "k_sac_lean", "k_sac_reduce", "k_sac_apply", "k_sac_gather", "k_sac_sumsq", "k_sac_finalize", "k_ppo_fwd_bwd", "k_ppo_values_gae", "k_bptt_actor", "k_model_rollout", "k_rollout_lean",
+KEYS = ["k_sac_fwd_bwd", "k_sac_lean", "k_sac_reduce", "k_sac_apply", "k_sac_gather", "k_sac_sumsq", "k_sac_finalize", "k_ppo_", "k_moments", "k_bptt_actor", "k_model_rollout", "k_rollout_lean",
         "k_critic_fwd", "k_ensemble_forward", "k_openloop_pendulum", "k_hold_steps", "k_reward_eval", "k_mlp_vjp", "k_ens_nll"]
 COLS = ("VGPR", "vspill", "scratch", "SGPR", "sspill", "LDS", "occ", "code")
 
