@@ -895,7 +895,8 @@ int mbpo_icem_update(const float *rows, int32_t row_len, int32_t reward_col, int
                      float *values, int32_t *workspace, void *stream);
 /* The same with the reference's constraint term (icem_optimizer.py:99,157-166): particle_cost[c * n_particles + p] = the user's
  * cost_fn on the trajectory of candidate c, particle p (evaluated by the host between the rollout and this launch — a Python
- * callable cannot run in a kernel); objective[c] = reward[c] - lambda_constraint * relu(cost[c]), cost[c] = mean (cost_use_max:
+ * callable cannot run in a kernel — or written by mbpo_traj_cost_eval, "term costs" below, for a cost given as a term table);
+ * objective[c] = reward[c] - lambda_constraint * relu(cost[c]), cost[c] = mean (cost_use_max:
  * max, `use_pessimism`) over the particles.  particle_cost NULL: mbpo_icem_update. */
 int mbpo_icem_update_constrained(const float *rows, int32_t row_len, int32_t reward_col, int32_t n_candidates, int32_t n_particles,
                                  int32_t horizon, int32_t u_dim, const float *candidates, int32_t n_elites, int32_t n_prev, float alpha,
@@ -919,6 +920,25 @@ int mbpo_icem_update_batched(const float *rows, int32_t row_len, int32_t reward_
                              float alpha, int32_t use_max, const float *particle_cost, float lambda_constraint, int32_t cost_use_max,
                              float *mean, float *std, float *best_value, float *best_sequence, float *prev_elites, float *values,
                              int32_t *workspace, void *stream);
+
+/* ---- term costs: a trajectory constraint written as a term table, evaluated on the rollout's rows -------------------------------
+ * replaces: vmap(cost_fn)(observation, action) between the rollout and the update (icem_optimizer.py:99,161-166) for a cost that can
+ *           be written as data (mbpo.systems.TermCost).  Not in the reference tree; build-defined: THIS TEXT IS THE DEFINITION.
+ * table is a term table ("term rewards" above: the same MBPO_REWARD_TERMS_FLOATS floats, read by the same device function).  rows is
+ * what mbpo_model_rollout writes with open-loop actions, step-major: row t * n_traj + i of row_len floats holds step t of trajectory
+ * i, obs at column 0, the action at column x_dim, the next state at column next_off (iCEM: row_len = 2 x_dim + A + 3 and next_off =
+ * x_dim + A + 2 with A the action width; u_dim <= A is the control width the dynamics see — an eta or tau column never enters).
+ *   c_t     = the table on z = [obs_t (x_dim) | action_t[:u_dim] | next_t (x_dim)], next_t reading obs_t where a component of the
+ *             row's next state is not finite (the term rewards' rule)
+ *   cost[i] = sum_t c_t    reduce 0: one fp32 accumulator from 0 in ascending t, every sum rounded on its own — bit for bit the
+ *                          sequential fp32 sum of mbpo_reward_eval over the trajectory's rows
+ *           = max_t c_t    reduce 1: from c_0 in ascending t; a NaN c_t makes cost[i] NaN (as torch.max, not fmaxf)
+ * Positive means violated (mbpo_icem_update_constrained applies relu).  One thread per trajectory, no atomics; rows need no alignment.
+ * cost [n_traj] is overwritten in full; nothing else is written.  No workspace, no allocation, no host read-back; capturable.
+ * MBPO_ERR_ARG before any device use: n_steps < 1, n_traj < 0, x_dim < 1, u_dim < 1, next_off + x_dim > row_len, x_dim + u_dim >
+ * next_off, reduce not 0 or 1, or with n_traj > 0 a NULL table, rows or cost.  n_traj == 0: MBPO_OK, nothing is launched. */
+int mbpo_traj_cost_eval(const float *table, const float *rows, int32_t row_len, int32_t next_off, int32_t n_steps, int64_t n_traj,
+                        int32_t x_dim, int32_t u_dim, int32_t reduce, float *cost, void *stream);
 
 /* ---- one-shot all-reduce over xGMI peer memory (multi-GPU SAC gradient exchange) ------------------------
  * replaces: the live form of the reference's jax.lax.pmean(grad) (sac/utils.py:29-33) for vectors small enough that a

@@ -9,8 +9,11 @@
 //   *_batched      the same for B independent problems in one launch each (batched MPC): k_icem_sample_batched (grid.y = problem,
 //                  seed = seeds[b]) and k_icem_update[_lds]<true> (one workgroup per problem); the objective kernels run unchanged
 //                  over all problems' candidates.  Problem b's bits are the single-problem launches' with its seed and slices.
+//   k_traj_cost    the constraint term of a cost written as a term table (mbpo.systems.TermCost): one thread per trajectory walks the
+//                  rollout's rows in step order, reward_terms_eval on every step, summed or maximised over the horizon.
 // HBM-bound bookkeeping around the rollout; everything stays on the device, the host only sequences the launches.
 #include "common.hpp"
+#include "reward_terms.hpp"
 
 #define ICEM_MAX_HU 4096
 
@@ -459,5 +462,103 @@ extern "C" int mbpo_icem_update_batched(const float *rows, int32_t row_len, int3
   if (mbpo_knob(KNOB_ICEM_UPDATE) != 0 && lds <= 60 * 1024) hipLaunchKernelGGL(k_icem_update_lds<true>, dim3(n_problems), dim3(1024), lds, st, A);
   else hipLaunchKernelGGL(k_icem_update<true>, dim3(n_problems), dim3(1024), 0, st, A);
   MBPO_CHECK_LAUNCH("icem_update_batched");
+  return MBPO_OK;
+}
+
+// ---- term costs (include/mbpo_hip.h "term costs") -------------------------------------------------------------------
+// cost[i] of trajectory i from the rollout's step-major rows (row t * n_traj + i): the term table on (obs, action[:UE], next_obs) of
+// every step, through reward_terms_eval as every other call site runs it.  A 256-thread workgroup takes a tile of TJ = 256 / slots
+// consecutive trajectories and `slots` steps at a time: thread (slot s, lane j) evaluates step t0 + s of trajectory tile * TJ + j, so
+// neighbouring lanes read neighbouring rows of one step, which are contiguous in memory.  With slots = 1 one thread owns one trajectory
+// and walks t = 0 .. H - 1 (the form for many trajectories: the rows stream through once, no barrier).  With few trajectories that walk
+// is H dependent round trips to memory on a handful of workgroups (19.6 us at 5150 trajectories x 20 steps), so the host spreads the
+// steps over up to TRAJ_COST_MAX_SLOTS slots: the stage costs of a round land in LDS and the tile's slot-0 threads fold them in ascending
+// t into the accumulator they carry across rounds — the same additions in the same order, so the bits do not depend on `slots`.
+// The table is staged once per workgroup in LDS (all lanes walk the same records: broadcast reads).  Rows carry no alignment promise:
+// every column is a scalar load.  The grid is capped at TRAJ_COST_MAX_BLOCKS workgroups; past it a workgroup strides over tiles.  No
+// atomics, no workspace.
+//   sum: acc = acc + c_t from 0 in ascending t, each sum rounded to fp32 — the sequential sum of mbpo_reward_eval's values.
+//   max: c_0, then icem_max: a NaN stage cost makes the trajectory's cost NaN (fmaxf alone would drop it; torch's max keeps it).
+#define TRAJ_COST_BLOCK 256
+#define TRAJ_COST_MAX_BLOCKS 2048
+#define TRAJ_COST_MAX_SLOTS 32
+__device__ __forceinline__ float traj_cost_fold(float acc, float c, int t, int reduce) {
+  if (reduce == 0) return __fadd_rn(acc, c);
+  return t == 0 ? c : icem_max(acc, c);
+}
+
+__global__ void __launch_bounds__(TRAJ_COST_BLOCK) k_traj_cost(const float *table, const float *rows, int row_len, int next_off, int H,
+                                                               long long n_traj, int X, int UE, int reduce, int slots, float *cost) {
+  __shared__ float s_tab[MBPO_REWARD_TERMS_FLOATS];
+  __shared__ float s_c[TRAJ_COST_BLOCK];      // [slot][lane]: the stage costs of one round
+  for (int idx = threadIdx.x; idx < MBPO_REWARD_TERMS_FLOATS; idx += TRAJ_COST_BLOCK) s_tab[idx] = table[idx];
+  __syncthreads();
+  const int TJ = TRAJ_COST_BLOCK / slots, slot = threadIdx.x / TJ, lane = threadIdx.x - slot * TJ;
+  const long long n_tiles = (n_traj + TJ - 1) / TJ;
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {      // (workgroup-uniform bounds: the barriers below are reached by all)
+    const long long i = tile * TJ + lane;
+    const bool live = i < n_traj;
+    float acc = 0.f;
+    for (int t0 = 0; t0 < H; t0 += slots) {
+      const int t = t0 + slot;
+      float c = 0.f;
+      if (live && t < H) {
+        const float *r = rows + ((long long)t * n_traj + i) * row_len;
+        c = reward_terms_eval(s_tab, r, r + X, reward_terms_next(r + next_off, r, X), X, UE);
+      }
+      if (slots == 1) {
+        acc = traj_cost_fold(acc, c, t, reduce);
+      } else {
+        s_c[threadIdx.x] = c;
+        __syncthreads();
+        if (slot == 0) {
+          const int nt = H - t0 < slots ? H - t0 : slots;
+          for (int k = 0; k < nt; ++k) acc = traj_cost_fold(acc, s_c[k * TJ + lane], t0 + k, reduce);
+        }
+        __syncthreads();
+      }
+    }
+    if (slot == 0 && live) cost[i] = acc;
+  }
+}
+
+// Step slots per workgroup: 1 (one thread per trajectory) once the tiles give every CU two workgroups, else doubled — up to the horizon
+// and to TRAJ_COST_MAX_SLOTS — until they do.  (Measured at 329600 trajectories x 20 steps, 1288 workgroups at slots = 1, in one
+// session: 46.7 us at slots = 1 against 53.2 us at slots = 2, so the doubling stops there.)  Test hook (not part of include/mbpo_hip.h): mbpo_debug_set_traj_cost_slots(1, 2, 4, ..,
+// 32) forces a value, -1 restores this choice; tests/test_gpu_term_cost.py runs every value on the same rows.
+static int traj_cost_slots(int H, long long n_traj) {
+  const int forced = mbpo_knob_override(KNOB_TRAJ_COST_SLOTS);
+  if (forced >= 1) return forced;
+  const long long want = 2LL * mbpo_num_cus();
+  int slots = 1;
+  while (slots < TRAJ_COST_MAX_SLOTS && slots < H && (n_traj + TRAJ_COST_BLOCK / slots - 1) / (TRAJ_COST_BLOCK / slots) < want) slots *= 2;
+  return slots;
+}
+
+extern "C" int mbpo_debug_set_traj_cost_slots(int slots) {
+  MBPO_REQUIRE(slots == -1 || (slots >= 1 && slots <= TRAJ_COST_MAX_SLOTS && (slots & (slots - 1)) == 0), MBPO_ERR_ARG,
+               "debug_set_traj_cost_slots: slots must be -1 or a power of two in [1, %d]", TRAJ_COST_MAX_SLOTS);
+  return mbpo_knob_set_override(KNOB_TRAJ_COST_SLOTS, slots);
+}
+
+extern "C" int mbpo_traj_cost_eval(const float *table, const float *rows, int32_t row_len, int32_t next_off, int32_t n_steps, int64_t n_traj,
+                                   int32_t x_dim, int32_t u_dim, int32_t reduce, float *cost, void *stream) {
+  MBPO_REQUIRE(n_steps >= 1, MBPO_ERR_ARG, "traj_cost_eval: n_steps=%d < 1", n_steps);
+  MBPO_REQUIRE(n_traj >= 0, MBPO_ERR_ARG, "traj_cost_eval: n_traj < 0");
+  MBPO_REQUIRE(x_dim >= 1 && u_dim >= 1, MBPO_ERR_ARG, "traj_cost_eval: x_dim and u_dim must be positive");
+  MBPO_REQUIRE(next_off >= 0 && (long long)next_off + x_dim <= row_len, MBPO_ERR_ARG,
+               "traj_cost_eval: next_off=%d + x_dim=%d leaves the row (row_len=%d)", next_off, x_dim, row_len);
+  MBPO_REQUIRE((long long)x_dim + u_dim <= next_off, MBPO_ERR_ARG, "traj_cost_eval: x_dim=%d + u_dim=%d overlaps next_off=%d", x_dim, u_dim,
+               next_off);
+  MBPO_REQUIRE(reduce == 0 || reduce == 1, MBPO_ERR_ARG, "traj_cost_eval: reduce=%d is neither 0 (sum) nor 1 (max)", reduce);
+  MBPO_REQUIRE(n_traj <= 0x7fffffffffffffffLL / row_len / n_steps, MBPO_ERR_ARG, "traj_cost_eval: n_steps * n_traj * row_len overflows int64");
+  if (n_traj == 0) return MBPO_OK;
+  MBPO_REQUIRE(table && rows && cost, MBPO_ERR_ARG, "traj_cost_eval: null pointer");
+  const int slots = traj_cost_slots(n_steps, n_traj), TJ = TRAJ_COST_BLOCK / slots;
+  const long long tiles = (n_traj + TJ - 1) / TJ;
+  hipLaunchKernelGGL(k_traj_cost, dim3((unsigned)(tiles < TRAJ_COST_MAX_BLOCKS ? tiles : TRAJ_COST_MAX_BLOCKS)), dim3(TRAJ_COST_BLOCK), 0,
+                     (hipStream_t)stream, table, rows, (int)row_len, (int)next_off, (int)n_steps, (long long)n_traj, (int)x_dim, (int)u_dim,
+                     (int)reduce, slots, cost);
+  MBPO_CHECK_LAUNCH("traj_cost_eval");
   return MBPO_OK;
 }

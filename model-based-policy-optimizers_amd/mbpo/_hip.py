@@ -25,6 +25,7 @@ REWARD_TERMS_MAX_GROUPS, REWARD_TERMS_MAX_TERMS = 16, 128
 REWARD_TERMS_FLOATS = 4 + 4 * REWARD_TERMS_MAX_GROUPS + 4 * REWARD_TERMS_MAX_TERMS
 TERM_FN_IDS = {"identity": 0, "square": 1, "abs": 2, "relu": 3, "cos": 4, "sin": 5}
 TERM_LINK_IDS = {"identity": 0, "sqrt": 1, "exp": 2, "tanh": 3}
+COST_REDUCE_IDS = {"sum": 0, "max": 1}     # mbpo_traj_cost_eval's reduce (include/mbpo_hip.h "term costs")
 
 _LIB_PATH = Path(__file__).resolve().parent / "_lib" / "libmbpo_hip.so"
 
@@ -291,6 +292,10 @@ def _bind_optional(lib: C.CDLL) -> None:
     if fn is not None:
         fn.restype = C.c_int
         fn.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, vp, vp]
+    fn = getattr(lib, "mbpo_traj_cost_eval", None)   # (bound when present, as mbpo_reward_eval)
+    if fn is not None:
+        fn.restype = C.c_int
+        fn.argtypes = [vp, vp, i32, i32, i32, i64, i32, i32, i32, vp, vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

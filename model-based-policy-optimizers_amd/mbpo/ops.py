@@ -438,6 +438,28 @@ def reward_eval(reward_kind: int, reward_params: torch.Tensor, x: torch.Tensor, 
     return out
 
 
+def traj_cost_eval(table: torch.Tensor, rows: torch.Tensor, n_steps: int, n_traj: int, x_dim: int, u_dim: int, next_off: int,
+                   reduce: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mbpo_traj_cost_eval: [n_traj], the term table `table` on every step of every trajectory of the step-major rollout rows
+    [n_steps * n_traj, row_len] (obs at column 0, action at x_dim, next state at next_off), summed (reduce 0) or maximised (1) over
+    the steps.  One launch, no allocation when `out` is given."""
+    lib = load()
+    _req(table, "table")
+    _req(rows, "rows")
+    if table.numel() < _hip.REWARD_TERMS_FLOATS:
+        raise ValueError(f"a term table holds {_hip.REWARD_TERMS_FLOATS} floats, table {table.numel()}")
+    n_steps, n_traj = int(n_steps), int(n_traj)
+    if rows.dim() != 2 or n_steps < 1 or n_traj < 0 or rows.shape[0] != n_steps * n_traj:
+        raise ValueError(f"rows must be [n_steps * n_traj, row_len] = [{n_steps} * {n_traj}, row_len], got {tuple(rows.shape)}")
+    if out is None:
+        out = torch.empty(n_traj, device=rows.device, dtype=torch.float32)
+    elif _req(out, "out").shape != (n_traj,):
+        raise ValueError(f"out must be [{n_traj}]")
+    check(lib.mbpo_traj_cost_eval(table.data_ptr(), rows.data_ptr(), rows.shape[1], int(next_off), n_steps, n_traj, int(x_dim), int(u_dim),
+                                  int(reduce), out.data_ptr(), current_stream_ptr()), "mbpo_traj_cost_eval")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ user-defined System (non-fused)
 def policy_act(policy_params: torch.Tensor, policy_spec: MlpSpec, obs: torch.Tensor, norm_mean=None, norm_std=None,
                deterministic: bool = False, action_clip: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0,

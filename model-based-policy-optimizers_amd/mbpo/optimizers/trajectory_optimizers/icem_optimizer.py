@@ -8,8 +8,11 @@ with all optimizer state in flat device vectors; the host only sequences launche
 device noise is Philox(seed = split key, offset = iteration).  A user `cost_fn` (icem_optimizer.py:99,161-166: a callable over one
 trajectory, `cost_fn(observation [H, x], action [H, u]) -> scalar`) cannot run inside the kernels: it is evaluated between the
 rollout launch and the update launch, vmapped over all (candidate, particle) trajectories with torch.func.vmap on the device rows
-(the reference vmaps it too), and enters the objective inside mbpo_icem_update_constrained: reward - lambda_constraint * relu(cost),
-cost summarised over particles by mean (use_pessimism: max).  use_optimism -> max over particles of the reward.
+(the reference vmaps it too).  A cost written as data, `cost_fn=TermCost(...)` (mbpo.systems), needs no Python there: one launch of
+mbpo_traj_cost_eval evaluates its term table on the rollout's rows — (x_t, u_t, x_{t+1}) of every step, summed or maximised over the
+horizon — into a preallocated buffer, and the iteration stays a pure launch chain, single and batched.  Either way the cost enters the
+objective inside mbpo_icem_update_constrained: reward - lambda_constraint * relu(cost), cost summarised over particles by mean
+(use_pessimism: max).  use_optimism -> max over particles of the reward.
 
 Batched MPC: `init(key, batch_size=B)` makes a state for B independent problems (best_sequence [B, H, U], best_reward [B], key = B
 host integers) and `optimize` / `act` on such a state plan for obs [B, x] in one launch chain per iteration —
@@ -35,6 +38,7 @@ from mbpo.replay import ReplayBufferState
 from mbpo.systems.base_systems import System
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
 from mbpo.systems.rewards.base_rewards import RewardParams
+from mbpo.systems.term_cost import TermCost
 from mbpo.systems.termination import without_termination
 from mbpo.systems.time_adaptive import refuse_time_adaptive
 from mbpo.utils import keys as K
@@ -83,6 +87,8 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         super().__init__(*args, **kwargs)
         refuse_time_adaptive(self.system, "iCEM")
         self.cost_fn = cost_fn       # evaluated on the host side of the seam, between two launches (see the module docstring)
+        self._term_cost = cost_fn if isinstance(cost_fn, TermCost) else None      # ... or on the device, by mbpo_traj_cost_eval
+        self._check_term_cost(self.system)
         self.lib = _hip.load()
         self.horizon, self.action_dim = int(horizon), int(action_dim)
         self.opt_params, self.key = opt_params, key
@@ -97,7 +103,19 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
 
     def set_system(self, system):
         refuse_time_adaptive(system, "iCEM")      # (single and batched: the candidates' objective sums per-step rewards)
+        self._check_term_cost(system)
         super().set_system(system)
+
+    def _check_term_cost(self, system):
+        """A TermCost's widths against the system's: u_dim is the control width the dynamics see, not action_dim."""
+        tc = self._term_cost
+        if tc is None or system is None:
+            return
+        if tc.x_dim != system.x_dim:
+            raise ValueError(f"cost_fn is a TermCost at x_dim {tc.x_dim}, the system has x_dim {system.x_dim}")
+        if tc.u_dim != system.u_dim:
+            raise ValueError(f"cost_fn is a TermCost at u_dim {tc.u_dim}, the system has u_dim {system.u_dim} (the control width the "
+                             f"dynamics see; its action_dim is {system.action_dim})")
 
     # -- reference API ------------------------------------------------------------------------------------------------
     def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None, batch_size: Optional[int] = None) -> iCemOptimizerState:
@@ -129,6 +147,8 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                               actions=f(H, N, U), cand=f(NC, H, U), values=f(NC), rank=torch.zeros(NC, device=dev, dtype=torch.int32),
                               u_min=vec(p.u_min), u_max=vec(p.u_max), obs=f(N, self.system.x_dim), first=f(N, self.system.x_dim),
                               steps=f(N), done=f(N), rows=f(H * N, 2 * self.system.x_dim + U + 3))
+            if self._term_cost is not None:
+                self._bufs["term_cost"] = f(N)
         return self._bufs
 
     def _batched_buffers(self, dev, B: int):
@@ -147,10 +167,13 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                                rank=torch.zeros(B * NC, device=dev, dtype=torch.int32), u_min=_bound_vec(p.u_min, U, dev),
                                u_max=_bound_vec(p.u_max, U, dev), obs=f(NT, X), first=f(NT, X), steps=f(NT), done=f(NT),
                                rows=f(H * NT, 2 * X + U + 3))
+            if self._term_cost is not None:
+                self._bbufs["term_cost"] = f(NT)
         return self._bbufs
 
     def optimize(self, initial_state: torch.Tensor, opt_state: iCemOptimizerState) -> iCemOptimizerState:
         assert self.system is not None, "iCem optimizer requires system to be defined."
+        self._check_term_cost(self.system)      # (a system assigned without set_system)
         if opt_state.batched:
             return self._optimize_batched(initial_state, opt_state)
         p, H, U = self.opt_params, self.horizon, self.action_dim
@@ -184,7 +207,9 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             ops.model_rollout(x_dim=X, u_dim=U, actions=b["actions"], obs=b["obs"], first_obs=b["first"], steps=b["steps"], done=b["done"],
                               n_steps=H, episode_length=2 ** 30, seed=particles_key, offset=it, out=b["rows"], **spec)
             cost_ptr = None
-            if self.cost_fn is not None:
+            if self._term_cost is not None:
+                cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, b["N"], next_off=X + U + 2, out=b["term_cost"]).data_ptr()
+            elif self.cost_fn is not None:
                 rows3 = b["rows"].reshape(H, b["N"], -1)
                 obs_t = rows3[:, :, :X].transpose(0, 1)                    # [N, H, x]: transitions.observation per (candidate, particle)
                 act_t = rows3[:, :, X:X + U].transpose(0, 1)               # [N, H, u]
@@ -252,7 +277,9 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                               n_steps=H, episode_length=2 ** 30, seed=0, offset=it, out=b["rows"], member_idx=draw.get("member_idx"),
                               model_noise=draw.get("model_noise"), **spec)
             cost_ptr = None
-            if self.cost_fn is not None:
+            if self._term_cost is not None:
+                cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, NT, next_off=X + U + 2, out=b["term_cost"]).data_ptr()
+            elif self.cost_fn is not None:
                 rows3 = b["rows"].reshape(H, NT, -1)
                 obs_t = rows3[:, :, :X].transpose(0, 1)
                 act_t = rows3[:, :, X:X + U].transpose(0, 1)

@@ -7,5 +7,6 @@ from mbpo.systems.rewards.base_rewards import RewardParams, Reward
 from mbpo.systems.ensemble_system import EnsembleDynamics, EnsembleDynamicsParams, EnsembleSystem, LearnedReward
 from mbpo.systems.rewards.pendulum_reward import QuadraticReward
 from mbpo.systems.rewards.term_reward import TermReward, TermRewardParams, Term, Group
+from mbpo.systems.term_cost import TermCost
 from mbpo.systems.termination import BoxTermination
 from mbpo.systems.time_adaptive import TimeAdaptive

@@ -749,6 +749,68 @@ def main():
 
     if want("icem_batched_case"): attempt(icem_batched_case, 20)
 
+    # ---------------------------------------------------------------- constrained iCEM: the cost as a term table (one launch) vs a torch callable (vmap)
+    def icem_term_cost_case(H):
+        """One Pendulum `optimize` at the reference's defaults, single and at batch_size 64, in three forms in one session — no cost, the
+        speed constraint max_t(|theta_dot_t| - 5) as a TermCost (mbpo_traj_cost_eval), the same constraint as a torch callable (vmap) —
+        timed in alternating rounds (median, min and max of the rounds), and mbpo_traj_cost_eval alone at the two sizes."""
+        from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
+        from mbpo.systems import Group, PendulumSystem, Term, TermCost
+        p = iCemParams()
+        system = PendulumSystem()
+        X, U = system.x_dim, system.u_dim
+        table = TermCost(X, U, bias=-5.0, groups=[Group([Term("x", 2, "abs")])], reduce="max")
+        forms = {"no_cost": None, "term_cost": table, "callable": lambda o, a: o[:, 2].abs().max() - 5.0}
+        opts = {k: iCemTO(horizon=H, action_dim=U, opt_params=p, system=system, cost_fn=cf) for k, cf in forms.items()}
+        cfg = {"num_samples": p.num_samples, "num_particles": p.num_particles, "num_elites": p.num_elites, "num_steps": p.num_steps,
+               "horizon": H, "x": X, "u": U, "system": "Pendulum", "constraint": "max_t(|theta_dot_t| - 5)"}
+        x1 = torch.tensor([math.cos(2.5), math.sin(2.5), 4.5], device=dev)      # falling, close to the limit: the constraint binds
+        ROUNDS = 5
+        for B, reps in ((None, 20), (64, 5)):
+            calls = {}
+            for k, opt in opts.items():
+                st = opt.init(0, batch_size=B)
+                x0 = x1 if B is None else x1.expand(B, X).contiguous()
+                calls[k] = (lambda opt=opt, x0=x0, st=st: opt.optimize(x0, st))
+                timed(calls[k], 2, warm=2)
+            times = {k: [] for k in calls}
+            for _ in range(ROUNDS):
+                for k, fn in calls.items():
+                    times[k].append(timed(fn, reps, warm=0))
+            med = {k: sorted(v)[ROUNDS // 2] for k, v in times.items()}
+            for k, v in times.items():
+                out.append({"kernel": f"iCemTO.optimize, cost_fn: {k}", "entry": "mbpo_icem_sample + mbpo_model_rollout"
+                            + (" + mbpo_traj_cost_eval" if k == "term_cost" else " + torch.func.vmap(cost_fn)" if k == "callable" else "")
+                            + " + mbpo_icem_update x num_steps", "config": dict(cfg, B=1 if B is None else B, batched=B is not None),
+                            "eager_us": med[k] * 1e6, "eager_us_min": min(v) * 1e6, "eager_us_max": max(v) * 1e6, "rounds": ROUNDS,
+                            "calls_per_round": reps, "bound": "launch" if B is None else "rollout",
+                            "over_no_cost_us": (med[k] - med["no_cost"]) * 1e6,
+                            "note": "HIP-event time of one eager optimize call; the three forms alternate round by round in one session"})
+                log(f"icem optimize B={B or 1} cost_fn={k}: {med[k] * 1e6:.1f} us (min {min(v) * 1e6:.1f}, max {max(v) * 1e6:.1f}; "
+                    f"{(med[k] - med['no_cost']) * 1e6:+.1f} us over no cost)")
+            # the kernel alone, on the rows the last rollout left
+            b = opts["term_cost"]._bufs if B is None else opts["term_cost"]._bbufs
+            n, rows, buf = (b["N"] if B is None else b["NT"]), b["rows"], b["term_cost"]
+            t, te = both(lambda: table.trajectory_cost(rows, H, n, out=buf), 200)
+            out.append(hbm_entry("k_traj_cost", "mbpo_traj_cost_eval", dict(cfg, n_traj=n, row_len=rows.shape[1], reduce="max", terms=1), t,
+                                 4 * H * n * rows.shape[1] + 4 * n, "the rows' 64 B sectors once (40 B rows: every sector is touched) + 4 B per cost"))
+            log(f"traj_cost_eval n_traj={n}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+            # the same launch with one thread per trajectory forced (what the dispatch picks once the tiles fill the device)
+            lib = _hip.load()
+            lib.mbpo_debug_set_traj_cost_slots(1)
+            try:
+                t1, _ = both(lambda: table.trajectory_cost(rows, H, n, out=buf), 200)
+            finally:
+                lib.mbpo_debug_set_traj_cost_slots(-1)
+            out.append(hbm_entry("k_traj_cost (slots forced to 1)", "mbpo_traj_cost_eval", dict(cfg, n_traj=n, row_len=rows.shape[1], reduce="max",
+                                                                                             terms=1, slots=1), t1,
+                                 4 * H * n * rows.shape[1] + 4 * n, "as above"))
+            log(f"traj_cost_eval n_traj={n}, one thread per trajectory: {t1 * 1e6:.1f} us")
+            for opt in opts.values():
+                opt._bufs = opt._bbufs = None
+
+    if want("icem_term_cost_case"): icem_term_cost_case(20)
+
     res = {"device": torch.cuda.get_device_name(0), "roofs": {"hbm_GBs": HBM_PEAK_GBS, "mfma_f32_TFLOPs": MFMA_F32_PEAK_TF},
            "note": "device_us = HIP-event average per call with the calls captured into a hipGraph and replayed (device time, inputs resident in HBM; multi-launch ops timed whole); eager_us = the same call issued from Python",
            "kernels": out}
