@@ -1,14 +1,25 @@
 #!/usr/bin/env python
 """MPC on the true Pendulum with iCEM, every planning iteration a launch chain on the MI355X path:
 
-    mbpo_icem_sample -> mbpo_model_rollout (open loop) -> [mbpo_traj_cost_eval] -> mbpo_icem_update
+    mbpo_icem_sample -> mbpo_model_rollout (open loop) -> [mbpo_plan_reward_eval] -> [mbpo_traj_cost_eval] -> mbpo_icem_update
 
     python examples/icem_pendulum.py [--steps 100] [--horizon 20] [--speed-limit V] [--lambda-constraint L] [--seed 0]
+                                     [--targets A0,A1,...] [--track AMPL,PERIOD]
 
 --speed-limit V: the plan is constrained to |thetadot| <= V at every step of the horizon — a TermCost, max_t(|thetadot_{t+1}| - V), written as
 data and evaluated on the rollout's rows by one launch (iCemTO(cost_fn=TermCost(...), use_pessimism=True)); the objective of a candidate
 is its reward minus lambda_constraint * max(cost, 0).  The run prints the return and the largest speed the true system reached.  Without
 the option the same planner runs unconstrained.
+
+--targets A0,A1,...: batched MPC, one environment per target angle (rad), all planned in one launch chain: the Pendulum's own reward with
+a target angle per problem, PlanRewardParams.stack(system.reward, [[PendulumRewardParams(target_angle=a)] for a in targets]) in the
+state's reward_params.  Prints each environment's final angle error and its return under its own target.
+
+--track AMPL,PERIOD: one environment follows the target angle AMPL * sin(2 pi t / PERIOD) (t and PERIOD in seconds, dt = 0.05).  The
+planner previews the reference over its horizon — a [1, H, 3] table whose target column is refilled IN PLACE before every `act`
+(no new object, no reallocation; the launch reads what the table holds).  Prints the tracking error.
+
+A torque-limited pendulum cannot hold every angle: the prints are a record of what happened, not a claim.
 """
 from __future__ import annotations
 
@@ -30,7 +41,11 @@ def main():
     ap.add_argument("--speed-limit", type=float, default=None, metavar="V", help="constrain the plan to |thetadot| <= V (a TermCost)")
     ap.add_argument("--lambda-constraint", type=float, default=1e4, metavar="L")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--targets", type=str, default=None, metavar="A0,A1,...", help="batched MPC: one environment per target angle (rad)")
+    ap.add_argument("--track", type=str, default=None, metavar="AMPL,PERIOD", help="follow AMPL * sin(2 pi t / PERIOD), previewed over the horizon")
     args = ap.parse_args()
+    if args.targets is not None and args.track is not None:
+        raise SystemExit("--targets and --track are two runs")
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: the HIP path has no CPU fallback")
     from mbpo.optimizers import iCemParams, iCemTO
@@ -42,6 +57,10 @@ def main():
         cost = TermCost(system.x_dim, system.u_dim, bias=-args.speed_limit, groups=[Group([Term("x_next", 2, "abs")])], reduce="max")
     opt = iCemTO(horizon=args.horizon, action_dim=system.action_dim, opt_params=iCemParams(lambda_constraint=args.lambda_constraint),
                  system=system, cost_fn=cost, use_pessimism=cost is not None)
+    if args.targets is not None:
+        return run_targets(args, opt, system, dev)
+    if args.track is not None:
+        return run_track(args, opt, system, dev)
     state = opt.init(args.seed)
     sp = state.system_params
     x = torch.tensor([math.cos(math.pi), math.sin(math.pi), 0.0], device=dev)      # hanging down, at rest
@@ -53,6 +72,59 @@ def main():
     limit = "none" if args.speed_limit is None else f"{args.speed_limit:g}"
     print(f"steps {args.steps}  speed limit {limit}  return {ret:.2f}  max |thetadot| {top:.3f}  final angle "
           f"{math.atan2(float(x[1]), float(x[0])):+.3f} rad")
+
+
+def _angle_error(x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """theta - target wrapped to [-pi, pi), the reward's own difference."""
+    d = torch.atan2(x[..., 1], x[..., 0]) - target
+    return torch.remainder(d + math.pi, 2 * math.pi) - math.pi
+
+
+def run_targets(args, opt, system, dev):
+    from mbpo.systems import PlanRewardParams
+    from mbpo.systems.rewards.pendulum_reward import PendulumRewardParams
+    angles = [float(a) for a in args.targets.split(",")]
+    B = len(angles)
+    prp = PlanRewardParams.stack(system.reward, [[PendulumRewardParams(target_angle=a)] for a in angles], dev)      # [B, 1, 3]
+    state = opt.init(args.seed, batch_size=B)
+    sp = state.system_params                                                    # the true system steps under its ordinary parameters
+    state = state.replace(system_params=sp.replace(reward_params=prp))
+    tgt = torch.tensor(angles, device=dev)
+    x = torch.tensor([math.cos(math.pi), math.sin(math.pi), 0.0], device=dev).repeat(B, 1)
+    ret = torch.zeros(B, device=dev)
+    for _ in range(args.steps):
+        u, state = opt.act(x, state)
+        ret += -(_angle_error(x, tgt) ** 2 + 0.1 * x[:, 2] ** 2) - 0.02 * u[:, 0] ** 2      # PendulumReward under each env's own target
+        x = system.step(x, u, sp).x_next
+    err = _angle_error(x, tgt)
+    for b in range(B):
+        print(f"env {b}  target {angles[b]:+.3f} rad  final angle error {float(err[b]):+.4f} rad  final |thetadot| {abs(float(x[b, 2])):.3f}  "
+              f"return {float(ret[b]):.2f}")
+
+
+def run_track(args, opt, system, dev):
+    from mbpo.systems import PlanRewardParams
+    from mbpo.systems.rewards.pendulum_reward import PendulumRewardParams
+    ampl, period = [float(v) for v in args.track.split(",")]
+    H, dt = args.horizon, 0.05
+    ref = ampl * torch.sin(2 * math.pi * dt * torch.arange(args.steps + H, dtype=torch.float32) / period).to(dev)
+    prp = PlanRewardParams.stack(system.reward, [[PendulumRewardParams(target_angle=0.0)] * H], dev)               # [1, H, 3]
+    state = opt.init(args.seed)
+    sp = state.system_params
+    state = state.replace(system_params=sp.replace(reward_params=prp))
+    ptr = prp.table.data_ptr()
+    x = torch.tensor([1.0, 0.0, 0.0], device=dev)                              # upright, at rest: where the reference starts
+    errs = []
+    for t in range(args.steps):
+        prp.table[0, :, 2].copy_(ref[t:t + H])                                  # the preview window, in place
+        u, state = opt.act(x, state)
+        x = system.step(x, u, sp).x_next
+        errs.append(float(_angle_error(x, ref[t + 1])))
+    assert prp.table.data_ptr() == ptr
+    e = torch.tensor(errs)
+    half = e[len(errs) // 2:]
+    print(f"steps {args.steps}  track {ampl:g} * sin(2 pi t / {period:g})  RMS angle error {float(e.pow(2).mean().sqrt()):.4f} rad "
+          f"(second half {float(half.pow(2).mean().sqrt()):.4f})  max |error| {float(e.abs().max()):.4f}  final {errs[-1]:+.4f}")
 
 
 if __name__ == "__main__":

@@ -940,6 +940,39 @@ int mbpo_icem_update_batched(const float *rows, int32_t row_len, int32_t reward_
 int mbpo_traj_cost_eval(const float *table, const float *rows, int32_t row_len, int32_t next_off, int32_t n_steps, int64_t n_traj,
                         int32_t x_dim, int32_t u_dim, int32_t reduce, float *cost, void *stream);
 
+/* ---- plan rewards: reward parameters per planned problem and per planned step, evaluated on the rollout's rows -------------------
+ * replaces: the vmapped reward_params of jax.vmap(iCemTO.optimize) over a batch of plans, and a reward whose parameters move along the
+ *           horizon (mbpo.systems.PlanRewardParams).  Not in the reference tree; build-defined: THIS TEXT IS THE DEFINITION.
+ * A plan reward is a reward kind and a parameter array params [PB][PH][param_len], PB in {1, n_problems}, PH in {1, n_steps}; an axis
+ * of size 1 is broadcast.  rows is what mbpo_model_rollout writes with open-loop actions over n_problems * group envs, step-major: row
+ * (t, b, j) — step t, problem b, env j of the problem — lies at rows + ((t * n_problems + b) * group + j) * row_len, obs at column 0,
+ * the action at column x_dim, the next state at column next_off (iCEM: row_len = 2 x_dim + A + 3, next_off = x_dim + A + 2, A the
+ * action width; u_dim <= A is the control width the dynamics see — on an optimistic system the eta columns lie between x_dim + u_dim
+ * and the reward column and are never read).  With episode_length = 2^30 and no termination the row's next state is the step's own.
+ *   r(t, b, j) = R_kind(params[PB > 1 ? b : 0][PH > 1 ? t : 0]; x = row[0 .. x_dim), u = row[x_dim .. x_dim + u_dim),
+ *                       x_next = row[next_off .. next_off + x_dim))
+ *   MBPO_REWARD_TERMS      the term table ("term rewards" above) through the one device function every other site calls, x_next reading
+ *                          x where a component of it is not finite; param_len >= MBPO_REWARD_TERMS_FLOATS.  Bit for bit mbpo_reward_eval.
+ *   MBPO_REWARD_QUADRATIC  [target (x_dim) | q (x_dim) | r (u_dim)], mbpo_reward_eval's expressions in their order, bit for bit;
+ *                          param_len >= 2 x_dim + u_dim
+ *   MBPO_REWARD_PENDULUM   [angle_cost, control_cost, target_angle] on x = [cos, sin, thetadot] and u[0], the rollout kernels' function;
+ *                          x_dim == 3, u_dim == 1, param_len >= 3
+ *   MBPO_REWARD_LEARNED    MBPO_ERR_UNSUPPORTED: the head is not a function of the row
+ * out[((t * n_problems + b) * group + j) * out_stride] = r(t, b, j).  Dense: out_stride = 1 into a buffer of its own, which the update
+ * kernels take as (rows = out, row_len = 1, reward_col = 0).  In place: out = rows + reward_col, out_stride = row_len; this aliasing is
+ * legal — a thread reads only the obs, control and next-state columns of its row and writes only that row's reward column, which no
+ * thread reads.  Every row's output is written; nothing else is written.  One thread per row, no atomics; rows and params need no
+ * alignment.  No workspace, no allocation, no host read-back; capturable.  params is read by the launch: a table refilled in place
+ * between two launches (or two replays of a captured one) is honoured.
+ * MBPO_ERR_ARG before any device use: an unknown kind, n_steps < 1, n_problems < 1, group < 0, x_dim < 1, u_dim < 1, param_problems not
+ * in {1, n_problems}, param_steps not in {1, n_steps}, param_len smaller than the kind reads, the Pendulum kind at other widths than
+ * 3 / 1, x_dim + u_dim > next_off, next_off + x_dim > row_len, out_stride < 1, an index product (n_steps * n_problems * group * row_len
+ * or * out_stride, param_problems * param_steps * param_len) that overflows int64, more than (2^31 - 1) * 256 rows, or with group > 0
+ * a NULL params, rows or out.  group == 0: MBPO_OK, nothing is launched. */
+int mbpo_plan_reward_eval(int32_t reward_kind, const float *params, int32_t param_problems, int32_t param_steps, int32_t param_len,
+                          const float *rows, int32_t row_len, int32_t next_off, int32_t n_steps, int32_t n_problems, int64_t group,
+                          int32_t x_dim, int32_t u_dim, float *out, int64_t out_stride, void *stream);
+
 /* ---- one-shot all-reduce over xGMI peer memory (multi-GPU SAC gradient exchange) ------------------------
  * replaces: the live form of the reference's jax.lax.pmean(grad) (sac/utils.py:29-33) for vectors small enough that a
  *           collective is pure latency.  Every rank owns an exchange REGION (mbpo_p2p_alloc -> 64-byte IPC handle, passed to

@@ -26,7 +26,8 @@
   X(BPTT_ZSTORE_MAX_MB, "MBPO_BPTT_ZSTORE_MAX_MB", 16384, false, "largest BPTT member pre-activation store; above it the backward sweep recomputes") \
   X(ICEM_UPDATE, nullptr, -1, false, "override only: 0 the global-memory k_icem_update, 1 k_icem_update_lds where it fits")         \
   X(BPTT_ZSTORE, nullptr, -1, false, "override only: 0 no BPTT pre-activation store (recompute)")                                   \
-  X(TRAJ_COST_SLOTS, nullptr, -1, false, "override only: step slots per k_traj_cost workgroup (1, 2, .., 32); unset: by horizon and trajectory count")
+  X(TRAJ_COST_SLOTS, nullptr, -1, false, "override only: step slots per k_traj_cost workgroup (1, 2, .., 32); unset: by horizon and trajectory count") \
+  X(PLAN_REWARD_FLAT, nullptr, -1, false, "override only: 1 k_plan_reward_flat also where k_plan_reward_grouped applies")
 
 enum KnobId {
 #define MBPO_KNOB_ID_(id, env, dflt, reread, meaning) KNOB_##id,

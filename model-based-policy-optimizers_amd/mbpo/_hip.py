@@ -296,6 +296,10 @@ def _bind_optional(lib: C.CDLL) -> None:
     if fn is not None:
         fn.restype = C.c_int
         fn.argtypes = [vp, vp, i32, i32, i32, i64, i32, i32, i32, vp, vp]
+    fn = getattr(lib, "mbpo_plan_reward_eval", None)   # (bound when present, as mbpo_traj_cost_eval)
+    if fn is not None:
+        fn.restype = C.c_int
+        fn.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, i64, i32, i32, vp, i64, vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

@@ -460,6 +460,41 @@ def traj_cost_eval(table: torch.Tensor, rows: torch.Tensor, n_steps: int, n_traj
     return out
 
 
+def plan_reward_eval(reward_kind: int, table: torch.Tensor, rows: torch.Tensor, n_steps: int, n_problems: int, group: int, x_dim: int,
+                     u_dim: int, next_off: int, out: Optional[torch.Tensor] = None, reward_col: Optional[int] = None) -> torch.Tensor:
+    """mbpo_plan_reward_eval: the reward of every row of the step-major rollout rows [n_steps * n_problems * group, row_len] (obs at
+    column 0, action at x_dim, next state at next_off) under table[b or 0][t or 0] — table [PB, PH, param_len], PB in {1, n_problems},
+    PH in {1, n_steps} — of row (t, b, j) = (t * n_problems + b) * group + j.  Dense: into `out` [n_rows] (allocated when None).  In
+    place: reward_col given, into that column of `rows`, which is returned.  One launch, no allocation when `out` is given."""
+    lib = load()
+    _req(table, "table")
+    _req(rows, "rows")
+    n_steps, n_problems, group = int(n_steps), int(n_problems), int(group)
+    if table.dim() != 3 or table.shape[0] not in (1, n_problems) or table.shape[1] not in (1, n_steps):
+        raise ValueError(f"table must be [PB, PH, param_len] with PB in (1, {n_problems}) and PH in (1, {n_steps}), got {tuple(table.shape)}")
+    n_rows = n_steps * n_problems * group
+    if rows.dim() != 2 or n_steps < 1 or n_problems < 1 or group < 0 or rows.shape[0] != n_rows:
+        raise ValueError(f"rows must be [n_steps * n_problems * group, row_len] = [{n_steps} * {n_problems} * {group}, row_len], got "
+                         f"{tuple(rows.shape)}")
+    row_len = rows.shape[1]
+    if reward_col is not None:
+        if out is not None:
+            raise ValueError("give `out` (dense) or `reward_col` (in place), not both")
+        if not (int(x_dim) + int(u_dim) <= int(reward_col) < row_len) or int(next_off) <= int(reward_col) < int(next_off) + int(x_dim):
+            raise ValueError(f"reward_col {reward_col} lies inside the columns the launch reads (or outside the row)")
+        out_ptr, out_stride, ret = rows.data_ptr() + 4 * int(reward_col), row_len, rows
+    else:
+        if out is None:
+            out = torch.empty(n_rows, device=rows.device, dtype=torch.float32)
+        elif _req(out, "out").shape != (n_rows,):
+            raise ValueError(f"out must be [{n_rows}]")
+        out_ptr, out_stride, ret = out.data_ptr(), 1, out
+    check(lib.mbpo_plan_reward_eval(int(reward_kind), table.data_ptr(), table.shape[0], table.shape[1], table.shape[2], rows.data_ptr(),
+                                    row_len, int(next_off), n_steps, n_problems, group, int(x_dim), int(u_dim), out_ptr, out_stride,
+                                    current_stream_ptr()), "mbpo_plan_reward_eval")
+    return ret
+
+
 # ------------------------------------------------------------------------------------------------ user-defined System (non-fused)
 def policy_act(policy_params: torch.Tensor, policy_spec: MlpSpec, obs: torch.Tensor, norm_mean=None, norm_std=None,
                deterministic: bool = False, action_clip: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0,

@@ -14,6 +14,12 @@ horizon — into a preallocated buffer, and the iteration stays a pure launch ch
 objective inside mbpo_icem_update_constrained: reward - lambda_constraint * relu(cost), cost summarised over particles by mean
 (use_pessimism: max).  use_optimism -> max over particles of the reward.
 
+Plan rewards: `opt_state.system_params.reward_params` may be a `PlanRewardParams(reward, table [PB, PH, param_len])` (mbpo.systems) —
+reward parameters per problem (PB = B) and per planned step (PH = horizon), an axis of size 1 broadcast.  The rollout then runs under
+one ordinary parameter object (its reward column is computed and not used), one launch of mbpo_plan_reward_eval writes the rewards
+under the table into a dense buffer, and the unchanged update launch reads that buffer as (rows = buffer, row_len = 1, reward_col = 0).  The table is read by that launch: refilled in place between two `act`
+calls it is honoured without a new object.  Without a PlanRewardParams every path issues exactly the launches it issued before.
+
 Batched MPC: `init(key, batch_size=B)` makes a state for B independent problems (best_sequence [B, H, U], best_reward [B], key = B
 host integers) and `optimize` / `act` on such a state plan for obs [B, x] in one launch chain per iteration —
 mbpo_icem_sample_batched -> one rollout over all B*NC*P envs -> mbpo_icem_update_batched (one workgroup per problem).  Problem b
@@ -37,6 +43,7 @@ from mbpo.optimizers.base_optimizer import BaseOptimizer
 from mbpo.replay import ReplayBufferState
 from mbpo.systems.base_systems import System
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
+from mbpo.systems.plan_reward import PlanRewardParams
 from mbpo.systems.rewards.base_rewards import RewardParams
 from mbpo.systems.term_cost import TermCost
 from mbpo.systems.termination import without_termination
@@ -117,6 +124,35 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             raise ValueError(f"cost_fn is a TermCost at u_dim {tc.u_dim}, the system has u_dim {system.u_dim} (the control width the "
                              f"dynamics see; its action_dim is {system.action_dim})")
 
+    def _plan_reward(self, opt_state, batch: Optional[int]):
+        """(plan reward or None, the system parameters the rollout runs under).  A PlanRewardParams is checked against the system, the
+        horizon and the batch and taken out of the parameters `rollout_spec` sees (it refuses one: iCEM alone consumes it)."""
+        sp = opt_state.system_params
+        prp = sp.reward_params
+        if not isinstance(prp, PlanRewardParams):
+            return None, sp
+        prp.check_plan(self.system, self.horizon, batch)
+        if not self.system.fused:
+            raise ValueError(f"a PlanRewardParams needs a fused system (PendulumSystem, EnsembleSystem): {type(self.system).__name__}.step "
+                             f"is user code that computes its own reward")
+        return prp, sp.replace(reward_params=prp.rollout_reward_params(self.system, sp))
+
+    def _reward_source(self, prp: Optional[PlanRewardParams], b: dict, n_problems: int, group: int):
+        """(pointer, row_len, reward_col) the update launch reads the rewards through: the rollout's own rows, or — one launch of
+        mbpo_plan_reward_eval — a dense [H * n_problems * group] buffer holding the rewards under the table.  Dense, not in place: a
+        4-byte store into every 40-byte row dirties every cache line of the rows, which then go back to memory whole (the Pendulum kind
+        at batch_size 64: 86.8 us in place against 42.3 us dense, profiles/r16_icem_plan_reward.json), and the update reads 4 bytes per
+        row instead of a strided column."""
+        rows = b["rows"]
+        if prp is None:
+            return rows.data_ptr(), rows.shape[1], self.system.x_dim + self.action_dim
+        X, U = self.system.x_dim, self.action_dim
+        if "plan_reward" not in b:
+            b["plan_reward"] = torch.zeros(rows.shape[0], device=rows.device, dtype=torch.float32)
+        out = ops.plan_reward_eval(prp.kind, prp.table, rows, self.horizon, n_problems, group, X, self.system.u_dim, next_off=X + U + 2,
+                                   out=b["plan_reward"])
+        return out.data_ptr(), 1, 0
+
     # -- reference API ------------------------------------------------------------------------------------------------
     def init(self, key: int, true_buffer_state: Optional[ReplayBufferState] = None, batch_size: Optional[int] = None) -> iCemOptimizerState:
         """batch_size=B: a state for B independent problems (see the module docstring); key = K.split(k, B) of the key k the
@@ -191,7 +227,8 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         b["best_seq"].copy_(b["mean"])
         b["prev"].zero_()
         optimizer_key, key = K.split(opt_state.key, 2)
-        spec = without_termination(self.system.rollout_spec(opt_state.system_params, dev))      # (rollout_actions ignores done)
+        prp, sys_params = self._plan_reward(opt_state, None)
+        spec = without_termination(self.system.rollout_spec(sys_params, dev))      # (rollout_actions ignores done)
         st = _hip.current_stream_ptr()
         lib = self.lib
         carry_key = optimizer_key
@@ -206,6 +243,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             b["steps"].zero_(); b["done"].zero_()
             ops.model_rollout(x_dim=X, u_dim=U, actions=b["actions"], obs=b["obs"], first_obs=b["first"], steps=b["steps"], done=b["done"],
                               n_steps=H, episode_length=2 ** 30, seed=particles_key, offset=it, out=b["rows"], **spec)
+            rew_ptr, rew_len, rew_col = self._reward_source(prp, b, 1, b["N"])
             cost_ptr = None
             if self._term_cost is not None:
                 cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, b["N"], next_off=X + U + 2, out=b["term_cost"]).data_ptr()
@@ -219,7 +257,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                 b["cost"] = cost
                 cost_ptr = cost.data_ptr()
             _hip.check(lib.mbpo_icem_update_constrained(
-                b["rows"].data_ptr(), b["rows"].shape[1], X + U, b["NC"], p.num_particles, H, U, b["cand"].data_ptr(), p.num_elites,
+                rew_ptr, rew_len, rew_col, b["NC"], p.num_particles, H, U, b["cand"].data_ptr(), p.num_elites,
                 self.num_prev, float(p.alpha), int(self.use_optimism), cost_ptr, float(p.lambda_constraint), int(self.use_pessimism),
                 b["mean"].data_ptr(), b["std"].data_ptr(), b["best_value"].data_ptr(), b["best_seq"].data_ptr(), b["prev"].data_ptr(),
                 b["values"].data_ptr(), b["rank"].data_ptr(), st), "mbpo_icem_update_constrained")
@@ -254,7 +292,8 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             seeds[it, 0], seeds[it, 1] = sk[:, 0], sk[:, 1]
             carry = K.split_many(sk[:, 0], 2)[:, 0]
         seeds_dev = torch.from_numpy(seeds.view(np.int64)).to(dev)
-        spec = without_termination(self.system.rollout_spec(opt_state.system_params, dev))      # (rollout_actions ignores done)
+        prp, sys_params = self._plan_reward(opt_state, B)
+        spec = without_termination(self.system.rollout_spec(sys_params, dev))      # (rollout_actions ignores done)
         draw = self._batched_ensemble_draws(spec, b)
         st = _hip.current_stream_ptr()
         lib = self.lib
@@ -276,6 +315,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             ops.model_rollout(x_dim=X, u_dim=U, actions=b["actions"], obs=b["obs"], first_obs=b["first"], steps=b["steps"], done=b["done"],
                               n_steps=H, episode_length=2 ** 30, seed=0, offset=it, out=b["rows"], member_idx=draw.get("member_idx"),
                               model_noise=draw.get("model_noise"), **spec)
+            rew_ptr, rew_len, rew_col = self._reward_source(prp, b, B, N)
             cost_ptr = None
             if self._term_cost is not None:
                 cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, NT, next_off=X + U + 2, out=b["term_cost"]).data_ptr()
@@ -289,7 +329,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                 b["cost"] = cost
                 cost_ptr = cost.data_ptr()
             _hip.check(lib.mbpo_icem_update_batched(
-                b["rows"].data_ptr(), b["rows"].shape[1], X + U, B, b["NC"], p.num_particles, H, U, b["cand"].data_ptr(), p.num_elites,
+                rew_ptr, rew_len, rew_col, B, b["NC"], p.num_particles, H, U, b["cand"].data_ptr(), p.num_elites,
                 self.num_prev, float(p.alpha), int(self.use_optimism), cost_ptr, float(p.lambda_constraint), int(self.use_pessimism),
                 b["mean"].data_ptr(), b["std"].data_ptr(), b["best_value"].data_ptr(), b["best_seq"].data_ptr(), b["prev"].data_ptr(),
                 b["values"].data_ptr(), b["rank"].data_ptr(), st), "mbpo_icem_update_batched")

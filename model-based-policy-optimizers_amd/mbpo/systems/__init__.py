@@ -8,5 +8,6 @@ from mbpo.systems.ensemble_system import EnsembleDynamics, EnsembleDynamicsParam
 from mbpo.systems.rewards.pendulum_reward import QuadraticReward
 from mbpo.systems.rewards.term_reward import TermReward, TermRewardParams, Term, Group
 from mbpo.systems.term_cost import TermCost
+from mbpo.systems.plan_reward import PlanRewardParams
 from mbpo.systems.termination import BoxTermination
 from mbpo.systems.time_adaptive import TimeAdaptive

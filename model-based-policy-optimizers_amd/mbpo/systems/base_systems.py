@@ -94,6 +94,8 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
         """`step` of a fused system; terminate=False drops the termination (rollout_policy's scan ignores SystemState.done)."""
         from mbpo import ops
         from mbpo.systems.termination import without_termination
+        from mbpo.systems.plan_reward import refuse_plan_reward
+        refuse_plan_reward(system_params, f"{type(self).__name__}.step")      # (rollout_spec refuses it too; here before any device use)
         if not self.fused:
             raise NotImplementedError(f"{type(self).__name__} must define step(x, u, system_params) itself (batched torch code)")
         dev = _device_of(x)
@@ -129,6 +131,8 @@ class System(ABC, Generic[DynamicsParams, RewardParams]):
     # System: its own `step` between the HIP policy and episode-bookkeeping kernels.
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
         from mbpo import _hip
+        from mbpo.systems.plan_reward import refuse_plan_reward
+        refuse_plan_reward(system_params, f"{type(self).__name__}.rollout_spec")
         return dict(system_kind=_hip.SYS_GENERIC, system=self, system_params=system_params)
 
     @property

@@ -554,6 +554,8 @@ class EnsembleSystem(System):
         return SystemParams(dynamics_params=dp, reward_params=dp, key=keys[2])      # one parameter object: fit updates both
 
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
+        from mbpo.systems.plan_reward import refuse_plan_reward
+        refuse_plan_reward(system_params, "EnsembleSystem.rollout_spec")      # (only iCEM consumes one, and takes it out first)
         rp = system_params.reward_params
         if self.calibrated and system_params.dynamics_params.calibration is None:      # (refused before anything touches the device)
             raise ValueError("calibrated=True but these dynamics parameters have no calibration: run EnsembleDynamics.calibrate "

@@ -8,6 +8,7 @@ import torch
 
 from mbpo import _hip
 from mbpo.systems.base_systems import System, SystemParams, SystemState, _device_of
+from mbpo.systems.plan_reward import refuse_plan_reward
 from mbpo.systems.dynamics.pendulum_dynamics import PendulumDynamics, PendulumDynamicsParams
 from mbpo.systems.rewards.pendulum_reward import PendulumReward, PendulumRewardParams
 from mbpo.systems.termination import BoxTermination, termination_spec
@@ -25,6 +26,7 @@ class PendulumSystem(System[PendulumDynamicsParams, PendulumRewardParams]):
         self.max_action = 1.0
 
     def rollout_spec(self, system_params: SystemParams, device) -> dict:
+        refuse_plan_reward(system_params, "PendulumSystem.rollout_spec")      # (only iCEM consumes one, and takes it out first)
         dp = system_params.dynamics_params or PendulumDynamicsParams()
         rp = system_params.reward_params or PendulumRewardParams()
         ck = (dataclasses.astuple(dp), dataclasses.astuple(rp), str(device), None if self.termination is None else self.termination.key,

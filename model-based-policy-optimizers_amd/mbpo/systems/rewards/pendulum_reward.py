@@ -67,4 +67,13 @@ class QuadraticReward(Reward[QuadraticRewardParams]):
         return _hip.REWARD_QUADRATIC, torch.tensor(list(p.target) + list(p.q) + list(p.r), dtype=torch.float32, device=device)
 
     def __call__(self, x, u, reward_params, x_next=None):
-        raise NotImplementedError("QuadraticReward is evaluated inside the fused System.step / rollout kernels")
+        """Host evaluation through mbpo_reward_eval (the rollout kernels' own expressions): Normal(reward, 0).  x_next never enters."""
+        from mbpo import ops
+        from mbpo.systems.base_systems import _device_of
+        dev = _device_of(x)
+        single = x.dim() == 1
+        xb = x.reshape(-1, self.x_dim).to(dev, torch.float32).contiguous()
+        ub = u.reshape(xb.shape[0], -1)[:, :self.u_dim].to(dev, torch.float32).contiguous()
+        r = ops.reward_eval(_hip.REWARD_QUADRATIC, self.kernel_spec(reward_params, dev)[1], xb, ub)
+        r = r[0] if single else r.reshape(x.shape[:-1])
+        return Normal(r, torch.zeros_like(r)), reward_params

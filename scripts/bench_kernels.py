@@ -811,6 +811,94 @@ def main():
 
     if want("icem_term_cost_case"): icem_term_cost_case(20)
 
+    # ---------------------------------------------------------------- iCEM plan rewards: parameters per problem and per step (one launch per iteration)
+    def icem_plan_reward_case(H):
+        """One Pendulum `optimize` at the reference's defaults, single and at batch_size 64, without and with a [B, H] Pendulum plan
+        reward, timed in alternating rounds (median, min and max of the rounds); and mbpo_plan_reward_eval alone on the rows the last
+        rollout left — the Pendulum kind [B, 1], the quadratic kind [B, H], a 12-term table [B, H], dense (as iCEM issues it) and in place — next
+        to mbpo_traj_cost_eval on the same rows in the same session."""
+        from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
+        from mbpo.systems import Group, PendulumSystem, PlanRewardParams, QuadraticReward, Term, TermCost, TermReward, TermRewardParams
+        from mbpo.systems.rewards.pendulum_reward import PendulumRewardParams, QuadraticRewardParams
+        p = iCemParams()
+        system = PendulumSystem()
+        X, U = system.x_dim, system.u_dim
+        opt = iCemTO(horizon=H, action_dim=U, opt_params=p, system=system)
+        cfg = {"num_samples": p.num_samples, "num_particles": p.num_particles, "num_elites": p.num_elites, "num_steps": p.num_steps,
+               "horizon": H, "x": X, "u": U, "system": "Pendulum"}
+        x1 = torch.tensor([math.cos(2.5), math.sin(2.5), 4.5], device=dev)
+        ROUNDS = 5
+
+        def term12(b, t):
+            c, s = math.cos(0.1 * b + 0.02 * t), math.sin(0.1 * b + 0.02 * t)
+            return TermRewardParams(X, U, 0.0, (
+                Group((Term("x", 0, "square", 1.0, c), Term("x", 1, "square", 1.0, s)), weight=-1.0, link="sqrt"),
+                Group((Term("x_next", 0, "square", -4.0, c), Term("x_next", 1, "square", -4.0, s)), weight=1.0, link="exp"),
+                Group((Term("x", 2, "square", -0.1, 0.0), Term("u", 0, "square", -0.02, 0.0), Term("x", 0, "cos", 0.05, 0.0),
+                       Term("x", 1, "sin", 0.05, 0.0), Term("x", 2, "abs", -0.01, 0.0), Term("x", 2, "relu", -0.01, 5.0),
+                       Term("u", 0, "abs", -0.01, 0.0), Term("x", 0, "identity", 0.1, 0.0)))))
+
+        for B, reps in ((None, 20), (64, 5)):
+            nb = 1 if B is None else B
+            plan = PlanRewardParams.stack(system.reward, [[PendulumRewardParams(target_angle=0.1 * b + 0.02 * t) for t in range(H)]
+                                                          for b in range(nb)], dev)
+            x0 = x1 if B is None else x1.expand(B, X).contiguous()
+            st = opt.init(0, batch_size=B)
+            stp = st.replace(system_params=st.system_params.replace(reward_params=plan))
+            calls = {"plain": lambda st=st, x0=x0: opt.optimize(x0, st), "plan_reward": lambda stp=stp, x0=x0: opt.optimize(x0, stp)}
+            for fn in calls.values():
+                timed(fn, 2, warm=2)
+            times = {k: [] for k in calls}
+            for _ in range(ROUNDS):
+                for k, fn in calls.items():
+                    times[k].append(timed(fn, reps, warm=0))
+            med = {k: sorted(v)[ROUNDS // 2] for k, v in times.items()}
+            for k, v in times.items():
+                out.append({"kernel": f"iCemTO.optimize, reward: {k}", "entry": "mbpo_icem_sample + mbpo_model_rollout"
+                            + (" + mbpo_plan_reward_eval" if k == "plan_reward" else "") + " + mbpo_icem_update x num_steps",
+                            "config": dict(cfg, B=nb, batched=B is not None, table=[nb, H, 3] if k == "plan_reward" else None),
+                            "eager_us": med[k] * 1e6, "eager_us_min": min(v) * 1e6, "eager_us_max": max(v) * 1e6, "rounds": ROUNDS,
+                            "calls_per_round": reps, "bound": "launch" if B is None else "rollout", "over_plain_us": (med[k] - med["plain"]) * 1e6,
+                            "note": "HIP-event time of one eager optimize call; the two forms alternate round by round in one session"})
+                log(f"icem optimize B={nb} reward={k}: {med[k] * 1e6:.1f} us (min {min(v) * 1e6:.1f}, max {max(v) * 1e6:.1f}; "
+                    f"{(med[k] - med['plain']) * 1e6:+.1f} us over plain)")
+            # the kernel alone, on the rows the last rollout left
+            b = opt._bufs if B is None else opt._bbufs
+            group, rows = b["N"], b["rows"]
+            n_rows, row_len = rows.shape
+            qr, tr = QuadraticReward(X, U), TermReward(X, U)
+            tables = {
+                "pendulum [B, 1]": (_hip.REWARD_PENDULUM, PlanRewardParams.stack(system.reward, [[PendulumRewardParams(target_angle=0.1 * bb)]
+                                                                                                 for bb in range(nb)], dev).table),
+                "quadratic [B, H]": (_hip.REWARD_QUADRATIC, PlanRewardParams.stack(qr, [[QuadraticRewardParams(
+                    [math.cos(0.1 * bb + 0.02 * t), math.sin(0.1 * bb + 0.02 * t), 0.0], [1.0, 1.0, 0.1], [0.02]) for t in range(H)]
+                    for bb in range(nb)], dev).table),
+                "12-term table [B, H]": (_hip.REWARD_TERMS, PlanRewardParams.stack(tr, [[term12(bb, t) for t in range(H)] for bb in range(nb)],
+                                                                                   dev).table)}
+            dense = torch.zeros(n_rows, device=dev)
+            for name, (kind, table) in tables.items():
+                for place in ("dense", "in place"):
+                    kw = dict(out=dense) if place == "dense" else dict(reward_col=X + U)
+                    fn = lambda kind=kind, table=table, kw=kw: ops.plan_reward_eval(kind, table, rows, H, nb, group, X, U, next_off=X + U + 2, **kw)
+                    t, te = both(fn, 200)
+                    # in place every cache line of the rows is dirtied by a 4-byte store and written back whole
+                    nbytes = 4 * n_rows * row_len * (1 if place == "dense" else 2) + (4 * n_rows if place == "dense" else 0) + 4 * table.numel()
+                    out.append(hbm_entry(f"k_plan_reward, {name}, {place}", "mbpo_plan_reward_eval",
+                                         dict(cfg, n_problems=nb, group=group, n_rows=n_rows, row_len=row_len, table=list(table.shape), output=place),
+                                         t, nbytes, "the rows' 64 B sectors once (40 B rows: every sector is touched) + the table once + dense: 4 B "
+                                         "per row written; in place: the rows' sectors written back"))
+                    log(f"plan_reward_eval {name}, {place}, n_rows={n_rows}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+            cost = TermCost(X, U, bias=-5.0, groups=[Group([Term("x", 2, "abs")])], reduce="max")
+            buf = torch.zeros(nb * group, device=dev)
+            t, te = both(lambda: cost.trajectory_cost(rows, H, nb * group, out=buf), 200)
+            out.append(hbm_entry("k_traj_cost (yardstick, same rows, same session)", "mbpo_traj_cost_eval",
+                                 dict(cfg, n_traj=nb * group, row_len=row_len, reduce="max", terms=1), t, 4 * n_rows * row_len + 4 * nb * group,
+                                 "the rows' 64 B sectors once + 4 B per trajectory"))
+            log(f"traj_cost_eval (yardstick) n_traj={nb * group}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+            opt._bufs = opt._bbufs = None
+
+    if want("icem_plan_reward_case"): icem_plan_reward_case(20)
+
     res = {"device": torch.cuda.get_device_name(0), "roofs": {"hbm_GBs": HBM_PEAK_GBS, "mfma_f32_TFLOPs": MFMA_F32_PEAK_TF},
            "note": "device_us = HIP-event average per call with the calls captured into a hipGraph and replayed (device time, inputs resident in HBM; multi-launch ops timed whole); eager_us = the same call issued from Python",
            "kernels": out}
