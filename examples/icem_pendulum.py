@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """MPC on the true Pendulum with iCEM, every planning iteration a launch chain on the MI355X path:
 
-    mbpo_icem_sample -> mbpo_model_rollout (open loop) -> [mbpo_plan_reward_eval] -> [mbpo_traj_cost_eval] -> mbpo_icem_update
+    mbpo_icem_sample -> mbpo_model_rollout (open loop) -> [mbpo_plan_reward_eval] -> [mbpo_terminal_value_eval] -> [mbpo_traj_cost_eval]
+                     -> mbpo_icem_update
 
     python examples/icem_pendulum.py [--steps 100] [--horizon 20] [--speed-limit V] [--lambda-constraint L] [--seed 0]
-                                     [--targets A0,A1,...] [--track AMPL,PERIOD]
+                                     [--targets A0,A1,...] [--track AMPL,PERIOD] [--terminal-value [--tv-horizon 5] [--sac-steps 30000]]
 
 --speed-limit V: the plan is constrained to |thetadot| <= V at every step of the horizon — a TermCost, max_t(|thetadot_{t+1}| - V), written as
 data and evaluated on the rollout's rows by one launch (iCemTO(cost_fn=TermCost(...), use_pessimism=True)); the objective of a candidate
@@ -18,6 +19,11 @@ state's reward_params.  Prints each environment's final angle error and its retu
 --track AMPL,PERIOD: one environment follows the target angle AMPL * sin(2 pi t / PERIOD) (t and PERIOD in seconds, dt = 0.05).  The
 planner previews the reference over its horizon — a [1, H, 3] table whose target column is refilled IN PLACE before every `act`
 (no new object, no reallocation; the launch reads what the table holds).  Prints the tracking error.
+
+--terminal-value: a short SAC run on the Pendulum (SACOptimizer(warm_start=True), whose learner state carries the policy, the target
+critics and the observation normaliser), then MPC on the true Pendulum at the short horizon --tv-horizon twice: with
+TerminalValue.from_sac(learner_state, weight=gamma^H / reward_scaling) — min(Q1, Q2) under the policy's mode action at the state the
+horizon ends in, added to every candidate's objective by one launch per iteration — and without it.  Both returns are printed, one seed.
 
 A torque-limited pendulum cannot hold every angle: the prints are a record of what happened, not a claim.
 """
@@ -43,6 +49,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--targets", type=str, default=None, metavar="A0,A1,...", help="batched MPC: one environment per target angle (rad)")
     ap.add_argument("--track", type=str, default=None, metavar="AMPL,PERIOD", help="follow AMPL * sin(2 pi t / PERIOD), previewed over the horizon")
+    ap.add_argument("--terminal-value", action="store_true", help="train SAC briefly, then plan at --tv-horizon with and without its critic")
+    ap.add_argument("--tv-horizon", type=int, default=5, metavar="H")
+    ap.add_argument("--sac-steps", type=int, default=30000, help="--terminal-value: environment steps of the SAC run")
     args = ap.parse_args()
     if args.targets is not None and args.track is not None:
         raise SystemExit("--targets and --track are two runs")
@@ -52,6 +61,10 @@ def main():
     from mbpo.systems import Group, PendulumSystem, Term, TermCost
     dev = torch.device("cuda:0")
     system = PendulumSystem()
+    if args.terminal_value:
+        if args.targets is not None or args.track is not None or args.speed_limit is not None:
+            raise SystemExit("--terminal-value is a run of its own")
+        return run_terminal_value(args, system, dev)
     cost = None
     if args.speed_limit is not None:
         cost = TermCost(system.x_dim, system.u_dim, bias=-args.speed_limit, groups=[Group([Term("x_next", 2, "abs")])], reduce="max")
@@ -125,6 +138,46 @@ def run_track(args, opt, system, dev):
     half = e[len(errs) // 2:]
     print(f"steps {args.steps}  track {ampl:g} * sin(2 pi t / {period:g})  RMS angle error {float(e.pow(2).mean().sqrt()):.4f} rad "
           f"(second half {float(half.pow(2).mean().sqrt()):.4f})  max |error| {float(e.abs().max()):.4f}  final {errs[-1]:+.4f}")
+
+
+def run_terminal_value(args, system, dev):
+    from mbpo.optimizers import SACOptimizer, TerminalValue, iCemParams, iCemTO
+    from mbpo.replay import UniformSamplingQueue
+    from mbpo.types import Transition
+    gamma, reward_scaling, H, n_true = 0.99, 1.0, args.tv_horizon, 2048
+    # a true buffer of start states all over the state space (SAC's environment resets draw from it)
+    gen = torch.Generator().manual_seed(args.seed)
+    th = (torch.rand(n_true, generator=gen) * 2 - 1) * math.pi
+    x = torch.stack([torch.cos(th), torch.sin(th), (torch.rand(n_true, generator=gen) * 2 - 1) * 8], dim=1).to(dev)
+    u = (torch.rand(n_true, 1, generator=gen) * 2 - 1).to(dev)
+    sp = system.init_params(args.seed)
+    st = system.step(x, u, sp)
+    s0 = system.reset()
+    dummy = Transition(observation=s0.x_next, action=torch.zeros(1, device=dev), reward=s0.reward, discount=torch.tensor(gamma, device=dev),
+                       next_observation=s0.x_next)
+    true_buffer = UniformSamplingQueue(max_replay_size=n_true, dummy_data_sample=dummy, sample_batch_size=1, device=dev)
+    tbs = true_buffer.insert(true_buffer.init(args.seed), Transition(observation=x, action=u, reward=st.reward.reshape(-1),
+                                                                     discount=torch.ones(n_true, device=dev), next_observation=st.x_next))
+    sac = SACOptimizer(system=system, true_buffer=true_buffer, warm_start=True, num_timesteps=args.sac_steps, num_evals=1,
+                       reward_scaling=reward_scaling, episode_length=200, normalize_observations=True, discounting=gamma, lr_policy=3e-4,
+                       lr_alpha=3e-4, lr_q=3e-4, num_envs=64, batch_size=128, grad_updates_per_step=32, max_replay_size=2 ** 15,
+                       min_replay_size=2 ** 9, num_eval_envs=1, tau=0.005, num_env_steps_between_updates=5)
+    out = sac.train(opt_state=sac.init(key=args.seed + 3, true_buffer_state=tbs))
+    learner_state = out.optimizer_state.learner_state                     # (warm_start=True: the learner as a value)
+    tv = TerminalValue.from_sac(learner_state, weight=gamma ** H / reward_scaling)
+    sac.close()
+    print(f"SAC: {args.sac_steps} environment steps, {int(learner_state.step_count)} gradient steps;  {tv}")
+    for name, value in (("with the critic", tv), ("without", None)):
+        opt = iCemTO(horizon=H, action_dim=system.action_dim, opt_params=iCemParams(), system=system, terminal_value=value)
+        state = opt.init(args.seed)
+        x = torch.tensor([math.cos(math.pi), math.sin(math.pi), 0.0], device=dev)      # hanging down, at rest
+        ret = 0.0
+        for _ in range(args.steps):
+            a, state = opt.act(x, state)
+            step = system.step(x, a, state.system_params)
+            x, ret = step.x_next, ret + float(step.reward)
+        print(f"horizon {H}  {name:16s} steps {args.steps}  return {ret:.2f}  final angle {math.atan2(float(x[1]), float(x[0])):+.3f} rad  "
+              f"final |thetadot| {abs(float(x[2])):.3f}")
 
 
 if __name__ == "__main__":

@@ -973,6 +973,52 @@ int mbpo_plan_reward_eval(int32_t reward_kind, const float *params, int32_t para
                           const float *rows, int32_t row_len, int32_t next_off, int32_t n_steps, int32_t n_problems, int64_t group,
                           int32_t x_dim, int32_t u_dim, float *out, int64_t out_stride, void *stream);
 
+/* ---- terminal values: a learned critic at the end of the planned horizon, evaluated on the rollout's rows ------------------------------
+ * replaces: nothing in the reference tree, whose iCEM objective is the sum of the horizon's rewards and nothing else.  Build-defined
+ *           (mbpo.optimizers.TerminalValue): THIS TEXT IS THE DEFINITION.
+ * For row i, x(i) = x + i * x_stride is a state of x_dim floats (iCEM: the next-state columns of trajectory i's last-step row, x_stride =
+ * row_len).  With n(x) = (x - norm_mean) / norm_std, a true division, or n(x) = x when both pointers are NULL:
+ *   kind V (action_dim == 0)  v(i) = min_k V_k(n(x(i))), k < critic.n_nets in {1, 2}; networks [x_dim] -> [1] (BPTT's twin target critic;
+ *                             PPO's value network with one net)
+ *   kind Q (action_dim  > 0)  a = tanh(loc(policy(n(x)))), loc the first action_dim of the policy's 2 action_dim outputs (the mode of
+ *                             SAC's NormalTanh policy), tanhf the accurate one;  v(i) = min(Q_1, Q_2)([n(x) | a]); critic.n_nets == 2,
+ *                             networks [x_dim + action_dim] -> [1].  action_dim is the policy's action width: on an optimistic system
+ *                             u_dim + x_dim, the critics having been trained on [u | eta].
+ *   bonus(i) = fl(weight * v(i))                                   the product rounded on its own (__fmul_rn)
+ *   out[i * out_stride] = bonus(i)                                 accumulate 0
+ *                       = fl(out[i * out_stride] + bonus(i))       accumulate 1: the sum rounded on its own (__fadd_rn)
+ *                       = -inf                                     either mode, where a component of x(i) is not finite: a store, not an
+ *                                                                  add, so a diverged trajectory ranks below every finite one and carries
+ *                                                                  no NaN into a ranking; the other rows of its tile keep their bits
+ * The minimum is torch.minimum's (a NaN wins).  There is no entropy term, no discounting and no reward un-scaling: weight is the caller's
+ * (typically gamma^H / reward_scaling for SAC's critics, r_std * gamma^H for BPTT's normalised critic); a constant shift of v changes no
+ * ranking and is not offered.  The value of a row depends on that row alone — not on n, its tile or its position.
+ * In iCEM: one launch with accumulate 1 between the reward source and mbpo_icem_update*, x = rows + ((H - 1) n_traj) row_len + next_off,
+ * x_stride = row_len, out = the last step's n_traj rewards of whichever source the update reads (the rows' reward column, out_stride =
+ * row_len; a plan reward's dense buffer, out_stride = 1), n = n_traj: the objective becomes J_i = sum_{t<H} r_t(i) + bonus(i) (the update
+ * ranks J_i / H, the reference's mean over steps).  Only those n_traj floats are touched; the update kernels are unchanged.
+ * One workgroup per tile of 16 rows, persistent; each out element is written by exactly one thread (no atomics); x needs no alignment.
+ * Nothing but out[i * out_stride], i < n, is written.  No workspace, no allocation, no host read-back; capturable.  The parameters and
+ * the normaliser are read by the launch: tensors refreshed in place between two launches (or two replays) are honoured.
+ * MBPO_ERR_ARG before any device use: x_dim < 1, action_dim < 0, n < 0, accumulate not 0 or 1, a network with bad sizes
+ * (mbpo_mlp_desc's rules), critic.n_nets outside {1, 2} or kind Q with one critic, critic.dims[0] != x_dim + action_dim, a critic that
+ * does not end in one output, kind Q with policy.n_nets != 1, policy.dims[0] != x_dim or a policy that does not end in 2 action_dim
+ * outputs, exactly one of norm_mean / norm_std set, x_stride < x_dim, out_stride < 1, n * x_stride or n * out_stride overflowing
+ * int64, or with n > 0 a NULL critic.params, policy.params (kind Q), x or out.  MBPO_ERR_UNSUPPORTED (the message says so by name):
+ * hidden layers of a network that do not share one width in {64, 128, 256} (what the wave chains take, as mbpo_ensemble_mlp_forward's
+ * generic kernel), action_dim > 64, or shapes whose tiles do not fit the LDS.  Policy and critics may differ in width; the kernel is
+ * built for the larger one.  n == 0: MBPO_OK, nothing is launched. */
+typedef struct mbpo_terminal_value_desc {
+  int32_t x_dim, action_dim;            /* action_dim == 0: kind V */
+  mbpo_mlp_desc critic;                 /* n_nets 1 or 2 (kind Q: 2); [x_dim + action_dim] -> [1] */
+  mbpo_mlp_desc policy;                 /* kind Q: [x_dim] -> [2*action_dim]; ignored for kind V */
+  const float *norm_mean, *norm_std;    /* [x_dim], both or neither */
+  const float *x;  int64_t x_stride;    /* terminal state of row i at x + i*x_stride (floats); no alignment assumed */
+  float *out;      int64_t out_stride;  /* out[i*out_stride] */
+  int64_t n;  float weight;  int32_t accumulate;   /* 1: out += bonus, 0: out = bonus */
+} mbpo_terminal_value_desc;
+int mbpo_terminal_value_eval(const mbpo_terminal_value_desc *d, void *stream);
+
 /* ---- one-shot all-reduce over xGMI peer memory (multi-GPU SAC gradient exchange) ------------------------
  * replaces: the live form of the reference's jax.lax.pmean(grad) (sac/utils.py:29-33) for vectors small enough that a
  *           collective is pure latency.  Every rank owns an exchange REGION (mbpo_p2p_alloc -> 64-byte IPC handle, passed to

@@ -13,6 +13,7 @@ from typing import Optional, Sequence
 import torch
 
 MBPO_MAX_LAYERS = 8
+ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3
 ACT_IDS = {"swish": 0, "silu": 0, "relu": 1, "tanh": 2}
 
 SYS_PENDULUM, SYS_ENSEMBLE = 0, 1
@@ -47,6 +48,18 @@ class MlpDesc(C.Structure):
         ("n_layers", C.c_int32),
         ("dims", C.c_int32 * (MBPO_MAX_LAYERS + 1)),
         ("activation", C.c_int32),
+    ]
+
+
+class TerminalValueDesc(C.Structure):
+    """mbpo_terminal_value_desc"""
+    _fields_ = [
+        ("x_dim", C.c_int32), ("action_dim", C.c_int32),
+        ("critic", MlpDesc), ("policy", MlpDesc),
+        ("norm_mean", C.c_void_p), ("norm_std", C.c_void_p),
+        ("x", C.c_void_p), ("x_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_stride", C.c_int64),
+        ("n", C.c_int64), ("weight", C.c_float), ("accumulate", C.c_int32),
     ]
 
 
@@ -300,6 +313,10 @@ def _bind_optional(lib: C.CDLL) -> None:
     if fn is not None:
         fn.restype = C.c_int
         fn.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, i64, i32, i32, vp, i64, vp]
+    fn = getattr(lib, "mbpo_terminal_value_eval", None)   # (bound when present, as mbpo_plan_reward_eval)
+    if fn is not None:
+        fn.restype = C.c_int
+        fn.argtypes = [C.POINTER(TerminalValueDesc), vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

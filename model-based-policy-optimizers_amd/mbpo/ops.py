@@ -495,6 +495,59 @@ def plan_reward_eval(reward_kind: int, table: torch.Tensor, rows: torch.Tensor, 
     return ret
 
 
+def terminal_value_eval(*, x_dim: int, action_dim: int, critic_params: torch.Tensor, critic_dims: Sequence[int], n_critics: int,
+                        activation: str = "swish", policy_params: Optional[torch.Tensor] = None, policy_dims: Optional[Sequence[int]] = None,
+                        policy_activation: str = "swish", norm_mean: Optional[torch.Tensor] = None,
+                        norm_std: Optional[torch.Tensor] = None, x: torch.Tensor, x_offset: int = 0, x_stride: Optional[int] = None,
+                        out: Optional[torch.Tensor] = None, out_offset: int = 0, out_stride: int = 1, n: Optional[int] = None,
+                        weight: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """mbpo_terminal_value_eval (include/mbpo_hip.h "terminal values"): out[out_offset + i * out_stride] = (or +=, accumulate)
+    fl(weight * V(x_i)), x_i the x_dim floats of `x` at x_offset + i * x_stride (offsets and strides in floats of the flattened
+    tensors), i < n; -inf where x_i is not finite.  action_dim 0: V = min over `n_critics` state-value nets; action_dim > 0: V =
+    min(Q1, Q2)([n(x) | tanh(loc(policy(n(x))))]).  x [n, x_dim] with the defaults; `out` is allocated [n] when None.  One launch, no
+    allocation when `out` is given.  Shapes the wave chains do not take (hidden widths outside 64 / 128 / 256) are a ValueError."""
+    lib = load()
+    _req(x, "x")
+    X, A = int(x_dim), int(action_dim)
+    if x_stride is None:
+        x_stride = X
+    if n is None:
+        n = (x.numel() - int(x_offset)) // int(x_stride) if x.numel() else 0
+    n, x_offset, x_stride, out_offset, out_stride = int(n), int(x_offset), int(x_stride), int(out_offset), int(out_stride)
+    if n < 0 or x_offset < 0 or out_offset < 0:
+        raise ValueError("n, x_offset and out_offset must be >= 0")
+    if n > 0 and x_stride >= X and x_offset + (n - 1) * x_stride + X > x.numel():
+        raise ValueError(f"x holds {x.numel()} floats; {n} states of {X} at offset {x_offset}, stride {x_stride} end at "
+                         f"{x_offset + (n - 1) * x_stride + X}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an `out` to add into")
+        out = torch.empty(out_offset + max(n - 1, 0) * max(out_stride, 1) + (1 if n else 0), device=x.device, dtype=torch.float32)
+    _req(out, "out")
+    if n > 0 and out_stride >= 1 and out_offset + (n - 1) * out_stride + 1 > out.numel():
+        raise ValueError(f"out holds {out.numel()} floats; {n} values at offset {out_offset}, stride {out_stride} end at "
+                         f"{out_offset + (n - 1) * out_stride + 1}")
+    d = _hip.TerminalValueDesc()
+    d.x_dim, d.action_dim = X, A
+    d.critic = mlp_desc(_req(critic_params, "critic_params"), critic_dims, activation, int(n_critics))
+    if A > 0:
+        if policy_params is None or policy_dims is None:
+            raise ValueError("action_dim > 0 (kind Q) needs policy_params and policy_dims")
+        d.policy = mlp_desc(_req(policy_params, "policy_params"), policy_dims, policy_activation, 1)
+    for name, t in (("norm_mean", norm_mean), ("norm_std", norm_std)):
+        if t is not None and _req(t, name).numel() != X:
+            raise ValueError(f"{name} holds {t.numel()} floats, x_dim is {X}")
+    d.norm_mean, d.norm_std = ptr(norm_mean), ptr(norm_std)
+    d.x, d.x_stride = x.data_ptr() + 4 * x_offset, x_stride
+    d.out, d.out_stride = out.data_ptr() + 4 * out_offset, out_stride
+    d.n, d.weight, d.accumulate = n, float(weight), int(bool(accumulate))
+    rc = lib.mbpo_terminal_value_eval(C.byref(d), current_stream_ptr())
+    if rc == _hip.ERR_UNSUPPORTED:
+        raise ValueError("mbpo_terminal_value_eval: " + lib.mbpo_last_error().decode("utf-8", "replace"))
+    check(rc, "mbpo_terminal_value_eval")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ user-defined System (non-fused)
 def policy_act(policy_params: torch.Tensor, policy_spec: MlpSpec, obs: torch.Tensor, norm_mean=None, norm_std=None,
                deterministic: bool = False, action_clip: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0,

@@ -20,6 +20,14 @@ one ordinary parameter object (its reward column is computed and not used), one 
 under the table into a dense buffer, and the unchanged update launch reads that buffer as (rows = buffer, row_len = 1, reward_col = 0).  The table is read by that launch: refilled in place between two `act`
 calls it is honoured without a new object.  Without a PlanRewardParams every path issues exactly the launches it issued before.
 
+Terminal value: `iCemTO(..., terminal_value=TerminalValue(...))` (mbpo.optimizers) adds weight * V(x_H) — a learned critic at the state the
+horizon ends in: SAC's twin Q under its policy's mode action, BPTT's twin target critic, PPO's value network — to every trajectory's
+objective.  One launch of mbpo_terminal_value_eval, after the reward source and before the update, adds it into the last step's rewards
+the update launch reads (the rows' own reward column, or the plan reward's dense buffer); the update kernels are unchanged, and a
+trajectory whose terminal state is not finite gets -inf there.  It composes with a TermCost, a callable cost_fn, use_optimism /
+use_pessimism, the TS modes and warm starts, none of which reads the reward column.  With terminal_value=None every path issues exactly
+the launches it issued before.
+
 Batched MPC: `init(key, batch_size=B)` makes a state for B independent problems (best_sequence [B, H, U], best_reward [B], key = B
 host integers) and `optimize` / `act` on such a state plan for obs [B, x] in one launch chain per iteration —
 mbpo_icem_sample_batched -> one rollout over all B*NC*P envs -> mbpo_icem_update_batched (one workgroup per problem).  Problem b
@@ -40,6 +48,7 @@ import torch
 
 from mbpo import _hip, ops
 from mbpo.optimizers.base_optimizer import BaseOptimizer
+from mbpo.optimizers.trajectory_optimizers.terminal_value import TerminalValue
 from mbpo.replay import ReplayBufferState
 from mbpo.systems.base_systems import System
 from mbpo.systems.dynamics.base_dynamics import DynamicsParams
@@ -90,9 +99,13 @@ class iCemTrainingOutput(OptimizerTrainingOutPut, Generic[DynamicsParams, Reward
 
 class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
     def __init__(self, horizon: int, action_dim: int, key: int = K.PRNGKey(0), opt_params: iCemParams = iCemParams(), cost_fn=None,
-                 use_optimism: bool = False, use_pessimism: bool = False, *args, **kwargs):
+                 use_optimism: bool = False, use_pessimism: bool = False, *args, terminal_value: Optional[TerminalValue] = None, **kwargs):
         super().__init__(*args, **kwargs)
         refuse_time_adaptive(self.system, "iCEM")
+        if terminal_value is not None and not isinstance(terminal_value, TerminalValue):
+            raise ValueError(f"terminal_value must be a TerminalValue (mbpo.optimizers) or None, got {type(terminal_value).__name__}")
+        self.terminal_value = terminal_value      # a learned critic at x_H, added on the device (see the module docstring)
+        self._check_terminal_value(self.system)
         self.cost_fn = cost_fn       # evaluated on the host side of the seam, between two launches (see the module docstring)
         self._term_cost = cost_fn if isinstance(cost_fn, TermCost) else None      # ... or on the device, by mbpo_traj_cost_eval
         self._check_term_cost(self.system)
@@ -111,7 +124,25 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
     def set_system(self, system):
         refuse_time_adaptive(system, "iCEM")      # (single and batched: the candidates' objective sums per-step rewards)
         self._check_term_cost(system)
+        self._check_terminal_value(system)
         super().set_system(system)
+
+    def _check_terminal_value(self, system):
+        """A TerminalValue's widths against the system's: x_dim, and kind Q's action width against system.action_dim."""
+        if self.terminal_value is not None:
+            self.terminal_value.check_system(system)
+
+    def _add_terminal_value(self, b: dict, prp: Optional[PlanRewardParams], rew_len: int, rew_col: int, n: int) -> None:
+        """One launch of mbpo_terminal_value_eval (accumulate): weight * V(x_H) of every trajectory — x_H the next-state columns of its
+        last-step row — added into the last step's reward of whichever source the update reads (the rows' own reward column, or the
+        plan reward's dense buffer).  Only those n values are touched."""
+        tv = self.terminal_value
+        if tv is None:
+            return
+        rows, H, X, U = b["rows"], self.horizon, self.system.x_dim, self.action_dim
+        row_len, last = rows.shape[1], (H - 1) * n
+        tv.eval_into(rows, last * row_len + X + U + 2, row_len, rows if prp is None else b["plan_reward"], last * rew_len + rew_col,
+                     rew_len, n, accumulate=True)
 
     def _check_term_cost(self, system):
         """A TermCost's widths against the system's: u_dim is the control width the dynamics see, not action_dim."""
@@ -210,6 +241,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
     def optimize(self, initial_state: torch.Tensor, opt_state: iCemOptimizerState) -> iCemOptimizerState:
         assert self.system is not None, "iCem optimizer requires system to be defined."
         self._check_term_cost(self.system)      # (a system assigned without set_system)
+        self._check_terminal_value(self.system)
         if opt_state.batched:
             return self._optimize_batched(initial_state, opt_state)
         p, H, U = self.opt_params, self.horizon, self.action_dim
@@ -244,6 +276,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             ops.model_rollout(x_dim=X, u_dim=U, actions=b["actions"], obs=b["obs"], first_obs=b["first"], steps=b["steps"], done=b["done"],
                               n_steps=H, episode_length=2 ** 30, seed=particles_key, offset=it, out=b["rows"], **spec)
             rew_ptr, rew_len, rew_col = self._reward_source(prp, b, 1, b["N"])
+            self._add_terminal_value(b, prp, rew_len, rew_col, b["N"])
             cost_ptr = None
             if self._term_cost is not None:
                 cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, b["N"], next_off=X + U + 2, out=b["term_cost"]).data_ptr()
@@ -316,6 +349,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                               n_steps=H, episode_length=2 ** 30, seed=0, offset=it, out=b["rows"], member_idx=draw.get("member_idx"),
                               model_noise=draw.get("model_noise"), **spec)
             rew_ptr, rew_len, rew_col = self._reward_source(prp, b, B, N)
+            self._add_terminal_value(b, prp, rew_len, rew_col, NT)
             cost_ptr = None
             if self._term_cost is not None:
                 cost_ptr = self._term_cost.trajectory_cost(b["rows"], H, NT, next_off=X + U + 2, out=b["term_cost"]).data_ptr()
@@ -378,8 +412,14 @@ class iCEMOptimizer(BaseOptimizer):
     once (init makes a batched state, act(obs [B, x]) returns actions [B, u]); None keeps the single-state interface."""
 
     def __init__(self, horizon: int, opt_params: iCemParams = iCemParams(), system: Optional[System] = None, key: int = K.PRNGKey(0),
-                 batch_size: Optional[int] = None, **agent_kwargs):
+                 batch_size: Optional[int] = None, terminal_value: Optional[TerminalValue] = None, **agent_kwargs):
         refuse_time_adaptive(system, "iCEM")
+        if terminal_value is not None:
+            if not isinstance(terminal_value, TerminalValue):
+                raise ValueError(f"terminal_value must be a TerminalValue (mbpo.optimizers) or None, got {type(terminal_value).__name__}")
+            terminal_value.check_system(system)
+            agent_kwargs = dict(agent_kwargs, terminal_value=terminal_value)
+        self.terminal_value = terminal_value
         super().__init__(system, key)
         self.horizon, self.key, self.opt_params = horizon, key, opt_params
         self.batch_size = None if batch_size is None else int(batch_size)
@@ -391,6 +431,8 @@ class iCEMOptimizer(BaseOptimizer):
 
     def set_system(self, system):
         refuse_time_adaptive(system, "iCEM")
+        if self.terminal_value is not None:
+            self.terminal_value.check_system(system)
         super().set_system(system)
 
     @property

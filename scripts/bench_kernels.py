@@ -899,6 +899,84 @@ def main():
 
     if want("icem_plan_reward_case"): icem_plan_reward_case(20)
 
+    # ---------------------------------------------------------------- iCEM terminal value: a learned critic at x_H (one launch per iteration)
+    def icem_terminal_value_case():
+        """mbpo_terminal_value_eval alone under graph replay at 5150 rows (one problem) and 329 600 rows (batch_size 64), kind V (a twin
+        64 x 3 critic) and kind Q (a 64 x 3 policy and twin 64 x 3 Q), x = 3, A = 1, strided exactly as iCEM passes it (states in the
+        next-state columns of 10-float rows, the sum into the rows' reward column), next to mbpo_ensemble_mlp_forward with two 64 x 3
+        members on the same number of DENSE rows in the same session (the yardstick: the same wave chains, no gather, no policy); and one
+        Pendulum `optimize` — H = 20 at the defaults, H = 5 without and with the value — single and at batch_size 64, median of five
+        alternating rounds."""
+        from mbpo.optimizers import TerminalValue
+        from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
+        from mbpo.systems import PendulumSystem
+        X, A, hid = 3, 1, [64, 64, 64]
+        vd, qd, pd = [X, *hid, 1], [X + A, *hid, 1], [X, *hid, 2 * A]
+        gg = torch.Generator().manual_seed(11)
+        noisy = lambda dims, n=1: (lambda p: p + 0.1 * torch.randn(p.shape, generator=gg))(lecun_flat(dims, gg, n)).to(dev)
+        mean, std = torch.randn(X, generator=gg).to(dev), (torch.rand(X, generator=gg) + 0.5).to(dev)
+        values = {"V": TerminalValue(X, noisy(vd, 2), vd, n_critics=2, norm_mean=mean, norm_std=std, weight=0.95),
+                  "Q": TerminalValue(X, noisy(qd, 2), qd, policy_params=noisy(pd), policy_dims=pd, norm_mean=mean, norm_std=std, weight=0.95)}
+        row_len, reward_col, next_off = 2 * X + A + 3, X + A, X + A + 2
+        macs = {"V": 2 * mlp_macs(vd), "Q": 2 * mlp_macs(qd) + mlp_macs(pd)}
+        for n in (5150, 64 * 5150):
+            rows = torch.randn(n, row_len, generator=gg).to(dev)
+            for kind, tv in values.items():
+                t, te = both(lambda tv=tv: tv.eval_into(rows, next_off, row_len, rows, reward_col, row_len, n, accumulate=True), 200)
+                rows.copy_(torch.randn(n, row_len, generator=gg))      # (the sums ran away: fresh numbers for the next form)
+                out.append(mfma_entry(f"k_terminal_value<64>, kind {kind}", "mbpo_terminal_value_eval",
+                                      {"n": n, "x": X, "A": A, "critic": vd if kind == "V" else qd, "n_critics": 2,
+                                       "policy": pd if kind == "Q" else None, "x_stride": row_len, "out_stride": row_len, "accumulate": 1},
+                                      t, 2 * macs[kind] * n, "2 flop per MAC of every network, per row"))
+                log(f"terminal_value_eval kind {kind}, n={n}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+            for lean in (1, 0):      # the yardstick: the dispatch's throughput kernel (3 inputs: it applies), and the generic wave-chain kernel
+                _hip.load().mbpo_debug_set_ens_lean(lean)
+                try:
+                    spec = ops.MlpSpec(vd, "swish", 2)
+                    pe, xd = noisy(vd, 2), torch.randn(n, X, generator=gg).to(dev)
+                    ty, te = both(lambda: ops.ensemble_mlp_forward(pe, spec, xd), 200)
+                finally:
+                    _hip.load().mbpo_debug_set_ens_lean(-1)
+                which = "k_ens_fwd_lean" if lean else "k_ensemble_forward<64>"
+                out.append(mfma_entry(f"{which} (yardstick, same rows, same session)", "mbpo_ensemble_mlp_forward",
+                                      {"n": n, "dims": vd, "members": 2, "input": "dense", "note": "allocates its output per call"}, ty,
+                                      2 * 2 * mlp_macs(vd) * n, "2 flop per MAC of both members, per row"))
+                log(f"ensemble_mlp_forward {which} 2 x {vd}, n={n}: {ty * 1e6:.1f} us (eager {te * 1e6:.1f})")
+        # one optimize
+        system = PendulumSystem()
+        p = iCemParams()
+        x1 = torch.tensor([math.cos(2.5), math.sin(2.5), 4.5], device=dev)
+        forms = {"H20": (20, None), "H5": (5, None), "H5 + V": (5, values["V"]), "H5 + Q": (5, values["Q"])}
+        opts = {k: iCemTO(horizon=h, action_dim=A, opt_params=p, system=system, terminal_value=tv) for k, (h, tv) in forms.items()}
+        ROUNDS = 5
+        for B, reps in ((None, 20), (64, 5)):
+            calls = {}
+            for k, opt in opts.items():
+                st = opt.init(0, batch_size=B)
+                x0 = x1 if B is None else x1.expand(B, X).contiguous()
+                calls[k] = (lambda opt=opt, x0=x0, st=st: opt.optimize(x0, st))
+                timed(calls[k], 2, warm=2)
+            times = {k: [] for k in calls}
+            for _ in range(ROUNDS):
+                for k, fn in calls.items():
+                    times[k].append(timed(fn, reps, warm=0))
+            med = {k: sorted(v)[ROUNDS // 2] for k, v in times.items()}
+            for k, v in times.items():
+                out.append({"kernel": f"iCemTO.optimize, {k}", "entry": "mbpo_icem_sample + mbpo_model_rollout"
+                            + (" + mbpo_terminal_value_eval" if "+" in k else "") + " + mbpo_icem_update x num_steps",
+                            "config": {"num_samples": p.num_samples, "num_particles": p.num_particles, "num_elites": p.num_elites,
+                                       "num_steps": p.num_steps, "horizon": forms[k][0], "system": "Pendulum", "B": 1 if B is None else B,
+                                       "batched": B is not None, "terminal_value": k.split("+ ")[1] if "+" in k else None},
+                            "eager_us": med[k] * 1e6, "eager_us_min": min(v) * 1e6, "eager_us_max": max(v) * 1e6, "rounds": ROUNDS,
+                            "calls_per_round": reps, "bound": "launch" if B is None else "rollout", "over_H5_us": (med[k] - med["H5"]) * 1e6,
+                            "note": "HIP-event time of one eager optimize call; the forms alternate round by round in one session"})
+                log(f"icem optimize B={B or 1} {k}: {med[k] * 1e6:.1f} us (min {min(v) * 1e6:.1f}, max {max(v) * 1e6:.1f}; "
+                    f"{(med[k] - med['H5']) * 1e6:+.1f} us over H5)")
+            for opt in opts.values():
+                opt._bufs = opt._bbufs = None
+
+    if want("icem_terminal_value_case"): icem_terminal_value_case()
+
     res = {"device": torch.cuda.get_device_name(0), "roofs": {"hbm_GBs": HBM_PEAK_GBS, "mfma_f32_TFLOPs": MFMA_F32_PEAK_TF},
            "note": "device_us = HIP-event average per call with the calls captured into a hipGraph and replayed (device time, inputs resident in HBM; multi-launch ops timed whole); eager_us = the same call issued from Python",
            "kernels": out}
