@@ -40,6 +40,8 @@ class BpttConfig:
     critic_dims: Sequence[int]     # [x, features..., 1]
     horizon: int = 20
     act: str = "swish"
+    actor_act: Optional[str] = None      # None: `act`
+    critic_act: Optional[str] = None     # None: `act`
     init_stddev: float = 1.0
     discount: float = 0.99
     lambda_: float = 0.97
@@ -49,6 +51,10 @@ class BpttConfig:
     lr_critic: float = 1e-3
     wd_critic: float = 1e-5
     tau: float = 0.005
+
+    def __post_init__(self):
+        self.actor_act = self.actor_act or self.act
+        self.critic_act = self.critic_act or self.act
 
     @property
     def P(self):
@@ -65,7 +71,7 @@ def inv_softplus(x: float) -> float:
 
 def actor_forward(cfg: BpttConfig, params, obs_n):
     """Actor.__call__ (:131-142): mu, sig = split(MLP(obs)); sig = clip(softplus(sig + inv_softplus(init_std)), 1e-6, 1e2)."""
-    out = nets.mlp_forward(params, cfg.actor_dims, obs_n, cfg.act)
+    out = nets.mlp_forward(params, cfg.actor_dims, obs_n, cfg.actor_act)
     u = cfg.u_dim
     mu, raw = out[..., :u], out[..., u:]
     sig = torch.clamp(F.softplus(raw + inv_softplus(cfg.init_stddev)), 1e-6, 1e2)
@@ -75,8 +81,8 @@ def actor_forward(cfg: BpttConfig, params, obs_n):
 def critic_forward(cfg: BpttConfig, params, obs_n):
     """Critic.__call__ (:155-172): two independent MLPs -> (v1, v2)."""
     C = cfg.C
-    v1 = nets.mlp_forward(params[:C], cfg.critic_dims, obs_n, cfg.act)[..., 0]
-    v2 = nets.mlp_forward(params[C:2 * C], cfg.critic_dims, obs_n, cfg.act)[..., 0]
+    v1 = nets.mlp_forward(params[:C], cfg.critic_dims, obs_n, cfg.critic_act)[..., 0]
+    v2 = nets.mlp_forward(params[C:2 * C], cfg.critic_dims, obs_n, cfg.critic_act)[..., 0]
     return v1, v2
 
 

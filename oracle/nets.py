@@ -49,7 +49,30 @@ def unflatten(params: torch.Tensor, dims: Sequence[int]) -> List[Tuple[torch.Ten
     return out
 
 
+_TAP = None      # optional recorder of every pre-activation: called as _TAP(z, act) while a `tap` block is open
+
+
+class tap:
+    """with nets.tap(fn): every activation(z, act) inside the block first calls fn(z, act) — how a test reads the pre-activations
+    of an oracle run (e.g. the distance of relu units from their kink) without changing what the run computes."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __enter__(self):
+        global _TAP
+        self.prev, _TAP = _TAP, self.fn
+        return self
+
+    def __exit__(self, *exc):
+        global _TAP
+        _TAP = self.prev
+        return False
+
+
 def activation(x: torch.Tensor, act: str) -> torch.Tensor:
+    if _TAP is not None:
+        _TAP(x, act)
     if act in ("swish", "silu"):
         return x * torch.sigmoid(x)
     if act == "relu":

@@ -24,7 +24,7 @@ FIT_SITE_HOLDOUT = 1
 
 def eval_metrics(params: torch.Tensor, dims: Sequence[int], n_members: int, rows: torch.Tensor, idx: torch.Tensor, x_dim: int, u_dim: int,
                  predict_delta: bool = True, min_std: float = 1e-3, reward_off: Optional[int] = None,
-                 next_obs_off: Optional[int] = None) -> torch.Tensor:
+                 next_obs_off: Optional[int] = None, act: str = "swish") -> torch.Tensor:
     """[2, E] in the dtype of `params` (pass doubles for the fp64 reference)."""
     P = nets.n_params(dims)
     X = x_dim
@@ -33,7 +33,7 @@ def eval_metrics(params: torch.Tensor, dims: Sequence[int], n_members: int, rows
     t = b[:, noff:noff + X] - (b[:, :X] if predict_delta else 0.0)
     out = []
     for e in range(n_members):
-        y = nets.mlp_forward(params[e * P:(e + 1) * P], dims, b[:, :X + u_dim], "swish")
+        y = nets.mlp_forward(params[e * P:(e + 1) * P], dims, b[:, :X + u_dim], act)
         mu, sigma = y[:, :X], F.softplus(y[:, X:2 * X]) + min_std
         q = (t - mu) / sigma
         nll = (0.5 * q * q + torch.log(sigma)).sum(dim=1)

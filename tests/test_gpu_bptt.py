@@ -19,10 +19,11 @@ from oracle import systems as osys
 pytestmark = pytest.mark.gpu
 
 
-def _setup(X, U, H, n, system, E, seed, hidden=(64, 64, 64)):
+def _setup(X, U, H, n, system, E, seed, hidden=(64, 64, 64), acts=("swish", "swish", "swish")):
+    """acts: the activations of (actor, critics, ensemble members)."""
     g = torch.Generator().manual_seed(seed)
     cfg = obptt.BpttConfig(x_dim=X, u_dim=U, actor_dims=[X, *hidden, 2 * U], critic_dims=[X, *hidden, 1], horizon=H,
-                           discount=0.97, lambda_=0.9, ent_coef=0.05, init_stddev=1.0)
+                           discount=0.97, lambda_=0.9, ent_coef=0.05, init_stddev=1.0, actor_act=acts[0], critic_act=acts[1])
     ap = onets.init_mlp_flat(cfg.actor_dims, g) + 0.02 * torch.randn(cfg.P, generator=g)
     cp = torch.cat([onets.init_mlp_flat(cfg.critic_dims, g) + 0.02 * torch.randn(cfg.C, generator=g) for _ in range(2)])
     if X == 3:
@@ -40,8 +41,8 @@ def _setup(X, U, H, n, system, E, seed, hidden=(64, 64, 64)):
         dd = [X + U, *hidden, 2 * X]
         dp = torch.cat([onets.init_mlp_flat(dd, g) * 0.5 + 0.01 * torch.randn(onets.n_params(dd), generator=g) for _ in range(E)])
         tgt, q, r = torch.randn(X, generator=g) * 0.3, torch.rand(X, generator=g), torch.rand(U, generator=g) * 0.2
-        tsys = obptt.TorchEnsembleSystem(dp, dd, E, X, U, tgt, q, r)
-        extra = dict(dd=dd, dp=dp, tgt=tgt, q=q, r=r)
+        tsys = obptt.TorchEnsembleSystem(dp, dd, E, X, U, tgt, q, r, act=acts[2])
+        extra = dict(dd=dd, dp=dp, tgt=tgt, q=q, r=r, act=acts[2])
     return cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, tsys, extra
 
 
@@ -49,7 +50,8 @@ def _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, n,
     from mbpo import _hip, ops
     op = ops.BpttActorGrad(x_dim=cfg.x_dim, u_dim=cfg.u_dim, horizon=cfg.horizon, actor_dims=cfg.actor_dims,
                            critic_dims=cfg.critic_dims, n=n, device=dev, init_stddev=cfg.init_stddev, discount=cfg.discount,
-                           lambda_=cfg.lambda_, ent_coef=cfg.ent_coef, seed=seed)
+                           lambda_=cfg.lambda_, ent_coef=cfg.ent_coef, seed=seed, actor_activation=cfg.actor_act,
+                           critic_activation=cfg.critic_act)
     kw = {}
     if system == "pendulum":
         pp = osys.PendulumParams()
@@ -58,7 +60,7 @@ def _run_hip(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, n,
     else:
         kw.update(system_kind=_hip.SYS_ENSEMBLE, reward_kind=_hip.REWARD_QUADRATIC,
                   reward_params=torch.cat([extra["tgt"], extra["q"], extra["r"]]).to(dev), dyn_params=extra["dp"].to(dev),
-                  dyn_spec=ops.MlpSpec(extra["dd"], "swish", extra["dp"].numel() // onets.n_params(extra["dd"])))
+                  dyn_spec=ops.MlpSpec(extra["dd"], extra["act"], extra["dp"].numel() // onets.n_params(extra["dd"])))
     op(actor_params=ap.to(dev), target_critic_params=cp.to(dev), init_states=x0.to(dev), state_mean=s_mean.to(dev),
        state_std=s_std.to(dev), reward_mean_std=r_ms.to(dev), act_noise=noise.to(dev) if explicit_noise else None, offset=offset, **kw)
     torch.cuda.synchronize()
@@ -84,7 +86,7 @@ def _oracle(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms, system, extra, X,
     g_ref, loss_ref, aux = obptt.actor_grads(cfg, tsys, ap, cp, x0, noise, s_mean, s_std, r_ms[0], r_ms[1])
     d = lambda t: t.double()
     tsys64 = obptt.TorchPendulumSystem() if system == "pendulum" else obptt.TorchEnsembleSystem(
-        d(extra["dp"]), extra["dd"], E, X, U, d(extra["tgt"]), d(extra["q"]), d(extra["r"]))
+        d(extra["dp"]), extra["dd"], E, X, U, d(extra["tgt"]), d(extra["q"]), d(extra["r"]), act=extra["act"])
     g64, loss64, aux64 = obptt.actor_grads(cfg, tsys64, d(ap), d(cp), d(x0), d(noise), d(s_mean), d(s_std), d(r_ms[0]), d(r_ms[1]))
     return g_ref, aux, g64, loss64, aux64
 

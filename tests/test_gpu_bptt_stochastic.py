@@ -21,8 +21,8 @@ class TsEnsembleSystem:
     """Differentiable trajectory-sampling ensemble with a quadratic reward: row i at horizon step t takes member members[i, t]
     (x' = [x +] mu_m (+ (softplus(raw_m) + min_std) * eps[i, t])).  A step counter walks the horizon; set_draws rewinds it."""
 
-    def __init__(self, params, dims, E, X, U, tgt, q, r, predict_delta=True, min_std=MIN_STD):
-        self.params, self.dims, self.E, self.X, self.U = params, list(dims), E, X, U
+    def __init__(self, params, dims, E, X, U, tgt, q, r, predict_delta=True, min_std=MIN_STD, act="swish"):
+        self.params, self.dims, self.E, self.X, self.U, self.act = params, list(dims), E, X, U, act
         self.tgt, self.q, self.r, self.predict_delta, self.min_std = tgt, q, r, predict_delta, min_std
         self.members = self.eps = None
         self.t = 0
@@ -33,7 +33,7 @@ class TsEnsembleSystem:
 
     def step(self, x, u):
         X, n = self.X, x.shape[0]
-        y = onets.ensemble_forward(self.params, self.dims, self.E, torch.cat([x, u], dim=1))
+        y = onets.ensemble_forward(self.params, self.dims, self.E, torch.cat([x, u], dim=1), self.act)
         ym = y[self.members[:, self.t].long(), torch.arange(n)]
         nxt = ym[:, :X] + x if self.predict_delta else ym[:, :X]
         if self.eps is not None:
@@ -43,10 +43,10 @@ class TsEnsembleSystem:
         return nxt, rew
 
 
-def _ts_setup(X, U, H, n, E, seed=0):
+def _ts_setup(X, U, H, n, E, seed=0, **setup_kw):
     """tests/test_gpu_bptt.py's setup; the members' raw-std output bias is shifted to -2 (sigma ~ 0.13: a fitted model's aleatoric
     noise, so that H-step noisy rollouts stay in the range the tolerances were set for)."""
-    cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, _, extra = _setup(X, U, H, n, "ensemble", E, seed)
+    cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, _, extra = _setup(X, U, H, n, "ensemble", E, seed, **setup_kw)
     dd, dp = extra["dd"], extra["dp"].clone()
     P = onets.n_params(dd)
     for e in range(E):
@@ -68,12 +68,12 @@ def _run_ts(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, extra, n, mode, wi
     from mbpo import _hip, ops
     op = ops.BpttActorGrad(x_dim=cfg.x_dim, u_dim=cfg.u_dim, horizon=cfg.horizon, actor_dims=cfg.actor_dims, critic_dims=cfg.critic_dims,
                            n=n, device=dev, init_stddev=cfg.init_stddev, discount=cfg.discount, lambda_=cfg.lambda_, ent_coef=cfg.ent_coef,
-                           seed=seed)
+                           seed=seed, actor_activation=cfg.actor_act, critic_activation=cfg.critic_act)
     E = extra["dp"].numel() // onets.n_params(extra["dd"])
     op(actor_params=ap.to(dev), target_critic_params=cp.to(dev), init_states=x0.to(dev), state_mean=s_mean.to(dev), state_std=s_std.to(dev),
        reward_mean_std=r_ms.to(dev), act_noise=noise.to(dev), offset=offset, rng_dev=rng_dev, system_kind=_hip.SYS_ENSEMBLE,
        reward_kind=_hip.REWARD_QUADRATIC, reward_params=torch.cat([extra["tgt"], extra["q"], extra["r"]]).to(dev),
-       dyn_params=extra["dp"].to(dev), dyn_spec=ops.MlpSpec(extra["dd"], "swish", E), ens_predict_delta=delta, ens_mode=_mode_id(mode),
+       dyn_params=extra["dp"].to(dev), dyn_spec=ops.MlpSpec(extra["dd"], extra["act"], E), ens_predict_delta=delta, ens_mode=_mode_id(mode),
        ens_sample_noise=with_noise, ens_min_std=MIN_STD, member_idx=None if members is None else members.to(dev).contiguous(),
        model_noise=None if eps is None else eps.to(dev).contiguous())
     torch.cuda.synchronize()
@@ -82,10 +82,10 @@ def _run_ts(dev, cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, extra, n, mode, wi
 
 def _ts_oracle(cfg, ap, cp, x0, noise, s_mean, s_std, r_ms, extra, E, members, eps, delta):
     X, U = cfg.x_dim, cfg.u_dim
-    sys32 = TsEnsembleSystem(extra["dp"], extra["dd"], E, X, U, extra["tgt"], extra["q"], extra["r"], delta).set_draws(members, eps)
+    sys32 = TsEnsembleSystem(extra["dp"], extra["dd"], E, X, U, extra["tgt"], extra["q"], extra["r"], delta, act=extra["act"]).set_draws(members, eps)
     g_ref, _, aux = obptt.actor_grads(cfg, sys32, ap, cp, x0, noise, s_mean, s_std, r_ms[0], r_ms[1])
     d = lambda t: t.double()
-    sys64 = TsEnsembleSystem(d(extra["dp"]), extra["dd"], E, X, U, d(extra["tgt"]), d(extra["q"]), d(extra["r"]), delta)
+    sys64 = TsEnsembleSystem(d(extra["dp"]), extra["dd"], E, X, U, d(extra["tgt"]), d(extra["q"]), d(extra["r"]), delta, act=extra["act"])
     sys64.set_draws(members, None if eps is None else d(eps))
     g64, loss64, aux64 = obptt.actor_grads(cfg, sys64, d(ap), d(cp), d(x0), d(noise), d(s_mean), d(s_std), d(r_ms[0]), d(r_ms[1]))
     assert sys32.t == sys64.t == cfg.horizon

@@ -34,13 +34,14 @@ CHILD_TIMEOUT_S = 600
 _SAC_64 = dict(X=4, U=1, hidden=(64, 64, 64), B=200, normalize=True)
 _SAC_U2 = dict(X=4, U=2, hidden=(64, 64, 64), B=200, normalize=False)
 _SAC_128 = dict(X=3, U=1, hidden=(128, 128, 128), B=104, normalize=True)
+_SAC_ACT = dict(case="sac_thin_rt")      # tests/activation_cases.py: 64 x 3, u = 1, B = 40, policy relu / critics tanh, clear of relu's kink
 _SAC_LAYERED = dict(X=4, U=2, hidden=(48, 80), q_hidden=(200, 72, 40), B=100, normalize=True)
 _PPO_LAYERED = dict(X=4, U=2, hidden=(48, 80), v_hidden=(200, 72, 40), B=20, T=7, normalize=True, norm_adv=False)
 _PPO_REF = dict(X=3, U=1, hidden=(64, 64), B=128, T=40, normalize=True, norm_adv=True)       # the reference's test shape
 
 JOBS = {
-    "MBPO_SAC_SPLIT=0": [("sac", _SAC_64), ("sac", _SAC_U2), ("sac", _SAC_128)],      # k_sac_fwd_bwd<64,4,false> and <128,2,false>
-    "MBPO_SAC_JVP=0": [("sac", _SAC_64), ("sac", _SAC_128)],                          # reverse-mode dQ/da in the actor role at u = 1
+    "MBPO_SAC_SPLIT=0": [("sac", _SAC_64), ("sac", _SAC_U2), ("sac", _SAC_128), ("sac", _SAC_ACT)],      # k_sac_fwd_bwd<64,4,false> and <128,2,false>
+    "MBPO_SAC_JVP=0": [("sac", _SAC_64), ("sac", _SAC_128), ("sac", _SAC_ACT)],       # reverse-mode dQ/da in the actor role at u = 1
     "MBPO_PPO_SP2=0": [("ppo", dict(name="sp2_neq"))],                                # <64,4,false> with more than two tiles per CU
     "MBPO_PPO_VALUES_GAE=0": [("ppo", _PPO_REF), ("ppo", dict(name="h128_u2"))],      # k_ppo_values<64> / <128> + GAE scan + moments
     "MBPO_LAYERED_GROUP=0": [("sac", _SAC_LAYERED), ("ppo", _PPO_LAYERED)],
@@ -53,6 +54,9 @@ def _cus(dev):
 
 
 def _sac_inputs(item):
+    if "case" in item:
+        import activation_cases as ac
+        return ac.inputs(item["case"])
     from test_gpu_sac import _make
     return _make(item["X"], item["U"], item["hidden"], item["B"], 6, item["normalize"], q_hidden=item.get("q_hidden"), **mt.SAC_CFG)
 
@@ -73,7 +77,7 @@ def _run_item(dev, kind, item):
     if kind == "sac":
         from test_gpu_sac import _updater
         cfg, st, batch, noise, nm, ns = _sac_inputs(item)
-        up = _updater(dev, cfg, item["B"])
+        up = _updater(dev, cfg, batch.shape[0], policy_activation=cfg.policy_act, q_activation=cfg.q_act)
         up.load_state(st.params.to(dev), st.target_q.to(dev))
         up.sgd_step(batch.to(dev), d(nm), d(ns), *[n.to(dev) for n in noise])
         up.finalize()

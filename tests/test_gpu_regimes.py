@@ -235,8 +235,9 @@ def test_sac_regimes_thin_layer_variant(dev, monkeypatch, reg):
 
 @pytest.mark.parametrize("act,scale", [("relu", 10.0), ("tanh", 6.0), ("swish", 8.0)])
 def test_sac_saturated_hidden_layers_every_activation(dev, act, scale):
-    """Hidden weights scaled by 6-10 (many |pre-activations| > 20) with relu, tanh and swish policy and critic layers: the layered path,
-    the only one that takes relu and tanh."""
+    """Hidden weights scaled by 6-10 (many |pre-activations| > 20) with relu, tanh and swish policy and critic layers, on widths
+    (40, 72) / (136, 24) that sac_plan sends to the layered path.  Every path honours the activation (the fused kernels under relu and
+    tanh: tests/test_gpu_activations.py); only the lean kernels refuse anything but swish and fall back to the generic ones."""
     X, U, B = 5, 2, 70
     cfg, st, batch, noise, nm, ns = _make(X, U, (40, 72), B, 21, True, q_hidden=(136, 24), policy_act=act, q_act=act, reward_scaling=1.5)
     st.params = _place(st.params, cfg.policy_dims, 0, U, loc=0.3, hidden_scale=scale)

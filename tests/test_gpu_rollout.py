@@ -99,7 +99,7 @@ def _pendulum_obs(N, gen):
 
 def _run_rollout_case(dev, *, N, S, L, AR, X, U, system, E=0, mode="mean", sample_noise=False, ppo=False,
                       env_major=False, normalize=False, deterministic=False, hidden=(64, 64, 64), seed=0,
-                      init_steps=None, atol=2e-4, replicate=0):
+                      init_steps=None, atol=2e-4, replicate=0, policy_act="swish", member_act="swish", check64=False):
     from mbpo import ops, _hip
     g = torch.Generator().manual_seed(seed)
     pdims = [X, *hidden, 2 * U]
@@ -138,16 +138,18 @@ def _run_rollout_case(dev, *, N, S, L, AR, X, U, system, E=0, mode="mean", sampl
             rparams = torch.cat([tgt, q, r])
             rk = _hip.REWARD_QUADRATIC
         osystem = osys.EnsembleSystem(dpar, ddims, E, X, U, mode=mode, predict_delta=True, sample_noise=sample_noise,
-                                      min_std=1e-3, reward_fn=rfn)
-        kw.update(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dpar.to(dev), dyn_spec=ops.MlpSpec(ddims, "swish", E),
+                                      min_std=1e-3, reward_fn=rfn, act=member_act)
+        kw.update(system_kind=_hip.SYS_ENSEMBLE, dyn_params=dpar.to(dev), dyn_spec=ops.MlpSpec(ddims, member_act, E),
                   ens_mode={"mean": _hip.ENS_MEAN, "ts1": _hip.ENS_TS1, "tsinf": _hip.ENS_TSINF}[mode],
                   ens_predict_delta=True, ens_sample_noise=sample_noise, ens_min_std=1e-3, reward_kind=rk)
     st0 = oro.EnvState(obs0, first, steps0, done0)
-    st_ref, rows_ref = oro.rollout(osystem, ppar, pdims, st0, S, L, AR, norm_mean=nm, norm_std=ns, policy_noise=pnoise,
+    st_ref, rows_ref = oro.rollout(osystem, ppar, pdims, st0, S, L, AR, act=policy_act, norm_mean=nm, norm_std=ns, policy_noise=pnoise,
                                    model_noise=mnoise, member_idx=midx, deterministic=deterministic, ppo_extras=ppo,
                                    env_major=env_major)
+    if dev is None:          # host only: the oracle's rows of the case (tests/test_cpu_activation_cases.py)
+        return rows_ref
     obs_d, steps_d, done_d = obs0.to(dev), steps0.to(dev), done0.to(dev)
-    rows = ops.model_rollout(policy_params=ppar.to(dev), policy_spec=ops.MlpSpec(pdims, "swish", 1), x_dim=X, u_dim=U,
+    rows = ops.model_rollout(policy_params=ppar.to(dev), policy_spec=ops.MlpSpec(pdims, policy_act, 1), x_dim=X, u_dim=U,
                              obs=obs_d, first_obs=first.to(dev), steps=steps_d, done=done_d, n_steps=S, episode_length=L,
                              action_repeat=AR, reward_params=rparams.to(dev),
                              norm_mean=None if nm is None else nm.to(dev), norm_std=None if ns is None else ns.to(dev),
@@ -164,13 +166,25 @@ def _run_rollout_case(dev, *, N, S, L, AR, X, U, system, E=0, mode="mean", sampl
     assert torch.equal(done_d.cpu(), st_ref.done)
     torch.testing.assert_close(rows, rows_ref, atol=atol, rtol=atol)
     torch.testing.assert_close(obs_d.cpu(), st_ref.obs, atol=atol, rtol=atol)
+    if check64:
+        # the same run of the oracle in float64 (the reward closures promote their float32 constants)
+        c = lambda t: None if t is None else t.double()
+        osystem64 = osystem if system == "pendulum" else osys.EnsembleSystem(
+            dpar.double(), ddims, E, X, U, mode=mode, predict_delta=True, sample_noise=sample_noise, min_std=1e-3, reward_fn=rfn,
+            act=member_act)
+        st64, rows64 = oro.rollout(osystem64, ppar.double(), pdims, oro.EnvState(c(obs0), c(first), c(steps0), c(done0)), S, L, AR,
+                                   act=policy_act, norm_mean=c(nm), norm_std=c(ns), policy_noise=c(pnoise), model_noise=c(mnoise),
+                                   member_idx=midx, deterministic=deterministic, ppo_extras=ppo, env_major=env_major)
+        assert rows64.dtype == torch.float64
+        torch.testing.assert_close(rows.double(), rows64, atol=atol, rtol=atol)
+        torch.testing.assert_close(obs_d.cpu().double(), st64.obs, atol=atol, rtol=atol)
     if replicate:
         # full-size property: envs are independent, so `replicate` copies of the N envs (in other tiles / workgroups) must
         # reproduce the N-env rows bit for bit
         k = replicate
         rep = lambda t, dim=0: None if t is None else t.repeat_interleave(1, 0).repeat(*[k if d == dim else 1 for d in range(t.dim())]).to(dev)
         obs_k, steps_k, done_k = rep(obs0), rep(steps0), rep(done0)
-        rows_k = ops.model_rollout(policy_params=ppar.to(dev), policy_spec=ops.MlpSpec(pdims, "swish", 1), x_dim=X, u_dim=U,
+        rows_k = ops.model_rollout(policy_params=ppar.to(dev), policy_spec=ops.MlpSpec(pdims, policy_act, 1), x_dim=X, u_dim=U,
                                    obs=obs_k, first_obs=rep(first), steps=steps_k, done=done_k, n_steps=S, episode_length=L,
                                    action_repeat=AR, reward_params=rparams.to(dev),
                                    norm_mean=None if nm is None else nm.to(dev), norm_std=None if ns is None else ns.to(dev),

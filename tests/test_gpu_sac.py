@@ -120,19 +120,32 @@ def test_sac_layered_path_any_widths(dev, X, U, hidden, q_hidden, B, normalize):
     torch.testing.assert_close(outs[0][2], st_new.target_q, atol=1e-7, rtol=1e-6)
 
 
-def test_sac_layered_path_equals_fused_path_on_a_padded_network(dev):
+def padded_network_inputs(act, seed):
+    """The inputs of test_sac_layered_path_equals_fused_path_on_a_padded_network (host only)."""
+    return _make(4, 1, (60, 60, 60), 96, seed, True, discounting=0.95, policy_act=act, q_act=act)
+
+
+# relu: the first seed in 0..63 at which the oracle is clear of relu's kink (tests/activation_cases.py; test_cpu_activation_cases.py
+# re-derives it), so that the two device paths, which round differently, see no unit change sign
+PADDED_NETWORK_CASES = [("swish", 8), ("tanh", 8), ("relu", 2)]      # relu: G 1.14e-6, min |z| 1.15e-5 over 155 520 units
+
+
+@pytest.mark.parametrize("act,seed", PADDED_NETWORK_CASES)
+def test_sac_layered_path_equals_fused_path_on_a_padded_network(dev, act, seed):
     """The same logical 60-wide networks twice: zero-padded to 64 through the fused kernel (what the trainer does, ops.py 'hidden-width
-    padding') and unpadded through the layered path (60 is not a kernel width).  Gradients of the logical entries agree."""
+    padding') and unpadded through the layered path (60 is not a kernel width).  Gradients of the logical entries agree — under every
+    activation: the padding argument rests on act(0) = 0, which holds for swish, tanh and relu alike."""
     from mbpo import ops
     X, U, B = 4, 1, 96
-    cfg, st, batch, noise, nm, ns = _make(X, U, (60, 60, 60), B, 8, True, discounting=0.95)
+    cfg, st, batch, noise, nm, ns = padded_network_inputs(act, seed)
     cfg_pad = osac.SacConfig(x_dim=X, u_dim=U, policy_dims=ops.padded_dims(cfg.policy_dims, 64), q_dims=ops.padded_dims(cfg.q_dims, 64),
-                             discounting=0.95)
+                             discounting=0.95, policy_act=act, q_act=act)
     P, Q = cfg.P, cfg.Q
     pol = ops.embed_mlp_params(st.params[:P], cfg.policy_dims, 64)
     q = ops.embed_mlp_params(st.params[P:P + 2 * Q], cfg.q_dims, 64, n_nets=2)
     tq = ops.embed_mlp_params(st.target_q, cfg.q_dims, 64, n_nets=2)
-    up_l, up_f = _updater(dev, cfg, B), _updater(dev, cfg_pad, B)
+    akw = dict(policy_activation=act, q_activation=act)
+    up_l, up_f = _updater(dev, cfg, B, **akw), _updater(dev, cfg_pad, B, **akw)
     up_l.load_state(st.params.to(dev), st.target_q.to(dev))
     up_f.load_state(torch.cat([pol, q, st.params[-1:]]).to(dev), tq.to(dev))
     for up in (up_l, up_f):
@@ -144,6 +157,9 @@ def test_sac_layered_path_equals_fused_path_on_a_padded_network(dev):
                          ops.extract_mlp_params(gf[cfg_pad.P:cfg_pad.P + 2 * cfg_pad.Q], cfg.q_dims, 64, n_nets=2), gf[-1:]])
     torch.testing.assert_close(up_l.grads.cpu(), g_fused, atol=1e-6, rtol=1e-4)
     torch.testing.assert_close(up_l.metrics.cpu(), up_f.metrics.cpu(), atol=1e-6, rtol=2e-5)
+    # and both are the logical network's gradient under that activation (test_sac_layered_path_any_widths' tolerance)
+    g64, _ = osac.grads(cfg, st.params.double(), st.target_q.double(), batch.double(), *[n.double() for n in noise], nm.double(), ns.double())
+    torch.testing.assert_close(g_fused.double(), g64, atol=2e-6 + 2e-6 * float(g64.abs().max()), rtol=2e-4)
 
 
 @pytest.mark.parametrize("X,U,hidden,B", [
