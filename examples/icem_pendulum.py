@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """MPC on the true Pendulum with iCEM, every planning iteration a launch chain on the MI355X path:
 
-    mbpo_icem_sample -> mbpo_model_rollout (open loop) -> [mbpo_plan_reward_eval] -> [mbpo_terminal_value_eval] -> [mbpo_traj_cost_eval]
+    mbpo_icem_sample -> [mbpo_icem_seed_candidates] -> mbpo_model_rollout (open loop) -> [mbpo_plan_reward_eval] -> [mbpo_terminal_value_eval] -> [mbpo_traj_cost_eval]
                      -> mbpo_icem_update
 
     python examples/icem_pendulum.py [--steps 100] [--horizon 20] [--speed-limit V] [--lambda-constraint L] [--seed 0]
-                                     [--targets A0,A1,...] [--track AMPL,PERIOD] [--terminal-value [--tv-horizon 5] [--sac-steps 30000]]
+                                     [--targets A0,A1,...] [--track AMPL,PERIOD] [--terminal-value] [--policy-prior [K]] [--tv-horizon 5] [--sac-steps 30000]
 
 --speed-limit V: the plan is constrained to |thetadot| <= V at every step of the horizon — a TermCost, max_t(|thetadot_{t+1}| - V), written as
 data and evaluated on the rollout's rows by one launch (iCemTO(cost_fn=TermCost(...), use_pessimism=True)); the objective of a candidate
@@ -24,6 +24,11 @@ planner previews the reference over its horizon — a [1, H, 3] table whose targ
 critics and the observation normaliser), then MPC on the true Pendulum at the short horizon --tv-horizon twice: with
 TerminalValue.from_sac(learner_state, weight=gamma^H / reward_scaling) — min(Q1, Q2) under the policy's mode action at the state the
 horizon ends in, added to every candidate's objective by one launch per iteration — and without it.  Both returns are printed, one seed.
+
+--policy-prior [K]: the same short SAC run, then MPC at --tv-horizon with PolicyPrior.from_sac(learner_state, n_candidates=K) (K = 24
+when omitted): once per `act` the policy is rolled closed-loop through the model from the current state, K proposals — its mode sequence
+and K - 1 noisy ones — and one launch per iteration puts them into the first K of the sampled candidates.  Alone: with the prior and
+without.  Together with --terminal-value the short-horizon MPC runs four ways from the one SAC run: plain, critic only, prior only, both.
 
 A torque-limited pendulum cannot hold every angle: the prints are a record of what happened, not a claim.
 """
@@ -50,8 +55,10 @@ def main():
     ap.add_argument("--targets", type=str, default=None, metavar="A0,A1,...", help="batched MPC: one environment per target angle (rad)")
     ap.add_argument("--track", type=str, default=None, metavar="AMPL,PERIOD", help="follow AMPL * sin(2 pi t / PERIOD), previewed over the horizon")
     ap.add_argument("--terminal-value", action="store_true", help="train SAC briefly, then plan at --tv-horizon with and without its critic")
+    ap.add_argument("--policy-prior", type=int, nargs="?", const=24, default=None, metavar="K",
+                    help="train SAC briefly, then plan at --tv-horizon with K of its policy's rollouts among the candidates and without")
     ap.add_argument("--tv-horizon", type=int, default=5, metavar="H")
-    ap.add_argument("--sac-steps", type=int, default=30000, help="--terminal-value: environment steps of the SAC run")
+    ap.add_argument("--sac-steps", type=int, default=30000, help="--terminal-value / --policy-prior: environment steps of the SAC run")
     args = ap.parse_args()
     if args.targets is not None and args.track is not None:
         raise SystemExit("--targets and --track are two runs")
@@ -61,9 +68,9 @@ def main():
     from mbpo.systems import Group, PendulumSystem, Term, TermCost
     dev = torch.device("cuda:0")
     system = PendulumSystem()
-    if args.terminal_value:
+    if args.terminal_value or args.policy_prior is not None:
         if args.targets is not None or args.track is not None or args.speed_limit is not None:
-            raise SystemExit("--terminal-value is a run of its own")
+            raise SystemExit("--terminal-value / --policy-prior is a run of its own")
         return run_terminal_value(args, system, dev)
     cost = None
     if args.speed_limit is not None:
@@ -141,7 +148,7 @@ def run_track(args, opt, system, dev):
 
 
 def run_terminal_value(args, system, dev):
-    from mbpo.optimizers import SACOptimizer, TerminalValue, iCemParams, iCemTO
+    from mbpo.optimizers import PolicyPrior, SACOptimizer, TerminalValue, iCemParams, iCemTO
     from mbpo.replay import UniformSamplingQueue
     from mbpo.types import Transition
     gamma, reward_scaling, H, n_true = 0.99, 1.0, args.tv_horizon, 2048
@@ -164,11 +171,19 @@ def run_terminal_value(args, system, dev):
                        min_replay_size=2 ** 9, num_eval_envs=1, tau=0.005, num_env_steps_between_updates=5)
     out = sac.train(opt_state=sac.init(key=args.seed + 3, true_buffer_state=tbs))
     learner_state = out.optimizer_state.learner_state                     # (warm_start=True: the learner as a value)
-    tv = TerminalValue.from_sac(learner_state, weight=gamma ** H / reward_scaling)
+    tv = TerminalValue.from_sac(learner_state, weight=gamma ** H / reward_scaling) if args.terminal_value else None
+    prior = PolicyPrior.from_sac(learner_state, n_candidates=args.policy_prior) if args.policy_prior is not None else None
     sac.close()
-    print(f"SAC: {args.sac_steps} environment steps, {int(learner_state.step_count)} gradient steps;  {tv}")
-    for name, value in (("with the critic", tv), ("without", None)):
-        opt = iCemTO(horizon=H, action_dim=system.action_dim, opt_params=iCemParams(), system=system, terminal_value=value)
+    print(f"SAC: {args.sac_steps} environment steps, {int(learner_state.step_count)} gradient steps;  " +
+          ";  ".join(str(v) for v in (tv, prior) if v is not None))
+    if prior is None:
+        runs = (("with the critic", tv, None), ("without", None, None))
+    elif tv is None:
+        runs = (("with the prior", None, prior), ("without", None, None))
+    else:
+        runs = (("plain", None, None), ("critic only", tv, None), ("prior only", None, prior), ("critic and prior", tv, prior))
+    for name, value, pp in runs:
+        opt = iCemTO(horizon=H, action_dim=system.action_dim, opt_params=iCemParams(), system=system, terminal_value=value, policy_prior=pp)
         state = opt.init(args.seed)
         x = torch.tensor([math.cos(math.pi), math.sin(math.pi), 0.0], device=dev)      # hanging down, at rest
         ret = 0.0

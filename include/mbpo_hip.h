@@ -1019,6 +1019,55 @@ typedef struct mbpo_terminal_value_desc {
 } mbpo_terminal_value_desc;
 int mbpo_terminal_value_eval(const mbpo_terminal_value_desc *d, void *stream);
 
+/* ---- policy priors: a learned policy's closed-loop action sequences among iCEM's candidates -------------------------------------------
+ * replaces: nothing in the reference tree, whose iCEM samples every candidate around (mean, std).  Build-defined
+ *           (mbpo.optimizers.PolicyPrior; TD-MPC's policy trajectories among the CEM samples, LOOP's actor prior): THIS TEXT IS THE DEFINITION.
+ * Proposals.  Once per `optimize`, before the first iteration, the policy is rolled closed-loop through the model: for every problem b, K
+ * proposals of H steps from x0[b],
+ *   a_t = squash(loc(pi(n(x_t))) + noise_scale * scale * eps)          the rollout kernels' own NormalTanh path (tanh, optional action_clip,
+ *                                                                      the trainer's normaliser n), through ONE mbpo_model_rollout over
+ *                                                                      B K envs with a policy and an explicit policy_noise; no new rollout
+ *                                                                      kernel, whichever kernel the dispatch picks for the descriptor
+ * under the system's descriptor without termination and with episode_length = 2^30, as iCEM's candidate rollouts run.  A stochastic
+ * ensemble (ts1 / tsinf, or sample_noise) runs its proposals in MBPO_ENS_MEAN without model noise: proposals are action sequences, their
+ * only randomness is the policy's.  The optimistic mode already is ENS_MEAN plus halluc_beta and runs unchanged at action width u + x.  A
+ * plan reward is taken out of the parameters as for the candidate rollouts; the proposal rollout's reward column is never read.
+ *   eps [H][B K][A] = mbpo_philox_fill_grouped(seeds = prior_key[b], offset 0, MBPO_STREAM_POLICY_NOISE, n_steps H, n_problems B,
+ *                     group K A), times noise_scale where that is not 1; with include_mode, eps of proposal k = 0 is zeroed: the policy's
+ *                     mode sequence.  prior_key = split(optimizer_key, 3)[2]; split(k, 3)[:2] == split(k, 2), so the key chain of a run
+ *                     without a prior, and every number it draws, is untouched.  The single path is the same call with n_problems = 1:
+ *                     problem b of a batched call equals its single call by construction.
+ * Seeding.  In iteration it (every iteration, TD-MPC's scheme; or only it = 0), after mbpo_icem_sample[_batched] and before the candidate
+ * rollout, one launch of mbpo_icem_seed_candidates overwrites the sampled slots [0, K) of every problem with the clipped proposals; with
+ * init_mean (LOOP's scheme) a launch before the first sample launch writes the clipped proposal 0 into mean[b] in place of the warm start.
+ *   p(b, k, t, a) = src[t * src_step_stride + (b * n_seed + k) * src_traj_stride + a]      k < n_seed = K, t < horizon = H, a < u_dim = A
+ *                   (iCEM: src = proposal rows + x_dim, src_traj_stride = row_len, src_step_stride = B K row_len — the action columns of
+ *                   the step-major rows mbpo_model_rollout wrote; no dense copy in between)
+ *   v             = fminf(fmaxf(p, u_min[a]), u_max[a])                                    mbpo_icem_sample's clip expression
+ *   finite(b, k)  = every one of the H A elements p(b, k, ., .) is finite (neither NaN nor an infinity)
+ * Where finite(b, k), with NC = n_candidates, P = n_particles, B = n_problems, and only when actions / candidates are set:
+ *   candidates[((b NC + k) H + t) A + a]               = v
+ *   actions[(t (B NC P) + (b NC + k) P + p) A + a]     = v     for every p < P   (the rollout's [H][B NC P][A] layout)
+ * and, where mean != NULL, k == 0 and finite(b, 0):
+ *   mean[(b H + t) A + a]                              = v
+ * Nothing else is written: a proposal with a non-finite element (a diverged model state fed the policy a NaN) is DROPPED, not repaired —
+ * its slot keeps the sampled candidate, mean[b] keeps the warm start — and the slots [n_seed, NC) keep their bits.  The Philox element
+ * of a sampled slot does not depend on the other slots, so in iteration 0 the slots [K, num_samples) equal those of a run without a prior.
+ * actions and candidates are both NULL (the mean-only call) or both set; at least one of (actions, mean) is set.  src must not overlap an
+ * output.  No alignment is assumed anywhere (the rows' stride is odd).  One wave per (b, k): a wave-wide vote on "any element not
+ * finite", then plain vector stores.  No workspace, no allocation, no atomics, no host read-back; capturable.  src and the bounds are
+ * read by the launch: refilled in place between two launches (or two replays) they are honoured.
+ * MBPO_ERR_ARG before any device use: n_problems < 1, n_seed < 1, n_seed > n_candidates, horizon < 1, u_dim < 1, n_particles < 1,
+ * horizon * u_dim overflowing int32, a stride smaller than u_dim, strides under which steps and trajectories overlap — neither
+ * src_step_stride >= (n_problems n_seed - 1) src_traj_stride + u_dim (step-major, iCEM's) nor src_traj_stride >= (horizon - 1)
+ * src_step_stride + u_dim (trajectory-major) —, an index product (horizon * src_step_stride + n_problems * n_seed * src_traj_stride, horizon *
+ * n_problems * n_candidates * n_particles * u_dim) that overflows int64, a NULL src, u_min or u_max, exactly one of actions / candidates
+ * set, actions and mean both NULL, more than 2^31 - 1 workgroups of four proposals.  The grid is flat over (b, k): n_problems has no
+ * bound of its own. */
+int mbpo_icem_seed_candidates(const float *src, int64_t src_step_stride, int64_t src_traj_stride, int32_t n_problems, int32_t n_seed,
+                              int32_t n_candidates, int32_t horizon, int32_t u_dim, int32_t n_particles, const float *u_min,
+                              const float *u_max, float *actions, float *candidates, float *mean, void *stream);
+
 /* ---- one-shot all-reduce over xGMI peer memory (multi-GPU SAC gradient exchange) ------------------------
  * replaces: the live form of the reference's jax.lax.pmean(grad) (sac/utils.py:29-33) for vectors small enough that a
  *           collective is pure latency.  Every rank owns an exchange REGION (mbpo_p2p_alloc -> 64-byte IPC handle, passed to

@@ -317,6 +317,10 @@ def _bind_optional(lib: C.CDLL) -> None:
     if fn is not None:
         fn.restype = C.c_int
         fn.argtypes = [C.POINTER(TerminalValueDesc), vp]
+    fn = getattr(lib, "mbpo_icem_seed_candidates", None)   # (bound when present, as mbpo_terminal_value_eval)
+    if fn is not None:
+        fn.restype = C.c_int
+        fn.argtypes = [vp, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.mbpo_episode_step.restype = C.c_int
     lib.mbpo_episode_step.argtypes = [C.POINTER(EpisodeStepDesc), vp]
     lib.mbpo_running_stats_workspace_floats.restype = C.c_int64

@@ -548,6 +548,34 @@ def terminal_value_eval(*, x_dim: int, action_dim: int, critic_params: torch.Ten
     return out
 
 
+def icem_seed_candidates(src: torch.Tensor, src_offset: int, src_step_stride: int, src_traj_stride: int, n_problems: int, n_seed: int,
+                         n_candidates: int, horizon: int, u_dim: int, n_particles: int, u_min: torch.Tensor, u_max: torch.Tensor,
+                         actions: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
+                         mean: Optional[torch.Tensor] = None) -> None:
+    """mbpo_icem_seed_candidates (include/mbpo_hip.h "policy priors"): proposal (b, k), the floats of `src` at src_offset + t *
+    src_step_stride + (b * n_seed + k) * src_traj_stride + a (offsets and strides in floats of the flattened tensor), clipped to
+    [u_min, u_max], into slot k < n_seed of problem b in `candidates` [B, NC, H, A] and, n_particles-fold, in `actions` [H, B * NC * P, A];
+    proposal 0 also into `mean` [B, H, A] when given.  A proposal with a non-finite element is dropped: nothing is written for it.
+    `actions` and `candidates` go together; `mean` alone is the mean-only call.  One launch, no allocation."""
+    lib = load()
+    _req(src, "src")
+    B, K, NC, H, A, P = int(n_problems), int(n_seed), int(n_candidates), int(horizon), int(u_dim), int(n_particles)
+    off, ss, ts = int(src_offset), int(src_step_stride), int(src_traj_stride)
+    if min(B, K, H, A, P) >= 1 and off >= 0 and ss >= A and ts >= A and off + (H - 1) * ss + (B * K - 1) * ts + A > src.numel():
+        raise ValueError(f"src holds {src.numel()} floats; {B * K} proposals of {H} steps at offset {off}, strides {ss} / {ts} end at "
+                         f"{off + (H - 1) * ss + (B * K - 1) * ts + A}")
+    if off < 0:
+        raise ValueError("src_offset must be >= 0")
+    for t, nm in ((u_min, "u_min"), (u_max, "u_max")):
+        if _req(t, nm).numel() != A:
+            raise ValueError(f"{nm} must be [{A}]")
+    for t, nm, n in ((actions, "actions", H * B * NC * P * A), (candidates, "candidates", B * NC * H * A), (mean, "mean", B * H * A)):
+        if t is not None and _req(t, nm).numel() != n:
+            raise ValueError(f"{nm} holds {t.numel()} floats, expected {n}")
+    check(lib.mbpo_icem_seed_candidates(src.data_ptr() + 4 * off, ss, ts, B, K, NC, H, A, P, u_min.data_ptr(), u_max.data_ptr(), ptr(actions),
+                                        ptr(candidates), ptr(mean), current_stream_ptr()), "mbpo_icem_seed_candidates")
+
+
 # ------------------------------------------------------------------------------------------------ user-defined System (non-fused)
 def policy_act(policy_params: torch.Tensor, policy_spec: MlpSpec, obs: torch.Tensor, norm_mean=None, norm_std=None,
                deterministic: bool = False, action_clip: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0,

@@ -4,4 +4,5 @@ from mbpo.optimizers.policy_optimizers.brax_optimizers import BraxOptimizer, Bra
 from mbpo.optimizers.policy_optimizers.bptt_optimizer import BPTTOptimizer, BPTTState
 from mbpo.optimizers.policy_optimizers.sac.sac import SAC
 from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCEMOptimizer, iCemOptimizerState, iCemParams, iCemTO
+from mbpo.optimizers.trajectory_optimizers.policy_prior import PolicyPrior            # (not in the reference: the actor among iCEM's candidates)
 from mbpo.optimizers.trajectory_optimizers.terminal_value import TerminalValue      # (not in the reference: a critic at iCEM's horizon)

@@ -28,6 +28,15 @@ trajectory whose terminal state is not finite gets -inf there.  It composes with
 use_pessimism, the TS modes and warm starts, none of which reads the reward column.  With terminal_value=None every path issues exactly
 the launches it issued before.
 
+Policy prior: `iCemTO(..., policy_prior=PolicyPrior(...))` (mbpo.optimizers; include/mbpo_hip.h "policy priors") puts a learned policy's
+closed-loop rollouts among the candidates.  Once per `optimize`, before the first iteration, the policy is rolled through the model from
+the initial state — K proposals per problem, one mbpo_philox_fill_grouped for their noise under split(optimizer_key, 3)[2] and one
+mbpo_model_rollout with the policy — and in every iteration (every_iteration; else the first only) one launch of
+mbpo_icem_seed_candidates, between the sample launch and the candidate rollout, overwrites the sampled slots [0, K) with the clipped
+proposals, reading the action columns of the proposal rollout's rows in place.  A proposal with a non-finite action is dropped: its slot
+keeps the sample.  init_mean also writes the mode proposal into the mean the first sample launch reads.  The existing key chain is
+untouched (split(k, 3)[:2] == split(k, 2)); with policy_prior=None every path issues exactly the launches it issued before.
+
 Batched MPC: `init(key, batch_size=B)` makes a state for B independent problems (best_sequence [B, H, U], best_reward [B], key = B
 host integers) and `optimize` / `act` on such a state plan for obs [B, x] in one launch chain per iteration —
 mbpo_icem_sample_batched -> one rollout over all B*NC*P envs -> mbpo_icem_update_batched (one workgroup per problem).  Problem b
@@ -48,6 +57,7 @@ import torch
 
 from mbpo import _hip, ops
 from mbpo.optimizers.base_optimizer import BaseOptimizer
+from mbpo.optimizers.trajectory_optimizers.policy_prior import PolicyPrior
 from mbpo.optimizers.trajectory_optimizers.terminal_value import TerminalValue
 from mbpo.replay import ReplayBufferState
 from mbpo.systems.base_systems import System
@@ -99,9 +109,16 @@ class iCemTrainingOutput(OptimizerTrainingOutPut, Generic[DynamicsParams, Reward
 
 class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
     def __init__(self, horizon: int, action_dim: int, key: int = K.PRNGKey(0), opt_params: iCemParams = iCemParams(), cost_fn=None,
-                 use_optimism: bool = False, use_pessimism: bool = False, *args, terminal_value: Optional[TerminalValue] = None, **kwargs):
+                 use_optimism: bool = False, use_pessimism: bool = False, *args, terminal_value: Optional[TerminalValue] = None,
+                 policy_prior: Optional[PolicyPrior] = None, **kwargs):
         super().__init__(*args, **kwargs)
         refuse_time_adaptive(self.system, "iCEM")
+        if policy_prior is not None and not isinstance(policy_prior, PolicyPrior):
+            raise ValueError(f"policy_prior must be a PolicyPrior (mbpo.optimizers) or None, got {type(policy_prior).__name__}")
+        self.policy_prior = policy_prior          # a learned policy's rollouts among the candidates (see the module docstring)
+        if policy_prior is not None:
+            policy_prior.check_optimizer(opt_params.num_samples)
+        self._check_policy_prior(self.system)
         if terminal_value is not None and not isinstance(terminal_value, TerminalValue):
             raise ValueError(f"terminal_value must be a TerminalValue (mbpo.optimizers) or None, got {type(terminal_value).__name__}")
         self.terminal_value = terminal_value      # a learned critic at x_H, added on the device (see the module docstring)
@@ -125,7 +142,56 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         refuse_time_adaptive(system, "iCEM")      # (single and batched: the candidates' objective sums per-step rewards)
         self._check_term_cost(system)
         self._check_terminal_value(system)
+        self._check_policy_prior(system)
         super().set_system(system)
+
+    def _check_policy_prior(self, system):
+        """A PolicyPrior's widths against the system's: x_dim, its action width against system.action_dim, its hidden width against an
+        ensemble's members (a narrower policy gets its zero-padded copy here)."""
+        if self.policy_prior is not None:
+            self.policy_prior.check_system(system)
+
+    def _proposal_buffers(self, d: dict, B: int, dev) -> None:
+        """The proposal rollout's buffers for B problems, allocated with the others: B * K envs of H steps."""
+        pp = self.policy_prior
+        if pp is None:
+            return
+        H, U, X, n = self.horizon, self.action_dim, self.system.x_dim, B * pp.n_candidates
+        f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        d.update(pp_obs=f(n, X), pp_first=f(n, X), pp_steps=f(n), pp_done=f(n), pp_rows=f(H * n, 2 * X + U + 3), pp_noise=f(H, n, U),
+                 pp_seeds=torch.zeros(B, device=dev, dtype=torch.int64))
+
+    def _propose(self, b: dict, B: int, x0: torch.Tensor, prior_keys, spec: dict) -> None:
+        """Once per `optimize`: K closed-loop rollouts of the policy per problem from x0 [B, x] into b["pp_rows"] (step-major, B * K envs),
+        their noise drawn per problem under prior_keys (B integers) — include/mbpo_hip.h "policy priors"."""
+        pp = self.policy_prior
+        H, U, X, Kp = self.horizon, self.action_dim, self.system.x_dim, pp.n_candidates
+        if "pp_rows" not in b or b["pp_rows"].shape[0] != H * B * Kp:      # (a prior assigned, or resized, after the buffers were made)
+            pp.check_optimizer(self.opt_params.num_samples)
+            self._proposal_buffers(b, B, b["dev"])
+        b["pp_seeds"].copy_(torch.from_numpy(np.asarray([int(k) & K.MASK for k in prior_keys], dtype=np.uint64).view(np.int64)))
+        _hip.check(self.lib.mbpo_philox_fill_grouped(b["pp_seeds"].data_ptr(), 0, _hip.STREAM_POLICY_NOISE, H, B, Kp * U, 0, 0, 0,
+                                                     b["pp_noise"].data_ptr(), _hip.current_stream_ptr()), "mbpo_philox_fill_grouped")
+        if pp.include_mode:
+            b["pp_noise"].view(H, B, Kp, U)[:, :, 0].zero_()      # proposal 0: the policy's mode sequence
+        if pp.noise_scale != 1.0:
+            b["pp_noise"].mul_(pp.noise_scale)
+        b["pp_obs"].view(B, Kp, X).copy_(x0.reshape(B, 1, X).expand(B, Kp, X))
+        b["pp_first"].copy_(b["pp_obs"])
+        b["pp_steps"].zero_(); b["pp_done"].zero_()
+        ops.model_rollout(x_dim=X, u_dim=U, obs=b["pp_obs"], first_obs=b["pp_first"], steps=b["pp_steps"], done=b["pp_done"], n_steps=H,
+                          episode_length=2 ** 30, seed=0, offset=0, out=b["pp_rows"], policy_noise=b["pp_noise"], **pp.rollout_kwargs(),
+                          **PolicyPrior.proposal_spec(spec))
+
+    def _seed(self, b: dict, B: int, candidates: bool, mean: bool) -> None:
+        """One launch of mbpo_icem_seed_candidates on the action columns of the proposal rows: into the sampled slots [0, K) of every
+        problem (candidates and their particle-replicated actions) and / or proposal 0 into the mean."""
+        pp, X = self.policy_prior, self.system.x_dim
+        row_len = b["pp_rows"].shape[1]
+        ops.icem_seed_candidates(b["pp_rows"], X, B * pp.n_candidates * row_len, row_len, B, pp.n_candidates, b["NC"], self.horizon,
+                                 self.action_dim, self.opt_params.num_particles, b["u_min"], b["u_max"],
+                                 actions=b["actions"] if candidates else None, candidates=b["cand"] if candidates else None,
+                                 mean=b["mean"] if mean else None)
 
     def _check_terminal_value(self, system):
         """A TerminalValue's widths against the system's: x_dim, and kind Q's action width against system.action_dim."""
@@ -216,6 +282,7 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                               steps=f(N), done=f(N), rows=f(H * N, 2 * self.system.x_dim + U + 3))
             if self._term_cost is not None:
                 self._bufs["term_cost"] = f(N)
+            self._proposal_buffers(self._bufs, 1, dev)
         return self._bufs
 
     def _batched_buffers(self, dev, B: int):
@@ -236,12 +303,14 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
                                rows=f(H * NT, 2 * X + U + 3))
             if self._term_cost is not None:
                 self._bbufs["term_cost"] = f(NT)
+            self._proposal_buffers(self._bbufs, B, dev)
         return self._bbufs
 
     def optimize(self, initial_state: torch.Tensor, opt_state: iCemOptimizerState) -> iCemOptimizerState:
         assert self.system is not None, "iCem optimizer requires system to be defined."
         self._check_term_cost(self.system)      # (a system assigned without set_system)
         self._check_terminal_value(self.system)
+        self._check_policy_prior(self.system)
         if opt_state.batched:
             return self._optimize_batched(initial_state, opt_state)
         p, H, U = self.opt_params, self.horizon, self.action_dim
@@ -263,6 +332,12 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         spec = without_termination(self.system.rollout_spec(sys_params, dev))      # (rollout_actions ignores done)
         st = _hip.current_stream_ptr()
         lib = self.lib
+        pp = self.policy_prior
+        if pp is not None:
+            self._propose(b, 1, x0, [K.split(optimizer_key, 3)[2]], spec)
+            if pp.init_mean:      # LOOP's scheme: the search starts from the mode proposal (a non-finite one keeps the warm start)
+                self._seed(b, 1, candidates=False, mean=True)
+                b["best_seq"].copy_(b["mean"])
         carry_key = optimizer_key
         for it in range(p.num_steps):
             sampling_key, particles_key = K.split(carry_key, 2)          # :170-173 (the carried key is the first sampling split)
@@ -270,6 +345,8 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
             _hip.check(lib.mbpo_icem_sample(b["mean"].data_ptr(), b["std"].data_ptr(), b["prev"].data_ptr(), b["u_min"].data_ptr(),
                                             b["u_max"].data_ptr(), p.num_samples, self.num_prev, H, U, p.num_particles, float(p.exponent),
                                             sampling_key, it, None, b["actions"].data_ptr(), b["cand"].data_ptr(), st), "mbpo_icem_sample")
+            if pp is not None and (it == 0 or pp.every_iteration):
+                self._seed(b, 1, candidates=True, mean=False)
             b["obs"].copy_(x0.expand(b["N"], X))
             b["first"].copy_(b["obs"])
             b["steps"].zero_(); b["done"].zero_()
@@ -330,11 +407,19 @@ class iCemTO(BaseOptimizer, Generic[DynamicsParams, RewardParams]):
         draw = self._batched_ensemble_draws(spec, b)
         st = _hip.current_stream_ptr()
         lib = self.lib
+        pp = self.policy_prior
+        if pp is not None:
+            self._propose(b, B, x0, K.split_many(ks[:, 0], 3)[:, 2], spec)      # (the proposals run in ENS_MEAN: `draw` is not theirs)
+            if pp.init_mean:
+                self._seed(b, B, candidates=False, mean=True)
+                b["best_seq"].copy_(b["mean"])
         for it in range(p.num_steps):
             _hip.check(lib.mbpo_icem_sample_batched(b["mean"].data_ptr(), b["std"].data_ptr(), b["prev"].data_ptr(), b["u_min"].data_ptr(),
                                                     b["u_max"].data_ptr(), p.num_samples, self.num_prev, H, U, p.num_particles,
                                                     float(p.exponent), B, seeds_dev[it, 0].data_ptr(), it, b["actions"].data_ptr(),
                                                     b["cand"].data_ptr(), st), "mbpo_icem_sample_batched")
+            if pp is not None and (it == 0 or pp.every_iteration):
+                self._seed(b, B, candidates=True, mean=False)
             b["obs"].view(B, N, X).copy_(x0[:, None, :].expand(B, N, X))
             b["first"].copy_(b["obs"])
             b["steps"].zero_(); b["done"].zero_()
@@ -412,8 +497,16 @@ class iCEMOptimizer(BaseOptimizer):
     once (init makes a batched state, act(obs [B, x]) returns actions [B, u]); None keeps the single-state interface."""
 
     def __init__(self, horizon: int, opt_params: iCemParams = iCemParams(), system: Optional[System] = None, key: int = K.PRNGKey(0),
-                 batch_size: Optional[int] = None, terminal_value: Optional[TerminalValue] = None, **agent_kwargs):
+                 batch_size: Optional[int] = None, terminal_value: Optional[TerminalValue] = None,
+                 policy_prior: Optional[PolicyPrior] = None, **agent_kwargs):
         refuse_time_adaptive(system, "iCEM")
+        if policy_prior is not None:
+            if not isinstance(policy_prior, PolicyPrior):
+                raise ValueError(f"policy_prior must be a PolicyPrior (mbpo.optimizers) or None, got {type(policy_prior).__name__}")
+            policy_prior.check_optimizer(opt_params.num_samples)
+            policy_prior.check_system(system)
+            agent_kwargs = dict(agent_kwargs, policy_prior=policy_prior)
+        self.policy_prior = policy_prior
         if terminal_value is not None:
             if not isinstance(terminal_value, TerminalValue):
                 raise ValueError(f"terminal_value must be a TerminalValue (mbpo.optimizers) or None, got {type(terminal_value).__name__}")
@@ -433,6 +526,8 @@ class iCEMOptimizer(BaseOptimizer):
         refuse_time_adaptive(system, "iCEM")
         if self.terminal_value is not None:
             self.terminal_value.check_system(system)
+        if self.policy_prior is not None:
+            self.policy_prior.check_system(system)
         super().set_system(system)
 
     @property

@@ -977,6 +977,82 @@ def main():
 
     if want("icem_terminal_value_case"): icem_terminal_value_case()
 
+    # ---------------------------------------------------------------- iCEM policy prior: a policy's rollouts among the candidates
+    def icem_policy_prior_case():
+        """One Pendulum `optimize` at the reference's defaults (H = 20) and at H = 5, single and at batch_size 64, without a prior and
+        with K = 24 proposals of a 64 x 2 policy seeded in every iteration and in the first only, median of five alternating rounds; and
+        mbpo_icem_seed_candidates alone under graph replay on the proposal rows of the last call, next to mbpo_traj_cost_eval on the
+        same session's candidate rows (the yardstick)."""
+        from mbpo.optimizers import PolicyPrior
+        from mbpo.optimizers.trajectory_optimizers.icem_optimizer import iCemParams, iCemTO
+        from mbpo.systems import Group, PendulumSystem, Term, TermCost
+        X, A, KP = 3, 1, 24
+        pd = [X, 64, 64, 2 * A]
+        gg = torch.Generator().manual_seed(13)
+        pol = (lambda p: p + 0.1 * torch.randn(p.shape, generator=gg))(lecun_flat(pd, gg, 1)).to(dev)
+        mean, std = (torch.randn(X, generator=gg) * 0.1).to(dev), (torch.rand(X, generator=gg) + 0.5).to(dev)
+        prior = lambda every: PolicyPrior(X, pol, pd, norm_mean=mean, norm_std=std, n_candidates=KP, every_iteration=every)
+        system = PendulumSystem()
+        p = iCemParams()
+        x1 = torch.tensor([math.cos(2.5), math.sin(2.5), 4.5], device=dev)
+        ROUNDS = 5
+        for H in (20, 5):
+            forms = {"plain": None, "prior, every iteration": prior(True), "prior, first iteration": prior(False)}
+            opts = {k: iCemTO(horizon=H, action_dim=A, opt_params=p, system=system, policy_prior=pp) for k, pp in forms.items()}
+            for B, reps in ((None, 20), (64, 5)):
+                nb = 1 if B is None else B
+                calls = {}
+                for k, opt in opts.items():
+                    st = opt.init(0, batch_size=B)
+                    x0 = x1 if B is None else x1.expand(B, X).contiguous()
+                    calls[k] = (lambda opt=opt, x0=x0, st=st: opt.optimize(x0, st))
+                    timed(calls[k], 2, warm=2)
+                times = {k: [] for k in calls}
+                for _ in range(ROUNDS):
+                    for k, fn in calls.items():
+                        times[k].append(timed(fn, reps, warm=0))
+                med = {k: sorted(v)[ROUNDS // 2] for k, v in times.items()}
+                for k, v in times.items():
+                    out.append({"kernel": f"iCemTO.optimize, {k}", "entry": "mbpo_icem_sample"
+                                + (" + mbpo_icem_seed_candidates" if forms[k] is not None else "") + " + mbpo_model_rollout + mbpo_icem_update x num_steps"
+                                + ("; once: mbpo_philox_fill_grouped + mbpo_model_rollout (policy)" if forms[k] is not None else ""),
+                                "config": {"num_samples": p.num_samples, "num_particles": p.num_particles, "num_elites": p.num_elites,
+                                           "num_steps": p.num_steps, "horizon": H, "system": "Pendulum", "B": nb, "batched": B is not None,
+                                           "n_candidates": KP if forms[k] is not None else None, "policy": pd if forms[k] is not None else None},
+                                "eager_us": med[k] * 1e6, "eager_us_min": min(v) * 1e6, "eager_us_max": max(v) * 1e6, "rounds": ROUNDS,
+                                "calls_per_round": reps, "bound": "launch" if B is None else "rollout",
+                                "over_plain_us": (med[k] - med["plain"]) * 1e6,
+                                "note": "HIP-event time of one eager optimize call; the forms alternate round by round in one session"})
+                    log(f"icem optimize H={H} B={nb} {k}: {med[k] * 1e6:.1f} us (min {min(v) * 1e6:.1f}, max {max(v) * 1e6:.1f}; "
+                        f"{(med[k] - med['plain']) * 1e6:+.1f} us over plain)")
+                # the seed launch alone, on the proposal rows the last call left, into that optimizer's own candidate buffers
+                opt = opts["prior, every iteration"]
+                b = opt._bufs if B is None else opt._bbufs
+                src, row_len = b["pp_rows"], b["pp_rows"].shape[1]
+                NC, P = b["NC"], p.num_particles
+                fn = lambda: ops.icem_seed_candidates(src, X, nb * KP * row_len, row_len, nb, KP, NC, H, A, P, b["u_min"], b["u_max"],
+                                                      actions=b["actions"], candidates=b["cand"])
+                t, te = both(fn, 200)
+                n_el = nb * KP * H * A
+                out.append(hbm_entry("k_icem_seed", "mbpo_icem_seed_candidates",
+                                     {"n_problems": nb, "n_seed": KP, "n_candidates": NC, "horizon": H, "u_dim": A, "n_particles": P,
+                                      "src_traj_stride": row_len, "src_step_stride": nb * KP * row_len}, t, 4 * n_el * (2 + 1 + P),
+                                     "every proposal element read twice (4 B of a 40 B row each), written once as a candidate and P times as "
+                                     "an action"))
+                log(f"icem_seed_candidates H={H} B={nb}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+                rows = b["rows"]
+                cost = TermCost(X, A, bias=-5.0, groups=[Group([Term("x", 2, "abs")])], reduce="max")
+                buf = torch.zeros(nb * b["N"], device=dev)
+                t, te = both(lambda: cost.trajectory_cost(rows, H, nb * b["N"], out=buf), 200)
+                out.append(hbm_entry("k_traj_cost (yardstick, same session's candidate rows)", "mbpo_traj_cost_eval",
+                                     {"n_traj": nb * b["N"], "horizon": H, "row_len": rows.shape[1], "reduce": "max", "terms": 1}, t,
+                                     4 * rows.numel() + 4 * nb * b["N"], "the rows' 64 B sectors once + 4 B per trajectory"))
+                log(f"traj_cost_eval (yardstick) H={H} n_traj={nb * b['N']}: {t * 1e6:.1f} us (eager {te * 1e6:.1f})")
+                for o in opts.values():
+                    o._bufs = o._bbufs = None
+
+    if want("icem_policy_prior_case"): icem_policy_prior_case()
+
     res = {"device": torch.cuda.get_device_name(0), "roofs": {"hbm_GBs": HBM_PEAK_GBS, "mfma_f32_TFLOPs": MFMA_F32_PEAK_TF},
            "note": "device_us = HIP-event average per call with the calls captured into a hipGraph and replayed (device time, inputs resident in HBM; multi-launch ops timed whole); eager_us = the same call issued from Python",
            "kernels": out}
