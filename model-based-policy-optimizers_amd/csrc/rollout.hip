@@ -25,6 +25,18 @@ extern "C" int mbpo_debug_set_rollout_stamps(void *buf) {
   return MBPO_OK;
 }
 
+// Test hook (not part of include/mbpo_hip.h): which kernel mbpo_model_rollout launched last, as the launch sites recorded it
+// (RolloutKernelId, rollout_shared.hpp) — out[0 .. 11) = {family, H, X, PEND, PIPE, LR, W, TM, SB, HL, TA}; family 0: none yet.
+static RolloutKernelId g_ro_last = {RO_FAMILY_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+void rollout_note_kernel(const RolloutKernelId &id) { g_ro_last = id; }
+extern "C" int mbpo_debug_last_rollout_kernel(int32_t *out, int32_t n) {
+  MBPO_REQUIRE(out && n >= 11, MBPO_ERR_ARG, "debug_last_rollout_kernel: needs room for 11 ints");
+  const int v[11] = {g_ro_last.family, g_ro_last.h, g_ro_last.x, g_ro_last.pend, g_ro_last.pipe, g_ro_last.lr,
+                     g_ro_last.wide, g_ro_last.term, g_ro_last.start, g_ro_last.hal, g_ro_last.ta};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return MBPO_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Open-loop rollout of the analytic Pendulum system (rollout_actions, utils/optimizer_utils.py:26-38 — the iCEM planner's candidate
 // evaluation, icem_optimizer.py:146-160): no network, so a 16-env tile on a 768-thread workgroup has 16 busy lanes per step (the
@@ -302,6 +314,7 @@ static int rollout_dispatch(const mbpo_rollout_desc *d, const RolloutReq &q, con
   switch (pl.path) {
   case RO_PATH_OPENLOOP: {
     const dim3 ogrid((unsigned)((d->n_envs + 255) / 256));
+    rollout_note_kernel({RO_FAMILY_OPENLOOP, 0, 3, 1, 0, 0, 0, A.term_low != nullptr, A.start.rows != nullptr, 0, 0});
     if (A.start.rows) hipLaunchKernelGGL(k_openloop_pendulum<true>, ogrid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL(k_openloop_pendulum<false>, ogrid, dim3(256), 0, st, A);
     return MBPO_OK;

@@ -23,6 +23,7 @@ int rollout64_launch(int lr, const RolloutFlags &f, const RolloutArgs64 &AA, con
                 static_cast<RolloutArgs64 &>(AH) = AA;
                 if constexpr (HL.value) AH.halluc_beta = halluc_beta;
                 if constexpr (TA.value) AH.hold = *hold;
+                rollout_note_kernel({RO_FAMILY_64, 64, 0, 0, 0, LR.value, W.value, TM.value, SB.value, HL.value, TA.value});
                 return mbpo_launch<k_model_rollout64<W.value, LR.value, TM.value, SB.value, HL.value, TA.value>>(grid, block, lds, st, "model_rollout", AH);
               }
             });

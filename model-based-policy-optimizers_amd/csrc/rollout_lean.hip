@@ -544,6 +544,7 @@ int rollout_lean_launch(const RoLeanArgs &A, int grid, bool pipe, void *stream) 
   const bool start = A.a.start.rows != nullptr;
 #define RL_LAUNCH_S(X_, P_, PP_, LR_, T_, S_)                                                                               \
   {                                                                                                                         \
+    rollout_note_kernel({RO_FAMILY_LEAN, 64, X_, P_, PP_, LR_, 0, T_, S_, 0, 0});                                           \
     rc = mbpo_launch<k_rollout_lean<X_, P_, PP_, LR_, T_, S_>>(grid, RL_THREADS, RL_LDS_BYTES, st, "rollout_lean", A);      \
     if (rc != MBPO_OK) return rc;                                                                                           \
   }

@@ -67,6 +67,18 @@ struct RolloutArgs {
   StartBuf start;                         // rows == NULL: no start buffer (first_obs stays what the caller set)
 };
 
+// Which kernel mbpo_model_rollout launched last, for the tests (mbpo_debug_last_rollout_kernel, rollout.hip): every launch site stores the
+// template arguments it instantiates the kernel with, next to its mbpo_launch.  Host only; a field a family does not have is 0.
+#define RO_FAMILY_NONE 0
+#define RO_FAMILY_64 1          // k_model_rollout64
+#define RO_FAMILY_WIDE 2        // k_model_rollout<128 | 256> (term: the run-time box flag)
+#define RO_FAMILY_LEAN 3        // k_rollout_lean
+#define RO_FAMILY_OPENLOOP 4    // k_openloop_pendulum
+struct RolloutKernelId {
+  int family, h, x, pend, pipe, lr, wide, term, start, hal, ta;
+};
+void rollout_note_kernel(const RolloutKernelId &id);
+
 // Fresh starts (include/mbpo_hip.h): the physical row of the true buffer that env `env` takes as its next start state after a reset at
 // the launch's step s: idx = randint(sample_position, insert_position) of element s * N + env of stream START, wrapped and moved
 // through the ring's head as k_replay_gather does.  An empty range yields sample_position (span 0), as mbpo_replay_sample does.

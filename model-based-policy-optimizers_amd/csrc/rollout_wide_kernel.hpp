@@ -345,6 +345,7 @@ static int rollout_wide_launch_lr(int H, const RolloutFlags &f, const RolloutArg
             static_cast<RolloutArgs &>(AH) = A;
             if constexpr (HL.value) AH.halluc_beta = halluc_beta;
             if constexpr (TA.value) AH.hold = *hold;
+            rollout_note_kernel({RO_FAMILY_WIDE, H256.value ? 256 : 128, 0, 0, 0, LR, 0, f.term, SB.value, HL.value, TA.value});
             return mbpo_launch<k_model_rollout<H256.value ? 256 : 128, LR, SB.value, HL.value, TA.value>>(grid, block, lds, st, "model_rollout", AH);
           }
         });

@@ -114,6 +114,14 @@ def test_test_hooks_without_a_device(lib):
         assert lib.mbpo_debug_eval_fastmath(fn, None, None, 4, None) < 0 and b"unknown helper" in lib.mbpo_last_error()
     assert lib.mbpo_debug_eval_fastmath(2, None, None, -1, None) < 0 and b"n=-1" in lib.mbpo_last_error()
     assert lib.mbpo_debug_eval_fastmath(2, None, None, 4, None) < 0 and b"null" in lib.mbpo_last_error()
+    # which rollout kernel ran last (tests/test_gpu_rollout_matrix.py): read-only, eleven ints, family 0 before any launch
+    assert hasattr(lib, "mbpo_debug_last_rollout_kernel") and "mbpo_debug_last_rollout_kernel" not in _declared()
+    lib.mbpo_debug_last_rollout_kernel.argtypes = [C.c_void_p, C.c_int32]
+    lib.mbpo_debug_last_rollout_kernel.restype = C.c_int
+    ids = (C.c_int32 * 11)(*([7] * 11))
+    assert lib.mbpo_debug_last_rollout_kernel(ids, 10) < 0 and b"11 ints" in lib.mbpo_last_error()
+    assert lib.mbpo_debug_last_rollout_kernel(None, 11) < 0
+    assert lib.mbpo_debug_last_rollout_kernel(ids, 11) == 0 and 0 <= ids[0] <= 4 and (ids[0] != 0 or list(ids) == [0] * 11)
     X, U, H, n, E = 4, 1, 5, 48, 5
     d = _hip.BpttDesc()
     d.x_dim, d.u_dim, d.horizon, d.n = X, U, H, n
