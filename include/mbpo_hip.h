@@ -470,6 +470,12 @@ int mbpo_gae_scan_discounts(const float *truncation, const float *termination, c
  *   target_q [2Q];  adam_m [NP];  adam_v [NP];  step_count [1] (optax's count, kept as a float: it only feeds Adam's bias
  *                   corrections 1 - b^count, which are exactly 1.0f long before a float stops counting at 2^24; it plays NO part
  *                   in the random streams)
+ *                   SATURATION: every optimizer here (this one, mbpo_ppo_*, mbpo_adamw_step) advances its count as a float32
+ *                   `count + 1.0f`, so the stored count reaches 16 777 216 = 2^24 and stays there: 2^24 + 1 rounds back to 2^24.
+ *                   optax's int32 count saturates at 2^31 - 1 instead.  The update is the same on both sides of 2^24 (both
+ *                   corrections are exactly 1.0f from count ~ 17 000 on: 0.999^count < 2^-25), so only the NUMBER read back
+ *                   differs: a caller that needs the true number of steps beyond 2^24 keeps an integer of its own
+ *                   (tests/test_gpu_optimizer_trained_state.py pins the stored value and the update across 2^24).
  *   grads    [NP]   written by mbpo_sac_grads, read by mbpo_sac_apply (all-reduce it in between for N>1 ranks —
  *                   the live form of the reference's dead jax.lax.pmean, sac/utils.py:29-33)
  * Three entry points so that the multi-GPU exchange sits at the reference's pmean position:
@@ -555,7 +561,8 @@ int mbpo_sac_finalize_advance(const mbpo_sac_desc *d, uint64_t *rng_dev, uint64_
  *           Inside the loss: policy logits and value baseline on [B,T] samples, bootstrap value, compute_gae (stop-gradient),
  *           advantage normalisation over the whole minibatch (losses.py:101-102), clipped surrogate, 0.5*MSE value loss, entropy bonus
  *           with a fresh NormalTanh sample.
- * Flat state: params [P+V] = [ policy | value ]; adam_m/adam_v [P+V]; step_count [1]; grads [P+V].
+ * Flat state: params [P+V] = [ policy | value ]; adam_m/adam_v [P+V]; step_count [1] (a float32 that stops at 2^24: see the
+ *             SATURATION note at mbpo_sac_desc's step_count); grads [P+V].
  *   mbpo_ppo_grads : grads, metrics[0..3] = total_loss, policy_loss, v_loss, entropy_loss (losses.py:121-126); bumps step_count
  *   mbpo_ppo_apply : grads *= grad_scale; [clip_by_global_norm over the whole [P+V] gradient;] AdamW.  All-reduce `grads` in
  *                    between for N>1 ranks (ppo.py:149-154's pmean): the clip norm is that of the reduced, scaled gradient.
@@ -710,7 +717,9 @@ int mbpo_mlp_layered_vjp(const mbpo_mlp_desc *mlp, const float *x, int64_t n, co
  * replaces: actor_optimizer.update/apply_updates (bptt_optimizer.py:218-225, 374-378), critic_optimizer + soft_update
  *           (:406-410; utils/optimizer_utils.py:155-161).
  * grads *= grad_scale; if apply_if_finite and any gradient is non-finite the whole update (params, moments, count) is
- * skipped; count (device scalar) advances by one otherwise; grad_norm_out (optional) = optax.global_norm(grads);
+ * skipped; count (device scalar, a float32 that stops at 2^24: the SATURATION note at mbpo_sac_desc's step_count) advances by one
+ * otherwise; grad_norm_out (optional) = optax.global_norm(grads), +inf when a finite gradient's square overflows (the step is then
+ * taken: v = +inf there and that parameter moves by its weight decay alone, as optax in float32);
  * target (optional) <- (1 - tau) * target + tau * new_params.   workspace >= 2 * ceil(n / 256) + 4 floats (sum-of-squares and
  * non-finite counts per block); need not be initialised.  grad_norm_out is overwritten; params, moments, count and target are state.
  */

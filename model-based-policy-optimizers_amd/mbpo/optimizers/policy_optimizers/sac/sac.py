@@ -74,7 +74,8 @@ class TrainingState:
     q_optimizer_state: Any
     q_params: torch.Tensor
     target_q_params: torch.Tensor
-    gradient_steps: torch.Tensor
+    gradient_steps: torch.Tensor      # the optimizer's float32 step_count: it reads 2^24 from the 16 777 216th step on (mbpo_hip.h,
+                                      # SATURATION), where the reference's own int32 counter goes on counting
     env_steps: int
     alpha_optimizer_state: Any
     alpha_params: torch.Tensor

@@ -178,12 +178,13 @@ def normalizer_update(x: torch.Tensor, mean, std, size):
     return new_mean, torch.maximum(new_std, torch.full_like(new_std, EPS)), total
 
 
-def apply_if_finite_adamw(p, g, m, v, count, lr, wd):
-    """optax.apply_if_finite(adamw): skip the whole update (params, moments, count) when any gradient is non-finite."""
+def apply_if_finite_adamw(p, g, m, v, count, lr, wd, adam=None):
+    """optax.apply_if_finite(adamw): skip the whole update (params, moments, count) when any gradient is non-finite.
+    `adam`: keywords for adamw_step (its constants)."""
     if not bool(torch.isfinite(g).all()):
         return p, m, v, count
     count = count + 1
-    p2, m2, v2 = adamw_step(p, g, m, v, count, lr, wd)
+    p2, m2, v2 = adamw_step(p, g, m, v, count, lr, wd, **(adam or {}))
     return p2, m2, v2, count
 
 

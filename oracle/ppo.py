@@ -110,11 +110,11 @@ def init_state(cfg: PpoConfig, gen: torch.Generator, dtype=torch.float32) -> Ppo
 
 
 def minibatch_step(cfg: PpoConfig, st: PpoState, data, ent_noise, norm_mean=None, norm_std=None,
-                   grad_override: Optional[torch.Tensor] = None):
-    """ppo.py:142-156: one adamw update on one minibatch."""
+                   grad_override: Optional[torch.Tensor] = None, adam: Optional[dict] = None):
+    """ppo.py:142-156: one adamw update on one minibatch.  `adam`: keywords for adamw_step (its constants)."""
     g, terms, _, _ = grads(cfg, st.params, data, ent_noise, norm_mean, norm_std)
     if grad_override is not None:
         g = grad_override
     count = st.count + 1
-    p, m, v = adamw_step(st.params, g, st.adam_m, st.adam_v, count, cfg.lr, cfg.wd)
+    p, m, v = adamw_step(st.params, g, st.adam_m, st.adam_v, count, cfg.lr, cfg.wd, **(adam or {}))
     return PpoState(p, m, v, count), terms, g

@@ -143,9 +143,14 @@ def clip_by_global_norm(g: torch.Tensor, max_norm: float) -> torch.Tensor:
     return g if bool(n < max_norm) else (g / n) * max_norm
 
 
-def adamw_step(p, g, m, v, count: int, lr: float, wd: float, b1=0.9, b2=0.999, eps=1e-8):
-    m = b1 * m + (1 - b1) * g
-    v = b2 * v + (1 - b2) * g * g
+def adamw_step(p, g, m, v, count: int, lr: float, wd: float, b1=0.9, b2=0.999, eps=1e-8, one_minus_b1=None, one_minus_b2=None):
+    """one_minus_b1 / one_minus_b2 (default: 1 - b1, 1 - b2 in Python double): optax forms (1 - decay) in double and casts THAT to
+    float32, so in float32 arithmetic the weights of g and g^2 are f32(0.1) and f32(0.001), not 1 - f32(0.9) and 1 - f32(0.999).
+    A caller that wants the float32 constants of optax and of the kernels, widened, passes all five (tests/optimizer_state_cases.py)."""
+    one_minus_b1 = 1 - b1 if one_minus_b1 is None else one_minus_b1
+    one_minus_b2 = 1 - b2 if one_minus_b2 is None else one_minus_b2
+    m = b1 * m + one_minus_b1 * g
+    v = b2 * v + one_minus_b2 * g * g
     m_hat = m / (1 - b1 ** count)
     v_hat = v / (1 - b2 ** count)
     u = m_hat / (torch.sqrt(v_hat) + eps) + wd * p
@@ -174,8 +179,8 @@ def init_state(cfg: SacConfig, gen: torch.Generator, init_log_alpha: float = 0.0
 
 
 def sgd_step(cfg: SacConfig, st: SacState, batch, noise_alpha, noise_critic, noise_actor, norm_mean=None, norm_std=None,
-             grad_override: Optional[torch.Tensor] = None):
-    """SAC.sgd_step (sac.py:227-281).  Returns (new state, metrics dict, flat grad)."""
+             grad_override: Optional[torch.Tensor] = None, adam: Optional[dict] = None):
+    """SAC.sgd_step (sac.py:227-281).  Returns (new state, metrics dict, flat grad).  `adam`: keywords for adamw_step (its constants)."""
     g, (cl, ac, al) = grads(cfg, st.params, st.target_q, batch, noise_alpha, noise_critic, noise_actor, norm_mean, norm_std)
     if grad_override is not None:   # multi-rank tests: the pmean'd gradient
         g = grad_override
@@ -185,7 +190,7 @@ def sgd_step(cfg: SacConfig, st: SacState, batch, noise_alpha, noise_critic, noi
     for sl, lr, wd in ((slice(0, P), cfg.lr_policy, cfg.wd_policy), (slice(P, P + 2 * Q), cfg.lr_q, cfg.wd_q),
                        (slice(P + 2 * Q, P + 2 * Q + 1), cfg.lr_alpha, cfg.wd_alpha)):
         gg = clip_by_global_norm(g[sl], cfg.max_grad_norm)
-        new_p[sl], new_m[sl], new_v[sl] = adamw_step(st.params[sl], gg, st.adam_m[sl], st.adam_v[sl], count, lr, wd)
+        new_p[sl], new_m[sl], new_v[sl] = adamw_step(st.params[sl], gg, st.adam_m[sl], st.adam_v[sl], count, lr, wd, **(adam or {}))
     new_tq = st.target_q * (1 - cfg.tau) + new_p[P:P + 2 * Q] * cfg.tau          # sac.py:260-261
     metrics = {"critic_loss": cl, "actor_loss": ac, "alpha_loss": al, "alpha": float(torch.exp(new_p[-1]))}
     return SacState(new_p, new_tq, new_m, new_v, count), metrics, g
